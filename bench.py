@@ -19,6 +19,10 @@ layers) is run and timed after the timed region, with the all-gather reported se
 round-1 behaviour (N independent meshes, no data-path collective, weak scaling) as a secondary mode.
 
 Contract: python bench.py --gpus N --steps K --warmup W  -> rank 0 prints ONE JSON line.
+A plain run does only what that line's headline needs: set-up, W warm-up steps, the K timed steps, the line.  `--full` adds every
+other figure behind the timed region (roofline objects from evented steps, the HIP-graph figure, the back-projection, the VAE, the
+CPU baseline, the attention A/B, the reference operating point; N > 1: the exchange timing).  `--dump-outputs DIR` writes what the
+last timed step computed (latents, noise prediction) as float32 .npy files, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -45,6 +49,21 @@ WORKLOADS = {
 }
 D, HEADS, N_DOUBLE, N_SINGLE = 3072, 24, 19, 38
 PEAK_BF16_TFLOPS = 2500.0  # dense MFMA peak, MI355X_MICROARCH.md
+DUMP_BYTES_PER_ARRAY = 32 << 20   # --dump-outputs: two arrays, at most 64 MB in all
+
+
+def dump_outputs(out_dir, arrays):
+    """{name: 2-D float tensor} -> out_dir/<name>.npy in float32.  An array above DUMP_BYTES_PER_ARRAY keeps a fixed sample of its rows
+    (numpy seed 0, ascending row order), so the same arguments give files of the same shape and content from run to run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        row_bytes = a[0].nbytes if a.shape[0] else 1
+        if a.nbytes > DUMP_BYTES_PER_ARRAY:
+            keep = np.sort(np.random.default_rng(0).choice(a.shape[0], DUMP_BYTES_PER_ARRAY // row_bytes, replace=False))
+            a = a[keep]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def token_counts(name):
@@ -316,7 +335,17 @@ def main():
     ap.add_argument("--cpu-config1", action="store_true",
                     help="also run BASELINE configs[0] (512^2 x 4 views, S = 9728, 4 denoise steps, fp32) to COMPLETION on the host "
                          "cores with the oracle (~35 min on the GPU box's 64 threads; 50 min on the 8-core build container: profiles/r02_cpu_config1_container.json): the one CPU number that is not extrapolated (SURVEY 8d)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the roofline objects (evented steps after the timed region), the HIP-graph figure, the back-projection, "
+                         "the VAE, the CPU baseline, the attention A/B and the reference operating point; N > 1 also the exchange timing.  A plain run "
+                         "only sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed as float32 DIR/<name>.npy: latents.npy (the latents after the "
+                         "scheduler step, all image tokens) and noise_pred.npy (the transformer's prediction for the noise tokens); an array above "
+                         "%d MB is cut to a fixed, seeded sample of its rows" % (DUMP_BYTES_PER_ARRAY >> 20))
     args = ap.parse_args()
+    if (args.cpu_full_step or args.cpu_config1) and not args.full:
+        ap.error("--cpu-full-step / --cpu-config1 change the CPU baseline, which only --full runs")
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs an MI355X; no HIP device visible (there is no CPU fallback)")
@@ -333,7 +362,8 @@ def main():
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
                "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
         sys.stdout.flush()
-        os.execv(sys.executable, cmd)
+        import subprocess    # a fresh child process, not exec: this process has already initialised the HIP runtime
+        sys.exit(subprocess.call(cmd))
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -425,6 +455,7 @@ def main():
         model.attn_events = events
         v = model.forward(lat, t_in)
         ops.sched_step(lat, v, sched.dsigma(i), n_noise_tokens=n_noise_sched, cond=cond)
+        return v
 
     def barrier():
         if world > 1:
@@ -449,42 +480,53 @@ def main():
     barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    v = None
     for i in range(args.warmup, total):
-        one_step(i, None)
+        v = one_step(i, None)
     torch.cuda.synchronize()
     barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and v is not None:
+        # the last timed step's results, taken before anything else runs a step on the same buffers.  Sequence parallel: every rank's slice, in rank order
+        outs = {"latents": lat.float().cpu(), "noise_pred": v[:n_noise_sched].float().cpu()}
+        if ulysses:
+            import torch.distributed as dist
+            parts = [None] * world
+            dist.all_gather_object(parts, outs)
+            outs = {k: torch.cat([p[k] for p in parts], 0) for k in outs}
+        if rank == 0:
+            dump_outputs(args.dump_outputs, outs)
+        del outs
     if use_graph:
         model.release_graph()
-    events = []
-    one_step(total - 1, events)      # the dominant kernel's launches of one step, HIP events on the launch stream around each
-    torch.cuda.synchronize()
-    model.attn_events = None
-    # the same steps replayed as ONE HIP graph (what UTX_HIP_GRAPH=1 makes the denoise loop do), reported beside the default path
-    graph_ms = None
-    if not ulysses and not use_graph and os.environ.get("UTX_BENCH_GRAPH_FIGURE", "1") != "0":
-        try:
-            model.capture_graph(warm=False)
-            one_step(0)
-            torch.cuda.synchronize()
-            n_graph = min(args.steps, 4)          # a figure beside the line, not a second timed region
-            tg = time.perf_counter()
-            for i in range(args.warmup, args.warmup + n_graph):
-                one_step(i, None)
-            torch.cuda.synchronize()
-            graph_ms = (time.perf_counter() - tg) / n_graph * 1e3
-        except Exception as e:  # noqa: BLE001 -- a reporting extra
-            graph_ms = "error: %r" % (e,)
-        finally:
-            model.release_graph()
-    # GEMM-only roofline: ONE extra eager step behind the timed region with HIP events around every large-M GEMM of the main stream
-    # (the text-side GEMMs of the double blocks run beside them on the second stream, as in the timed steps)
-    gemm_ev = []
-    model.gemm_events = gemm_ev
-    one_step(total - 1, None)
-    torch.cuda.synchronize()
-    model.gemm_events = None
+    events, gemm_ev, graph_ms = [], [], None
+    if args.full:
+        one_step(total - 1, events)      # the dominant kernel's launches of one step, HIP events on the launch stream around each
+        torch.cuda.synchronize()
+        model.attn_events = None
+        # the same steps replayed as ONE HIP graph (what UTX_HIP_GRAPH=1 makes the denoise loop do), reported beside the default path
+        if not ulysses and not use_graph and os.environ.get("UTX_BENCH_GRAPH_FIGURE", "1") != "0":
+            try:
+                model.capture_graph(warm=False)
+                one_step(0)
+                torch.cuda.synchronize()
+                n_graph = min(args.steps, 4)          # a figure beside the line, not a second timed region
+                tg = time.perf_counter()
+                for i in range(args.warmup, args.warmup + n_graph):
+                    one_step(i, None)
+                torch.cuda.synchronize()
+                graph_ms = (time.perf_counter() - tg) / n_graph * 1e3
+            except Exception as e:  # noqa: BLE001 -- a reporting extra
+                graph_ms = "error: %r" % (e,)
+            finally:
+                model.release_graph()
+        # GEMM-only roofline: ONE extra eager step behind the timed region with HIP events around every large-M GEMM of the main stream
+        # (the text-side GEMMs of the double blocks run beside them on the second stream, as in the timed steps)
+        model.gemm_events = gemm_ev
+        one_step(total - 1, None)
+        torch.cuda.synchronize()
+        model.gemm_events = None
     if world > 1:
         import torch.distributed as dist
         tt = torch.tensor([dt], device=dev, dtype=torch.float64)
@@ -496,7 +538,7 @@ def main():
     # node has run yet.  A collective that hangs would take the ONE stdout line of an otherwise measured job with it, so a watchdog on every rank ends the job cleanly after
     # UTX_BENCH_EXTRAS_TIMEOUT seconds (default 420): rank 0 prints the contract's line from the timed region alone and says so in it; cancelled where the full line is printed.
     watchdog = None
-    if world > 1:
+    if world > 1 and args.full:
         import threading
 
         def _extras_timed_out():
@@ -517,7 +559,7 @@ def main():
     # ---- N > 1, one job: un-overlapped cost of the two exchanges of a layer on the real buffers (outside the timed region),
     # and the view-sharded back-projection with its ONE all-gather -- every rank takes part, rank 0 reports
     exchange = None
-    if ulysses:
+    if ulysses and args.full:
         ex = model.ex
         tmp = torch.empty(ex.S_loc, shape.dim, dtype=torch.bfloat16, device=dev)
         reps = 8
@@ -542,7 +584,7 @@ def main():
                     "bytes_per_rank_per_layer": ex.bytes_per_layer, "layers": N_DOUBLE + N_SINGLE, "head_groups": ex.G,
                     "note": "measured back to back without compute; in the step the Q/K/V exchange of the 38 single blocks runs beside the MLP half of the projection GEMM"}
     bp = None
-    if world > 1:
+    if world > 1 and args.full:
         try:
             from unitex_amd.texturetools.benchmarks import time_backprojection
             bp = time_backprojection(50000, 1024, 2048, iters=2, warmup=1, device=dev, view_shard=(rank, world))
@@ -574,7 +616,6 @@ def main():
             fl -= (attn_launch_flops - attn_last) + 2.0 * dead * 3072 * (3072 + 4 * 3072) + 2.0 * dead * (5 * 3072) * 3072
             fl_attn -= (attn_launch_flops - attn_last)
             attn_launch_flops = (attn_launch_flops * (n_attn - 1) + attn_last) / n_attn      # mean over the step's calls, as attn_avg_ms is
-        achieved = attn_launch_flops / (attn_avg_ms * 1e-3) / 1e12
         value = (1 if ulysses else world) * args.steps / dt
         par = "DIAGNOSTIC --sp-self-test: the sequence-parallel plan on ONE rank, every all-to-all issued to itself through RCCL (not a speed)" if args.sp_self_test else \
             ("ulysses sp%d: ONE job, 2 all-to-alls / layer (RCCL) + view-sharded back-projection with one all-gather" % world) if ulysses \
@@ -603,16 +644,18 @@ def main():
                        # wrong-result ablations do not exist in this library) and every UTX_* variable of the environment
                        "launch_options": _lib.get_options(), "gemm_launches_per_step": _gemm_census(model), "ablation_build": bool(_lib.load_library().utx_is_ablation_build()),
                        "env_UTX": {k: v for k, v in sorted(os.environ.items()) if k.startswith("UTX_")}},
-            "roofline": {"bound": "mfma", "kernel": "attn_fwd_fp8_kernel (+ three MX quantiser passes, not in the launch time)" if args.fp8_attn else ("attn_fwd_q64_kernel (4 x 64, generated stream; + flag memset + repair-pass launch of attn_fwd_glds_kernel)" if _lib.get_options().get("UTX_ATTN_Q64") == 1 and (not ulysses or model.sp_kv_dedup) else "attn_fwd_glds_kernel"), "launches_per_call": "full rounds + key-split tail round (same kernel) + attn_merge_kernel; a 'launch' below is one utx_attn_fwd_bf16 call", "achieved": achieved, "peak": 5000.0 if args.fp8_attn else PEAK_BF16_TFLOPS,
-                         "unit": "TFLOP/s", "frac": achieved / (5000.0 if args.fp8_attn else PEAK_BF16_TFLOPS), "traffic": None,
-                         "launches_timed": len(attn_ms), "avg_launch_ms": attn_avg_ms,
-                         "timed_in": "one extra step behind the timed region, HIP events on the launch stream around every attention call (the timed region itself carries no events: it is the product's launch path)",
-                         "flops_per_launch": attn_launch_flops,
-                         # context, not the judged fraction: an MFMA-only stream of the same shape sustains 1.73 PF on random operands
-                         # on this board (power-limited clock, profiles/r01_perf_attn_q64.log)
-                         "sustained_mfma_only_tflops": 1730.0, "frac_of_sustained": achieved / 1730.0,
-                         "attention_share_of_step_time": (attn_avg_ms * n_attn) / (dt / args.steps * 1e3)},
         }
+        if args.full:
+            achieved = attn_launch_flops / (attn_avg_ms * 1e-3) / 1e12
+            out["roofline"] = {"bound": "mfma", "kernel": "attn_fwd_fp8_kernel (+ three MX quantiser passes, not in the launch time)" if args.fp8_attn else ("attn_fwd_q64_kernel (4 x 64, generated stream; + flag memset + repair-pass launch of attn_fwd_glds_kernel)" if _lib.get_options().get("UTX_ATTN_Q64") == 1 and (not ulysses or model.sp_kv_dedup) else "attn_fwd_glds_kernel"), "launches_per_call": "full rounds + key-split tail round (same kernel) + attn_merge_kernel; a 'launch' below is one utx_attn_fwd_bf16 call", "achieved": achieved, "peak": 5000.0 if args.fp8_attn else PEAK_BF16_TFLOPS,
+                               "unit": "TFLOP/s", "frac": achieved / (5000.0 if args.fp8_attn else PEAK_BF16_TFLOPS), "traffic": None,
+                               "launches_timed": len(attn_ms), "avg_launch_ms": attn_avg_ms,
+                               "timed_in": "one extra step behind the timed region, HIP events on the launch stream around every attention call (the timed region itself carries no events: it is the product's launch path)",
+                               "flops_per_launch": attn_launch_flops,
+                               # context, not the judged fraction: an MFMA-only stream of the same shape sustains 1.73 PF on random operands
+                               # on this board (power-limited clock, profiles/r01_perf_attn_q64.log)
+                               "sustained_mfma_only_tflops": 1730.0, "frac_of_sustained": achieved / 1730.0,
+                               "attention_share_of_step_time": (attn_avg_ms * n_attn) / (dt / args.steps * 1e3)}
         if gemm_ev:
             g_ms = sum(a.elapsed_time(b) for a, b, _ in gemm_ev)
             g_fl = sum(f for _, _, f in gemm_ev)
@@ -633,7 +676,7 @@ def main():
         # the per-launch figure is the one measured by tools/pmc_kernel.sh on THIS command and committed under profiles/
         try:
             tr = json.load(open(os.path.join(ROOT, "profiles", "pmc_traffic.json"))).get(args.workload)
-            if tr and world == 1 and not args.fp8_attn:
+            if tr and args.full and world == 1 and not args.fp8_attn:
                 out["roofline"]["traffic"] = tr["traffic_bytes_per_launch"]
                 out["roofline"]["traffic_unit"] = "bytes/launch (FETCH_SIZE x2 + WRITE_SIZE, %s)" % tr["source"]
                 out["roofline"]["algorithmic_hbm_bytes_per_launch"] = tr["algorithmic_bytes_per_launch"]
@@ -652,7 +695,7 @@ def main():
                         out["roofline_gemm"]["traffic_note"] = "bytes of ONE launch of the largest linear (M 50688, N 21504, K 3072; FETCH_SIZE x2 + WRITE_SIZE) against %d algorithmic: the re-reads are the 8 XCDs' separate L2s each streaming the operand panels of their 32 tiles (miss rate = the tile order's own at 1 ... 65 rounds, profiles/r06_gemm_l2_hit_vs_rounds.log)" % tr["gemm"]["algorithmic_bytes"]
         except OSError:
             pass
-        if world == 1:
+        if world == 1 and args.full:
             # metric (ii) of SURVEY 8d, geometry part: render -> UV back-projection of 6 x 1024^2 views into a 2048^2
             # atlas of a 50k-face mesh (outside the timed region; a few hundred ms)
             try:
@@ -682,7 +725,7 @@ def main():
                 out["config"]["backprojection"]["all_gather_bytes_received_per_rank"] = ag_bytes
         elif bp is not None:
             out["config"]["backprojection"] = bp
-        if world == 1:
+        if world == 1 and args.full:
             # VAE part of a job (HIP AutoencoderKL): pass 1 encodes the control strip + the 512^2 reference image and
             # decodes the strip, pass 2 (delight) encodes the control strip and decodes once more
             try:
@@ -703,7 +746,7 @@ def main():
                 del vae, img, zz
             except Exception as e:  # noqa: BLE001
                 out["config"]["vae_sec_per_mesh"] = "error: %r" % (e,)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             ncpu, phys = host_cores()
             try:
                 # one thread per physical core, capped at 64: on the 128-core hosts of the GPU boxes torch's fp32 GEMMs measured 0.14
@@ -723,9 +766,10 @@ def main():
                                        "sample": "failed: %r" % (e,)}
         # The extras below run in-process behind every measurement of the line.  They are product kernels on product shapes, but a device fault in one of them would take the ONE
         # stdout line with it: the line as it stands goes to STDERR first -- a safety copy in the logs, stdout keeps its single JSON line.
-        sys.stderr.write("bench.py core line (safety copy before the reporting extras): " + json.dumps(out) + "\n")
-        sys.stderr.flush()
-        if world == 1 and not args.sp_self_test and not args.fp8_attn and os.environ.get("UTX_BENCH_EXPERIMENTS", "1") != "0":
+        if args.full:
+            sys.stderr.write("bench.py core line (safety copy before the reporting extras): " + json.dumps(out) + "\n")
+            sys.stderr.flush()
+        if world == 1 and args.full and not args.sp_self_test and not args.fp8_attn and os.environ.get("UTX_BENCH_EXPERIMENTS", "1") != "0":
             try:
                 ab = attention_loop_ab(dev, S_exec, HEADS)
                 out["config"]["experiments"] = {"attention_q64_vs_fast8x32": ab}
@@ -733,15 +777,16 @@ def main():
                     ab["tokens"], int(ab["bit_identical"]), ab["q64_ms"], ab["fast8x32_ms"], ab["fast8x32_ms"] / ab["q64_ms"], ab["q64_tflops"], ab["fast8x32_tflops"])
             except Exception as e:  # noqa: BLE001 -- a reporting extra
                 out["config"]["experiments_summary"] = "failed: %r" % (e,)
-        if world == 1 and not args.sp_self_test and args.workload != "ref512x6" and os.environ.get("UTX_BENCH_REF_POINT", "1") != "0":
+        if world == 1 and args.full and not args.sp_self_test and args.workload != "ref512x6" and os.environ.get("UTX_BENCH_REF_POINT", "1") != "0":
             # the reference's own operating point (512^2 x 6 views, S = 13 824) on the same model, a few steps behind everything else: a flat scalar the driver's record keeps
             try:
                 out["config"]["ref512x6_ms_per_step"] = ref_point_ms(model, ops, sched, calculate_shift, shape, dev, prune)
             except Exception as e:  # noqa: BLE001 -- a reporting extra
                 out["config"]["ref512x6_ms_per_step"] = "error: %r" % (e,)
         # flat scalars (the driver's record drops nested objects of `config`)
-        out["config"]["attn_tflops"] = out["roofline"]["achieved"]
-        out["config"]["attn_frac"] = out["roofline"]["frac"]
+        if "roofline" in out:
+            out["config"]["attn_tflops"] = out["roofline"]["achieved"]
+            out["config"]["attn_frac"] = out["roofline"]["frac"]
         if "roofline_gemm" in out:
             out["config"]["gemm_frac"] = out["roofline_gemm"]["frac"]
             out["config"]["gemm_tflops"] = out["roofline_gemm"]["achieved"]

@@ -202,6 +202,27 @@ def test_bench_counts_the_gpus_under_a_job_without_trusting_a_placeholder_uuid()
     assert rec["index"] == 0 and len(rec["visible"]) == 3
 
 
+def test_bench_dump_outputs_is_float32_bounded_and_repeatable(tmp_path):
+    """bench.py --dump-outputs: float32 .npy per array; an array within the cap is written whole, a larger one as the same seeded row sample
+    on every run, and the files of one dump stay within 64 MB."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(os.path.dirname(HERE), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    g = torch.Generator().manual_seed(0)
+    small = torch.randn(1000, 64, generator=g).to(torch.bfloat16)
+    big = torch.randn(bench.DUMP_BYTES_PER_ARRAY // 256 + 5000, 64, generator=g).to(torch.bfloat16)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"latents": big, "noise_pred": small})
+    a_small, a_big = np.load(tmp_path / "a" / "noise_pred.npy"), np.load(tmp_path / "a" / "latents.npy")
+    assert a_small.dtype == np.float32 and np.array_equal(a_small, small.float().numpy())
+    assert a_big.dtype == np.float32 and a_big.nbytes <= bench.DUMP_BYTES_PER_ARRAY and a_big.shape[1] == 64
+    assert np.array_equal(a_big, np.load(tmp_path / "b" / "latents.npy"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 64 << 20
+    rows = {r.tobytes() for r in big.float().numpy()}
+    assert all(r.tobytes() in rows for r in a_big[:50])       # rows of the output, not a reduction of them
+
+
 def test_reproject_and_query_field_forwards_variant_switches(tmp_path):
     """host logic of RGBTextureFullPipelineBase.reproject_and_query_field (reference pipeline.py:313-347): the 2 x 3 grid is
     cut into six view images in (row, col) order, and `method` / `inpainting` reach the inverse renderer as method,
