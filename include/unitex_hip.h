@@ -385,6 +385,10 @@ typedef struct utx_backproject_desc {
     float cos_thresh, two_sqrt3;
 } utx_backproject_desc;
 int utx_backproject(utx_ctx* ctx, const utx_backproject_desc* d, utx_bvh* bvh, utx_stream stream);
+/* the same with perspective rays (uv_to_pcd(perspective=True), renderer_inverse.py:279-281): every ray of view v starts at the camera
+ * centre eyes[v] and points at the texel's surface point, d = (pos - eye) / max(|pos - eye|, 1e-12).  eyes [n_views][3] f32 = c2w[:, :3, 3];
+ * d->dirs and d->two_sqrt3 are not read.  Colour, alpha and the facing threshold as in utx_backproject. */
+int utx_backproject_persp(utx_ctx* ctx, const utx_backproject_desc* d, const float* eyes, utx_bvh* bvh, utx_stream stream);
 
 /* visibility hole filling k=3,5 + AND coverage + AND alpha>0.999 (renderer_inverse.py:326-343).
  * rayvis/alphaok/vis_out/tmp: [n_views][H][W] u8. */
@@ -410,6 +414,10 @@ int utx_nn_fill(utx_ctx* ctx, const float* pos, const void* winner, const float*
  * tmp: 2*n*H*W bytes.  vis [n][H][W] u8, alpha [n][H][W] f32 (optional).  radius = 15 (the reference's 31-wide pool, along W). */
 int utx_view_visibility(utx_ctx* ctx, const float* attr6, const float* rast, const float* fnormal, const float* dirs, int n, int H, int W,
                         float grad_thr, float cos_thr, int radius, void* tmp, void* vis, float* alpha, utx_stream stream);
+/* the same with perspective rays (mv_to_pcd(perspective=True), renderer_inverse.py:187-190): the facing test of pixel p of view v uses
+ * d = (attr6[p][0:3] - eyes[v]) / max(|attr6[p][0:3] - eyes[v]|, 1e-12).  eyes [n][3] f32 = c2w[:, :3, 3]. */
+int utx_view_visibility_persp(utx_ctx* ctx, const float* attr6, const float* rast, const float* fnormal, const float* eyes, int n, int H, int W,
+                              float grad_thr, float cos_thr, int radius, void* tmp, void* vis, float* alpha, utx_stream stream);
 
 /* exact k-NN gather in 3-D (bake_mv_to_uv_kdtree, renderer_inverse.py:367-433; search = torch_kdtree [3p], pcd/knn/__init__.py:103-113).
  * Sources and queries are dense arrays with optional byte masks (view pixels / atlas texels); k <= 32.

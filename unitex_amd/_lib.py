@@ -186,11 +186,14 @@ SYMBOLS = {
     "utx_bvh_trace_count": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
     "utx_bvh_depth": (c_int, [c_void_p]),
     "utx_backproject": (c_int, [c_void_p, C.POINTER(BackprojectDesc), c_void_p, c_void_p]),
+    "utx_backproject_persp": (c_int, [c_void_p, C.POINTER(BackprojectDesc), c_void_p, c_void_p, c_void_p]),
     "utx_dilate_visibility": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "utx_composite": (c_int, [c_void_p, c_void_p, c_void_p, C.POINTER(c_int), c_int, c_long, c_void_p, c_void_p, c_void_p]),
     "utx_seam_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "utx_view_visibility": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
+    "utx_view_visibility_persp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int,
+                                          c_void_p, c_void_p, c_void_p, c_void_p]),
     "utx_knn_workspace_bytes": (c_long, [c_long]),
     "utx_knn": (c_int, [c_void_p, C.POINTER(KnnDesc), c_void_p, c_long, c_void_p]),
     "utx_nn_fill_workspace_bytes": (c_long, [c_long]),

@@ -22,8 +22,11 @@ __device__ __forceinline__ float4 tap4(const float4* img, int H, int W, int x, i
 // UTX_BVH_PACKED_MAX_DEPTH (where the reference's stack overflow quirk could matter) and for A/B tests; MODE 2 (round 4, the default): a wave owns an
 // 8 x 8 TEXEL TILE of one view and its 64 parallel rays walk the packed tree as ONE PACKET (bvh_trace_packet: nodes through the scalar cache, per-lane
 // box / triangle tests, bit-identical results); 256 threads = a 16 x 16 block of texels, tiles without a covered texel skip the walk.
-template <int MODE>
-__global__ __launch_bounds__(256) void backproject_kernel(utx_backproject_desc p, const int* info, const float* aabb, const float4* nodes, const float4* tris) {
+// PERSP (renderer_inverse.py:279-281, perspective=True): every ray of view v starts at the camera centre eyes[v] = c2w[v][:3, 3] and points at the texel's
+// surface point, d = (pos - eye) / max(|pos - eye|, 1e-12); the orthographic arm (one direction per view, origin 2 sqrt(3) behind the point) is unchanged.
+template <int MODE, bool PERSP>
+__global__ __launch_bounds__(256) void backproject_kernel(utx_backproject_desc p, const float* eyes, const int* info, const float* aabb, const float4* nodes,
+                                                          const float4* tris) {
     __shared__ int pstack[MODE == 2 ? 4 * 192 : 1];      // MODE 2: the packets' DFS stacks, 64 x {node, mask lo, mask hi} per wave
     const long T = (long)p.T_h * p.T_w;
     long t;
@@ -62,11 +65,20 @@ __global__ __launch_bounds__(256) void backproject_kernel(utx_backproject_desc p
     float pos[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) pos[a] = (vert[3 * (long)f0 + a] * u + vert[3 * (long)f1 + a] * v) + vert[3 * (long)f2 + a] * w;
-    const float* d_in = (const float*)p.dirs + 3 * vw;
-    const float two_sqrt3 = p.two_sqrt3;
-    const float ro[3] = {pos[0] - two_sqrt3 * d_in[0], pos[1] - two_sqrt3 * d_in[1], pos[2] - two_sqrt3 * d_in[2]};
-    float dn = sqrtf(dot3(d_in, d_in)); if (dn < 1e-12f) dn = 1e-12f;
-    const float d[3] = {d_in[0] / dn, d_in[1] / dn, d_in[2] / dn};
+    float ro[3], d[3];
+    if constexpr (PERSP) {
+        const float* e = eyes + 3 * vw;
+        ro[0] = e[0]; ro[1] = e[1]; ro[2] = e[2];
+        const float dx = pos[0] - e[0], dy = pos[1] - e[1], dz = pos[2] - e[2];
+        float dn = sqrtf((dx * dx + dy * dy) + dz * dz); if (dn < 1e-12f) dn = 1e-12f;
+        d[0] = dx / dn; d[1] = dy / dn; d[2] = dz / dn;
+    } else {
+        const float* d_in = (const float*)p.dirs + 3 * vw;
+        const float two_sqrt3 = p.two_sqrt3;
+        ro[0] = pos[0] - two_sqrt3 * d_in[0]; ro[1] = pos[1] - two_sqrt3 * d_in[1]; ro[2] = pos[2] - two_sqrt3 * d_in[2];
+        float dn = sqrtf(dot3(d_in, d_in)); if (dn < 1e-12f) dn = 1e-12f;
+        d[0] = d_in[0] / dn; d[1] = d_in[1] / dn; d[2] = d_in[2] / dn;
+    }
     const float* n = (const float*)p.fnormal + 3 * (long)id;
     float ld = sqrtf(dot3(d, d)); if (ld < 1e-8f) ld = 1e-8f;
     const float nn[3] = {n[0], n[1], n[2]};
@@ -95,20 +107,27 @@ __global__ __launch_bounds__(256) void backproject_kernel(utx_backproject_desc p
     *rv = (hit == id && hit != -1 && cs < p.cos_thresh) ? 1 : 0;
 }
 
-extern "C" int utx_launch_backproject(const utx_backproject_desc* hp, const utx_bvh* bvh, hipStream_t stream) {
-    utx_backproject_desc p = *hp;
-    if (!bvh || p.T_h <= 0 || p.T_w <= 0 || p.view_count <= 0) return -2;
+template <bool PERSP>
+static void launch_backproject(const utx_backproject_desc& p, const float* eyes, const utx_bvh* bvh, int depth, hipStream_t stream) {
     const long T = (long)p.T_h * p.T_w;
     dim3 grid((unsigned)((T + 255) / 256), p.view_count);
-    const int depth = utx_bvh_depth_impl(const_cast<utx_bvh*>(bvh));      // first use after a build: waits for the build's depth word
-    if (depth < 0) return -7;
     if (depth <= UTX_BVH_PACKED_MAX_DEPTH && !g_utx_opt.bvh_stack_walk && g_utx_opt.bvh_packet) {
         dim3 gridp((unsigned)(((p.T_w + 15) / 16) * ((p.T_h + 15) / 16)), p.view_count);
-        hipLaunchKernelGGL(backproject_kernel<2>, gridp, dim3(256), 0, stream, p, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
+        hipLaunchKernelGGL((backproject_kernel<2, PERSP>), gridp, dim3(256), 0, stream, p, eyes, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
     } else if (depth <= UTX_BVH_PACKED_MAX_DEPTH && !g_utx_opt.bvh_stack_walk)
-        hipLaunchKernelGGL(backproject_kernel<1>, grid, dim3(256), 0, stream, p, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
+        hipLaunchKernelGGL((backproject_kernel<1, PERSP>), grid, dim3(256), 0, stream, p, eyes, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
     else
-        hipLaunchKernelGGL(backproject_kernel<0>, grid, dim3(256), 0, stream, p, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
+        hipLaunchKernelGGL((backproject_kernel<0, PERSP>), grid, dim3(256), 0, stream, p, eyes, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
+}
+
+// eyes == nullptr: orthographic rays along p.dirs; otherwise [n_views][3] camera centres (perspective), p.dirs / p.two_sqrt3 unused
+extern "C" int utx_launch_backproject(const utx_backproject_desc* hp, const float* eyes, const utx_bvh* bvh, hipStream_t stream) {
+    utx_backproject_desc p = *hp;
+    if (!bvh || p.T_h <= 0 || p.T_w <= 0 || p.view_count <= 0) return -2;
+    const int depth = utx_bvh_depth_impl(const_cast<utx_bvh*>(bvh));      // first use after a build: waits for the build's depth word
+    if (depth < 0) return -7;
+    if (eyes) launch_backproject<true>(p, eyes, bvh, depth, stream);
+    else launch_backproject<false>(p, nullptr, bvh, depth, stream);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

@@ -384,7 +384,13 @@ int utx_backproject(utx_ctx* ctx, const utx_backproject_desc* d, utx_bvh* bvh, u
     if (!d || !bvh || !d->rast2d || !d->verts || !d->faces || !d->fnormal || !d->vndc || !d->dirs || !d->images ||
         !d->color || !d->rayvis || !d->alphaok || d->view_begin < 0 || d->view_begin + d->view_count > d->n_views)
         return fail(ctx, -2, "utx_backproject");
-    UTX_CALL(ctx, "utx_backproject", utx_launch_backproject(d, bvh, (hipStream_t)stream));
+    UTX_CALL(ctx, "utx_backproject", utx_launch_backproject(d, nullptr, bvh, (hipStream_t)stream));
+}
+int utx_backproject_persp(utx_ctx* ctx, const utx_backproject_desc* d, const float* eyes, utx_bvh* bvh, utx_stream stream) {
+    if (!d || !eyes || !bvh || !d->rast2d || !d->verts || !d->faces || !d->fnormal || !d->vndc || !d->images ||
+        !d->color || !d->rayvis || !d->alphaok || d->view_begin < 0 || d->view_begin + d->view_count > d->n_views)
+        return fail(ctx, -2, "utx_backproject_persp");
+    UTX_CALL(ctx, "utx_backproject_persp", utx_launch_backproject(d, eyes, bvh, (hipStream_t)stream));
 }
 int utx_dilate_visibility(utx_ctx* ctx, const void* rayvis, const void* alphaok, const float* rast2d, int n_views, int H, int W,
                           void* tmp, void* vis_out, utx_stream stream) {
@@ -403,7 +409,12 @@ int utx_seam_mask(utx_ctx* ctx, const void* winner, const float* rast2d, int H, 
 int utx_view_visibility(utx_ctx* ctx, const float* attr6, const float* rast, const float* fnormal, const float* dirs, int n, int H, int W,
                         float grad_thr, float cos_thr, int radius, void* tmp, void* vis, float* alpha, utx_stream stream) {
     if (!attr6 || !rast || !fnormal || !dirs || !tmp || !vis) return fail(ctx, -2, "utx_view_visibility");
-    UTX_CALL(ctx, "utx_view_visibility", utx_launch_view_visibility(attr6, rast, fnormal, dirs, n, H, W, grad_thr, cos_thr, radius, tmp, vis, alpha, (hipStream_t)stream));
+    UTX_CALL(ctx, "utx_view_visibility", utx_launch_view_visibility(attr6, rast, fnormal, dirs, nullptr, n, H, W, grad_thr, cos_thr, radius, tmp, vis, alpha, (hipStream_t)stream));
+}
+int utx_view_visibility_persp(utx_ctx* ctx, const float* attr6, const float* rast, const float* fnormal, const float* eyes, int n, int H, int W,
+                              float grad_thr, float cos_thr, int radius, void* tmp, void* vis, float* alpha, utx_stream stream) {
+    if (!attr6 || !rast || !fnormal || !eyes || !tmp || !vis) return fail(ctx, -2, "utx_view_visibility_persp");
+    UTX_CALL(ctx, "utx_view_visibility_persp", utx_launch_view_visibility(attr6, rast, fnormal, nullptr, eyes, n, H, W, grad_thr, cos_thr, radius, tmp, vis, alpha, (hipStream_t)stream));
 }
 long utx_knn_workspace_bytes(long N) { return (long)utx_knn_workspace_bytes_impl(N); }
 int utx_knn(utx_ctx* ctx, const utx_knn_desc* d, void* work, long work_bytes, utx_stream stream) {

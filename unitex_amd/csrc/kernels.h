@@ -131,7 +131,7 @@ int utx_launch_rasterize(const float* pos, const int* tri, int F, int H, int W, 
 int utx_launch_interpolate(const float* attr, int C, const float* rast, const int* tri, long npix, float* out, hipStream_t stream);
 int utx_launch_condition_shade(const float* rast, const float* nrm, const float* pos, const float* bg3_host, long npix, void* out_normal, void* out_ccm, void* out_alpha, hipStream_t stream);
 int utx_launch_face_normals(const float* verts, const int* faces, int F, float* out, hipStream_t stream);
-int utx_launch_view_visibility(const float* attr6, const float* rast, const float* fnormal, const float* dirs, int n, int H, int W,
+int utx_launch_view_visibility(const float* attr6, const float* rast, const float* fnormal, const float* dirs, const float* eyes, int n, int H, int W,
                                float grad_thr, float cos_thr, int radius, void* tmp, void* vis, float* alpha, hipStream_t stream);
 size_t utx_knn_workspace_bytes_impl(long N);
 int utx_launch_knn(const KnnParams* p, void* work, size_t work_bytes, hipStream_t stream);
@@ -143,7 +143,7 @@ void utx_bvh_free_impl(utx_bvh* b);
 int utx_bvh_arrays_impl(utx_bvh* b, int** info, float** aabb, unsigned** codes_sorted, int** idx_sorted);
 int utx_bvh_trace_impl(utx_bvh* b, const float* ro, const float* rd, long R, int* tid, unsigned long long* visited, int force_stack, hipStream_t stream);
 int utx_bvh_depth_impl(utx_bvh* b);
-int utx_launch_backproject(const utx_backproject_desc* p, const utx_bvh* bvh, hipStream_t stream);
+int utx_launch_backproject(const utx_backproject_desc* p, const float* eyes, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_dilate_visibility(const void* rayvis, const void* alphaok, const void* rast2d, int n_views, int Hh, int Ww, void* tmp, void* vis_out, hipStream_t stream);
 int utx_launch_composite(const float* colors, const void* vis, const int* order, int n_order, long T, float* atlas, void* winner, hipStream_t stream);
 int utx_launch_seam_mask(const void* winner, const float* rast2d, int Hh, int Ww, void* tmp, void* seam, hipStream_t stream);

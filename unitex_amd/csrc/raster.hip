@@ -314,11 +314,13 @@ extern "C" int utx_launch_face_normals(const float* verts, const int* faces, int
 // ---- view-space visibility filter of mv_to_pcd with filt_gradient_points=True (renderer_inverse.py:189-209):
 //   grad  = sqrt(sum_c (d/dx attr_c)^2 + (d/dy attr_c)^2) over the 6 interpolated channels (position, vertex normal),
 //           torch.gradient differences: central (f[i+1] - f[i-1]) / 2 inside, one-sided at the image border;
-//   smooth = grad < grad_thr;   facing = cos(ray, face normal) < cos_thr   (orthographic: one ray direction per view)
+//   smooth = grad < grad_thr;   facing = cos(ray, face normal) < cos_thr   (orthographic: one ray direction per view; PERSP: the ray from the
+//           camera centre eyes[v] to the pixel's interpolated position, d = (attr[0:3] - eye) / max(|attr[0:3] - eye|, 1e-12), :187-190)
 //   visible = covered & facing & erode(smooth), where the reference's nn.MaxPool2d(31, 1, 15) runs on a [n, H, W, 1] tensor,
 //   i.e. it treats H as channels and pools along W only: the erosion is a 31-wide window along the image ROW (kept as is).
+template <bool PERSP>
 __global__ __launch_bounds__(256) void mv_grad_kernel(const float* attr, const float4* rast, const float* fnormal, const float* dirs,
-                                                      int n, int H, int W, float grad_thr, float cos_thr,
+                                                      const float* eyes, int n, int H, int W, float grad_thr, float cos_thr,
                                                       unsigned char* smooth, unsigned char* facing) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     const long npix = (long)n * H * W;
@@ -336,7 +338,14 @@ __global__ __launch_bounds__(256) void mv_grad_kernel(const float* attr, const f
     smooth[i] = (unsigned char)(sqrtf(acc) < grad_thr);
     const int id = (int)rast[i].w - 1;
     const float* fn = fnormal + 3 * (long)(id < 0 ? 0 : id);
-    const float* d = dirs + 3 * v;
+    float dp[3];
+    if constexpr (PERSP) {
+        const float* e = eyes + 3 * v;
+        const float dx = attr[6 * i] - e[0], dy = attr[6 * i + 1] - e[1], dz = attr[6 * i + 2] - e[2];
+        const float dl = fmaxf(sqrtf((dx * dx + dy * dy) + dz * dz), 1e-12f);
+        dp[0] = dx / dl; dp[1] = dy / dl; dp[2] = dz / dl;
+    }
+    const float* d = PERSP ? dp : dirs + 3 * v;
     const float nd = fmaxf(sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]), 1e-8f);
     const float nn = fmaxf(sqrtf((fn[0] * fn[0] + fn[1] * fn[1]) + fn[2] * fn[2]), 1e-8f);
     const float cs = ((d[0] * fn[0] + d[1] * fn[1]) + d[2] * fn[2]) / (nd * nn);
@@ -356,13 +365,17 @@ __global__ __launch_bounds__(256) void mv_visible_kernel(const unsigned char* sm
     vis[i] = (unsigned char)ok;
     if (alpha) alpha[i] = ok ? 1.0f : 0.0f;
 }
-extern "C" int utx_launch_view_visibility(const float* attr6, const float* rast, const float* fnormal, const float* dirs, int n, int H, int W,
+// eyes == nullptr: one ray direction per view (dirs); otherwise per-pixel rays from the camera centres eyes [n][3] (dirs unused)
+extern "C" int utx_launch_view_visibility(const float* attr6, const float* rast, const float* fnormal, const float* dirs, const float* eyes, int n, int H, int W,
                                           float grad_thr, float cos_thr, int radius, void* tmp, void* vis, float* alpha, hipStream_t stream) {
     const long npix = (long)n * H * W;
     if (npix <= 0 || radius < 0) return -1;
     unsigned char* smooth = (unsigned char*)tmp; unsigned char* facing = smooth + npix;
     const unsigned nb = (unsigned)((npix + 255) / 256);
-    hipLaunchKernelGGL(mv_grad_kernel, dim3(nb), dim3(256), 0, stream, attr6, (const float4*)rast, fnormal, dirs, n, H, W, grad_thr, cos_thr, smooth, facing);
+    if (eyes)
+        hipLaunchKernelGGL(mv_grad_kernel<true>, dim3(nb), dim3(256), 0, stream, attr6, (const float4*)rast, fnormal, dirs, eyes, n, H, W, grad_thr, cos_thr, smooth, facing);
+    else
+        hipLaunchKernelGGL(mv_grad_kernel<false>, dim3(nb), dim3(256), 0, stream, attr6, (const float4*)rast, fnormal, dirs, eyes, n, H, W, grad_thr, cos_thr, smooth, facing);
     hipLaunchKernelGGL(mv_visible_kernel, dim3(nb), dim3(256), 0, stream, smooth, facing, (const float4*)rast, n, H, W, radius, (unsigned char*)vis, alpha);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }

@@ -158,8 +158,10 @@ class BVH:
 
 
 def backproject(rast2d, verts, faces, fnormal, vndc, dirs, images, bvh, angle_deg=100.0, view_begin=0, view_count=None,
-                out=None):
-    """fused per-(view, texel) gather + visibility.  Returns color [n,Th,Tw,3], rayvis [n,Th,Tw] u8, alphaok u8."""
+                out=None, eyes=None):
+    """fused per-(view, texel) gather + visibility.  Returns color [n,Th,Tw,3], rayvis [n,Th,Tw] u8, alphaok u8.
+    eyes None: orthographic rays along dirs [n,3] (utx_backproject); eyes [n,3] = c2w[:, :3, 3]: perspective rays from the camera
+    centres (utx_backproject_persp; dirs is not read and may be None)."""
     ctx = get_ctx(rast2d.device.index)
     Th, Tw = rast2d.shape[:2]
     n, H, W = images.shape[:3]
@@ -172,13 +174,19 @@ def backproject(rast2d, verts, faces, fnormal, vndc, dirs, images, bvh, angle_de
         color, rayvis, alphaok = out
     d = BackprojectDesc()
     d.rast2d, d.verts, d.faces, d.fnormal = ptr(_f(rast2d)), ptr(_f(verts)), ptr(_i(faces)), ptr(_f(fnormal))
-    d.vndc, d.dirs, d.images = ptr(_f(vndc)), ptr(_f(dirs)), ptr(_f(images))
+    d.vndc, d.images = ptr(_f(vndc)), ptr(_f(images))
+    if eyes is None:
+        d.dirs = ptr(_f(dirs))
     d.color, d.rayvis, d.alphaok = ptr(color), ptr(rayvis), ptr(alphaok)
     d.T_h, d.T_w, d.V, d.n_views, d.H, d.W = Th, Tw, verts.shape[0], n, H, W
     d.view_begin, d.view_count = view_begin, (n - view_begin if view_count is None else view_count)
     d.cos_thresh = float(np.float32(math.cos(math.radians(angle_deg))))
     d.two_sqrt3 = float(np.float32(2.0 * math.sqrt(3.0)))
-    ctx.check(ctx.lib.utx_backproject(ctx.handle, C.byref(d), bvh.handle, ctx.stream()))
+    if eyes is None:
+        ctx.check(ctx.lib.utx_backproject(ctx.handle, C.byref(d), bvh.handle, ctx.stream()))
+    else:
+        assert eyes.shape == (n, 3)
+        ctx.check(ctx.lib.utx_backproject_persp(ctx.handle, C.byref(d), ptr(_f(eyes)), bvh.handle, ctx.stream()))
     return color, rayvis, alphaok
 
 
@@ -210,17 +218,23 @@ def seam_mask(winner, rast2d):
     return seam
 
 
-def view_visibility(attr6, rast, fnormal, dirs, grad_thr=0.20, angle_deg=115.0, radius=15):
+def view_visibility(attr6, rast, fnormal, dirs, grad_thr=0.20, angle_deg=115.0, radius=15, eyes=None):
     """mv_to_pcd's filt_gradient_points=True visibility (renderer_inverse.py:189-209): attr6 [n,H,W,6] interpolated
-    (position, vertex normal), rast [n,H,W,4], dirs [n,3] ray directions -> (vis u8 [n,H,W], alpha f32 [n,H,W])."""
+    (position, vertex normal), rast [n,H,W,4], dirs [n,3] ray directions -> (vis u8 [n,H,W], alpha f32 [n,H,W]).
+    eyes [n,3] = c2w[:, :3, 3] (dirs then unused, may be None): perspective, each pixel's ray runs from the camera centre to its position."""
     ctx = get_ctx(rast.device.index)
     n, H, W, _ = rast.shape
     tmp = torch.empty(2 * n * H * W, dtype=U8, device=rast.device)
     vis = torch.empty(n, H, W, dtype=U8, device=rast.device)
     alpha = torch.empty(n, H, W, dtype=F32, device=rast.device)
     cos_thr = float(np.float32(math.cos(math.radians(angle_deg))))
-    ctx.check(ctx.lib.utx_view_visibility(ctx.handle, ptr(_f(attr6)), ptr(_f(rast)), ptr(_f(fnormal)), ptr(_f(dirs)), n, H, W,
-                                          float(grad_thr), cos_thr, int(radius), ptr(tmp), ptr(vis), ptr(alpha), ctx.stream()))
+    if eyes is None:
+        ctx.check(ctx.lib.utx_view_visibility(ctx.handle, ptr(_f(attr6)), ptr(_f(rast)), ptr(_f(fnormal)), ptr(_f(dirs)), n, H, W,
+                                              float(grad_thr), cos_thr, int(radius), ptr(tmp), ptr(vis), ptr(alpha), ctx.stream()))
+    else:
+        assert eyes.shape == (n, 3)
+        ctx.check(ctx.lib.utx_view_visibility_persp(ctx.handle, ptr(_f(attr6)), ptr(_f(rast)), ptr(_f(fnormal)), ptr(_f(eyes)), n, H, W,
+                                                    float(grad_thr), cos_thr, int(radius), ptr(tmp), ptr(vis), ptr(alpha), ctx.stream()))
     return vis, alpha
 
 

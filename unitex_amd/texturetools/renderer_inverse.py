@@ -6,6 +6,8 @@ Kept call surface (as the reference orchestrator uses it, /root/reference/pipeli
     inv.update_from_file(mesh_path)
     textured_mesh, mask_2d_visiable, mask_2d, color_2d = inv.infer(mesh_path, c2ws=..., intrinsics=...,
         image_attrs=[6,H,W,3], perspective=False, H=, W=, H2D=, W2D=, method='reproject', ...)
+    perspective=True (the reference's default) casts each ray from the camera centre c2w[:3, 3] to the surface point
+    (renderer_inverse.py:187-190, 279-281); perspective=False, the pipeline's cameras, casts parallel rays along -c2w[:3, 2].
     inv.clear();  inv.register_query_field(fn)
 
 What runs where: every per-texel stage is a HIP kernel behind the C ABI (ops.py): clip transform,
@@ -155,9 +157,13 @@ class NVDiffRendererInverse:
             va = torch.cat([m.vertices, m.vertex_normals], dim=-1).contiguous()
             attrs = ops.interpolate(va, rast.view(n * H, W, 4), m.faces).view(n, H, W, 6)
         if filt_gradient_points:
-            assert not perspective
-            dirs = torch.nn.functional.normalize(-c2ws_cpu[:, :3, 2], dim=-1).contiguous().to(self.device)
-            vis, alpha = ops.view_visibility(attrs, rast, m.normals, dirs, grad_thr=grad_norm_threhold, angle_deg=ray_normal_angle_threhold)
+            if perspective:     # rays from the camera centre through each pixel's surface point (:187-189)
+                eyes = c2ws_cpu[:, :3, 3].contiguous().to(self.device)
+                vis, alpha = ops.view_visibility(attrs, rast, m.normals, None, grad_thr=grad_norm_threhold, angle_deg=ray_normal_angle_threhold,
+                                                 eyes=eyes)
+            else:
+                dirs = torch.nn.functional.normalize(-c2ws_cpu[:, :3, 2], dim=-1).contiguous().to(self.device)
+                vis, alpha = ops.view_visibility(attrs, rast, m.normals, dirs, grad_thr=grad_norm_threhold, angle_deg=ray_normal_angle_threhold)
         else:
             alpha = (rast[..., 3] > 0).float()
             vis = (rast[..., 3] > 0).to(torch.uint8)
@@ -228,7 +234,6 @@ class NVDiffRendererInverse:
         through the registered query field (the LTM hook) instead of the nearest-neighbour fill; filt_gradient_points adds
         the gradient / facing filter to the view masks.  Colours: 3 channels (rgb) or 9 (PBR stack) for 'kdtree', 3 for 'reproject'."""
         assert method in ("kdtree", "reproject")
-        assert not perspective, "the reference's texture path is orthographic (pipeline.py:208-210)"
         t_host0 = time.perf_counter()
         # keyword arguments of the reference's signature (renderer_inverse.py:635-659) that this build fixes at the values the pipeline uses: anything else is
         # refused, not dropped
@@ -253,7 +258,9 @@ class NVDiffRendererInverse:
         # the alpha channel the texels sample is mask_visiable (uv_to_pcd(alpha_attrs=alpha_visiable), :661-670)
         images = torch.cat([image_attrs[..., :3], mv["alpha"][..., None]], dim=-1).contiguous()
         _, c2ws_cpu = self._mvp(c2ws, intrinsics, perspective)
-        dirs = (-c2ws_cpu[:, :3, 2]).contiguous().to(dev)
+        # ray model per view (uv_to_pcd, :279-284): perspective -- from the camera centre to each texel's surface point; orthographic -- along -z of the camera
+        eyes = c2ws_cpu[:, :3, 3].contiguous().to(dev) if perspective else None
+        dirs = None if perspective else (-c2ws_cpu[:, :3, 2]).contiguous().to(dev)
         # UV-space raster: uv in [-1,1] used directly as clip xy, z = 0, w = 1 (renderer_inverse.py:268-274)
         uvclip = torch.cat([m.uvs_2d, torch.zeros_like(m.uvs_2d[:, :1]), torch.ones_like(m.uvs_2d[:, :1])], dim=-1).contiguous()
         with self._stage("uv_raster"):
@@ -271,7 +278,7 @@ class NVDiffRendererInverse:
         if v1 > v0:
             with self._stage("backproject"):
                 ops.backproject(rast2d, m.vertices, m.faces, m.normals, mv["ndc"].contiguous(), dirs, images, bvh,
-                                angle_deg=ray_normal_angle_threhold, view_begin=v0, view_count=v1 - v0, out=(color, rayvis, alphaok))
+                                angle_deg=ray_normal_angle_threhold, view_begin=v0, view_count=v1 - v0, out=(color, rayvis, alphaok), eyes=eyes)
         with self._stage("dilate_visibility"):
             vis = ops.dilate_visibility(rayvis, alphaok, rast2d)
         if world > 1:

@@ -3,7 +3,8 @@ grids) that feeds the DiT (reference: TextureTools/texturetools/video/export_nvd
 top of NVDiffRendererBase.simple_rendering, render/nvdiffrast/renderer_base.py:101-200).
 
 HIP path: clip transform -> rasterise per view -> interpolate vertex normals / positions -> fused shade +
-uint8 conversion kernel.  export_orbit_video (video/export_nvdiffrast_video.py:141-256): per frame clip transform ->
+uint8 conversion kernel; orthographic box views (the pipeline's) or, as the reference's defaults, a perspective
+camera (fov_deg) and / or the orbit ring (orbit=True).  export_orbit_video (video/export_nvdiffrast_video.py:141-256): per frame clip transform ->
 perspective raster -> fused UV interpolation + bilinear texture fetch + background composite (utx_texture_shade);
 frames are muxed on the host (Motion-JPEG in an MP4 container, or GIF -- there is no video encoder in this image)."""
 import io
@@ -47,6 +48,24 @@ def _vertex_normals(verts, faces, weighting="area"):
     return torch.nn.functional.normalize(n, dim=-1).float().contiguous()
 
 
+def condition_cameras(n_views, n_rows, n_cols, scale=0.85, fov_deg=49.1, perspective=False, orbit=True):
+    """(c2ws [n_views,4,4], intrinsics [3,3]) of export_condition (export_nvdiffrast_video.py:921-943): the orbit ring or the box views, a
+    perspective camera of fov_deg or an orthographic one of `scale`."""
+    if orbit:            # n_views + 1 cameras on the ring at radius 2.8, the last (= the first, 360 degrees on) dropped (export_nvdiffrast_video.py:921-922)
+        c2ws = camera.generate_orbit_views_c2ws(n_views + 1, radius=2.8, height=0.0, theta_0=0.0, degree=True)[:n_views]
+    elif n_views == 8:   # BASELINE configs[4]: the six axis views + two upper diagonals (camera.generate_views_c2ws; builder-defined)
+        c2ws, _ = camera.generate_views_c2ws(8, radius=2.8)
+    else:
+        c2ws = camera.generate_box_views_c2ws(radius=2.8)
+        sel = {1: [0], 2: [0, 2], 4: [0, 1, 2, 3], 6: [0, 1, 4, 2, 3, 5] if (n_rows, n_cols) == (2, 3) else list(range(6))}[n_views]
+        c2ws = c2ws[sel]
+    if perspective:      # export_nvdiffrast_video.py:938-943
+        intrinsics = camera.generate_intrinsics(fov_deg, fov_deg, fov=True, degree=True)
+    else:
+        intrinsics = camera.generate_intrinsics(scale, scale, fov=False, degree=False)
+    return c2ws, intrinsics
+
+
 class VideoExporter:
     def __init__(self, device="cuda", normal_weighting="angle", view_shard=(0, 1), process_group=None):
         self.device = torch.device(device if device != "cuda" else "cuda:%d" % torch.cuda.current_device())
@@ -58,7 +77,6 @@ class VideoExporter:
                          fov_deg=49.1, perspective=False, orbit=True, background=None, return_info=False,
                          return_image=True, return_mesh=False, return_camera=False):
         assert n_views == n_rows * n_cols, "Value Error: (n_views, n_rows, n_cols)=%s" % ((n_views, n_rows, n_cols),)
-        assert not orbit and not perspective, "the texture pipeline renders orthographic box views (pipeline.py:200-214)"
         if return_info or return_mesh or not return_image:
             # export_nvdiffrast_video.py:948-975: the set-up only / float arrays / the loaded mesh object -- forms the texture pipeline never asks for
             # (pipeline.py:200-216); the fused shade kernel produces the uint8 images directly
@@ -78,18 +96,12 @@ class VideoExporter:
         lo, hi = verts.min(0).values, verts.max(0).values
         s = (hi - lo).max() / (2.0 * geometry_scale)
         verts = ((verts - 0.5 * (lo + hi)) / s).contiguous()
-        if n_views == 8:     # BASELINE configs[4]: the six axis views + two upper diagonals (camera.generate_views_c2ws; builder-defined)
-            c2ws, _ = camera.generate_views_c2ws(8, radius=2.8)
-        else:
-            c2ws = camera.generate_box_views_c2ws(radius=2.8)
-            sel = {1: [0], 2: [0, 2], 4: [0, 1, 2, 3], 6: [0, 1, 4, 2, 3, 5] if (n_rows, n_cols) == (2, 3) else list(range(6))}[n_views]
-            c2ws = c2ws[sel]
-        intrinsics = camera.generate_intrinsics(scale, scale, fov=False, degree=False)
+        c2ws, intrinsics = condition_cameras(n_views, n_rows, n_cols, scale=scale, fov_deg=fov_deg, perspective=perspective, orbit=orbit)
         bg = camera.parse_color(background)
         dev = self.device
         vd, fd = verts.to(dev), faces.to(dev).contiguous()
         nrm = _vertex_normals(verts, faces, self.normal_weighting).to(dev)
-        mvp = torch.matmul(camera.intr_to_proj(intrinsics, perspective=False), camera.c2w_to_w2c(c2ws)).to(dev).contiguous()
+        mvp = torch.matmul(camera.intr_to_proj(intrinsics, perspective=perspective), camera.c2w_to_w2c(c2ws)).to(dev).contiguous()
         clip, _ = ops.transform_points(vd, mvp, want_ndc=False)
         from .distributed import gather_view_images, view_range
         rank, world = self.view_shard
