@@ -389,6 +389,11 @@ int utx_backproject(utx_ctx* ctx, const utx_backproject_desc* d, utx_bvh* bvh, u
  * centre eyes[v] and points at the texel's surface point, d = (pos - eye) / max(|pos - eye|, 1e-12).  eyes [n_views][3] f32 = c2w[:, :3, 3];
  * d->dirs and d->two_sqrt3 are not read.  Colour, alpha and the facing threshold as in utx_backproject. */
 int utx_backproject_persp(utx_ctx* ctx, const utx_backproject_desc* d, const float* eyes, utx_bvh* bvh, utx_stream stream);
+/* the same with a choice of view sampling (uv_to_pcd(grid_interpolate_mode=...), renderer_inverse.py:290-305).  eyes NULL: orthographic rays along d->dirs
+ * (as utx_backproject), else perspective rays from eyes [n_views][3] (as utx_backproject_persp).  sample_mode 0: grid_sample, bilinear, zero padding
+ * ('torch'; the same kernels as the two entry points above); 1: nvdiffrast dr.texture(ndc * 0.5 + 0.5, filter_mode='linear') with its default wrap
+ * boundary ('nvdiff'); a non-finite coordinate samples zero. */
+int utx_backproject_sampled(utx_ctx* ctx, const utx_backproject_desc* d, const float* eyes, int sample_mode, utx_bvh* bvh, utx_stream stream);
 
 /* visibility hole filling k=3,5 + AND coverage + AND alpha>0.999 (renderer_inverse.py:326-343).
  * rayvis/alphaok/vis_out/tmp: [n_views][H][W] u8. */
@@ -402,6 +407,11 @@ int utx_composite(utx_ctx* ctx, const float* colors, const void* vis, const int*
 
 /* seam mask (renderer_inverse.py:602-604): winner [H][W] int8 -> seam [H][W] u8; tmp [H][W] u8. */
 int utx_seam_mask(utx_ctx* ctx, const void* winner, const float* rast2d, int H, int W, void* tmp, void* seam, utx_stream stream);
+/* the same at other window sizes (bake_mv_to_uv_reproject_blur(kernel_size_boundary=k_boundary, kernel_size_boundary_blur=k_boundary_blur)):
+ * boundary radius k_boundary / 2, dilation radius k_boundary_blur / 2, coverage erosion radius k_boundary_blur / 2 + 2; both radii <= 15.
+ * tmp: 4 * H * W bytes. */
+int utx_seam_mask_sized(utx_ctx* ctx, const void* winner, const float* rast2d, int H, int W, int k_boundary, int k_boundary_blur, void* tmp, void* seam,
+                        utx_stream stream);
 
 /* exact 3-D nearest-seen-texel fill of unseen covered texels, in place on atlas (renderer_inverse.py:606-615).
  * pos [T][3] f32; nn_index [T] int32 (optional): chosen source texel or -1. */
@@ -435,6 +445,10 @@ int utx_knn(utx_ctx* ctx, const utx_knn_desc* d, void* work, long work_bytes, ut
 /* lens blur consumed on the seam only (image/lens_blur.py:260-280; renderer_inverse.py:620-624).
  * k49_host: HOST array, the collapsed real 7x7 kernel. src/dst [H][W][3] f32. */
 int utx_lens_blur_seam(utx_ctx* ctx, const float* src, const void* seam, int H, int W, const float* k49_host, float* dst, utx_stream stream);
+/* Gaussian blur consumed on the seam only (method='gaussian': torchvision gaussian_blur(img, (ksize, ksize)), sigma = 0.15 ksize + 0.35;
+ * renderer_inverse.py:618-619).  ksize odd, 1..31, ksize / 2 < min(H, W) (reflect padding).  w1_host: HOST array of the ksize fp32 1-D weights.
+ * src/dst [H][W][3] f32; the taps are summed in fp64. */
+int utx_gaussian_blur_seam(utx_ctx* ctx, const float* src, const void* seam, int H, int W, int ksize, const float* w1_host, float* dst, utx_stream stream);
 
 /* pull-push hole filling (texture/stitching/mip.py:51-95). kd/out [H][W][3] f32, mask [H][W] u8. */
 long utx_pull_push_workspace_bytes(int H, int W);

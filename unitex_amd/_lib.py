@@ -187,9 +187,11 @@ SYMBOLS = {
     "utx_bvh_depth": (c_int, [c_void_p]),
     "utx_backproject": (c_int, [c_void_p, C.POINTER(BackprojectDesc), c_void_p, c_void_p]),
     "utx_backproject_persp": (c_int, [c_void_p, C.POINTER(BackprojectDesc), c_void_p, c_void_p, c_void_p]),
+    "utx_backproject_sampled": (c_int, [c_void_p, C.POINTER(BackprojectDesc), c_void_p, c_int, c_void_p, c_void_p]),
     "utx_dilate_visibility": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "utx_composite": (c_int, [c_void_p, c_void_p, c_void_p, C.POINTER(c_int), c_int, c_long, c_void_p, c_void_p, c_void_p]),
     "utx_seam_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "utx_seam_mask_sized": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "utx_view_visibility": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int,
                                     c_void_p, c_void_p, c_void_p, c_void_p]),
     "utx_view_visibility_persp": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_float, c_int,
@@ -199,6 +201,7 @@ SYMBOLS = {
     "utx_nn_fill_workspace_bytes": (c_long, [c_long]),
     "utx_nn_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "utx_lens_blur_seam": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, C.POINTER(c_float), c_void_p, c_void_p]),
+    "utx_gaussian_blur_seam": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, C.POINTER(c_float), c_void_p, c_void_p]),
     "utx_pull_push_workspace_bytes": (c_long, [c_int, c_int]),
     "utx_pull_push": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "utx_chart_flood": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

@@ -18,13 +18,38 @@ __device__ __forceinline__ float4 tap4(const float4* img, int H, int W, int x, i
     return img[(long)y * W + x];
 }
 
+// nvdiffrast's 2-D linear lookup with the wrap boundary (indexTextureLinear + bilerp, restated): uv = ndc * 0.5 + 0.5 (two roundings, as
+// ndc_2d.mul(0.5).add(0.5)), u -= floor(u), u = u * W - 0.5, i0 = floor(u), i1 = i0 + 1, f = u - i0, indices wrapped into [0, W) (the same along v with H),
+// out = lerp(lerp(t00, t10, fu), lerp(t01, t11, fu), fv) with lerp(a, b, t) = a + t * (b - a).  For a finite u, u - floor(u) lies in [0, 1], so i0 lies in
+// [-1, W - 1] and i1 in [0, W]: after the wrap every tap is inside the view.
+__device__ __forceinline__ float lerp_nv(float a, float b, float t) { return a + t * (b - a); }
+__device__ __forceinline__ float4 tex_wrap_linear(const float4* img, int H, int W, float gx, float gy) {
+    if (!isfinite(gx) || !isfinite(gy)) return make_float4(0.f, 0.f, 0.f, 0.f);
+    float su = gx * 0.5f + 0.5f, sv = gy * 0.5f + 0.5f;
+    su = su - floorf(su); sv = sv - floorf(sv);
+    su = su * (float)W - 0.5f; sv = sv * (float)H - 0.5f;
+    const float fu0 = floorf(su), fv0 = floorf(sv);
+    int iu0 = (int)fu0, iv0 = (int)fv0, iu1 = iu0 + 1, iv1 = iv0 + 1;
+    const float fu = su - fu0, fv = sv - fv0;
+    if (iu0 < 0) iu0 += W;
+    if (iv0 < 0) iv0 += H;
+    if (iu1 >= W) iu1 -= W;
+    if (iv1 >= H) iv1 -= H;
+    const float4 t00 = img[(long)iv0 * W + iu0], t10 = img[(long)iv0 * W + iu1];
+    const float4 t01 = img[(long)iv1 * W + iu0], t11 = img[(long)iv1 * W + iu1];
+    return make_float4(lerp_nv(lerp_nv(t00.x, t10.x, fu), lerp_nv(t01.x, t11.x, fu), fv), lerp_nv(lerp_nv(t00.y, t10.y, fu), lerp_nv(t01.y, t11.y, fu), fv),
+                       lerp_nv(lerp_nv(t00.z, t10.z, fu), lerp_nv(t01.z, t11.z, fu), fv), lerp_nv(lerp_nv(t00.w, t10.w, fu), lerp_nv(t01.w, t11.w, fu), fv));
+}
+
 // MODE 1: stackless thread-per-ray walk over the packed tree (bvh_device.h); MODE 0: the reference's 64-entry stack walk, kept for trees deeper than
 // UTX_BVH_PACKED_MAX_DEPTH (where the reference's stack overflow quirk could matter) and for A/B tests; MODE 2 (round 4, the default): a wave owns an
 // 8 x 8 TEXEL TILE of one view and its 64 parallel rays walk the packed tree as ONE PACKET (bvh_trace_packet: nodes through the scalar cache, per-lane
 // box / triangle tests, bit-identical results); 256 threads = a 16 x 16 block of texels, tiles without a covered texel skip the walk.
 // PERSP (renderer_inverse.py:279-281, perspective=True): every ray of view v starts at the camera centre eyes[v] = c2w[v][:3, 3] and points at the texel's
 // surface point, d = (pos - eye) / max(|pos - eye|, 1e-12); the orthographic arm (one direction per view, origin 2 sqrt(3) behind the point) is unchanged.
-template <int MODE, bool PERSP>
+// SAMPLE (renderer_inverse.py:290-305, grid_interpolate_mode): 0 = grid_sample(bilinear, zero padding, align_corners=False); 1 = dr.texture(uv = ndc * 0.5 + 0.5,
+// filter_mode='linear') with nvdiffrast's default wrap boundary (its indexTextureLinear + bilerp restated below); a non-finite coordinate samples zero.
+template <int MODE, bool PERSP, int SAMPLE>
 __global__ __launch_bounds__(256) void backproject_kernel(utx_backproject_desc p, const float* eyes, const int* info, const float* aabb, const float4* nodes,
                                                           const float4* tris) {
     __shared__ int pstack[MODE == 2 ? 4 * 192 : 1];      // MODE 2: the packets' DFS stacks, 64 x {node, mask lo, mask hi} per wave
@@ -88,46 +113,59 @@ __global__ __launch_bounds__(256) void backproject_kernel(utx_backproject_desc p
     const float gx = (nd[2 * (long)f0] * u + nd[2 * (long)f1] * v) + nd[2 * (long)f2] * w;
     const float gy = (nd[2 * (long)f0 + 1] * u + nd[2 * (long)f1 + 1] * v) + nd[2 * (long)f2 + 1] * w;
     const int H = p.H, W = p.W;
-    const float ix = ((gx + 1.0f) * (float)W - 1.0f) * 0.5f;
-    const float iy = ((gy + 1.0f) * (float)H - 1.0f) * 0.5f;
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fx, y0 = (int)fy;
-    const float tx = ix - fx, ty = iy - fy;
-    const float w00 = (1.0f - tx) * (1.0f - ty), w01 = tx * (1.0f - ty), w10 = (1.0f - tx) * ty, w11 = tx * ty;
-    const float4* img = (const float4*)p.images + (long)vw * H * W;
-    const float4 a = tap4(img, H, W, x0, y0), b = tap4(img, H, W, x0 + 1, y0);
-    const float4 c = tap4(img, H, W, x0, y0 + 1), e = tap4(img, H, W, x0 + 1, y0 + 1);
-    oc[0] = ((a.x * w00 + b.x * w01) + c.x * w10) + e.x * w11;
-    oc[1] = ((a.y * w00 + b.y * w01) + c.y * w10) + e.y * w11;
-    oc[2] = ((a.z * w00 + b.z * w01) + c.z * w10) + e.z * w11;
-    const float sa = ((a.w * w00 + b.w * w01) + c.w * w10) + e.w * w11;
-    *ao = sa > 0.999f ? 1 : 0;
+    if constexpr (SAMPLE == 0) {
+        const float ix = ((gx + 1.0f) * (float)W - 1.0f) * 0.5f;
+        const float iy = ((gy + 1.0f) * (float)H - 1.0f) * 0.5f;
+        const float fx = floorf(ix), fy = floorf(iy);
+        const int x0 = (int)fx, y0 = (int)fy;
+        const float tx = ix - fx, ty = iy - fy;
+        const float w00 = (1.0f - tx) * (1.0f - ty), w01 = tx * (1.0f - ty), w10 = (1.0f - tx) * ty, w11 = tx * ty;
+        const float4* img = (const float4*)p.images + (long)vw * H * W;
+        const float4 a = tap4(img, H, W, x0, y0), b = tap4(img, H, W, x0 + 1, y0);
+        const float4 c = tap4(img, H, W, x0, y0 + 1), e = tap4(img, H, W, x0 + 1, y0 + 1);
+        oc[0] = ((a.x * w00 + b.x * w01) + c.x * w10) + e.x * w11;
+        oc[1] = ((a.y * w00 + b.y * w01) + c.y * w10) + e.y * w11;
+        oc[2] = ((a.z * w00 + b.z * w01) + c.z * w10) + e.z * w11;
+        const float sa = ((a.w * w00 + b.w * w01) + c.w * w10) + e.w * w11;
+        *ao = sa > 0.999f ? 1 : 0;
+    } else {
+        const float4 s = tex_wrap_linear((const float4*)p.images + (long)vw * H * W, H, W, gx, gy);
+        oc[0] = s.x; oc[1] = s.y; oc[2] = s.z;
+        *ao = s.w > 0.999f ? 1 : 0;
+    }
     const int hit = MODE == 2 ? bvh_trace_packet(nodes, tris, ro, d, true, pstack + (threadIdx.x >> 6) * 192, nullptr)
                   : MODE == 1 ? bvh_trace_packed(nodes, tris, ro, d, nullptr) : bvh_trace_one(info, aabb, vert, faces, ro, d);
     *rv = (hit == id && hit != -1 && cs < p.cos_thresh) ? 1 : 0;
 }
 
-template <bool PERSP>
+template <bool PERSP, int SAMPLE>
 static void launch_backproject(const utx_backproject_desc& p, const float* eyes, const utx_bvh* bvh, int depth, hipStream_t stream) {
     const long T = (long)p.T_h * p.T_w;
     dim3 grid((unsigned)((T + 255) / 256), p.view_count);
     if (depth <= UTX_BVH_PACKED_MAX_DEPTH && !g_utx_opt.bvh_stack_walk && g_utx_opt.bvh_packet) {
         dim3 gridp((unsigned)(((p.T_w + 15) / 16) * ((p.T_h + 15) / 16)), p.view_count);
-        hipLaunchKernelGGL((backproject_kernel<2, PERSP>), gridp, dim3(256), 0, stream, p, eyes, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
+        hipLaunchKernelGGL((backproject_kernel<2, PERSP, SAMPLE>), gridp, dim3(256), 0, stream, p, eyes, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
     } else if (depth <= UTX_BVH_PACKED_MAX_DEPTH && !g_utx_opt.bvh_stack_walk)
-        hipLaunchKernelGGL((backproject_kernel<1, PERSP>), grid, dim3(256), 0, stream, p, eyes, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
+        hipLaunchKernelGGL((backproject_kernel<1, PERSP, SAMPLE>), grid, dim3(256), 0, stream, p, eyes, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
     else
-        hipLaunchKernelGGL((backproject_kernel<0, PERSP>), grid, dim3(256), 0, stream, p, eyes, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
+        hipLaunchKernelGGL((backproject_kernel<0, PERSP, SAMPLE>), grid, dim3(256), 0, stream, p, eyes, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
 }
 
-// eyes == nullptr: orthographic rays along p.dirs; otherwise [n_views][3] camera centres (perspective), p.dirs / p.two_sqrt3 unused
-extern "C" int utx_launch_backproject(const utx_backproject_desc* hp, const float* eyes, const utx_bvh* bvh, hipStream_t stream) {
+// eyes == nullptr: orthographic rays along p.dirs; otherwise [n_views][3] camera centres (perspective), p.dirs / p.two_sqrt3 unused.
+// sample: 0 = grid_sample (zero padding), 1 = nvdiffrast linear filtering with wrap
+extern "C" int utx_launch_backproject(const utx_backproject_desc* hp, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream) {
     utx_backproject_desc p = *hp;
-    if (!bvh || p.T_h <= 0 || p.T_w <= 0 || p.view_count <= 0) return -2;
+    if (!bvh || p.T_h <= 0 || p.T_w <= 0 || p.view_count <= 0 || (sample != 0 && sample != 1)) return -2;
+    if (sample == 1 && (p.H <= 0 || p.W <= 0)) return -2;      // the wrap needs a non-empty view
     const int depth = utx_bvh_depth_impl(const_cast<utx_bvh*>(bvh));      // first use after a build: waits for the build's depth word
     if (depth < 0) return -7;
-    if (eyes) launch_backproject<true>(p, eyes, bvh, depth, stream);
-    else launch_backproject<false>(p, nullptr, bvh, depth, stream);
+    if (sample == 0) {
+        if (eyes) launch_backproject<true, 0>(p, eyes, bvh, depth, stream);
+        else launch_backproject<false, 0>(p, nullptr, bvh, depth, stream);
+    } else {
+        if (eyes) launch_backproject<true, 1>(p, eyes, bvh, depth, stream);
+        else launch_backproject<false, 1>(p, nullptr, bvh, depth, stream);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

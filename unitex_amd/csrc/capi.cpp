@@ -384,13 +384,20 @@ int utx_backproject(utx_ctx* ctx, const utx_backproject_desc* d, utx_bvh* bvh, u
     if (!d || !bvh || !d->rast2d || !d->verts || !d->faces || !d->fnormal || !d->vndc || !d->dirs || !d->images ||
         !d->color || !d->rayvis || !d->alphaok || d->view_begin < 0 || d->view_begin + d->view_count > d->n_views)
         return fail(ctx, -2, "utx_backproject");
-    UTX_CALL(ctx, "utx_backproject", utx_launch_backproject(d, nullptr, bvh, (hipStream_t)stream));
+    UTX_CALL(ctx, "utx_backproject", utx_launch_backproject(d, nullptr, 0, bvh, (hipStream_t)stream));
 }
 int utx_backproject_persp(utx_ctx* ctx, const utx_backproject_desc* d, const float* eyes, utx_bvh* bvh, utx_stream stream) {
     if (!d || !eyes || !bvh || !d->rast2d || !d->verts || !d->faces || !d->fnormal || !d->vndc || !d->images ||
         !d->color || !d->rayvis || !d->alphaok || d->view_begin < 0 || d->view_begin + d->view_count > d->n_views)
         return fail(ctx, -2, "utx_backproject_persp");
-    UTX_CALL(ctx, "utx_backproject_persp", utx_launch_backproject(d, eyes, bvh, (hipStream_t)stream));
+    UTX_CALL(ctx, "utx_backproject_persp", utx_launch_backproject(d, eyes, 0, bvh, (hipStream_t)stream));
+}
+int utx_backproject_sampled(utx_ctx* ctx, const utx_backproject_desc* d, const float* eyes, int sample_mode, utx_bvh* bvh, utx_stream stream) {
+    if (!d || !bvh || !d->rast2d || !d->verts || !d->faces || !d->fnormal || !d->vndc || (!eyes && !d->dirs) || !d->images ||
+        !d->color || !d->rayvis || !d->alphaok || d->view_begin < 0 || d->view_begin + d->view_count > d->n_views ||
+        (sample_mode != 0 && sample_mode != 1) || d->H <= 0 || d->W <= 0)
+        return fail(ctx, -2, "utx_backproject_sampled");
+    UTX_CALL(ctx, "utx_backproject_sampled", utx_launch_backproject(d, eyes, sample_mode, bvh, (hipStream_t)stream));
 }
 int utx_dilate_visibility(utx_ctx* ctx, const void* rayvis, const void* alphaok, const float* rast2d, int n_views, int H, int W,
                           void* tmp, void* vis_out, utx_stream stream) {
@@ -405,6 +412,12 @@ int utx_composite(utx_ctx* ctx, const float* colors, const void* vis, const int*
 int utx_seam_mask(utx_ctx* ctx, const void* winner, const float* rast2d, int H, int W, void* tmp, void* seam, utx_stream stream) {
     if (!winner || !rast2d || !tmp || !seam) return fail(ctx, -2, "utx_seam_mask");
     UTX_CALL(ctx, "utx_seam_mask", utx_launch_seam_mask(winner, rast2d, H, W, tmp, seam, (hipStream_t)stream));
+}
+int utx_seam_mask_sized(utx_ctx* ctx, const void* winner, const float* rast2d, int H, int W, int k_boundary, int k_boundary_blur, void* tmp, void* seam,
+                        utx_stream stream) {
+    if (!winner || !rast2d || !tmp || !seam || H <= 0 || W <= 0 || k_boundary < 0 || k_boundary_blur < 0 || k_boundary / 2 > 15 || k_boundary_blur / 2 > 15)
+        return fail(ctx, -2, "utx_seam_mask_sized");
+    UTX_CALL(ctx, "utx_seam_mask_sized", utx_launch_seam_mask_sized(winner, rast2d, H, W, k_boundary, k_boundary_blur, tmp, seam, (hipStream_t)stream));
 }
 int utx_view_visibility(utx_ctx* ctx, const float* attr6, const float* rast, const float* fnormal, const float* dirs, int n, int H, int W,
                         float grad_thr, float cos_thr, int radius, void* tmp, void* vis, float* alpha, utx_stream stream) {
@@ -430,6 +443,11 @@ int utx_nn_fill(utx_ctx* ctx, const float* pos, const void* winner, const float*
 int utx_lens_blur_seam(utx_ctx* ctx, const float* src, const void* seam, int H, int W, const float* k49_host, float* dst, utx_stream stream) {
     if (!src || !seam || !k49_host || !dst) return fail(ctx, -2, "utx_lens_blur_seam");
     UTX_CALL(ctx, "utx_lens_blur_seam", utx_launch_lens_blur_seam(src, seam, H, W, k49_host, dst, (hipStream_t)stream));
+}
+int utx_gaussian_blur_seam(utx_ctx* ctx, const float* src, const void* seam, int H, int W, int ksize, const float* w1_host, float* dst, utx_stream stream) {
+    if (!src || !seam || !w1_host || !dst || H <= 0 || W <= 0 || ksize < 1 || ksize > 31 || (ksize & 1) == 0 || ksize / 2 >= H || ksize / 2 >= W)
+        return fail(ctx, -2, "utx_gaussian_blur_seam");
+    UTX_CALL(ctx, "utx_gaussian_blur_seam", utx_launch_gaussian_blur_seam(src, seam, H, W, ksize, w1_host, dst, (hipStream_t)stream));
 }
 long utx_pull_push_workspace_bytes(int H, int W) { return (long)utx_pull_push_workspace_bytes_impl(H, W); }
 int utx_pull_push(utx_ctx* ctx, const float* kd, const void* mask, int H, int W, float* out, void* work, utx_stream stream) {

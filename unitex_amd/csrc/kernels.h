@@ -143,13 +143,15 @@ void utx_bvh_free_impl(utx_bvh* b);
 int utx_bvh_arrays_impl(utx_bvh* b, int** info, float** aabb, unsigned** codes_sorted, int** idx_sorted);
 int utx_bvh_trace_impl(utx_bvh* b, const float* ro, const float* rd, long R, int* tid, unsigned long long* visited, int force_stack, hipStream_t stream);
 int utx_bvh_depth_impl(utx_bvh* b);
-int utx_launch_backproject(const utx_backproject_desc* p, const float* eyes, const utx_bvh* bvh, hipStream_t stream);
+int utx_launch_backproject(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_dilate_visibility(const void* rayvis, const void* alphaok, const void* rast2d, int n_views, int Hh, int Ww, void* tmp, void* vis_out, hipStream_t stream);
 int utx_launch_composite(const float* colors, const void* vis, const int* order, int n_order, long T, float* atlas, void* winner, hipStream_t stream);
 int utx_launch_seam_mask(const void* winner, const float* rast2d, int Hh, int Ww, void* tmp, void* seam, hipStream_t stream);
+int utx_launch_seam_mask_sized(const void* winner, const float* rast2d, int Hh, int Ww, int k_boundary, int k_boundary_blur, void* tmp, void* seam, hipStream_t stream);
 size_t utx_nn_fill_workspace_bytes_impl(long T);
 int utx_launch_nn_fill(const float* pos, const void* winner, const float* rast2d, long T, float* atlas, int* nn_index, void* work, size_t work_bytes, hipStream_t stream);
 int utx_launch_lens_blur_seam(const float* src, const void* seam, int Hh, int Ww, const float* k49_host, float* dst, hipStream_t stream);
+int utx_launch_gaussian_blur_seam(const float* src, const void* seam, int Hh, int Ww, int ksize, const float* w1_host, float* dst, hipStream_t stream);
 size_t utx_pull_push_workspace_bytes_impl(int Hh, int Ww);
 int utx_launch_pull_push(const float* kd, const void* mask, int Hh, int Ww, float* out, void* work, hipStream_t stream);
 int utx_launch_chart_flood(const int* adj, const int* bucket, int F, int* chart, int* flag, hipStream_t stream);

@@ -1,5 +1,5 @@
 // Atlas post-processing of bake_mv_to_uv_reproject_blur (gfx950):
-//   seam mask, exact 3-D nearest-neighbour fill of unseen texels, lens blur on the seam, pull-push.
+//   seam mask, exact 3-D nearest-neighbour fill of unseen texels, lens or Gaussian blur on the seam, pull-push.
 // Reference: TextureTools/texturetools/render/nvdiffrast/renderer_inverse.py:603-627,
 // image/lens_blur.py:260-280, texture/stitching/mip.py:9-95, pcd/knn/__init__.py:103-113 (torch_kdtree [3p]).
 // All HBM-bound; -ffp-contract=off so the float sequences match oracle/geom_ref.py where it is bit-exact.
@@ -48,6 +48,71 @@ extern "C" int utx_launch_seam_mask(const void* winner, const float* rast2d, int
     const unsigned nb = (unsigned)((T + 255) / 256);
     hipLaunchKernelGGL(seam_bnd_kernel, dim3(nb), dim3(256), 0, stream, (const signed char*)winner, Hh, Ww, (unsigned char*)tmp);
     hipLaunchKernelGGL(seam_final_kernel, dim3(nb), dim3(256), 0, stream, (const unsigned char*)tmp, (const float4*)rast2d, Hh, Ww, (unsigned char*)seam);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// seam mask at any window sizes (bake_mv_to_uv_reproject_blur's kernel_size_boundary / kernel_size_boundary_blur, :598-604): boundary radius rb = kb // 2,
+// dilation radius rd = kbb // 2, coverage erosion radius re = rd + 2.  The identity above holds at every radius: bnd(p) <=> some in-image texel of the
+// (2 rb + 1)^2 window has another winner <=> the window's min or max winner differs from winner[p]; seam = dilate_rd(bnd) AND erode_re(coverage).
+// min, max, dilation and erosion are separable, so four passes of 2 r + 1 taps (rows, columns, rows, columns) replace the square windows; out-of-image
+// texels are skipped, as max_pool2d's -inf padding does.  tmp: 4 [H][W] byte planes.
+__global__ __launch_bounds__(256) void seam_rows1_kernel(const signed char* winner, const float4* rast2d, int Hh, int Ww, int rb, int re,
+                                                         signed char* rmin, signed char* rmax, unsigned char* rcov) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)Hh * Ww) return;
+    const int x = (int)(t % Ww);
+    const long row = t - x;
+    int lo = 127, hi = -128;
+    for (int xx = max(x - rb, 0); xx <= min(x + rb, Ww - 1); ++xx) { const int w = winner[row + xx]; lo = min(lo, w); hi = max(hi, w); }
+    int all = 1;
+    for (int xx = max(x - re, 0); xx <= min(x + re, Ww - 1); ++xx) all &= (rast2d[row + xx].w > 0.f);
+    rmin[t] = (signed char)lo; rmax[t] = (signed char)hi; rcov[t] = (unsigned char)all;
+}
+__global__ __launch_bounds__(256) void seam_cols1_kernel(const signed char* winner, const signed char* rmin, const signed char* rmax, const unsigned char* rcov,
+                                                         int Hh, int Ww, int rb, int re, unsigned char* bnd, unsigned char* ero) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)Hh * Ww) return;
+    const int y = (int)(t / Ww), x = (int)(t % Ww);
+    int lo = 127, hi = -128;
+    for (int yy = max(y - rb, 0); yy <= min(y + rb, Hh - 1); ++yy) { const long q = (long)yy * Ww + x; lo = min(lo, (int)rmin[q]); hi = max(hi, (int)rmax[q]); }
+    int all = 1;
+    for (int yy = max(y - re, 0); yy <= min(y + re, Hh - 1); ++yy) all &= rcov[(long)yy * Ww + x];
+    const int w0 = winner[t];
+    bnd[t] = (unsigned char)(lo != w0 || hi != w0);
+    ero[t] = (unsigned char)all;
+}
+__global__ __launch_bounds__(256) void seam_rows2_kernel(const unsigned char* bnd, int Hh, int Ww, int rd, unsigned char* rdil) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)Hh * Ww) return;
+    const int x = (int)(t % Ww);
+    const long row = t - x;
+    int any = 0;
+    for (int xx = max(x - rd, 0); xx <= min(x + rd, Ww - 1); ++xx) any |= bnd[row + xx];
+    rdil[t] = (unsigned char)any;
+}
+__global__ __launch_bounds__(256) void seam_cols2_kernel(const unsigned char* rdil, int Hh, int Ww, int rd, unsigned char* seam) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)Hh * Ww) return;
+    const int y = (int)(t / Ww), x = (int)(t % Ww);
+    int any = 0;
+    for (int yy = max(y - rd, 0); yy <= min(y + rd, Hh - 1); ++yy) any |= rdil[(long)yy * Ww + x];
+    seam[t] = (unsigned char)(any && seam[t]);      // seam holds the eroded coverage of pass 2
+}
+extern "C" int utx_launch_seam_mask_sized(const void* winner, const float* rast2d, int Hh, int Ww, int k_boundary, int k_boundary_blur, void* tmp, void* seam,
+                                          hipStream_t stream) {
+    const long T = (long)Hh * Ww;
+    if (Hh <= 0 || Ww <= 0 || k_boundary < 0 || k_boundary_blur < 0) return -2;
+    const int rb = k_boundary / 2, rd = k_boundary_blur / 2, re = rd + 2;
+    if (rb > 15 || rd > 15) return -2;
+    const unsigned nb = (unsigned)((T + 255) / 256);
+    unsigned char* p0 = (unsigned char*)tmp;
+    unsigned char *p1 = p0 + T, *p2 = p1 + T, *p3 = p2 + T;
+    hipLaunchKernelGGL(seam_rows1_kernel, dim3(nb), dim3(256), 0, stream, (const signed char*)winner, (const float4*)rast2d, Hh, Ww, rb, re,
+                       (signed char*)p0, (signed char*)p1, p2);
+    hipLaunchKernelGGL(seam_cols1_kernel, dim3(nb), dim3(256), 0, stream, (const signed char*)winner, (const signed char*)p0, (const signed char*)p1,
+                       (const unsigned char*)p2, Hh, Ww, rb, re, p3, (unsigned char*)seam);
+    hipLaunchKernelGGL(seam_rows2_kernel, dim3(nb), dim3(256), 0, stream, (const unsigned char*)p3, Hh, Ww, rd, p0);
+    hipLaunchKernelGGL(seam_cols2_kernel, dim3(nb), dim3(256), 0, stream, (const unsigned char*)p0, Hh, Ww, rd, (unsigned char*)seam);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
@@ -225,6 +290,53 @@ extern "C" int utx_launch_lens_blur_seam(const float* src, const void* seam, int
     if (T <= 0 || !k49_host) return -2;
     BlurK K; for (int i = 0; i < 49; ++i) K.k[i] = k49_host[i];
     hipLaunchKernelGGL(lens_blur_seam_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, stream, src, (const unsigned char*)seam, Hh, Ww, K, dst);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// ---------------------------------------------------------------------------------------------
+// Gaussian blur on the seam (method='gaussian': torchvision gaussian_blur(img, (k, k)), sigma = 0.15 k + 0.35), evaluated only where the seam
+// mask is set; src elsewhere.  w1: the host's fp32 1-D weights (torch CPU, as torchvision builds them); the 2-D weight is the one fp32 product
+// w1[i] * w1[j] (torchvision's torch.mm of two vectors, inner length 1).  Reflect padding of k // 2 (numpy's 'reflect': the edge texel is not
+// repeated; needs k // 2 < min(H, W)).  The taps are summed in fp64 and rounded once: the result is within a few fp32 ulps of the exact
+// sum of the fp32-weighted taps at every k up to 31 (torch's own fp32 conv order is unspecified).
+// ---------------------------------------------------------------------------------------------
+struct GaussK { float w[31]; };
+__device__ __forceinline__ int reflect_idx(int i, int n) {
+    if (i < 0) i = -i;
+    if (i >= n) i = 2 * (n - 1) - i;
+    return i;
+}
+__global__ __launch_bounds__(256) void gaussian_blur_seam_kernel(const float* src, const unsigned char* seam, int Hh, int Ww, int r, GaussK K, float* dst) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long)Hh * Ww) return;
+    float o0 = src[3 * t], o1 = src[3 * t + 1], o2 = src[3 * t + 2];
+    if (seam[t]) {
+        const int y = (int)(t / Ww), x = (int)(t % Ww);
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+        for (int dy = -r; dy <= r; ++dy) {
+            const int yy = reflect_idx(y + dy, Hh);
+            const float wy = K.w[dy + r];
+            for (int dx = -r; dx <= r; ++dx) {
+                const int xx = reflect_idx(x + dx, Ww);
+                const double kk = (double)(wy * K.w[dx + r]);
+                const float* c = src + 3 * ((long)yy * Ww + xx);
+                a0 = a0 + kk * (double)c[0];
+                a1 = a1 + kk * (double)c[1];
+                a2 = a2 + kk * (double)c[2];
+            }
+        }
+        o0 = (float)a0; o1 = (float)a1; o2 = (float)a2;
+    }
+    dst[3 * t] = o0; dst[3 * t + 1] = o1; dst[3 * t + 2] = o2;
+}
+extern "C" int utx_launch_gaussian_blur_seam(const float* src, const void* seam, int Hh, int Ww, int ksize, const float* w1_host, float* dst, hipStream_t stream) {
+    const long T = (long)Hh * Ww;
+    if (T <= 0 || Hh <= 0 || Ww <= 0 || !w1_host || ksize < 1 || ksize > 31 || (ksize & 1) == 0) return -2;
+    const int r = ksize / 2;
+    if (r >= Hh || r >= Ww) return -2;
+    GaussK K;
+    for (int i = 0; i < 31; ++i) K.w[i] = i < ksize ? w1_host[i] : 0.f;
+    hipLaunchKernelGGL(gaussian_blur_seam_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, stream, src, (const unsigned char*)seam, Hh, Ww, r, K, dst);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

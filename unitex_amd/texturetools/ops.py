@@ -158,10 +158,13 @@ class BVH:
 
 
 def backproject(rast2d, verts, faces, fnormal, vndc, dirs, images, bvh, angle_deg=100.0, view_begin=0, view_count=None,
-                out=None, eyes=None):
+                out=None, eyes=None, sample="grid"):
     """fused per-(view, texel) gather + visibility.  Returns color [n,Th,Tw,3], rayvis [n,Th,Tw] u8, alphaok u8.
     eyes None: orthographic rays along dirs [n,3] (utx_backproject); eyes [n,3] = c2w[:, :3, 3]: perspective rays from the camera
-    centres (utx_backproject_persp; dirs is not read and may be None)."""
+    centres (utx_backproject_persp; dirs is not read and may be None).
+    sample: 'grid' -- grid_sample, bilinear, zero padding (grid_interpolate_mode='torch'); 'nvdiff' -- nvdiffrast's linear filtering with
+    the wrap boundary (grid_interpolate_mode='nvdiff', utx_backproject_sampled(sample_mode=1))."""
+    assert sample in ("grid", "nvdiff"), "sample must be 'grid' or 'nvdiff', not %r" % (sample,)
     ctx = get_ctx(rast2d.device.index)
     Th, Tw = rast2d.shape[:2]
     n, H, W = images.shape[:3]
@@ -182,10 +185,13 @@ def backproject(rast2d, verts, faces, fnormal, vndc, dirs, images, bvh, angle_de
     d.view_begin, d.view_count = view_begin, (n - view_begin if view_count is None else view_count)
     d.cos_thresh = float(np.float32(math.cos(math.radians(angle_deg))))
     d.two_sqrt3 = float(np.float32(2.0 * math.sqrt(3.0)))
-    if eyes is None:
+    if eyes is not None:
+        assert eyes.shape == (n, 3)
+    if sample == "nvdiff":
+        ctx.check(ctx.lib.utx_backproject_sampled(ctx.handle, C.byref(d), None if eyes is None else ptr(_f(eyes)), 1, bvh.handle, ctx.stream()))
+    elif eyes is None:
         ctx.check(ctx.lib.utx_backproject(ctx.handle, C.byref(d), bvh.handle, ctx.stream()))
     else:
-        assert eyes.shape == (n, 3)
         ctx.check(ctx.lib.utx_backproject_persp(ctx.handle, C.byref(d), ptr(_f(eyes)), bvh.handle, ctx.stream()))
     return color, rayvis, alphaok
 
@@ -209,12 +215,24 @@ def composite(colors, vis, order):
     return atlas, winner
 
 
-def seam_mask(winner, rast2d):
+SEAM_RADIUS_MAX = 15      # k_boundary // 2 and k_boundary_blur // 2 (utx_seam_mask_sized)
+GAUSS_KSIZE_MAX = 31      # utx_gaussian_blur_seam
+
+
+def seam_mask(winner, rast2d, k_boundary=3, k_boundary_blur=3):
+    """winner [H,W] int8 (composite), rast2d [H,W,4] -> seam [H,W] u8 (bake_mv_to_uv_reproject_blur's boundary mask, :596-604):
+    the winner boundary within radius k_boundary // 2, dilated by k_boundary_blur // 2, inside the coverage eroded by k_boundary_blur // 2 + 2.
+    The defaults (3, 3) run utx_seam_mask; other sizes utx_seam_mask_sized (both radii <= 15)."""
     ctx = get_ctx(winner.device.index)
     H, W = winner.shape
-    tmp = torch.empty(H, W, dtype=U8, device=winner.device)
     seam = torch.empty(H, W, dtype=U8, device=winner.device)
-    ctx.check(ctx.lib.utx_seam_mask(ctx.handle, ptr(winner), ptr(_f(rast2d)), H, W, ptr(tmp), ptr(seam), ctx.stream()))
+    if k_boundary == 3 and k_boundary_blur == 3:
+        tmp = torch.empty(H, W, dtype=U8, device=winner.device)
+        ctx.check(ctx.lib.utx_seam_mask(ctx.handle, ptr(winner), ptr(_f(rast2d)), H, W, ptr(tmp), ptr(seam), ctx.stream()))
+    else:
+        tmp = torch.empty(4, H, W, dtype=U8, device=winner.device)
+        ctx.check(ctx.lib.utx_seam_mask_sized(ctx.handle, ptr(winner), ptr(_f(rast2d)), H, W, int(k_boundary), int(k_boundary_blur), ptr(tmp),
+                                              ptr(seam), ctx.stream()))
     return seam
 
 
@@ -328,6 +346,28 @@ def lens_blur_seam(src, seam, k49=None):
     arr = (C.c_float * 49)(*[float(x) for x in np.asarray(k49, dtype=np.float32).reshape(-1)])
     dst = torch.empty_like(src)
     ctx.check(ctx.lib.utx_lens_blur_seam(ctx.handle, ptr(_f(src)), ptr(seam), H, W, arr, ptr(dst), ctx.stream()))
+    return dst
+
+
+def gaussian_kernel1d(ksize):
+    """the 1-D weights of torchvision's gaussian_blur(img, (k, k)) with sigma=None, built the way it builds them (torch, float32, CPU):
+    sigma = 0.15 k + 0.35, x = linspace(-(k-1)/2, (k-1)/2, k), pdf = exp(-0.5 (x / sigma)^2), w = pdf / pdf.sum()."""
+    sigma = ksize * 0.15 + 0.35
+    half = (ksize - 1) * 0.5
+    x = torch.linspace(-half, half, steps=ksize, dtype=torch.float32)
+    pdf = torch.exp(-0.5 * (x / sigma).pow(2))
+    return pdf / pdf.sum()
+
+
+def gaussian_blur_seam(src, seam, ksize=5):
+    """src [H,W,3] f32, seam [H,W] u8 -> dst: torchvision's gaussian_blur(src, (ksize, ksize)) (reflect padding) where seam is set, src
+    elsewhere (bake_mv_to_uv_reproject_blur(method='gaussian'), :618-625).  ksize odd, 1..31, ksize // 2 < min(H, W)."""
+    ctx = get_ctx(src.device.index)
+    H, W = seam.shape
+    w1 = gaussian_kernel1d(int(ksize))
+    arr = (C.c_float * int(ksize))(*[float(x) for x in w1.numpy()])
+    dst = torch.empty_like(src)
+    ctx.check(ctx.lib.utx_gaussian_blur_seam(ctx.handle, ptr(_f(src)), ptr(seam), H, W, int(ksize), arr, ptr(dst), ctx.stream()))
     return dst
 
 

@@ -32,6 +32,24 @@ from . import camera, meshes, ops
 PRIORITY = [0, 3, 4, 1, 2, 5]  # frtbld -> f, b, l, r, t, d  (reference renderer_inverse.py:44)
 
 
+def _check_seam_sizes(k_boundary, k_boundary_blur):
+    """the seam windows of bake_mv_to_uv_reproject_blur: 2 (k // 2) + 1 wide, so any k >= 0; radii above ops.SEAM_RADIUS_MAX are not built"""
+    for name, k in (("reproject_kernel_size_boundary", k_boundary), ("reproject_kernel_size_boundary_blur", k_boundary_blur)):
+        if int(k) != k or k < 0:
+            raise ValueError("%s should be a non-negative integer. Got %r" % (name, k))
+        if k // 2 > ops.SEAM_RADIUS_MAX:
+            raise NotImplementedError("%s=%r: the seam mask is built up to a radius of %d (%s <= %d)" % (name, k, ops.SEAM_RADIUS_MAX, name,
+                                                                                                          2 * ops.SEAM_RADIUS_MAX + 1))
+
+
+def _check_gaussian_ksize(k):
+    """torchvision's gaussian_blur checks (ValueError for an even or negative size), then this build's cap"""
+    if int(k) != k or k % 2 == 0 or k < 0:
+        raise ValueError("kernel_size should have odd and positive integers. Got %r" % ([k, k],))
+    if k > ops.GAUSS_KSIZE_MAX:
+        raise NotImplementedError("reproject_kernel_size_blur=%r: the Gaussian seam blur is built up to a kernel size of %d" % (k, ops.GAUSS_KSIZE_MAX))
+
+
 class DeviceMesh:
     """PBRMesh of the reference (mesh/structure_v2.py:25-77) reduced to what the inverse renderer reads:
     vertices, faces, per-face normals, UVs mapped to [-1, 1], and the lazily built LBVH ('optix')."""
@@ -227,25 +245,33 @@ class NVDiffRendererInverse:
     def infer(self, blank_mesh, c2ws, intrinsics, image_attrs, H=512, W=512, H2D=2048, W2D=2048, perspective=True,
               grad_norm_threhold=0.20, ray_normal_angle_threhold=115.0, grid_interpolate_mode="torch", method="reproject",
               kdtree_n_neighbors=32, kdtree_n_neighbors_visiable=1, kdtree_n_neighbors_invisiable=32, kdtree_method="order_mean",
-              kdtree_inpainting=False, reproject_method="lens", reproject_inpainting=False, filt_gradient_points=True,
-              return_layers=False, **unused):
+              kdtree_inpainting=False, reproject_method="lens", reproject_kernel_size_boundary=3, reproject_kernel_size_boundary_blur=3,
+              reproject_kernel_size_blur=5, reproject_inpainting=False, filt_gradient_points=True, return_layers=False, **unused):
         """renderer_inverse.py:635-726.  method='reproject' is bake_mv_to_uv_reproject_blur (the pipeline's path),
         method='kdtree' bake_mv_to_uv_kdtree ('order_mean' | 'mean' | 'mvpaint'); *_inpainting=True routes the unseen texels
         through the registered query field (the LTM hook) instead of the nearest-neighbour fill; filt_gradient_points adds
-        the gradient / facing filter to the view masks.  Colours: 3 channels (rgb) or 9 (PBR stack) for 'kdtree', 3 for 'reproject'."""
+        the gradient / facing filter to the view masks.  Colours: 3 channels (rgb) or 9 (PBR stack) for 'kdtree', 3 for 'reproject'.
+        grid_interpolate_mode 'torch' | 'pytorch' samples the views as grid_sample (zero padding), 'nvdiff' | 'nvdiffrast' as nvdiffrast's
+        linear dr.texture (wrap boundary).  reproject_method 'lens' | 'gaussian' picks the seam blur; the seam is the winner boundary within
+        reproject_kernel_size_boundary // 2, dilated by reproject_kernel_size_boundary_blur // 2 (both radii <= 15), and 'gaussian' blurs it with
+        torchvision's gaussian_blur at reproject_kernel_size_blur (odd, <= 31; 'lens' ignores the size, as the reference does)."""
         assert method in ("kdtree", "reproject")
         t_host0 = time.perf_counter()
-        # keyword arguments of the reference's signature (renderer_inverse.py:635-659) that this build fixes at the values the pipeline uses: anything else is
+        # keyword arguments of the reference's signature (renderer_inverse.py:635-659) that this build fixes at the value the pipeline uses: anything else is
         # refused, not dropped
-        fixed = dict(reproject_kernel_size_boundary=3, reproject_kernel_size_boundary_blur=3, reproject_kernel_size_blur=5, return_mv_reproject_uv=False)
+        fixed = dict(return_mv_reproject_uv=False)
         for k_, v_ in unused.items():
             if k_ not in fixed:
                 raise TypeError("infer() got an unexpected keyword argument %r" % k_)
             if v_ != fixed[k_]:
                 raise NotImplementedError("infer(%s=%r): only %r (the pipeline's value) is built" % (k_, v_, fixed[k_]))
-        if grid_interpolate_mode not in ("torch", "pytorch"):
-            raise NotImplementedError("grid_interpolate_mode %r: the bilinear grid_sample form ('torch') is the one the pipeline uses and the one built" % (grid_interpolate_mode,))
-        assert reproject_method == "lens"
+        assert grid_interpolate_mode in ("torch", "pytorch", "nvdiff", "nvdiffrast")      # uv_to_pcd, :260
+        sample = "nvdiff" if grid_interpolate_mode in ("nvdiff", "nvdiffrast") else "grid"
+        assert reproject_method in ("gaussian", "lens")                                    # bake_mv_to_uv_reproject_blur, :587
+        if method == "reproject":
+            _check_seam_sizes(reproject_kernel_size_boundary, reproject_kernel_size_boundary_blur)
+            if reproject_method == "gaussian":
+                _check_gaussian_ksize(reproject_kernel_size_blur)
         assert len(self.index) == image_attrs.shape[0] == torch.as_tensor(c2ws).shape[0]
         m = self.pbr_mesh
         n = image_attrs.shape[0]
@@ -278,7 +304,8 @@ class NVDiffRendererInverse:
         if v1 > v0:
             with self._stage("backproject"):
                 ops.backproject(rast2d, m.vertices, m.faces, m.normals, mv["ndc"].contiguous(), dirs, images, bvh,
-                                angle_deg=ray_normal_angle_threhold, view_begin=v0, view_count=v1 - v0, out=(color, rayvis, alphaok), eyes=eyes)
+                                angle_deg=ray_normal_angle_threhold, view_begin=v0, view_count=v1 - v0, out=(color, rayvis, alphaok), eyes=eyes,
+                                sample=sample)
         with self._stage("dilate_visibility"):
             vis = ops.dilate_visibility(rayvis, alphaok, rast2d)
         if world > 1:
@@ -291,15 +318,19 @@ class NVDiffRendererInverse:
             with self._stage("composite"):
                 atlas, winner = ops.composite(color, vis, self.index)
             with self._stage("seam_mask"):
-                seam = ops.seam_mask(winner, rast2d)
+                seam = ops.seam_mask(winner, rast2d, reproject_kernel_size_boundary, reproject_kernel_size_boundary_blur)
             with self._stage("nn_fill"):
                 pos = ops.interpolate(m.vertices, rast2d, m.faces)
                 if reproject_inpainting:
                     self._fill_unseen(atlas, (winner >= 0).to(torch.uint8), rast2d[..., 3] > 0, pos, True)
                 else:
                     ops.nn_fill(atlas, winner, rast2d, pos)
-            with self._stage("lens_blur_seam"):
-                baked = ops.lens_blur_seam(atlas, seam)
+            if reproject_method == "gaussian":
+                with self._stage("gaussian_blur_seam"):
+                    baked = ops.gaussian_blur_seam(atlas, seam, reproject_kernel_size_blur)
+            else:
+                with self._stage("lens_blur_seam"):
+                    baked = ops.lens_blur_seam(atlas, seam)
         else:
             with self._stage("kdtree_bake"):
                 pos2d = ops.interpolate(m.vertices, rast2d, m.faces)
