@@ -5,17 +5,20 @@
 //
 // Replaces (diffusers [3p], called at /root/reference/flux_piplines/texturing/pipeline.py:226-238 and :683-692):
 // torch.nn.GroupNorm(32, C, eps=1e-6) + SiLU, F.scaled_dot_product_attention of the VAE mid block, Conv2d(3|16, C, 3).
-// All three are HBM-bound streaming kernels: 16-byte vector I/O, fp32 statistics, deterministic reduction order.
+// All three are HBM-bound streaming kernels: 16-byte vector I/O, fp64-accumulated shifted statistics, deterministic reduction order.
 #include "common.h"
 #include "kernels.h"
 
 #define GN_GROUPS 32
 #define GN_MAXBLK 1024
 
-// ---- GroupNorm pass 1: per-block partial (sum, sumsq) for each of the 32 groups.
-// thread -> (pixel, channel octet); an octet's first / last 4 channels may belong to different groups (C = 128).
-__global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict__ x, long npix, int C, float* __restrict__ partial) {
-    __shared__ float part[256][4];
+// ---- GroupNorm pass 1: per-block partial shifted sums (S = sum(x - P), Q = sum((x - P)^2)) for each of the 32 groups.
+// thread -> (pixel, channel octet); an octet's first / last 4 channels may belong to different groups (C = 128).  When C / 8 does not
+// divide 256 the last 256 % (C / 8) threads would start on a pixel another thread also reads: they add nothing (zeros into part[]).
+// P is the group's pilot, the bf16 element of pixel 0 at the group's first channel (the same value in every block): summing x - P
+// instead of x keeps E[x^2] - m^2 from cancelling when |mean| >> sigma.  A thread sums one octet half in fp32 and accumulates in fp64.
+__global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict__ x, long npix, int C, double* __restrict__ partial) {
+    __shared__ double part[256][4];
     const int oct_per_pix = C >> 3;
     const int cpg = C / GN_GROUPS;
     const int pix_per_it = 256 / oct_per_pix;
@@ -23,26 +26,25 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict_
     const long slab = (npix + gridDim.x - 1) / gridDim.x;
     const long p0 = (long)blockIdx.x * slab;
     const long p1 = (p0 + slab < npix) ? p0 + slab : npix;
-    float s0 = 0.f, q0 = 0.f, s1 = 0.f, q1 = 0.f;
-    for (long p = p0 + po; p < p1; p += pix_per_it) {
+    const float P0 = bf2f(x[((o * 8) / cpg) * cpg]), P1 = bf2f(x[((o * 8 + 4) / cpg) * cpg]);
+    double s0 = 0.0, q0 = 0.0, s1 = 0.0, q1 = 0.0;
+    for (long p = (po < pix_per_it) ? p0 + po : p1; p < p1; p += pix_per_it) {
         const uint4 v = *reinterpret_cast<const uint4*>(x + p * C + o * 8);
         const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        float s[2] = {0.f, 0.f}, q[2] = {0.f, 0.f};
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const float a = bf2f((uint16_t)(w[c] & 0xffff)), b = bf2f((uint16_t)(w[c] >> 16));
-            s0 += a + b; q0 += a * a + b * b;
+        for (int c = 0; c < 4; ++c) {
+            const float P = (c < 2) ? P0 : P1;
+            const float a = bf2f((uint16_t)(w[c] & 0xffff)) - P, b = bf2f((uint16_t)(w[c] >> 16)) - P;
+            s[c >> 1] += a + b; q[c >> 1] += a * a + b * b;
         }
-#pragma unroll
-        for (int c = 2; c < 4; ++c) {
-            const float a = bf2f((uint16_t)(w[c] & 0xffff)), b = bf2f((uint16_t)(w[c] >> 16));
-            s1 += a + b; q1 += a * a + b * b;
-        }
+        s0 += (double)s[0]; q0 += (double)q[0]; s1 += (double)s[1]; q1 += (double)q[1];
     }
     part[threadIdx.x][0] = s0; part[threadIdx.x][1] = q0; part[threadIdx.x][2] = s1; part[threadIdx.x][3] = q1;
     __syncthreads();
     if (threadIdx.x < GN_GROUPS) {
         const int g = threadIdx.x;
-        float s = 0.f, q = 0.f;
+        double s = 0.0, q = 0.0;
         for (int t = 0; t < 256; ++t) {   // fixed order -> deterministic
             const int to = t % oct_per_pix;
             if ((to * 8) / cpg == g) { s += part[t][0]; q += part[t][1]; }
@@ -54,22 +56,24 @@ __global__ __launch_bounds__(256) void gn_stats_kernel(const bf16_t* __restrict_
 }
 
 // ---- GroupNorm pass 2: finish the statistics (every block, same fixed order), normalise, affine, optional SiLU.
-__global__ __launch_bounds__(256) void gn_apply_kernel(const bf16_t* __restrict__ x, long npix, int C, const float* __restrict__ partial,
+// m = P + S/n, var = Q/n - (S/n)^2; the element is centred as (x - P) - S/n, both steps exact or O(sigma) in fp32.
+__global__ __launch_bounds__(256) void gn_apply_kernel(const bf16_t* __restrict__ x, long npix, int C, const double* __restrict__ partial,
                                                        int nblk_stats, const bf16_t* __restrict__ gamma, const bf16_t* __restrict__ beta,
                                                        float eps, int silu, bf16_t* __restrict__ y) {
-    __shared__ float mean_s[GN_GROUPS], rstd_s[GN_GROUPS];
+    __shared__ float pilot_s[GN_GROUPS], dmean_s[GN_GROUPS], rstd_s[GN_GROUPS];
     const int cpg = C / GN_GROUPS;
     if (threadIdx.x < GN_GROUPS) {
         double s = 0.0, q = 0.0;
         for (int b = 0; b < nblk_stats; ++b) {
-            s += (double)partial[((long)b * GN_GROUPS + threadIdx.x) * 2 + 0];
-            q += (double)partial[((long)b * GN_GROUPS + threadIdx.x) * 2 + 1];
+            s += partial[((long)b * GN_GROUPS + threadIdx.x) * 2 + 0];
+            q += partial[((long)b * GN_GROUPS + threadIdx.x) * 2 + 1];
         }
         const double n = (double)npix * cpg;
-        const double m = s / n;
-        double var = q / n - m * m;
+        const double d = s / n;
+        double var = q / n - d * d;
         if (var < 0.0) var = 0.0;
-        mean_s[threadIdx.x] = (float)m;
+        pilot_s[threadIdx.x] = bf2f(x[threadIdx.x * cpg]);
+        dmean_s[threadIdx.x] = (float)d;
         rstd_s[threadIdx.x] = (float)(1.0 / sqrt(var + (double)eps));
     }
     __syncthreads();
@@ -85,9 +89,9 @@ __global__ __launch_bounds__(256) void gn_apply_kernel(const bf16_t* __restrict_
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             const int g = (o * 8 + 2 * c) / cpg;   // both halves of a dword share the group (cpg >= 4, even offset)
-            const float m = mean_s[g], r = rstd_s[g];
-            float a = (bf2f((uint16_t)(w[c] & 0xffff)) - m) * r * bf2f((uint16_t)(gw[c] & 0xffff)) + bf2f((uint16_t)(bw[c] & 0xffff));
-            float b = (bf2f((uint16_t)(w[c] >> 16)) - m) * r * bf2f((uint16_t)(gw[c] >> 16)) + bf2f((uint16_t)(bw[c] >> 16));
+            const float P = pilot_s[g], d = dmean_s[g], r = rstd_s[g];
+            float a = ((bf2f((uint16_t)(w[c] & 0xffff)) - P) - d) * r * bf2f((uint16_t)(gw[c] & 0xffff)) + bf2f((uint16_t)(bw[c] & 0xffff));
+            float b = ((bf2f((uint16_t)(w[c] >> 16)) - P) - d) * r * bf2f((uint16_t)(gw[c] >> 16)) + bf2f((uint16_t)(bw[c] >> 16));
             if (silu) {   // GroupNorm output is a bf16 tensor in the reference; SiLU is applied to that
                 a = rbf(a); b = rbf(b);
                 a = a / (1.0f + __expf(-a)); b = b / (1.0f + __expf(-b));
@@ -185,7 +189,7 @@ static int grid_for(long work_items) {
     return (int)g;
 }
 
-extern "C" size_t utx_group_norm_workspace_bytes_impl(void) { return (size_t)GN_MAXBLK * GN_GROUPS * 2 * sizeof(float); }
+extern "C" size_t utx_group_norm_workspace_bytes_impl(void) { return (size_t)GN_MAXBLK * GN_GROUPS * 2 * sizeof(double); }
 
 extern "C" int utx_launch_group_norm(const void* x, long npix, int C, const void* gamma, const void* beta, float eps, int silu,
                                      void* y, void* work, hipStream_t stream) {
@@ -193,9 +197,9 @@ extern "C" int utx_launch_group_norm(const void* x, long npix, int C, const void
     long nb = (npix * (C >> 3) + 256 * 64 - 1) / (256 * 64);
     if (nb > GN_MAXBLK) nb = GN_MAXBLK;
     if (nb < 1) nb = 1;
-    hipLaunchKernelGGL(gn_stats_kernel, dim3((int)nb), dim3(256), 0, stream, (const bf16_t*)x, npix, C, (float*)work);
+    hipLaunchKernelGGL(gn_stats_kernel, dim3((int)nb), dim3(256), 0, stream, (const bf16_t*)x, npix, C, (double*)work);
     hipLaunchKernelGGL(gn_apply_kernel, dim3(grid_for(npix * (C >> 3))), dim3(256), 0, stream, (const bf16_t*)x, npix, C,
-                       (const float*)work, (int)nb, (const bf16_t*)gamma, (const bf16_t*)beta, eps, silu, (bf16_t*)y);
+                       (const double*)work, (int)nb, (const bf16_t*)gamma, (const bf16_t*)beta, eps, silu, (bf16_t*)y);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

@@ -58,6 +58,7 @@ class AutoencoderKL:
     shift_factor = 0.1159
     latent_channels = 16
     block_out_channels = (128, 256, 512, 512)
+    attn_score_elems = 1 << 30      # budget of one block of mid-attention scores, in bf16 elements (2 GiB); tests lower it to force blocking
 
     def __init__(self, state_dict, device="cuda:0"):
         self.device = torch.device(device)
@@ -141,7 +142,7 @@ class AutoencoderKL:
         vt = ops.gemm(w[name + ".to_v.weight"], h)                                   # V^T [C, S]; bias added after PV
         # scores are materialised one block of query rows at a time ([QB, S] bf16, <= ~2 GiB): softmax and P V are row-wise, so the
         # result is bit-identical to the whole [S, S] matrix (18.9 GB at 1024 x 6144, 550 GB at 2048^2 x 8 views)
-        QB = max(256, min(S, ((1 << 30) // S) // 256 * 256))
+        QB = max(256, min(S, (self.attn_score_elems // S) // 256 * 256))
         a = torch.empty(S, Cc, dtype=BF, device=self.device)
         sbuf = torch.empty(min(QB, S), S, dtype=BF, device=self.device)
         for r0 in range(0, S, QB):
