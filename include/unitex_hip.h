@@ -346,6 +346,42 @@ int utx_face_normals(utx_ctx* ctx, const float* verts, const int* faces, int F, 
 int utx_texture_shade(utx_ctx* ctx, const float* rast, const float* uv, const int* tri, const float* tex, int Ht, int Wt,
                       const float* bg3_host, long npix, void* out, utx_stream stream);
 
+/* geometry-buffer shading of the orbit video, VideoExporter.export_orbit_video(video_type=...) (video/export_nvdiffrast_video.py:141-256 ->
+ * export_video :37-139 -> simple_rendering, render/nvdiffrast/renderer_base.py:153-241; alpha = coverage, no dr.antialias).  One launch per
+ * frame: rast [npix][4]; tri [F][3]; attr = the per-vertex attribute the mode interpolates, vertex v at attr + v * attr_stride (floats):
+ *   UTX_GBUF_WORLD_NORMAL     v_nrm [V][3]                      interpolate, F.normalize, background -1          (:160-166)
+ *   UTX_GBUF_CAMERA_NORMAL    utx_camera_normals of the view    the same arm                                     (:168-176)
+ *   UTX_GBUF_WORLD_POSITION   v_pos [V][3]                      interpolate, background -1                       (:178-188)
+ *   UTX_GBUF_CAMERA_POSITION  utx_transform_points(w2c), xyz    interpolate, background 0                        (:228-235)
+ *   UTX_GBUF_Z_DEPTH          clip w (utx_transform_points)     one channel, background 0, repeated to three     (:153-158)
+ *   UTX_GBUF_DISTANCE         utx_transform_points(w2c), xyz    L2 norm of the interpolated value, background 0  (:236-241)
+ * The interpolation is utx_interpolate's, bit for bit.  Then export_video :120-131: scale2_dev (DEVICE {lo, hi}, or NULL) normalises the
+ * covered pixels to (x - lo) / (hi - lo); UTX_GBUF_NDC maps x * 0.5 + 0.5; UTX_GBUF_COMPOSITE x * alpha + bg3_host * (1 - alpha) (bg3_host: HOST
+ * array of 3 floats, always required).  out_u8 [npix][3] = clamp(0, 1) * 255 truncated; out_rgba_or_null [npix][4] fp32, alpha fourth
+ * (16-byte aligned).  rast must be 16-byte aligned too.
+ * Returns -2 for a mode outside 0..5, unknown flag bits, a null pointer, a rast / RGBA pointer off a 16-byte boundary, npix <= 0 or a
+ * stride below the mode's channels. */
+#define UTX_GBUF_WORLD_NORMAL 0
+#define UTX_GBUF_CAMERA_NORMAL 1
+#define UTX_GBUF_WORLD_POSITION 2
+#define UTX_GBUF_CAMERA_POSITION 3
+#define UTX_GBUF_Z_DEPTH 4
+#define UTX_GBUF_DISTANCE 5
+#define UTX_GBUF_NDC 1
+#define UTX_GBUF_COMPOSITE 2
+int utx_gbuffer_shade(utx_ctx* ctx, int mode, const float* rast, const int* tri, const float* attr, int attr_stride, const float* scale2_dev,
+                      int flags, const float* bg3_host, long npix, void* out_u8, float* out_rgba_or_null, utx_stream stream);
+
+/* (lo, hi) of a mode's buffer over the covered pixels of ONE frame -> scale2_dev[0..1] (export_video :120-125: min / max of the selected
+ * pixels, which export_video takes on its first frame and reuses); *empty_flag_dev = 1 if the frame covers no pixel (scale2_dev is then
+ * {+inf, -inf}), else 0.  Stream-ordered, no host synchronisation.  Same argument checks as utx_gbuffer_shade. */
+int utx_gbuffer_range(utx_ctx* ctx, int mode, const float* rast, const int* tri, const float* attr, int attr_stride, long npix,
+                      float* scale2_dev, int* empty_flag_dev, utx_stream stream);
+
+/* per-view, per-vertex camera-space normals of render_camera_normal (renderer_base.py:169-170): nrm [V][3], c2ws [n_views][4][4] ->
+ * out [n_views][V][3] = F.normalize(nrm @ c2ws[:3,:3]) with the fixed order (n0*R0j + n1*R1j) + n2*R2j. */
+int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws, int n_views, float* out, utx_stream stream);
+
 /* LBVH ray-mesh intersector (raytracing/__init__.py:12-83 RayTracing / rt_aprmis APRMISRayTracing; the build the
  * reference runs per mesh: raytracing/rt_aprmis/bvhhelpers.py:20-84).  verts/faces are borrowed and must stay alive while
  * the handle is used.

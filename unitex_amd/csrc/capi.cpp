@@ -1,5 +1,6 @@
 // C-ABI entry points of libunitex_hip.so (declared in include/unitex_hip.h).
 // Thin: argument validation, error bookkeeping, launch.  No torch, no hidden syncs.
+#include <cstdint>
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <string.h>
@@ -351,6 +352,28 @@ int utx_texture_shade(utx_ctx* ctx, const float* rast, const float* uv, const in
                       const float* bg3_host, long npix, void* out, utx_stream stream) {
     if (!rast || !uv || !tri || !tex || !out) return fail(ctx, -2, "utx_texture_shade");
     UTX_CALL(ctx, "utx_texture_shade", utx_launch_texture_shade(rast, uv, tri, tex, Ht, Wt, bg3_host, npix, out, (hipStream_t)stream));
+}
+
+int utx_gbuffer_shade(utx_ctx* ctx, int mode, const float* rast, const int* tri, const float* attr, int attr_stride, const float* scale2_dev,
+                      int flags, const float* bg3_host, long npix, void* out_u8, float* out_rgba_or_null, utx_stream stream) {
+    if (!rast || !tri || !attr || !bg3_host || !out_u8) return fail(ctx, -2, "utx_gbuffer_shade");
+    if (((uintptr_t)rast & 15) || ((uintptr_t)out_rgba_or_null & 15)) return fail(ctx, -2, "utx_gbuffer_shade");      // read / stored as float4
+    if (mode < 0 || mode > UTX_GBUF_DISTANCE || npix <= 0 || (flags & ~(UTX_GBUF_NDC | UTX_GBUF_COMPOSITE))) return fail(ctx, -2, "utx_gbuffer_shade");
+    if (attr_stride < (mode == UTX_GBUF_Z_DEPTH ? 1 : 3)) return fail(ctx, -2, "utx_gbuffer_shade");
+    UTX_CALL(ctx, "utx_gbuffer_shade", utx_launch_gbuffer_shade(mode, rast, tri, attr, attr_stride, scale2_dev, (flags & UTX_GBUF_NDC) != 0,
+                                                                (flags & UTX_GBUF_COMPOSITE) != 0, bg3_host, npix, out_u8, out_rgba_or_null, (hipStream_t)stream));
+}
+int utx_gbuffer_range(utx_ctx* ctx, int mode, const float* rast, const int* tri, const float* attr, int attr_stride, long npix,
+                      float* scale2_dev, int* empty_flag_dev, utx_stream stream) {
+    if (!rast || !tri || !attr || !scale2_dev || !empty_flag_dev) return fail(ctx, -2, "utx_gbuffer_range");
+    if ((uintptr_t)rast & 15) return fail(ctx, -2, "utx_gbuffer_range");      // read as float4
+    if (mode < 0 || mode > UTX_GBUF_DISTANCE || npix <= 0) return fail(ctx, -2, "utx_gbuffer_range");
+    if (attr_stride < (mode == UTX_GBUF_Z_DEPTH ? 1 : 3)) return fail(ctx, -2, "utx_gbuffer_range");
+    UTX_CALL(ctx, "utx_gbuffer_range", utx_launch_gbuffer_range(mode, rast, tri, attr, attr_stride, npix, scale2_dev, empty_flag_dev, (hipStream_t)stream));
+}
+int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws, int n_views, float* out, utx_stream stream) {
+    if (!nrm || !c2ws || !out) return fail(ctx, -2, "utx_camera_normals");
+    UTX_CALL(ctx, "utx_camera_normals", utx_launch_camera_normals(nrm, V, c2ws, n_views, out, (hipStream_t)stream));
 }
 
 int utx_condition_shade(utx_ctx* ctx, const float* rast, const float* nrm, const float* pos, const float* bg3_host, long npix,

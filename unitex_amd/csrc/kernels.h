@@ -136,6 +136,9 @@ int utx_launch_view_visibility(const float* attr6, const float* rast, const floa
 size_t utx_knn_workspace_bytes_impl(long N);
 int utx_launch_knn(const KnnParams* p, void* work, size_t work_bytes, hipStream_t stream);
 int utx_launch_texture_shade(const float* rast, const float* uv, const int* tri, const float* tex, int Ht, int Wt, const float* bg3_host, long npix, void* out, hipStream_t stream);
+int utx_launch_gbuffer_shade(int mode, const float* rast, const int* tri, const float* attr, int stride, const float* scale2, int ndc, int composite, const float* bg3_host, long npix, void* out_u8, float* out_rgba, hipStream_t stream);
+int utx_launch_gbuffer_range(int mode, const float* rast, const int* tri, const float* attr, int stride, long npix, float* scale2, int* empty, hipStream_t stream);
+int utx_launch_camera_normals(const float* nrm, int V, const float* c2ws, int n_views, float* out, hipStream_t stream);
 int utx_bvh_build_impl(const float* verts, int V, const int* faces, int F, utx_bvh** out, hipStream_t stream);
 size_t utx_bvh_workspace_bytes_impl(int F);
 int utx_bvh_build_ws_impl(const float* verts, int V, const int* faces, int F, void* work, size_t work_bytes, utx_bvh** out, hipStream_t stream);

@@ -289,6 +289,174 @@ extern "C" int utx_launch_texture_shade(const float* rast, const float* uv, cons
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
+// ---- geometry-buffer shading of the orbit video (VideoExporter.export_orbit_video(video_type=...) -> export_video,
+// video/export_nvdiffrast_video.py:37-139, on simple_rendering, render/nvdiffrast/renderer_base.py:153-241, with alpha = coverage):
+// one thread per pixel interpolates the triangle's three vertex attributes exactly as interpolate_kernel does (same operations, same
+// order: the value is bit-identical to utx_interpolate's), then, per MODE,
+//   NORMAL    v = n / max(sqrt((nx*nx + ny*ny) + nz*nz), 1e-12), background -1   (world_normal :160-166; camera_normal :168-176 with the
+//             per-view, per-vertex re-normalised camera_normals_kernel output as attribute)
+//   POSITION  v = p, background -1 (world_position :178-188) or 0 (camera_position :228-235: `fill`)
+//   DEPTH     v = the one interpolated channel (clip w), background 0, repeated to three (z_depth :153-158, export_video :107-108)
+//   DISTANCE  v = sqrt((px*px + py*py) + pz*pz) of the interpolated camera-space position, background 0, repeated (:236-241)
+// then export_video :120-131 in its order: covered pixels (v - lo) / (hi - lo) if scale2 = {lo, hi} is given; v * 0.5 + 0.5 if ndc;
+// v * alpha + bg * (1 - alpha) if composite; RGBA float frame (alpha fourth) and clamp(0, 1) * 255 truncated to uint8.
+// torch.lerp(fill, v, alpha) with alpha in {0, 1} returns v or fill exactly, so it is a select here.
+enum { GB_NORMAL = 0, GB_POSITION = 1, GB_DEPTH = 2, GB_DISTANCE = 3 };
+
+// keeps each product a scalar of its own: left alone, hipcc pairs two products of a sum into one packed multiply and adds its halves with a
+// cross-half packed add, the instruction pair tests/test_asm_hazards_cpu.py bans from every listing (unitex_amd/csrc/build.py, NO_PK).  No code is emitted.
+// Why not NO_PK on this file, the project's usual answer: the flag is per translation unit and would regenerate the rasteriser, utx_interpolate and
+// texture_shade_kernel, whose listings are clean today and whose speed and bit-exact results other tests and the rgb turntable rest on; the new
+// kernels belong in this file (they share its interpolation and its -ffp-contract=off).  The audit reads every listing on every run, so a compiler
+// that stops honouring the barrier is caught there, and NO_PK for the file remains the fallback.
+__device__ __forceinline__ float gb_scalar(float x) { asm volatile("" : "+v"(x)); return x; }
+__device__ __forceinline__ float gb_dot3(float x0, float y0, float x1, float y1, float x2, float y2) {
+    return (gb_scalar(x0 * y0) + gb_scalar(x1 * y1)) + gb_scalar(x2 * y2);
+}
+
+template <int MODE>
+__device__ __forceinline__ bool gbuffer_value(const float4 r, const int* tri, const float* attr, int stride, float fill, float v3[3]) {
+    const int id = (int)r.w - 1;
+    if (id < 0) { v3[0] = v3[1] = v3[2] = fill; return false; }
+    const float u = r.x, v = r.y, w = (1.0f - u) - v;
+    const float* a0 = attr + (long)stride * tri[3 * id + 0];
+    const float* a1 = attr + (long)stride * tri[3 * id + 1];
+    const float* a2 = attr + (long)stride * tri[3 * id + 2];
+    if constexpr (MODE == GB_DEPTH) {
+        v3[0] = v3[1] = v3[2] = gb_dot3(a0[0], u, a1[0], v, a2[0], w);
+    } else {
+        float p[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) p[c] = gb_dot3(a0[c], u, a1[c], v, a2[c], w);
+        if constexpr (MODE == GB_NORMAL) {
+            const float len = fmaxf(sqrtf(gb_dot3(p[0], p[0], p[1], p[1], p[2], p[2])), 1e-12f);
+            v3[0] = p[0] / len; v3[1] = p[1] / len; v3[2] = p[2] / len;
+        } else if constexpr (MODE == GB_DISTANCE) {
+            v3[0] = v3[1] = v3[2] = sqrtf(gb_dot3(p[0], p[0], p[1], p[1], p[2], p[2]));
+        } else {
+            v3[0] = p[0]; v3[1] = p[1]; v3[2] = p[2];
+        }
+    }
+    return true;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void gbuffer_shade_kernel(const float4* rast, const int* tri, const float* attr, int stride, float fill,
+                                                            const float* scale2, int ndc, int composite, float bg0, float bg1, float bg2,
+                                                            long npix, unsigned char* out_u8, float4* out_rgba) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    float c[3];
+    const bool covered = gbuffer_value<MODE>(rast[i], tri, attr, stride, fill, c);
+    const float a = covered ? 1.0f : 0.0f;
+    if (scale2 && covered) {
+        const float lo = scale2[0], hi = scale2[1];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[k] = (c[k] - lo) / (hi - lo);
+    }
+    const float bg[3] = {bg0, bg1, bg2};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (ndc) c[k] = c[k] * 0.5f + 0.5f;
+        if (composite) c[k] = gb_scalar(c[k] * a) + gb_scalar(bg[k] * (1.0f - a));
+        out_u8[3 * i + k] = (unsigned char)(fminf(fmaxf(c[k], 0.f), 1.f) * 255.0f);
+    }
+    if (out_rgba) out_rgba[i] = make_float4(c[0], c[1], c[2], a);
+}
+
+// mode of the ABI (unitex_hip.h UTX_GBUF_*) -> kernel arm, background fill of the buffer, vertex stride is the caller's
+extern "C" int utx_launch_gbuffer_shade(int mode, const float* rast, const int* tri, const float* attr, int stride, const float* scale2,
+                                        int ndc, int composite, const float* bg3_host, long npix, void* out_u8, float* out_rgba,
+                                        hipStream_t stream) {
+    if (npix <= 0 || stride <= 0 || !bg3_host) return -2;
+    const dim3 g((unsigned)((npix + 255) / 256)), b(256);
+#define GB_LAUNCH(M, FILL) hipLaunchKernelGGL(gbuffer_shade_kernel<M>, g, b, 0, stream, (const float4*)rast, tri, attr, stride, FILL, scale2, \
+                                              ndc, composite, bg3_host[0], bg3_host[1], bg3_host[2], npix, (unsigned char*)out_u8, (float4*)out_rgba)
+    switch (mode) {
+        case 0: case 1: GB_LAUNCH(GB_NORMAL, -1.0f); break;     // world_normal, camera_normal
+        case 2: GB_LAUNCH(GB_POSITION, -1.0f); break;           // world_position
+        case 3: GB_LAUNCH(GB_POSITION, 0.0f); break;            // camera_position
+        case 4: GB_LAUNCH(GB_DEPTH, 0.0f); break;               // z_depth
+        case 5: GB_LAUNCH(GB_DISTANCE, 0.0f); break;            // distance
+        default: return -2;
+    }
+#undef GB_LAUNCH
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// (lo, hi) of the buffer over the covered pixels of one frame (export_video :120-125 rgb_sel.min() / .max(), taken on the first frame only):
+// per-wave shuffle reduction, one atomic pair per wave.  Floats are ordered through their bit patterns (non-negative: as signed ints,
+// negative: reversed as unsigned), so the result is the exact min / max whatever the order.  empty stays 1 if no pixel is covered.
+__global__ void gbuffer_range_init_kernel(float* scale2, int* empty) {
+    scale2[0] = __int_as_float(0x7f800000); scale2[1] = __int_as_float(0xff800000); *empty = 1;
+}
+
+__device__ __forceinline__ void atomic_min_float(float* addr, float v) {
+    if (v >= 0.f) atomicMin((int*)addr, __float_as_int(v)); else atomicMax((unsigned int*)addr, __float_as_uint(v));
+}
+__device__ __forceinline__ void atomic_max_float(float* addr, float v) {
+    if (v >= 0.f) atomicMax((int*)addr, __float_as_int(v)); else atomicMin((unsigned int*)addr, __float_as_uint(v));
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void gbuffer_range_kernel(const float4* rast, const int* tri, const float* attr, int stride, long npix,
+                                                            float* scale2, int* empty) {
+    float lo = __int_as_float(0x7f800000), hi = __int_as_float(0xff800000);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (long)gridDim.x * blockDim.x) {
+        float c[3];
+        if (gbuffer_value<MODE>(rast[i], tri, attr, stride, 0.f, c))
+            for (int k = 0; k < 3; ++k) { lo = fminf(lo, c[k]); hi = fmaxf(hi, c[k]); }
+    }
+    for (int off = warpSize / 2; off > 0; off >>= 1) {
+        lo = fminf(lo, __shfl_down(lo, off));
+        hi = fmaxf(hi, __shfl_down(hi, off));
+    }
+    if ((threadIdx.x & (warpSize - 1)) == 0 && lo <= hi) {
+        atomic_min_float(scale2, lo + 0.0f);      // + 0.0f canonicalises -0
+        atomic_max_float(scale2 + 1, hi + 0.0f);
+        atomicAnd(empty, 0);
+    }
+}
+
+extern "C" int utx_launch_gbuffer_range(int mode, const float* rast, const int* tri, const float* attr, int stride, long npix, float* scale2,
+                                        int* empty, hipStream_t stream) {
+    if (npix <= 0 || stride <= 0) return -2;
+    long nb = (npix + 255) / 256; if (nb > 1024) nb = 1024;
+    const dim3 g((unsigned)nb), b(256);
+    hipLaunchKernelGGL(gbuffer_range_init_kernel, dim3(1), dim3(1), 0, stream, scale2, empty);
+#define GB_RANGE(M) hipLaunchKernelGGL(gbuffer_range_kernel<M>, g, b, 0, stream, (const float4*)rast, tri, attr, stride, npix, scale2, empty)
+    switch (mode) {
+        case 0: case 1: GB_RANGE(GB_NORMAL); break;
+        case 2: case 3: GB_RANGE(GB_POSITION); break;
+        case 4: GB_RANGE(GB_DEPTH); break;
+        case 5: GB_RANGE(GB_DISTANCE); break;
+        default: return -2;
+    }
+#undef GB_RANGE
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// per-view, per-vertex camera-space normals of render_camera_normal (renderer_base.py:169-170): out[n][v] = normalize(nrm[v] @ c2ws[n][:3,:3]),
+// out_j = (n0*R0j + n1*R1j) + n2*R2j, F.normalize eps 1e-12
+__global__ __launch_bounds__(256) void camera_normals_kernel(const float* nrm, int V, const float* c2ws, float* out) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    const float* m = c2ws + 16 * blockIdx.y;
+    const float x = nrm[3 * v], y = nrm[3 * v + 1], z = nrm[3 * v + 2];
+    float c[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) c[j] = gb_dot3(x, m[j], y, m[4 + j], z, m[8 + j]);
+    const float len = fmaxf(sqrtf(gb_dot3(c[0], c[0], c[1], c[1], c[2], c[2])), 1e-12f);
+    float* o = out + 3 * ((long)blockIdx.y * V + v);
+    o[0] = c[0] / len; o[1] = c[1] / len; o[2] = c[2] / len;
+}
+
+extern "C" int utx_launch_camera_normals(const float* nrm, int V, const float* c2ws, int n_views, float* out, hipStream_t stream) {
+    if (V <= 0 || n_views <= 0) return -2;
+    hipLaunchKernelGGL(camera_normals_kernel, dim3((V + 255) / 256, n_views), dim3(256), 0, stream, nrm, V, c2ws, out);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
 // ---- per-face unit normals (mesh/structure_v2.py:49-50: cross(v1 - v0, v2 - v0), F.normalize eps 1e-12); same float32
 // operation order as oracle/geom_ref.py face_normals (this file is compiled with -ffp-contract=off).
 __global__ __launch_bounds__(256) void face_normals_kernel(const float* verts, const int* faces, int F, float* out) {

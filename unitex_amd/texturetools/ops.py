@@ -95,6 +95,53 @@ def texture_shade(rast, uv01, tri, tex, bg=(1.0, 1.0, 1.0)):
     return out
 
 
+GBUFFER_MODES = {"world_normal": 0, "camera_normal": 1, "world_position": 2, "camera_position": 3, "z_depth": 4, "distance": 5}
+
+
+def _gbuffer_attr(mode, attr):
+    """per-vertex attribute [V,C] (a view of a wider contiguous tensor is fine: e.g. clip[..., 3:] or cam[..., :3] of transform_points)
+    -> (tensor, stride in floats); C = 1 for z_depth, 3 otherwise."""
+    m = GBUFFER_MODES[mode]
+    assert attr.is_cuda and attr.dtype == F32 and attr.dim() == 2 and attr.shape[1] == (1 if m == 4 else 3)
+    assert attr.shape[1] == 1 or attr.stride(1) == 1, "the channels of a vertex must be adjacent"
+    return m, attr, int(attr.stride(0))
+
+
+def gbuffer_shade(mode, rast, tri, attr, scale2=None, ndc=False, bg=(1.0, 1.0, 1.0), want_rgba=False):
+    """rast [H,W,4], per-vertex attr of `mode` (see utx_gbuffer_shade) -> uint8 RGB [H,W,3] (, float RGBA [H,W,4]).
+    scale2: CUDA float32 [2] = (lo, hi) to normalise the covered pixels with, or None; bg=None skips the composite."""
+    ctx = get_ctx(rast.device.index)
+    H, W = rast.shape[:2]
+    m, attr, stride = _gbuffer_attr(mode, attr)
+    out = torch.empty(H, W, 3, dtype=U8, device=rast.device)
+    rgba = torch.empty(H, W, 4, dtype=F32, device=rast.device) if want_rgba else None
+    flags = (1 if ndc else 0) | (2 if bg is not None else 0)
+    bgv = (C.c_float * 3)(*[float(b) for b in (bg if bg is not None else (0.0, 0.0, 0.0))])
+    ctx.check(ctx.lib.utx_gbuffer_shade(ctx.handle, m, ptr(_f(rast)), ptr(_i(tri)), ptr(attr), stride, ptr(_f(scale2) if scale2 is not None else None),
+                                        flags, bgv, H * W, ptr(out), ptr(rgba), ctx.stream()))
+    return (out, rgba) if want_rgba else out
+
+
+def gbuffer_range(mode, rast, tri, attr, out=None):
+    """(lo, hi) of the mode's buffer over the covered pixels of this frame, and the 'covers nothing' flag, both left on the device:
+    returns a CUDA float32 [3] whose [:2] is the scale2 of gbuffer_shade and whose [2], viewed as int32, is 1 if the frame is empty."""
+    ctx = get_ctx(rast.device.index)
+    m, attr, stride = _gbuffer_attr(mode, attr)
+    out = torch.empty(3, dtype=F32, device=rast.device) if out is None else out
+    ctx.check(ctx.lib.utx_gbuffer_range(ctx.handle, m, ptr(_f(rast)), ptr(_i(tri)), ptr(attr), stride, rast.shape[0] * rast.shape[1],
+                                        ptr(out), C.c_void_p(out.data_ptr() + 8), ctx.stream()))
+    return out
+
+
+def camera_normals(nrm, c2ws):
+    """nrm [V,3], c2ws [n,4,4] -> [n,V,3] = normalize(nrm @ c2ws[:, :3, :3]) per vertex."""
+    ctx = get_ctx(nrm.device.index)
+    V, n = nrm.shape[0], c2ws.shape[0]
+    out = torch.empty(n, V, 3, dtype=F32, device=nrm.device)
+    ctx.check(ctx.lib.utx_camera_normals(ctx.handle, ptr(_f(nrm)), V, ptr(_f(c2ws)), n, ptr(out), ctx.stream()))
+    return out
+
+
 class BVH:
     """utx_bvh handle (RayTracing / APRMISRayTracing of the reference)."""
 

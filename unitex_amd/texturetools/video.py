@@ -6,7 +6,9 @@ HIP path: clip transform -> rasterise per view -> interpolate vertex normals / p
 uint8 conversion kernel; orthographic box views (the pipeline's) or, as the reference's defaults, a perspective
 camera (fov_deg) and / or the orbit ring (orbit=True).  export_orbit_video (video/export_nvdiffrast_video.py:141-256): per frame clip transform ->
 perspective raster -> fused UV interpolation + bilinear texture fetch + background composite (utx_texture_shade);
-frames are muxed on the host (Motion-JPEG in an MP4 container, or GIF -- there is no video encoder in this image)."""
+the geometry video types (world / camera normal, world / camera position, z_depth, distance) swap that last kernel for the fused geometry-buffer
+shade (utx_gbuffer_shade; alpha = coverage, no dr.antialias); frames are muxed on the host (Motion-JPEG in an MP4 container, or GIF -- there is
+no video encoder in this image)."""
 import io
 import math
 import os
@@ -137,16 +139,25 @@ class VideoExporter:
                            save_frames=False, save_grid=False, save_cover=False, save_camera=False, rename_with_euler=False,
                            render_size=1024, fps=15, return_frames=False):
         """turntable of a textured mesh on a white background.  mesh_obj: path to a textured .glb, a TexturedMesh
-        (renderer_inverse.py) or (verts, faces, uvs01, texture_u8_top_down)."""
+        (renderer_inverse.py) or (verts, faces, uvs01, texture_u8_top_down[, vertex_normals]).
+        video_type: 'rgb' or a geometry buffer of the same mesh ('world_normal', 'camera_normal', 'world_position', 'camera_position',
+        'z_depth', 'distance'; export_nvdiffrast_video.py:157-175): normals / positions mapped x*0.5+0.5, depths normalised with the (min, max) of
+        the FIRST frame's covered pixels (later frames may leave [0, 1] and are clamped in the file).  Vertex normals are
+        _vertex_normals(self.normal_weighting) unless the mesh tuple brings its own.
+        return_frames: True -> the uint8 frames, 'rgba' -> the float RGBA frames of export_video (geometry types only)."""
         ext = os.path.splitext(video_path)[1]
         assert ext in [".mp4", ".gif"]
-        if video_type != "rgb":
-            raise NotImplementedError("video_type %s: only the 'rgb' turntable of the texture pipeline is built" % video_type)
+        assert video_type in ["rgb", "albedo", "world_normal", "camera_normal", "world_position", "camera_position", "z_depth", "distance"]
+        if video_type == "albedo":       # uv_rendering has no render_albedo: the reference's render_result['albedo'] raises (export_video :103)
+            raise KeyError("albedo")
+        assert return_frames != "rgba" or video_type != "rgb", "return_frames='rgba' is for the geometry video types"
+        vnrm = None
         if isinstance(mesh_obj, str):
             verts, faces, uvs, tex = meshes.load_mesh(mesh_obj)
             verts = meshes.normalise_to_bbox(verts, 1.0)              # texture.mesh.scale_to_bbox() (:178)
         elif isinstance(mesh_obj, (tuple, list)):
-            verts, faces, uvs, tex = mesh_obj
+            verts, faces, uvs, tex = mesh_obj[:4]
+            vnrm = mesh_obj[4] if len(mesh_obj) > 4 else None
         else:
             verts, faces, uvs, tex = mesh_obj.vertices, mesh_obj.faces, mesh_obj.uv, mesh_obj.texture
         assert uvs is not None and tex is not None, "missing map_Kd in texture"
@@ -173,10 +184,45 @@ class VideoExporter:
         texd = torch.from_numpy(np.ascontiguousarray(np.asarray(tex)[::-1, :, :3]).astype(np.float32) / np.float32(255.0)).to(dev).contiguous()
         mvp = torch.matmul(camera.intr_to_proj(intrinsics, perspective=perspective), camera.c2w_to_w2c(c2ws)).to(dev).contiguous()
         clip, _ = ops.transform_points(vd, mvp, want_ndc=False)
-        frames = []
-        for i in range(c2ws.shape[0]):
-            rast = ops.rasterize(clip[i].contiguous(), fd, render_size, render_size)
-            frames.append(ops.texture_shade(rast, uvd, fd, texd, bg=(1.0, 1.0, 1.0)).cpu().numpy())
+        frames, rgba = [], []
+        if video_type == "rgb":
+            for i in range(c2ws.shape[0]):
+                rast = ops.rasterize(clip[i].contiguous(), fd, render_size, render_size)
+                frames.append(ops.texture_shade(rast, uvd, fd, texd, bg=(1.0, 1.0, 1.0)).cpu().numpy())
+        else:
+            # per-view vertex attributes in one launch each for all frames; utx_transform_points has the reference's row layout
+            # ([x, y, z, 1] @ M^T), so M = w2c gives the camera-space positions and M = mvp the clip w (no copies: strided views)
+            if video_type in ("world_normal", "camera_normal"):
+                nd = (torch.as_tensor(np.asarray(vnrm), dtype=torch.float32) if vnrm is not None
+                      else _vertex_normals(torch.as_tensor(np.asarray(verts), dtype=torch.float32), torch.as_tensor(np.asarray(faces)), self.normal_weighting))
+                nd = nd.to(dev).contiguous()
+                per_view = ops.camera_normals(nd, c2ws.to(dev, torch.float32).contiguous()) if video_type == "camera_normal" else None
+                attr_of = (lambda i: per_view[i]) if per_view is not None else (lambda i: nd)
+            elif video_type == "world_position":
+                attr_of = lambda i: vd
+            elif video_type == "z_depth":
+                attr_of = lambda i: clip[i, :, 3:]
+            else:
+                cam, _ = ops.transform_points(vd, camera.c2w_to_w2c(c2ws).to(dev, torch.float32).contiguous(), want_ndc=False)
+                attr_of = lambda i: cam[i, :, :3]
+            normalize, ndc = video_type in ("z_depth", "distance"), video_type not in ("z_depth", "distance")
+            scale = None
+            for i in range(c2ws.shape[0]):
+                rast = ops.rasterize(clip[i].contiguous(), fd, render_size, render_size)
+                if normalize and i == 0:      # (min, max) of the first frame's covered pixels, reused by every frame (export_video :120-125)
+                    scale = ops.gbuffer_range(video_type, rast, fd, attr_of(0))
+                u8 = ops.gbuffer_shade(video_type, rast, fd, attr_of(i), scale2=scale[:2] if normalize else None, ndc=ndc,
+                                       bg=(1.0, 1.0, 1.0), want_rgba=return_frames == "rgba")
+                if return_frames == "rgba":
+                    u8, fl = u8
+                    rgba.append(fl.cpu().numpy())
+                if normalize and i == 0:      # the flag rides on frame 0's copy: one transfer, no extra synchronisation
+                    host = torch.cat([scale.view(torch.uint8), u8.reshape(-1)]).cpu().numpy()
+                    if host[8:12].view(np.int32)[0] != 0:
+                        raise RuntimeError("video_type %s: the first frame covers no pixel, there is no (min, max) to normalise with" % video_type)
+                    frames.append(host[12:].reshape(render_size, render_size, 3))
+                else:
+                    frames.append(u8.cpu().numpy())
         os.makedirs(os.path.dirname(os.path.abspath(video_path)), exist_ok=True)
         if ext == ".gif":
             write_gif(video_path, frames, fps)
@@ -196,6 +242,8 @@ class VideoExporter:
             Image.fromarray(g).save(base + "_grid.png")
         if save_camera:
             torch.save({"c2ws": c2ws, "intrinsics": intrinsics, "perspective": perspective}, base + "_camera.pth")
+        if return_frames == "rgba":
+            return rgba
         return frames if return_frames else video_path
 
 
