@@ -490,6 +490,32 @@ int utx_gaussian_blur_seam(utx_ctx* ctx, const float* src, const void* seam, int
 long utx_pull_push_workspace_bytes(int H, int W);
 int utx_pull_push(utx_ctx* ctx, const float* kd, const void* mask, int H, int W, float* out, void* work, utx_stream stream);
 
+/* ---- C-channel (PBR stack) bake: renderer_inverse.py:635-726 with image_attrs of 9 channels (albedo, metallic-roughness, bump).  Visibility,
+ * winner, seam and the nearest-neighbour search read no colour: they run once, and colour is gathered from the winning view only.  1 <= C <= 16
+ * everywhere; all C-channel images are interleaved [..][C] f32 and every channel is processed on its own (the reference's blurs and pull-push are
+ * depthwise), with the 3-channel kernels' expressions: channels [3g, 3g+3) of a result equal the 3-channel entry point's result on that group bit for bit. */
+
+/* visibility-only back-projection: utx_backproject_sampled without the colour gather.  d->images is the view ALPHA plane [n_views][H][W] f32,
+ * d->color is not read or written (may be NULL); eyes / sample_mode as in utx_backproject_sampled.  rayvis / alphaok are bit-identical to those of
+ * utx_backproject_sampled on [n][H][W][4] images whose fourth channel is that plane, on every traversal mode. */
+int utx_backproject_vis(utx_ctx* ctx, const utx_backproject_desc* d, const float* eyes, int sample_mode, utx_bvh* bvh, utx_stream stream);
+/* utx_composite's priority scan without colours: vis [n_views][T] u8, order_host (HOST array, n_order <= 8 view ids < n_views) -> winner [T] int8. */
+int utx_composite_winner(utx_ctx* ctx, const void* vis, int n_views, const int* order_host, int n_order, long T, void* winner, utx_stream stream);
+/* atlas [T][C] = images [n_views][H][W][C] sampled at the texel's NDC in view winner[t] (vndc [n_views][V][2], rast2d [T][4], faces [F][3]), with the taps,
+ * weights and summation order of utx_backproject_sampled(sample_mode); zeros where winner[t] < 0.  For C = 3 it equals utx_composite(utx_backproject). */
+int utx_gather_winner(utx_ctx* ctx, const float* rast2d, const int* faces, const float* vndc, const float* images, const void* winner, long T, int V,
+                      int n_views, int H, int W, int C, int sample_mode, float* atlas, utx_stream stream);
+/* utx_nn_fill on atlas [T][C]: one search, C floats copied.  nn_index [T] int32 is REQUIRED here (the search's result, -1 = not filled);
+ * work as for utx_nn_fill (utx_nn_fill_workspace_bytes(T)). */
+int utx_nn_fill_c(utx_ctx* ctx, const float* pos, const void* winner, const float* rast2d, long T, int C, float* atlas, int* nn_index,
+                  void* work, long work_bytes, utx_stream stream);
+/* utx_lens_blur_seam / utx_gaussian_blur_seam on src / dst [H][W][C] f32. */
+int utx_lens_blur_seam_c(utx_ctx* ctx, const float* src, const void* seam, int H, int W, int C, const float* k49_host, float* dst, utx_stream stream);
+int utx_gaussian_blur_seam_c(utx_ctx* ctx, const float* src, const void* seam, int H, int W, int C, int ksize, const float* w1_host, float* dst, utx_stream stream);
+/* utx_pull_push on kd / out [H][W][C] f32; utx_pull_push_workspace_bytes_c returns 0 for a C outside 1..16. */
+long utx_pull_push_workspace_bytes_c(int H, int W, int C);
+int utx_pull_push_c(utx_ctx* ctx, const float* kd, const void* mask, int H, int W, int C, float* out, void* work, utx_stream stream);
+
 /* tensor_to_image (renderer_utils.py:62-83): clamp*255 -> u8 by truncation, optional vertical flip. */
 int utx_to_u8(utx_ctx* ctx, const float* src, long n_rows, long row_elems, int flip, void* dst, utx_stream stream);
 

@@ -207,6 +207,14 @@ SYMBOLS = {
     "utx_gaussian_blur_seam": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, C.POINTER(c_float), c_void_p, c_void_p]),
     "utx_pull_push_workspace_bytes": (c_long, [c_int, c_int]),
     "utx_pull_push": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "utx_backproject_vis": (c_int, [c_void_p, C.POINTER(BackprojectDesc), c_void_p, c_int, c_void_p, c_void_p]),
+    "utx_composite_winner": (c_int, [c_void_p, c_void_p, c_int, C.POINTER(c_int), c_int, c_long, c_void_p, c_void_p]),
+    "utx_gather_winner": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "utx_nn_fill_c": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
+    "utx_lens_blur_seam_c": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, C.POINTER(c_float), c_void_p, c_void_p]),
+    "utx_gaussian_blur_seam_c": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, C.POINTER(c_float), c_void_p, c_void_p]),
+    "utx_pull_push_workspace_bytes_c": (c_long, [c_int, c_int, c_int]),
+    "utx_pull_push_c": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "utx_chart_flood": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "utx_to_u8": (c_int, [c_void_p, c_void_p, c_long, c_long, c_int, c_void_p, c_void_p]),
 }

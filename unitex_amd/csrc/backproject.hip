@@ -41,6 +41,28 @@ __device__ __forceinline__ float4 tex_wrap_linear(const float4* img, int H, int 
                        lerp_nv(lerp_nv(t00.z, t10.z, fu), lerp_nv(t01.z, t11.z, fu), fv), lerp_nv(lerp_nv(t00.w, t10.w, fu), lerp_nv(t01.w, t11.w, fu), fv));
 }
 
+// the same two lookups on a one-channel plane [H][W] f32 (the visibility-only kernel's alpha): same taps, same weights, same order
+__device__ __forceinline__ float tap1(const float* img, int H, int W, int x, int y) {
+    if (x < 0 || x >= W || y < 0 || y >= H) return 0.f;
+    return img[(long)y * W + x];
+}
+// the wrap-mode taps of tex_wrap_linear for any channel count: the four tap offsets (in pixels) and the two lerp fractions; false for a non-finite coordinate
+__device__ __forceinline__ bool wrap_taps(int H, int W, float gx, float gy, long& o00, long& o10, long& o01, long& o11, float& fu, float& fv) {
+    if (!isfinite(gx) || !isfinite(gy)) return false;
+    float su = gx * 0.5f + 0.5f, sv = gy * 0.5f + 0.5f;
+    su = su - floorf(su); sv = sv - floorf(sv);
+    su = su * (float)W - 0.5f; sv = sv * (float)H - 0.5f;
+    const float fu0 = floorf(su), fv0 = floorf(sv);
+    int iu0 = (int)fu0, iv0 = (int)fv0, iu1 = iu0 + 1, iv1 = iv0 + 1;
+    fu = su - fu0; fv = sv - fv0;
+    if (iu0 < 0) iu0 += W;
+    if (iv0 < 0) iv0 += H;
+    if (iu1 >= W) iu1 -= W;
+    if (iv1 >= H) iv1 -= H;
+    o00 = (long)iv0 * W + iu0; o10 = (long)iv0 * W + iu1; o01 = (long)iv1 * W + iu0; o11 = (long)iv1 * W + iu1;
+    return true;
+}
+
 // MODE 1: stackless thread-per-ray walk over the packed tree (bvh_device.h); MODE 0: the reference's 64-entry stack walk, kept for trees deeper than
 // UTX_BVH_PACKED_MAX_DEPTH (where the reference's stack overflow quirk could matter) and for A/B tests; MODE 2 (round 4, the default): a wave owns an
 // 8 x 8 TEXEL TILE of one view and its 64 parallel rays walk the packed tree as ONE PACKET (bvh_trace_packet: nodes through the scalar cache, per-lane
@@ -49,7 +71,9 @@ __device__ __forceinline__ float4 tex_wrap_linear(const float4* img, int H, int 
 // surface point, d = (pos - eye) / max(|pos - eye|, 1e-12); the orthographic arm (one direction per view, origin 2 sqrt(3) behind the point) is unchanged.
 // SAMPLE (renderer_inverse.py:290-305, grid_interpolate_mode): 0 = grid_sample(bilinear, zero padding, align_corners=False); 1 = dr.texture(uv = ndc * 0.5 + 0.5,
 // filter_mode='linear') with nvdiffrast's default wrap boundary (its indexTextureLinear + bilerp restated below); a non-finite coordinate samples zero.
-template <int MODE, bool PERSP, int SAMPLE>
+// VIS (utx_backproject_vis, the 9-channel bake): visibility only -- p.images is the alpha plane [n][H][W] f32, p.color is not touched; the alpha expression, the ray
+// and the walk are the ones of the colour kernel, so rayvis / alphaok come out bit-identical.
+template <int MODE, bool PERSP, int SAMPLE, bool VIS = false>
 __global__ __launch_bounds__(256) void backproject_kernel(utx_backproject_desc p, const float* eyes, const int* info, const float* aabb, const float4* nodes,
                                                           const float4* tris) {
     __shared__ int pstack[MODE == 2 ? 4 * 192 : 1];      // MODE 2: the packets' DFS stacks, 64 x {node, mask lo, mask hi} per wave
@@ -70,19 +94,19 @@ __global__ __launch_bounds__(256) void backproject_kernel(utx_backproject_desc p
     const int vw = p.view_begin + blockIdx.y;
     const float4 r = inside ? ((const float4*)p.rast2d)[t] : make_float4(0.f, 0.f, 0.f, 0.f);
     const int id = (int)r.w - 1;
-    float* oc = (float*)p.color + ((long)vw * T + t) * 3;
+    float* oc = VIS ? nullptr : (float*)p.color + ((long)vw * T + t) * 3;
     unsigned char* rv = (unsigned char*)p.rayvis + (long)vw * T + t;
     unsigned char* ao = (unsigned char*)p.alphaok + (long)vw * T + t;
     if constexpr (MODE == 2) {
         if (__ballot(id >= 0) == 0) {      // nothing of this tile is covered
-            if (inside) { oc[0] = 0.f; oc[1] = 0.f; oc[2] = 0.f; *rv = 0; *ao = 0; }
+            if (inside) { if constexpr (!VIS) { oc[0] = 0.f; oc[1] = 0.f; oc[2] = 0.f; } *rv = 0; *ao = 0; }
             return;
         }
         if (id < 0) {      // an uncovered texel of a covered tile stays in the wave (the packet walk is wave-wide) with its ray switched off
-            if (inside) { oc[0] = 0.f; oc[1] = 0.f; oc[2] = 0.f; *rv = 0; *ao = 0; }
+            if (inside) { if constexpr (!VIS) { oc[0] = 0.f; oc[1] = 0.f; oc[2] = 0.f; } *rv = 0; *ao = 0; }
             return;      // (the packet walk below ballots over the lanes that are still here)
         }
-    } else if (id < 0) { oc[0] = 0.f; oc[1] = 0.f; oc[2] = 0.f; *rv = 0; *ao = 0; return; }
+    } else if (id < 0) { if constexpr (!VIS) { oc[0] = 0.f; oc[1] = 0.f; oc[2] = 0.f; } *rv = 0; *ao = 0; return; }
     const float* vert = (const float*)p.verts;
     const int* faces = (const int*)p.faces;
     const float u = r.x, v = r.y, w = (1.0f - u) - v;
@@ -113,7 +137,24 @@ __global__ __launch_bounds__(256) void backproject_kernel(utx_backproject_desc p
     const float gx = (nd[2 * (long)f0] * u + nd[2 * (long)f1] * v) + nd[2 * (long)f2] * w;
     const float gy = (nd[2 * (long)f0 + 1] * u + nd[2 * (long)f1 + 1] * v) + nd[2 * (long)f2 + 1] * w;
     const int H = p.H, W = p.W;
-    if constexpr (SAMPLE == 0) {
+    if constexpr (VIS) {
+        const float* img = (const float*)p.images + (long)vw * H * W;
+        float sa;
+        if constexpr (SAMPLE == 0) {
+            const float ix = ((gx + 1.0f) * (float)W - 1.0f) * 0.5f;
+            const float iy = ((gy + 1.0f) * (float)H - 1.0f) * 0.5f;
+            const float fx = floorf(ix), fy = floorf(iy);
+            const int x0 = (int)fx, y0 = (int)fy;
+            const float tx = ix - fx, ty = iy - fy;
+            const float w00 = (1.0f - tx) * (1.0f - ty), w01 = tx * (1.0f - ty), w10 = (1.0f - tx) * ty, w11 = tx * ty;
+            const float a = tap1(img, H, W, x0, y0), b = tap1(img, H, W, x0 + 1, y0), c = tap1(img, H, W, x0, y0 + 1), e = tap1(img, H, W, x0 + 1, y0 + 1);
+            sa = ((a * w00 + b * w01) + c * w10) + e * w11;
+        } else {
+            long o00, o10, o01, o11; float fu, fv;
+            sa = wrap_taps(H, W, gx, gy, o00, o10, o01, o11, fu, fv) ? lerp_nv(lerp_nv(img[o00], img[o10], fu), lerp_nv(img[o01], img[o11], fu), fv) : 0.f;
+        }
+        *ao = sa > 0.999f ? 1 : 0;
+    } else if constexpr (SAMPLE == 0) {
         const float ix = ((gx + 1.0f) * (float)W - 1.0f) * 0.5f;
         const float iy = ((gy + 1.0f) * (float)H - 1.0f) * 0.5f;
         const float fx = floorf(ix), fy = floorf(iy);
@@ -138,17 +179,17 @@ __global__ __launch_bounds__(256) void backproject_kernel(utx_backproject_desc p
     *rv = (hit == id && hit != -1 && cs < p.cos_thresh) ? 1 : 0;
 }
 
-template <bool PERSP, int SAMPLE>
+template <bool PERSP, int SAMPLE, bool VIS = false>
 static void launch_backproject(const utx_backproject_desc& p, const float* eyes, const utx_bvh* bvh, int depth, hipStream_t stream) {
     const long T = (long)p.T_h * p.T_w;
     dim3 grid((unsigned)((T + 255) / 256), p.view_count);
     if (depth <= UTX_BVH_PACKED_MAX_DEPTH && !g_utx_opt.bvh_stack_walk && g_utx_opt.bvh_packet) {
         dim3 gridp((unsigned)(((p.T_w + 15) / 16) * ((p.T_h + 15) / 16)), p.view_count);
-        hipLaunchKernelGGL((backproject_kernel<2, PERSP, SAMPLE>), gridp, dim3(256), 0, stream, p, eyes, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
+        hipLaunchKernelGGL((backproject_kernel<2, PERSP, SAMPLE, VIS>), gridp, dim3(256), 0, stream, p, eyes, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
     } else if (depth <= UTX_BVH_PACKED_MAX_DEPTH && !g_utx_opt.bvh_stack_walk)
-        hipLaunchKernelGGL((backproject_kernel<1, PERSP, SAMPLE>), grid, dim3(256), 0, stream, p, eyes, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
+        hipLaunchKernelGGL((backproject_kernel<1, PERSP, SAMPLE, VIS>), grid, dim3(256), 0, stream, p, eyes, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
     else
-        hipLaunchKernelGGL((backproject_kernel<0, PERSP, SAMPLE>), grid, dim3(256), 0, stream, p, eyes, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
+        hipLaunchKernelGGL((backproject_kernel<0, PERSP, SAMPLE, VIS>), grid, dim3(256), 0, stream, p, eyes, bvh->info, bvh->aabb, bvh->nodes, bvh->tris);
 }
 
 // eyes == nullptr: orthographic rays along p.dirs; otherwise [n_views][3] camera centres (perspective), p.dirs / p.two_sqrt3 unused.
@@ -165,6 +206,22 @@ extern "C" int utx_launch_backproject(const utx_backproject_desc* hp, const floa
     } else {
         if (eyes) launch_backproject<true, 1>(p, eyes, bvh, depth, stream);
         else launch_backproject<false, 1>(p, nullptr, bvh, depth, stream);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// visibility only (the 9-channel bake): p.images = alpha [n][H][W] f32, p.color unused.  Same traversal choice, same options.
+extern "C" int utx_launch_backproject_vis(const utx_backproject_desc* hp, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream) {
+    utx_backproject_desc p = *hp;
+    if (!bvh || p.T_h <= 0 || p.T_w <= 0 || p.view_count <= 0 || p.H <= 0 || p.W <= 0 || (sample != 0 && sample != 1)) return -2;
+    const int depth = utx_bvh_depth_impl(const_cast<utx_bvh*>(bvh));
+    if (depth < 0) return -7;
+    if (sample == 0) {
+        if (eyes) launch_backproject<true, 0, true>(p, eyes, bvh, depth, stream);
+        else launch_backproject<false, 0, true>(p, nullptr, bvh, depth, stream);
+    } else {
+        if (eyes) launch_backproject<true, 1, true>(p, eyes, bvh, depth, stream);
+        else launch_backproject<false, 1, true>(p, nullptr, bvh, depth, stream);
     }
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
@@ -238,5 +295,77 @@ extern "C" int utx_launch_composite(const float* colors, const void* vis, const 
     for (int i = 0; i < 8; ++i) o.v[i] = i < n_order ? order[i] : 0;
     hipLaunchKernelGGL(composite_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, stream, colors, (const unsigned char*)vis, o, T,
                        atlas, (signed char*)winner);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// the same scan without colours (the 9-channel bake): vis [n_views][T] u8 + order -> winner [T] int8
+__global__ __launch_bounds__(256) void composite_winner_kernel(const unsigned char* vis, OrderArg ord, long T, signed char* winner) {
+    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= T) return;
+    int wv = -1;
+    for (int i = 0; i < ord.n; ++i) { const int vw = ord.v[i]; if (vis[(long)vw * T + t]) { wv = vw; break; } }
+    winner[t] = (signed char)wv;
+}
+
+extern "C" int utx_launch_composite_winner(const void* vis, int n_views, const int* order, int n_order, long T, void* winner, hipStream_t stream) {
+    if (n_order <= 0 || n_order > 8 || T <= 0 || n_views <= 0) return -2;
+    OrderArg o; o.n = n_order;
+    for (int i = 0; i < 8; ++i) o.v[i] = i < n_order ? order[i] : 0;
+    for (int i = 0; i < n_order; ++i) if (o.v[i] < 0 || o.v[i] >= n_views) return -2;
+    hipLaunchKernelGGL(composite_winner_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, stream, (const unsigned char*)vis, o, T, (signed char*)winner);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// ---------------------------------------------------------------------------------------------
+// winner gather (the 9-channel bake): colour is sampled ONLY from the view that won the texel, after visibility, winner and seam -- none of which
+// reads colour -- are known.  One thread per (texel, channel) of atlas [T][C]: consecutive lanes write consecutive floats (a thread per texel would
+// store 4 C bytes at a stride of 4 C), and the C lanes of a texel read the same raster record, face and NDC (one request, broadcast) and adjacent
+// floats of each tap.  NDC as backproject_kernel computes it; taps, weights and summation order as its SAMPLE arms, per channel, so for C = 3 the atlas
+// equals utx_composite(utx_backproject) bit for bit.  images [n][H][W][C] f32; texels without a winner are written as zeros.
+// ---------------------------------------------------------------------------------------------
+template <int SAMPLE>
+__global__ __launch_bounds__(256) void gather_winner_kernel(const float4* rast2d, const int* faces, const float* vndc, const float* images, const signed char* winner,
+                                                            long T, int V, int n_views, int H, int W, int C, float* atlas) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T * C) return;
+    const long t = i / C;
+    const int ch = (int)(i - t * C);
+    const int vw = winner[t];
+    float o = 0.f;
+    const float4 r = rast2d[t];
+    const int id = (int)r.w - 1;
+    if (vw >= 0 && vw < n_views && id >= 0) {
+        const float u = r.x, v = r.y, w = (1.0f - u) - v;
+        const int f0 = faces[3 * (long)id], f1 = faces[3 * (long)id + 1], f2 = faces[3 * (long)id + 2];
+        const float* nd = vndc + (long)vw * V * 2;
+        const float gx = (nd[2 * (long)f0] * u + nd[2 * (long)f1] * v) + nd[2 * (long)f2] * w;
+        const float gy = (nd[2 * (long)f0 + 1] * u + nd[2 * (long)f1 + 1] * v) + nd[2 * (long)f2 + 1] * w;
+        const float* img = images + (long)vw * H * W * C + ch;
+        if constexpr (SAMPLE == 0) {
+            const float ix = ((gx + 1.0f) * (float)W - 1.0f) * 0.5f;
+            const float iy = ((gy + 1.0f) * (float)H - 1.0f) * 0.5f;
+            const float fx = floorf(ix), fy = floorf(iy);
+            const int x0 = (int)fx, y0 = (int)fy;
+            const float tx = ix - fx, ty = iy - fy;
+            const float w00 = (1.0f - tx) * (1.0f - ty), w01 = tx * (1.0f - ty), w10 = (1.0f - tx) * ty, w11 = tx * ty;
+            auto tap = [&](int x, int y) -> float { return (x < 0 || x >= W || y < 0 || y >= H) ? 0.f : img[((long)y * W + x) * C]; };
+            const float a = tap(x0, y0), b = tap(x0 + 1, y0), c = tap(x0, y0 + 1), e = tap(x0 + 1, y0 + 1);
+            o = ((a * w00 + b * w01) + c * w10) + e * w11;
+        } else {
+            long o00, o10, o01, o11; float fu, fv;
+            if (wrap_taps(H, W, gx, gy, o00, o10, o01, o11, fu, fv))
+                o = lerp_nv(lerp_nv(img[o00 * C], img[o10 * C], fu), lerp_nv(img[o01 * C], img[o11 * C], fu), fv);
+        }
+    }
+    atlas[i] = o;
+}
+
+extern "C" int utx_launch_gather_winner(const float* rast2d, const int* faces, const float* vndc, const float* images, const void* winner, long T, int V, int n_views,
+                                        int H, int W, int C, int sample, float* atlas, hipStream_t stream) {
+    if (T <= 0 || V <= 0 || n_views <= 0 || n_views > 127 || H <= 0 || W <= 0 || C < 1 || C > 16 || (sample != 0 && sample != 1)) return -2;
+    const long n = T * C;
+    const dim3 grid((unsigned)((n + 255) / 256));
+    if (sample == 0) hipLaunchKernelGGL(gather_winner_kernel<0>, grid, dim3(256), 0, stream, (const float4*)rast2d, faces, vndc, images, (const signed char*)winner, T, V, n_views, H, W, C, atlas);
+    else hipLaunchKernelGGL(gather_winner_kernel<1>, grid, dim3(256), 0, stream, (const float4*)rast2d, faces, vndc, images, (const signed char*)winner, T, V, n_views, H, W, C, atlas);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }

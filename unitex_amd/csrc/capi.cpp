@@ -477,6 +477,42 @@ int utx_pull_push(utx_ctx* ctx, const float* kd, const void* mask, int H, int W,
     if (!kd || !mask || !out || !work) return fail(ctx, -2, "utx_pull_push");
     UTX_CALL(ctx, "utx_pull_push", utx_launch_pull_push(kd, mask, H, W, out, work, (hipStream_t)stream));
 }
+/* ---- the C-channel (PBR stack) bake: visibility and winner without colour, one gather from the winning view, C-channel post-processing ---- */
+int utx_backproject_vis(utx_ctx* ctx, const utx_backproject_desc* d, const float* eyes, int sample_mode, utx_bvh* bvh, utx_stream stream) {
+    if (!d || !bvh || !d->rast2d || !d->verts || !d->faces || !d->fnormal || !d->vndc || (!eyes && !d->dirs) || !d->images ||
+        !d->rayvis || !d->alphaok || d->view_begin < 0 || d->view_count <= 0 || d->view_begin + d->view_count > d->n_views ||
+        (sample_mode != 0 && sample_mode != 1) || d->H <= 0 || d->W <= 0)
+        return fail(ctx, -2, "utx_backproject_vis");
+    UTX_CALL(ctx, "utx_backproject_vis", utx_launch_backproject_vis(d, eyes, sample_mode, bvh, (hipStream_t)stream));
+}
+int utx_composite_winner(utx_ctx* ctx, const void* vis, int n_views, const int* order_host, int n_order, long T, void* winner, utx_stream stream) {
+    if (!vis || !order_host || !winner) return fail(ctx, -2, "utx_composite_winner");
+    UTX_CALL(ctx, "utx_composite_winner", utx_launch_composite_winner(vis, n_views, order_host, n_order, T, winner, (hipStream_t)stream));
+}
+int utx_gather_winner(utx_ctx* ctx, const float* rast2d, const int* faces, const float* vndc, const float* images, const void* winner, long T, int V,
+                      int n_views, int H, int W, int C, int sample_mode, float* atlas, utx_stream stream) {
+    if (!rast2d || !faces || !vndc || !images || !winner || !atlas || C < 1 || C > 16) return fail(ctx, -2, "utx_gather_winner");
+    UTX_CALL(ctx, "utx_gather_winner", utx_launch_gather_winner(rast2d, faces, vndc, images, winner, T, V, n_views, H, W, C, sample_mode, atlas, (hipStream_t)stream));
+}
+int utx_nn_fill_c(utx_ctx* ctx, const float* pos, const void* winner, const float* rast2d, long T, int C, float* atlas, int* nn_index,
+                  void* work, long work_bytes, utx_stream stream) {
+    if (!pos || !winner || !rast2d || !atlas || !nn_index || !work || C < 1 || C > 16) return fail(ctx, -2, "utx_nn_fill_c");
+    UTX_CALL(ctx, "utx_nn_fill_c", utx_launch_nn_fill_c(pos, winner, rast2d, T, C, atlas, nn_index, work, (size_t)work_bytes, (hipStream_t)stream));
+}
+int utx_lens_blur_seam_c(utx_ctx* ctx, const float* src, const void* seam, int H, int W, int C, const float* k49_host, float* dst, utx_stream stream) {
+    if (!src || !seam || !k49_host || !dst || C < 1 || C > 16) return fail(ctx, -2, "utx_lens_blur_seam_c");
+    UTX_CALL(ctx, "utx_lens_blur_seam_c", utx_launch_lens_blur_seam_c(src, seam, H, W, C, k49_host, dst, (hipStream_t)stream));
+}
+int utx_gaussian_blur_seam_c(utx_ctx* ctx, const float* src, const void* seam, int H, int W, int C, int ksize, const float* w1_host, float* dst, utx_stream stream) {
+    if (!src || !seam || !w1_host || !dst || C < 1 || C > 16 || H <= 0 || W <= 0 || ksize < 1 || ksize > 31 || (ksize & 1) == 0 || ksize / 2 >= H || ksize / 2 >= W)
+        return fail(ctx, -2, "utx_gaussian_blur_seam_c");
+    UTX_CALL(ctx, "utx_gaussian_blur_seam_c", utx_launch_gaussian_blur_seam_c(src, seam, H, W, C, ksize, w1_host, dst, (hipStream_t)stream));
+}
+long utx_pull_push_workspace_bytes_c(int H, int W, int C) { return (long)utx_pull_push_workspace_bytes_c_impl(H, W, C); }
+int utx_pull_push_c(utx_ctx* ctx, const float* kd, const void* mask, int H, int W, int C, float* out, void* work, utx_stream stream) {
+    if (!kd || !mask || !out || !work || C < 1 || C > 16) return fail(ctx, -2, "utx_pull_push_c");
+    UTX_CALL(ctx, "utx_pull_push_c", utx_launch_pull_push_c(kd, mask, H, W, C, out, work, (hipStream_t)stream));
+}
 int utx_chart_flood(utx_ctx* ctx, const int* adj, const int* bucket, int F, int* chart, int* flag, utx_stream stream) {
     if (!adj || !bucket || !chart || !flag) return fail(ctx, -2, "utx_chart_flood");
     const int rc = utx_launch_chart_flood(adj, bucket, F, chart, flag, (hipStream_t)stream);

@@ -163,6 +163,8 @@ __global__ __launch_bounds__(256) void nn_bounds_kernel(const unsigned* keys, co
     const int j = vals[i];
     spos[i] = make_float4(pos[3 * (long)j], pos[3 * (long)j + 1], pos[3 * (long)j + 2], __int_as_float(j));
 }
+// COPY3 false (utx_nn_fill_c): the search alone -- nn_index is the result, the C-channel copy is nn_copy_c_kernel's
+template <bool COPY3>
 __global__ __launch_bounds__(256) void nn_query_kernel(const float* pos, const signed char* winner, const float4* rast2d, long T,
                                                        const float4* __restrict__ spos, const int* __restrict__ cell_start, const int* __restrict__ cell_end,
                                                        float* atlas, int* nn_index, int NN_G) {
@@ -222,7 +224,7 @@ __global__ __launch_bounds__(256) void nn_query_kernel(const float* pos, const s
         const float rr = (float)r * cs;
         if (bi >= 0 && best < rr * rr * 0.99999f) break;
     }
-    if (bi >= 0) { atlas[3 * t] = atlas[3 * (long)bi]; atlas[3 * t + 1] = atlas[3 * (long)bi + 1]; atlas[3 * t + 2] = atlas[3 * (long)bi + 2]; }
+    if constexpr (COPY3) { if (bi >= 0) { atlas[3 * t] = atlas[3 * (long)bi]; atlas[3 * t + 1] = atlas[3 * (long)bi + 1]; atlas[3 * t + 2] = atlas[3 * (long)bi + 2]; } }
     if (nn_index) nn_index[t] = bi;
 }
 
@@ -233,8 +235,18 @@ extern "C" size_t utx_nn_fill_workspace_bytes_impl(long T) {
     return (size_t)T * 16 + (size_t)T * 16 + NN_G * NN_G * NN_G * 8 + tmp + 512;
 }
 
-extern "C" int utx_launch_nn_fill(const float* pos, const void* winner, const float* rast2d, long T, float* atlas, int* nn_index,
-                                  void* work, size_t work_bytes, hipStream_t stream) {
+// atlas [T][C], one thread per float: texels the search gave a source copy its C floats (sources are seen texels, targets unseen ones: no overlap)
+__global__ __launch_bounds__(256) void nn_copy_c_kernel(const int* nn_index, long T, int C, float* atlas) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= T * C) return;
+    const long t = i / C;
+    const int bi = nn_index[t];
+    if (bi >= 0) atlas[i] = atlas[(long)bi * C + (i - t * C)];
+}
+
+// C == 0: the 3-channel fill (the copy inside the query kernel); C >= 1: search once into nn_index (required), then the C-channel copy
+static int nn_fill_any(const float* pos, const void* winner, const float* rast2d, long T, int C, float* atlas, int* nn_index,
+                       void* work, size_t work_bytes, hipStream_t stream) {
     if (T <= 0) return -2;
     if (work_bytes < utx_nn_fill_workspace_bytes_impl(T)) return -2;
     const int NN_G = nn_grid(T);
@@ -250,9 +262,24 @@ extern "C" int utx_launch_nn_fill(const float* pos, const void* winner, const fl
     hipLaunchKernelGGL(nn_keys_kernel, dim3(nb), dim3(256), 0, stream, pos, (const signed char*)winner, T, keys, vals, NN_G);
     if (rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_s, vals, vals_s, (size_t)T, 0, 32, stream) != hipSuccess) return -7;
     hipLaunchKernelGGL(nn_bounds_kernel, dim3(nb), dim3(256), 0, stream, keys_s, vals_s, pos, T, cell_start, cell_end, spos);
-    hipLaunchKernelGGL(nn_query_kernel, dim3(nb), dim3(256), 0, stream, pos, (const signed char*)winner, (const float4*)rast2d, T, spos,
-                       cell_start, cell_end, atlas, nn_index, NN_G);
+    if (C == 0) {
+        hipLaunchKernelGGL(nn_query_kernel<true>, dim3(nb), dim3(256), 0, stream, pos, (const signed char*)winner, (const float4*)rast2d, T, spos,
+                           cell_start, cell_end, atlas, nn_index, NN_G);
+    } else {
+        hipLaunchKernelGGL(nn_query_kernel<false>, dim3(nb), dim3(256), 0, stream, pos, (const signed char*)winner, (const float4*)rast2d, T, spos,
+                           cell_start, cell_end, atlas, nn_index, NN_G);
+        hipLaunchKernelGGL(nn_copy_c_kernel, dim3((unsigned)((T * C + 255) / 256)), dim3(256), 0, stream, (const int*)nn_index, T, C, atlas);
+    }
     return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+extern "C" int utx_launch_nn_fill(const float* pos, const void* winner, const float* rast2d, long T, float* atlas, int* nn_index,
+                                  void* work, size_t work_bytes, hipStream_t stream) {
+    return nn_fill_any(pos, winner, rast2d, T, 0, atlas, nn_index, work, work_bytes, stream);
+}
+extern "C" int utx_launch_nn_fill_c(const float* pos, const void* winner, const float* rast2d, long T, int C, float* atlas, int* nn_index,
+                                    void* work, size_t work_bytes, hipStream_t stream) {
+    if (C < 1 || C > 16 || !nn_index) return -2;
+    return nn_fill_any(pos, winner, rast2d, T, C, atlas, nn_index, work, work_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -290,6 +317,35 @@ extern "C" int utx_launch_lens_blur_seam(const float* src, const void* seam, int
     if (T <= 0 || !k49_host) return -2;
     BlurK K; for (int i = 0; i < 49; ++i) K.k[i] = k49_host[i];
     hipLaunchKernelGGL(lens_blur_seam_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, stream, src, (const unsigned char*)seam, Hh, Ww, K, dst);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// C channels, one thread per float of src / dst [H][W][C] (depthwise, as lens_blur_torch: groups = channels): the per-channel expression is the one above
+__global__ __launch_bounds__(256) void lens_blur_seam_c_kernel(const float* src, const unsigned char* seam, int Hh, int Ww, int C, BlurK K, float* dst) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)Hh * Ww * C) return;
+    const long t = i / C;
+    const int ch = (int)(i - t * C);
+    float o = src[i];
+    if (seam[t]) {
+        const int y = (int)(t / Ww), x = (int)(t % Ww);
+        float a = 0.f;
+        for (int dy = -3; dy <= 3; ++dy) for (int dx = -3; dx <= 3; ++dx) {
+            const int yy = y + dy, xx = x + dx;
+            if (yy < 0 || yy >= Hh || xx < 0 || xx >= Ww) continue;
+            const float kk = K.k[(dy + 3) * 7 + (dx + 3)];
+            const float c0 = src[((long)yy * Ww + xx) * C + ch];
+            a = a + kk * (((c0 * c0) * (c0 * c0)) * c0);
+        }
+        o = fminf(fmaxf(powf(fmaxf(a, 0.f), 0.2f), 0.f), 1.f);
+    }
+    dst[i] = o;
+}
+extern "C" int utx_launch_lens_blur_seam_c(const float* src, const void* seam, int Hh, int Ww, int C, const float* k49_host, float* dst, hipStream_t stream) {
+    const long n = (long)Hh * Ww * C;
+    if (Hh <= 0 || Ww <= 0 || C < 1 || C > 16 || !k49_host) return -2;
+    BlurK K; for (int i = 0; i < 49; ++i) K.k[i] = k49_host[i];
+    hipLaunchKernelGGL(lens_blur_seam_c_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, src, (const unsigned char*)seam, Hh, Ww, C, K, dst);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
@@ -337,6 +393,40 @@ extern "C" int utx_launch_gaussian_blur_seam(const float* src, const void* seam,
     GaussK K;
     for (int i = 0; i < 31; ++i) K.w[i] = i < ksize ? w1_host[i] : 0.f;
     hipLaunchKernelGGL(gaussian_blur_seam_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, stream, src, (const unsigned char*)seam, Hh, Ww, r, K, dst);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// C channels, one thread per float (depthwise, as gaussian_blur): the same taps, weights and fp64 sum per channel
+__global__ __launch_bounds__(256) void gaussian_blur_seam_c_kernel(const float* src, const unsigned char* seam, int Hh, int Ww, int C, int r, GaussK K, float* dst) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)Hh * Ww * C) return;
+    const long t = i / C;
+    const int ch = (int)(i - t * C);
+    float o = src[i];
+    if (seam[t]) {
+        const int y = (int)(t / Ww), x = (int)(t % Ww);
+        double a = 0.0;
+        for (int dy = -r; dy <= r; ++dy) {
+            const int yy = reflect_idx(y + dy, Hh);
+            const float wy = K.w[dy + r];
+            for (int dx = -r; dx <= r; ++dx) {
+                const int xx = reflect_idx(x + dx, Ww);
+                const double kk = (double)(wy * K.w[dx + r]);
+                a = a + kk * (double)src[((long)yy * Ww + xx) * C + ch];
+            }
+        }
+        o = (float)a;
+    }
+    dst[i] = o;
+}
+extern "C" int utx_launch_gaussian_blur_seam_c(const float* src, const void* seam, int Hh, int Ww, int C, int ksize, const float* w1_host, float* dst, hipStream_t stream) {
+    if (Hh <= 0 || Ww <= 0 || C < 1 || C > 16 || !w1_host || ksize < 1 || ksize > 31 || (ksize & 1) == 0) return -2;
+    const int r = ksize / 2;
+    if (r >= Hh || r >= Ww) return -2;
+    const long n = (long)Hh * Ww * C;
+    GaussK K;
+    for (int i = 0; i < 31; ++i) K.w[i] = i < ksize ? w1_host[i] : 0.f;
+    hipLaunchKernelGGL(gaussian_blur_seam_c_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, src, (const unsigned char*)seam, Hh, Ww, C, r, K, dst);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
@@ -422,6 +512,90 @@ extern "C" int utx_launch_pull_push(const float* kd, const void* mask, int Hh, i
     for (int l = n - 1; l >= 0; --l) {
         const long px = (long)hs[l] * wsz[l];
         hipLaunchKernelGGL(pp_push_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, stream, kds[l], ms[l], hs[l], wsz[l], l == 0 ? 1 : 0, cur, fill[l]);
+        cur = fill[l];
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// C channels, colour interleaved [h][w][C], one thread per float (depthwise, as the reference's pull_push); per channel the expressions of the two kernels above.
+__global__ __launch_bounds__(256) void pp_pull_c_kernel(const float* kd, const unsigned char* mask, int Hh, int Ww, int C, int zero_outside,
+                                                        float* kd_mip, unsigned char* mask_mip) {
+    const int h2 = Hh / 2, w2 = Ww / 2;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)h2 * w2 * C) return;
+    const long t = i / C;
+    const int c = (int)(i - t * C);
+    const int y = (int)(t / w2), x = (int)(t % w2);
+    float a = 0.f, k = 0.f;
+    for (int dy = 0; dy < 2; ++dy) for (int dx = 0; dx < 2; ++dx) {
+        const long q = (long)(2 * y + dy) * Ww + (2 * x + dx);
+        const float m = mask[q] ? 1.0f : 0.0f;
+        a = a + m;
+        const float vv = (zero_outside && !mask[q]) ? 0.f : kd[q * C + c];
+        k = k + vv;
+    }
+    a = a * 0.25f;
+    k = k * 0.25f;
+    if (a > 0.f && a < 1.f) k = k / a;
+    kd_mip[i] = k;
+    if (c == 0) mask_mip[t] = a > 0.f ? 1 : 0;
+}
+__global__ __launch_bounds__(256) void pp_push_c_kernel(const float* kd, const unsigned char* mask, int Hh, int Ww, int C, const float* kd_mip, float* out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (long)Hh * Ww * C) return;
+    const long t = i / C;
+    const int c = (int)(i - t * C);
+    if (mask[t]) { out[i] = kd[i]; return; }
+    const int y = (int)(t / Ww), x = (int)(t % Ww);
+    const int h2 = Hh / 2, w2 = Ww / 2;
+    const int ii = y >> 1, j = x >> 1, py = y & 1, px = x & 1;
+    const int iy = py ? min(ii + 1, h2 - 1) : max(ii - 1, 0);
+    const int jx = px ? min(j + 1, w2 - 1) : max(j - 1, 0);
+    const float c_ = kd_mip[((long)ii * w2 + j) * C + c], cx = kd_mip[((long)ii * w2 + jx) * C + c];
+    const float cy = kd_mip[((long)iy * w2 + j) * C + c], cxy = kd_mip[((long)iy * w2 + jx) * C + c];
+    const float w9 = 0.5625f, w3 = 0.1875f, w1 = 0.0625f;
+    float r;
+    if (!py && !px) r = ((cxy * w1 + cy * w3) + cx * w3) + c_ * w9;
+    else if (!py && px) r = ((cy * w3 + cxy * w1) + c_ * w9) + cx * w3;
+    else if (py && !px) r = ((cx * w3 + c_ * w9) + cxy * w1) + cy * w3;
+    else r = ((c_ * w9 + cx * w3) + cy * w3) + cxy * w1;
+    out[i] = r;
+}
+
+extern "C" size_t utx_pull_push_workspace_bytes_c_impl(int Hh, int Ww, int C) {
+    if (C < 1 || C > 16) return 0;
+    size_t tot = 0;
+    int h = Hh, w = Ww;
+    for (int l = 0; l < 32 && h >= 2 && w >= 2; ++l) { h /= 2; w /= 2; tot += (size_t)h * w * (2 * 4 * (size_t)C + 1) + 64; }
+    return tot + 256;
+}
+
+extern "C" int utx_launch_pull_push_c(const float* kd, const void* mask, int Hh, int Ww, int C, float* out, void* work, hipStream_t stream) {
+    if (Hh <= 0 || Ww <= 0 || C < 1 || C > 16) return -2;
+    int n = 0;
+    { int lh = 0, lw = 0; while ((1 << (lh + 1)) <= Hh) ++lh; while ((1 << (lw + 1)) <= Ww) ++lw; n = (lh < lw ? lh : lw) - 2; if (n < 0) n = 0; }
+    const long T = (long)Hh * Ww;
+    if (n == 0) { return hipMemcpyAsync(out, kd, T * 4 * C, hipMemcpyDeviceToDevice, stream) == hipSuccess ? 0 : -7; }
+    if (n > 16) return -2;
+    float* kds[17]; float* fill[17]; unsigned char* ms[17]; int hs[17], wsz[17];
+    char* p = (char*)work;
+    hs[0] = Hh; wsz[0] = Ww; kds[0] = (float*)kd; ms[0] = (unsigned char*)mask; fill[0] = out;
+    for (int l = 1; l <= n; ++l) {
+        hs[l] = hs[l - 1] / 2; wsz[l] = wsz[l - 1] / 2;
+        const size_t px = (size_t)hs[l] * wsz[l];
+        kds[l] = (float*)p; p += px * 4 * C;
+        fill[l] = (float*)p; p += px * 4 * C;
+        ms[l] = (unsigned char*)p; p += (px + 63) & ~(size_t)63;
+    }
+    for (int l = 1; l <= n; ++l) {
+        const long px = (long)hs[l] * wsz[l] * C;
+        hipLaunchKernelGGL(pp_pull_c_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, stream, kds[l - 1], ms[l - 1], hs[l - 1], wsz[l - 1], C,
+                           l == 1 ? 1 : 0, kds[l], ms[l]);
+    }
+    const float* cur = kds[n];
+    for (int l = n - 1; l >= 0; --l) {
+        const long px = (long)hs[l] * wsz[l] * C;
+        hipLaunchKernelGGL(pp_push_c_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, stream, kds[l], ms[l], hs[l], wsz[l], C, cur, fill[l]);
         cur = fill[l];
     }
     return hipGetLastError() == hipSuccess ? 0 : -4;

@@ -164,20 +164,30 @@ def unify_uv_indexing(verts, faces, uvs, faces_uv):
     return verts[vi], inv.reshape(-1, 3).astype(np.int32), uvs[ti]
 
 
-def save_glb(path, verts, faces, uvs, texture_rgb_u8):
+def save_glb(path, verts, faces, uvs, texture_rgb_u8, metallic_roughness_u8=None, bump_u8=None):
     """Minimal glTF 2.0 binary with one textured primitive (PBR metallic 0 / roughness 1, as
-    link_rgb_to_mesh sets them: io/link_pbr_to_mesh.py:16-23).  texture row 0 = top of the image."""
+    link_rgb_to_mesh sets them: io/link_pbr_to_mesh.py:16-23).  texture row 0 = top of the image.
+    With metallic_roughness_u8 and bump_u8 (both or neither; the 9-channel bake) the material is link_pbr_to_mesh's (io/link_pbr_to_mesh.py:34-60):
+    baseColorTexture, metallicRoughnessTexture and normalTexture, and no baseColorFactor / metallicFactor / roughnessFactor (the reference passes None for
+    all three, so glTF's defaults apply).  Without them the file is byte for byte what it always was."""
     import io
     from PIL import Image
-    buf = io.BytesIO()
-    Image.fromarray(texture_rgb_u8).save(buf, format="PNG", compress_level=int(os.environ.get("UTX_PNG_LEVEL", "1")))      # lossless either way; level 6 costs 5x the time
-    png = buf.getvalue()
+    if (metallic_roughness_u8 is None) != (bump_u8 is None):
+        raise ValueError("save_glb: metallic_roughness_u8 and bump_u8 go together (link_pbr_to_mesh takes all three textures)")
+    pngs = []
+    for img in (texture_rgb_u8, metallic_roughness_u8, bump_u8):
+        if img is None:
+            continue
+        buf = io.BytesIO()
+        Image.fromarray(img).save(buf, format="PNG", compress_level=int(os.environ.get("UTX_PNG_LEVEL", "1")))      # lossless either way; level 6 costs 5x the time
+        pngs.append(buf.getvalue())
+    png = pngs[0]
     v = np.ascontiguousarray(verts, dtype=np.float32)
     t = np.ascontiguousarray(np.stack([uvs[:, 0], 1.0 - uvs[:, 1]], -1), dtype=np.float32)  # glTF v is top-down
     idx = np.ascontiguousarray(faces, dtype=np.uint32).reshape(-1)
     chunks, offs = [], []
     pos = 0
-    for b in (v.tobytes(), t.tobytes(), idx.tobytes(), png):
+    for b in [v.tobytes(), t.tobytes(), idx.tobytes(), png] + pngs[1:]:
         pad = (-len(b)) % 4
         offs.append((pos, len(b)))
         chunks.append(b + b"\x00" * pad)
@@ -201,6 +211,12 @@ def save_glb(path, verts, faces, uvs, texture_rgb_u8):
                       {"bufferView": 1, "componentType": 5126, "count": int(t.shape[0]), "type": "VEC2"},
                       {"bufferView": 2, "componentType": 5125, "count": int(idx.shape[0]), "type": "SCALAR"}],
     }
+    if len(pngs) == 3:
+        gltf["materials"] = [{"pbrMetallicRoughness": {"baseColorTexture": {"index": 0}, "metallicRoughnessTexture": {"index": 1}},
+                              "normalTexture": {"index": 2}}]
+        gltf["textures"] = [{"source": i, "sampler": 0} for i in range(3)]
+        gltf["images"] = [{"bufferView": 3 + i, "mimeType": "image/png"} for i in range(3)]
+        gltf["bufferViews"] += [{"buffer": 0, "byteOffset": offs[4 + i][0], "byteLength": offs[4 + i][1]} for i in range(2)]
     js = json.dumps(gltf, separators=(",", ":")).encode()
     js += b" " * ((-len(js)) % 4)
     with open(path, "wb") as f:
@@ -224,6 +240,12 @@ _GLTF_NCOMP = {"SCALAR": 1, "VEC2": 2, "VEC3": 3, "VEC4": 4, "MAT4": 16}
 def load_glb(path):
     """glTF 2.0 binary reader: all triangle primitives of all meshes (node transforms applied), merged.
     Returns verts [V,3] f32, faces [F,3] i32, uvs [V,2] f32 in [0,1] with v bottom-up | None, texture u8 [H,W,3] | None."""
+    js, binc = _glb_chunks(path)
+    return _gltf_scene_to_mesh(js, path, binc)
+
+
+def _glb_chunks(path):
+    """the JSON chunk (parsed) and the BIN chunk of a .glb"""
     with open(path, "rb") as f:
         blob = f.read()
     magic, version, total = struct.unpack_from("<III", blob, 0)
@@ -238,7 +260,42 @@ def load_glb(path):
         elif ctype == 0x004E4942:
             binc = data
         off += 8 + clen + ((-clen) % 4)
-    return _gltf_scene_to_mesh(js, path, binc)
+    return js, binc
+
+
+def load_material_textures(path, material=0):
+    """the textures of one material of a .glb / .gltf, for callers of load_mesh that want more than the base colour:
+    {"base_color", "metallic_roughness", "normal": uint8 [H,W,3] (row 0 = top of the image) | None, "material": the material's JSON object}."""
+    import io
+    from PIL import Image
+    if path.lower().endswith(".glb"):
+        js, binc = _glb_chunks(path)
+    else:
+        with open(path, "r", encoding="utf-8") as f:
+            js, binc = json.load(f), None
+    mat = js["materials"][material]
+    bufs = {}
+
+    def buffer(i):
+        if i not in bufs:
+            b = js["buffers"][i]
+            bufs[i] = _gltf_uri_bytes(b["uri"], path) if "uri" in b else binc
+        return bufs[i]
+
+    def texture(ref):
+        if ref is None:
+            return None
+        img = js["images"][js["textures"][ref["index"]]["source"]]
+        if "bufferView" in img:
+            bv = js["bufferViews"][img["bufferView"]]
+            o = bv.get("byteOffset", 0)
+            data = buffer(bv.get("buffer", 0))[o: o + bv["byteLength"]]
+        else:
+            data = _gltf_uri_bytes(img["uri"], path)
+        return np.asarray(Image.open(io.BytesIO(data)).convert("RGB"))
+    pbr = mat.get("pbrMetallicRoughness", {})
+    return {"base_color": texture(pbr.get("baseColorTexture")), "metallic_roughness": texture(pbr.get("metallicRoughnessTexture")),
+            "normal": texture(mat.get("normalTexture")), "material": mat}
 
 
 def _gltf_uri_bytes(uri, path):

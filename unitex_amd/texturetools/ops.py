@@ -429,6 +429,114 @@ def pull_push(kd, mask):
     return out
 
 
+# ---- the C-channel (PBR stack) bake: visibility and winner without colour, one gather from the winning view, C-channel post-processing.
+# Every image is interleaved [..., C] f32, 1 <= C <= CHANNELS_MAX; channels [3g, 3g+3) of a result equal the 3-channel function's result on that group.
+CHANNELS_MAX = 16
+
+
+def backproject_vis(rast2d, verts, faces, fnormal, vndc, dirs, alpha, bvh, angle_deg=100.0, view_begin=0, view_count=None, out=None, eyes=None,
+                    sample="grid"):
+    """backproject() without the colour gather (utx_backproject_vis): alpha [n,H,W] f32 is the plane the texels sample.
+    Returns rayvis, alphaok [n,Th,Tw] u8 -- bit-identical to backproject()'s on images whose fourth channel is alpha."""
+    assert sample in ("grid", "nvdiff"), "sample must be 'grid' or 'nvdiff', not %r" % (sample,)
+    ctx = get_ctx(rast2d.device.index)
+    Th, Tw = rast2d.shape[:2]
+    n, H, W = alpha.shape
+    dev = rast2d.device
+    if out is None:
+        rayvis = torch.zeros(n, Th, Tw, dtype=U8, device=dev)
+        alphaok = torch.zeros(n, Th, Tw, dtype=U8, device=dev)
+    else:
+        rayvis, alphaok = out
+    d = BackprojectDesc()
+    d.rast2d, d.verts, d.faces, d.fnormal = ptr(_f(rast2d)), ptr(_f(verts)), ptr(_i(faces)), ptr(_f(fnormal))
+    d.vndc, d.images = ptr(_f(vndc)), ptr(_f(alpha))
+    if eyes is None:
+        d.dirs = ptr(_f(dirs))
+    else:
+        assert eyes.shape == (n, 3)
+    d.rayvis, d.alphaok = ptr(rayvis), ptr(alphaok)
+    d.T_h, d.T_w, d.V, d.n_views, d.H, d.W = Th, Tw, verts.shape[0], n, H, W
+    d.view_begin, d.view_count = view_begin, (n - view_begin if view_count is None else view_count)
+    d.cos_thresh = float(np.float32(math.cos(math.radians(angle_deg))))
+    d.two_sqrt3 = float(np.float32(2.0 * math.sqrt(3.0)))
+    ctx.check(ctx.lib.utx_backproject_vis(ctx.handle, C.byref(d), None if eyes is None else ptr(_f(eyes)), 1 if sample == "nvdiff" else 0, bvh.handle,
+                                          ctx.stream()))
+    return rayvis, alphaok
+
+
+def composite_winner(vis, order):
+    """vis [n,H,W] u8 -> winner [H,W] int8: the first view of `order` that sees the texel, -1 where none does (composite() without colours)"""
+    ctx = get_ctx(vis.device.index)
+    n, H, W = vis.shape
+    assert vis.dtype == U8 and vis.is_contiguous()
+    winner = torch.empty(H, W, dtype=torch.int8, device=vis.device)
+    arr = (C.c_int * len(order))(*order)
+    ctx.check(ctx.lib.utx_composite_winner(ctx.handle, ptr(vis), n, arr, len(order), H * W, ptr(winner), ctx.stream()))
+    return winner
+
+
+def gather_winner(rast2d, faces, vndc, images, winner, sample="grid"):
+    """atlas [Th,Tw,C]: images [n,H,W,C] sampled at every texel's NDC in its winning view (zeros where winner < 0), as backproject() samples"""
+    assert sample in ("grid", "nvdiff"), "sample must be 'grid' or 'nvdiff', not %r" % (sample,)
+    ctx = get_ctx(rast2d.device.index)
+    Th, Tw = rast2d.shape[:2]
+    n, H, W, Cc = images.shape
+    assert vndc.shape[0] == n and winner.shape == (Th, Tw) and winner.dtype == torch.int8 and winner.is_contiguous()
+    atlas = torch.empty(Th, Tw, Cc, dtype=F32, device=rast2d.device)
+    ctx.check(ctx.lib.utx_gather_winner(ctx.handle, ptr(_f(rast2d)), ptr(_i(faces)), ptr(_f(vndc)), ptr(_f(images)), ptr(winner), Th * Tw, vndc.shape[1], n,
+                                        H, W, Cc, 1 if sample == "nvdiff" else 0, ptr(atlas), ctx.stream()))
+    return atlas
+
+
+def nn_fill_c(atlas, winner, rast2d, pos):
+    """nn_fill() in place on atlas [H,W,C]; returns the search's nn_index [H*W] i32"""
+    ctx = get_ctx(atlas.device.index)
+    H, W = winner.shape
+    T = H * W
+    wb = ctx.lib.utx_nn_fill_workspace_bytes(T)
+    work = torch.empty(wb, dtype=U8, device=atlas.device)
+    idx = torch.empty(T, dtype=I32, device=atlas.device)
+    ctx.check(ctx.lib.utx_nn_fill_c(ctx.handle, ptr(_f(pos)), ptr(winner), ptr(_f(rast2d)), T, atlas.shape[-1], ptr(_f(atlas)), ptr(idx), ptr(work), wb,
+                                    ctx.stream()))
+    return idx
+
+
+def lens_blur_seam_c(src, seam, k49=None):
+    """lens_blur_seam() on src [H,W,C]"""
+    ctx = get_ctx(src.device.index)
+    H, W = seam.shape
+    if k49 is None:
+        k49 = lens_blur_kernel49()
+    arr = (C.c_float * 49)(*[float(x) for x in np.asarray(k49, dtype=np.float32).reshape(-1)])
+    dst = torch.empty_like(src)
+    ctx.check(ctx.lib.utx_lens_blur_seam_c(ctx.handle, ptr(_f(src)), ptr(seam), H, W, src.shape[-1], arr, ptr(dst), ctx.stream()))
+    return dst
+
+
+def gaussian_blur_seam_c(src, seam, ksize=5):
+    """gaussian_blur_seam() on src [H,W,C]"""
+    ctx = get_ctx(src.device.index)
+    H, W = seam.shape
+    w1 = gaussian_kernel1d(int(ksize))
+    arr = (C.c_float * int(ksize))(*[float(x) for x in w1.numpy()])
+    dst = torch.empty_like(src)
+    ctx.check(ctx.lib.utx_gaussian_blur_seam_c(ctx.handle, ptr(_f(src)), ptr(seam), H, W, src.shape[-1], int(ksize), arr, ptr(dst), ctx.stream()))
+    return dst
+
+
+def pull_push_c(kd, mask):
+    """pull_push() on kd [H,W,C]"""
+    ctx = get_ctx(kd.device.index)
+    H, W = mask.shape
+    Cc = kd.shape[-1]
+    wb = ctx.lib.utx_pull_push_workspace_bytes_c(H, W, Cc)
+    work = torch.empty(max(wb, 1), dtype=U8, device=kd.device)
+    out = torch.empty_like(kd)
+    ctx.check(ctx.lib.utx_pull_push_c(ctx.handle, ptr(_f(kd)), ptr(mask), H, W, Cc, ptr(out), ptr(work), ctx.stream()))
+    return out
+
+
 def to_u8(img, flip=False):
     ctx = get_ctx(img.device.index)
     rows = img.shape[0]

@@ -15,6 +15,11 @@ UV-space raster, fused gather + LBVH visibility, hole filling, priority composit
 NN fill, seam lens blur, pull-push, uint8 conversion.  No [6,2048,2048,3] intermediates other than the
 per-view colour layers that the composite (and, multi-GPU, the all-gather) consumes.
 
+Nine channels (the PBR stack: albedo 0:3, metallic-roughness 3:6, bump 6:9; renderer_inverse.py:716-721) with method='reproject' take a path of
+their own, because nothing in visibility, winner, seam or the nearest-neighbour search reads colour: visibility-only back-projection, winner from
+visibility, seam, then ONE gather of the nine channels from each texel's winning view, and C-channel fill / blur / pull-push.  No per-view colour
+layer exists on that path, and a view shard exchanges the u8 visibility layers only.
+
 Multi-GPU: views are sharded over ranks (`view_shard=(rank, world)`); each rank fills its
 views' colour/visibility layers, ONE all_gather (RCCL over xGMI, or gloo in the CPU tests) assembles the
 layers, and the composite + post-processing run replicated on every rank.
@@ -86,22 +91,47 @@ def load_device_mesh(path, device):
     return DeviceMesh(verts, faces, uvs, device)
 
 
-class TexturedMesh:
-    """what infer() returns in place of a trimesh.Trimesh: exposes .export(path) for .glb / .obj."""
+def _check_channels(shape):
+    """the reference bakes rgb or the 9-channel PBR stack with either method and refuses anything else (renderer_inverse.py:709-724)"""
+    if shape[-1] not in (3, 9):
+        raise NotImplementedError("shape %s is not supported" % (torch.Size(shape),))
 
-    def __init__(self, verts, faces, uvs01, texture_u8_top_down):
+
+class TexturedMesh:
+    """what infer() returns in place of a trimesh.Trimesh: exposes .export(path) for .glb / .obj.
+    .texture is the albedo (uint8 [H,W,3], top row first, i.e. already flipped as link_rgb_to_mesh / link_pbr_to_mesh flip it).  A 9-channel bake also
+    carries .metallic_roughness and .bump, converted and flipped the same way (link_pbr_to_mesh, io/link_pbr_to_mesh.py:34-60); both are None for an
+    rgb bake.  link_*_to_mesh's merge_vertices / fix_normals are trimesh calls on its own mesh object and are not reproduced: vertices, faces and UVs
+    are the blank mesh's, unchanged.
+    export('.glb') writes the three images as baseColorTexture / metallicRoughnessTexture / normalTexture with no factors (the reference passes None for
+    all three, so glTF's defaults apply).  export('.obj') writes <base>.png, <base>_metallic_roughness.png and <base>_bump.png and names them in the
+    .mtl as map_Kd / map_Pm / map_Bump; trimesh's own .mtl keys for a PBRMaterial are third-party code that is not available here, so the two extra
+    keys are this build's choice."""
+
+    def __init__(self, verts, faces, uvs01, texture_u8_top_down, metallic_roughness=None, bump=None):
         self.vertices, self.faces, self.uv, self.texture = verts, faces, uvs01, texture_u8_top_down
+        self.metallic_roughness, self.bump = metallic_roughness, bump
 
     def export(self, path):
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        pbr = self.metallic_roughness is not None
         if path.lower().endswith(".glb"):
-            meshes.save_glb(path, self.vertices, self.faces, self.uv, self.texture)
+            if pbr:
+                meshes.save_glb(path, self.vertices, self.faces, self.uv, self.texture, metallic_roughness_u8=self.metallic_roughness, bump_u8=self.bump)
+            else:
+                meshes.save_glb(path, self.vertices, self.faces, self.uv, self.texture)
         else:
             from PIL import Image
             base = os.path.splitext(path)[0]
-            Image.fromarray(self.texture).save(base + ".png", compress_level=int(os.environ.get("UTX_PNG_LEVEL", "1")))
+            level = int(os.environ.get("UTX_PNG_LEVEL", "1"))
+            Image.fromarray(self.texture).save(base + ".png", compress_level=level)
+            mtl = "newmtl material_0\nmap_Kd %s\n" % os.path.basename(base + ".png")
+            if pbr:
+                for key, suffix, img in (("map_Pm", "_metallic_roughness", self.metallic_roughness), ("map_Bump", "_bump", self.bump)):
+                    Image.fromarray(img).save(base + suffix + ".png", compress_level=level)
+                    mtl += "%s %s\n" % (key, os.path.basename(base + suffix + ".png"))
             with open(base + ".mtl", "w") as f:
-                f.write("newmtl material_0\nmap_Kd %s\n" % os.path.basename(base + ".png"))
+                f.write(mtl)
             meshes.save_obj(path, self.vertices, self.faces, self.uv, mtl=os.path.basename(base + ".mtl"))
         return path
 
@@ -250,12 +280,19 @@ class NVDiffRendererInverse:
         """renderer_inverse.py:635-726.  method='reproject' is bake_mv_to_uv_reproject_blur (the pipeline's path),
         method='kdtree' bake_mv_to_uv_kdtree ('order_mean' | 'mean' | 'mvpaint'); *_inpainting=True routes the unseen texels
         through the registered query field (the LTM hook) instead of the nearest-neighbour fill; filt_gradient_points adds
-        the gradient / facing filter to the view masks.  Colours: 3 channels (rgb) or 9 (PBR stack) for 'kdtree', 3 for 'reproject'.
+        the gradient / facing filter to the view masks.  Colours: 3 channels (rgb) or 9 (PBR stack: albedo, metallic-roughness, bump) for both methods;
+        nine channels return a TexturedMesh with .metallic_roughness and .bump, and with method='reproject' refuse return_layers=True (that path has no
+        per-view colour layers).
         grid_interpolate_mode 'torch' | 'pytorch' samples the views as grid_sample (zero padding), 'nvdiff' | 'nvdiffrast' as nvdiffrast's
         linear dr.texture (wrap boundary).  reproject_method 'lens' | 'gaussian' picks the seam blur; the seam is the winner boundary within
         reproject_kernel_size_boundary // 2, dilated by reproject_kernel_size_boundary_blur // 2 (both radii <= 15), and 'gaussian' blurs it with
         torchvision's gaussian_blur at reproject_kernel_size_blur (odd, <= 31; 'lens' ignores the size, as the reference does)."""
         assert method in ("kdtree", "reproject")
+        _check_channels(image_attrs.shape)
+        stack = method == "reproject" and image_attrs.shape[-1] != 3      # the 9-channel path: colour gathered from the winning view only
+        if stack and return_layers:
+            raise NotImplementedError("infer(return_layers=True) with %d channels and method='reproject': that path gathers colour from the winning view "
+                                      "only, the per-view colour layers do not exist" % image_attrs.shape[-1])
         t_host0 = time.perf_counter()
         # keyword arguments of the reference's signature (renderer_inverse.py:635-659) that this build fixes at the value the pipeline uses: anything else is
         # refused, not dropped
@@ -282,7 +319,7 @@ class NVDiffRendererInverse:
                                 ray_normal_angle_threhold=ray_normal_angle_threhold, filt_gradient_points=filt_gradient_points,
                                 want_points=(method == "kdtree"))
         # the alpha channel the texels sample is mask_visiable (uv_to_pcd(alpha_attrs=alpha_visiable), :661-670)
-        images = torch.cat([image_attrs[..., :3], mv["alpha"][..., None]], dim=-1).contiguous()
+        images = None if stack else torch.cat([image_attrs[..., :3], mv["alpha"][..., None]], dim=-1).contiguous()
         _, c2ws_cpu = self._mvp(c2ws, intrinsics, perspective)
         # ray model per view (uv_to_pcd, :279-284): perspective -- from the camera centre to each texel's surface point; orthographic -- along -z of the camera
         eyes = c2ws_cpu[:, :3, 3].contiguous().to(dev) if perspective else None
@@ -296,25 +333,53 @@ class NVDiffRendererInverse:
         v0, v1, per = view_range(rank, world, n)
         # the back-projection kernel writes EVERY texel of the views it is given; only a view shard (world > 1) leaves layers to others, and those start as zeros
         alloc = torch.zeros if (world > 1 or v1 - v0 < n) else torch.empty
-        color = alloc(n, H2D, W2D, 3, dtype=torch.float32, device=dev)
+        color = None if stack else alloc(n, H2D, W2D, 3, dtype=torch.float32, device=dev)
         rayvis = alloc(n, H2D, W2D, dtype=torch.uint8, device=dev)
         alphaok = alloc(n, H2D, W2D, dtype=torch.uint8, device=dev)
         with self._stage("bvh_build"):
             bvh = m.optix
+        vndc = mv["ndc"].contiguous()
         if v1 > v0:
             with self._stage("backproject"):
-                ops.backproject(rast2d, m.vertices, m.faces, m.normals, mv["ndc"].contiguous(), dirs, images, bvh,
-                                angle_deg=ray_normal_angle_threhold, view_begin=v0, view_count=v1 - v0, out=(color, rayvis, alphaok), eyes=eyes,
-                                sample=sample)
+                if stack:
+                    ops.backproject_vis(rast2d, m.vertices, m.faces, m.normals, vndc, dirs, mv["alpha"].contiguous(), bvh,
+                                        angle_deg=ray_normal_angle_threhold, view_begin=v0, view_count=v1 - v0, out=(rayvis, alphaok), eyes=eyes,
+                                        sample=sample)
+                else:
+                    ops.backproject(rast2d, m.vertices, m.faces, m.normals, vndc, dirs, images, bvh,
+                                    angle_deg=ray_normal_angle_threhold, view_begin=v0, view_count=v1 - v0, out=(color, rayvis, alphaok), eyes=eyes,
+                                    sample=sample)
         with self._stage("dilate_visibility"):
             vis = ops.dilate_visibility(rayvis, alphaok, rast2d)
         if world > 1:
             with self._stage("all_gather"):          # the one exchange step of the path
-                color, vis = self._gather_layers(color, vis, per, n)
+                if stack:
+                    from .distributed import gather_view_images
+                    vis = gather_view_images(vis, rank, world, group=self.process_group)      # the u8 visibility layers only
+                else:
+                    color, vis = self._gather_layers(color, vis, per, n)
         mask_u8 = (rast2d[..., 3] > 0).to(torch.uint8).contiguous()
         winner = seam = None
-        if method == "reproject":
-            assert image_attrs.shape[-1] == 3
+        if stack:
+            with self._stage("composite"):
+                winner = ops.composite_winner(vis, self.index)
+            with self._stage("seam_mask"):
+                seam = ops.seam_mask(winner, rast2d, reproject_kernel_size_boundary, reproject_kernel_size_boundary_blur)
+            with self._stage("gather_winner"):
+                atlas = ops.gather_winner(rast2d, m.faces, vndc, image_attrs.contiguous(), winner, sample=sample)
+            with self._stage("nn_fill"):
+                pos = ops.interpolate(m.vertices, rast2d, m.faces)
+                if reproject_inpainting:
+                    self._fill_unseen(atlas, (winner >= 0).to(torch.uint8), rast2d[..., 3] > 0, pos, True)
+                else:
+                    ops.nn_fill_c(atlas, winner, rast2d, pos)
+            if reproject_method == "gaussian":
+                with self._stage("gaussian_blur_seam"):
+                    baked = ops.gaussian_blur_seam_c(atlas, seam, reproject_kernel_size_blur)
+            else:
+                with self._stage("lens_blur_seam"):
+                    baked = ops.lens_blur_seam_c(atlas, seam)
+        elif method == "reproject":
             with self._stage("composite"):
                 atlas, winner = ops.composite(color, vis, self.index)
             with self._stage("seam_mask"):
@@ -340,14 +405,19 @@ class NVDiffRendererInverse:
         with self._stage("pull_push"):
             if baked.shape[-1] == 3:
                 color_2d = ops.pull_push(baked, mask_u8)
+            elif stack:
+                color_2d = ops.pull_push_c(baked, mask_u8)
             else:   # PBR stack: three rgb groups through the same 3-channel kernel
                 color_2d = torch.cat([ops.pull_push(baked[..., c:c + 3].contiguous(), mask_u8) for c in range(0, baked.shape[-1], 3)], dim=-1)
         with self._stage("to_u8"):
-            tex = ops.to_u8(color_2d[..., :3].contiguous(), flip=True)  # tensor_to_image + FLIP_TOP_BOTTOM (link_pbr_to_mesh.py:17)
+            # tensor_to_image + FLIP_TOP_BOTTOM (link_pbr_to_mesh.py:17 / :46-48); nine channels: albedo 0:3, metallic-roughness 3:6, bump 6:9 (:716-721)
+            texs = [ops.to_u8(color_2d[..., c:c + 3].contiguous(), flip=True) for c in range(0, color_2d.shape[-1], 3)]
+            tex = texs[0]
         self.host_enqueue_ms = (time.perf_counter() - t_host0) * 1e3      # the host's wall time up to the last enqueue.  NOT free of device waits when the tree is fresh: the first utx_backproject behind utx_bvh_build_ws blocks in
         # hipEventSynchronize(depth_ready) until the build -- and everything queued in front of it -- has run (the depth picks the traversal on the host), so on a new mesh this figure
         # contains that GPU time; on a cached tree (DeviceMesh.optix, the benchmark's later iterations) it is enqueue time only.  The copies below wait for the GPU
-        textured = TexturedMesh(m.vertices.cpu().numpy(), m.faces.cpu().numpy(), m.uvs01, tex.cpu().numpy())
+        extra = [t.cpu().numpy() for t in texs[1:3]] if len(texs) == 3 else [None, None]
+        textured = TexturedMesh(m.vertices.cpu().numpy(), m.faces.cpu().numpy(), m.uvs01, tex.cpu().numpy(), *extra)
         self.last = {"rast2d": rast2d, "winner": winner, "seam": seam, "atlas_prefill": baked, "view_mask": mv["mask_visiable"]}
         out = (textured, vis.bool()[..., None], (rast2d[..., 3] > 0)[None, ..., None], color_2d[None])
         if return_layers:
