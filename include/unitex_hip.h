@@ -493,7 +493,8 @@ int utx_pull_push(utx_ctx* ctx, const float* kd, const void* mask, int H, int W,
 /* ---- C-channel (PBR stack) bake: renderer_inverse.py:635-726 with image_attrs of 9 channels (albedo, metallic-roughness, bump).  Visibility,
  * winner, seam and the nearest-neighbour search read no colour: they run once, and colour is gathered from the winning view only.  1 <= C <= 16
  * everywhere; all C-channel images are interleaved [..][C] f32 and every channel is processed on its own (the reference's blurs and pull-push are
- * depthwise), with the 3-channel kernels' expressions: channels [3g, 3g+3) of a result equal the 3-channel entry point's result on that group bit for bit. */
+ * depthwise) by the routine behind the 3-channel entry point, which passes C = 3: channels [3g, 3g+3) of a result equal the 3-channel entry point's
+ * result on that group bit for bit. */
 
 /* visibility-only back-projection: utx_backproject_sampled without the colour gather.  d->images is the view ALPHA plane [n_views][H][W] f32,
  * d->color is not read or written (may be NULL); eyes / sample_mode as in utx_backproject_sampled.  rayvis / alphaok are bit-identical to those of

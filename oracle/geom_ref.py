@@ -431,6 +431,8 @@ def _pull(kd, mask):
     """pull_push_mip (mip.py:9-24): 2x2 average of colour and alpha; partially covered cells are
     renormalised by their alpha; mask_mip = alpha > 0."""
     C, H, W = kd.shape
+    H, W = H // 2 * 2, W // 2 * 2          # avg_pool2d drops the last row / column of an odd size
+    kd, mask = kd[:, :H, :W], mask[:H, :W]
     a = mask.astype(np.float32).reshape(H // 2, 2, W // 2, 2)
     a = ((a[:, 0, :, 0] + a[:, 0, :, 1]) + a[:, 1, :, 0] + a[:, 1, :, 1]) * np.float32(0.25)
     k = kd.reshape(C, H // 2, 2, W // 2, 2)
@@ -442,7 +444,9 @@ def _pull(kd, mask):
 
 def _push(kd, mask, kd_mip, mask_mip):
     """pull_push_fill (mip.py:27-48): bilinear 2x upsample of the (replicate-padded) mip colour with weights
-    9/16, 3/16, 3/16, 1/16; only texels outside `mask` are replaced."""
+    9/16, 3/16, 3/16, 1/16; only texels outside `mask` are replaced.  The reference stops at an odd size (its upsampled image
+    is one short).  Here the last row / column of an odd size (fine index 2 * h2) has the padding cell h2 as its near cell and h2 - 1 as its far cell: both
+    are the last coarse cell, so it repeats the row / column before it (tests/test_pbr_stack_cpu.py holds this to hand-computed values)."""
     C, H, W = kd.shape
     p = np.pad(kd_mip, [(0, 0), (1, 1), (1, 1)], mode="edge")
     up = np.zeros((C, H, W), dtype=np.float32)
@@ -451,10 +455,11 @@ def _push(kd, mask, kd_mip, mask_mip):
         for px in (0, 1):
             # fine texel (2i+py, 2j+px): near coarse cell (i, j); far neighbours i-1/i+1, j-1/j+1
             ys, xs = (-1 if py == 0 else 1), (-1 if px == 0 else 1)
-            c = p[:, 1:-1, 1:-1]
-            cy = p[:, 1 + ys:p.shape[1] - 1 + ys, 1:-1]
-            cx = p[:, 1:-1, 1 + xs:p.shape[2] - 1 + xs]
-            cxy = p[:, 1 + ys:p.shape[1] - 1 + ys, 1 + xs:p.shape[2] - 1 + xs]
+            ny, nx = len(range(py, H, 2)), len(range(px, W, 2))
+            c = p[:, 1:1 + ny, 1:1 + nx]
+            cy = p[:, 1 + ys:1 + ys + ny, 1:1 + nx]
+            cx = p[:, 1:1 + ny, 1 + xs:1 + xs + nx]
+            cxy = p[:, 1 + ys:1 + ys + ny, 1 + xs:1 + xs + nx]
             up[:, py::2, px::2] = _push_order(c, cx, cy, cxy, py, px, w9, w3, w1)
     return np.where(mask[None], kd, up).astype(np.float32), mask
 

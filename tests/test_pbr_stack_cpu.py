@@ -159,3 +159,28 @@ def test_infer_channel_counts():
             assert str(e.value) == "shape torch.Size([6, 8, 8, %d]) is not supported" % C
     with pytest.raises(NotImplementedError, match="return_layers"):
         inv.infer(None, c2ws=c2ws, intrinsics=torch.eye(3), image_attrs=torch.zeros(6, 8, 8, 9), method="reproject", return_layers=True)
+
+
+def test_oracle_push_at_an_odd_size_is_the_replicate_padded_upsample():
+    """the reference stops at odd sizes, so G._push is the only statement of what the push kernel does there; it is held to values worked out by hand.
+    Bilinear 2x upsampling is separable, and along one axis a replicate-padded mip (v0, v1) gives the five fine texels v0, (3 v0 + v1) / 4, (v0 + 3 v1) / 4,
+    v1 and, for the fifth, whose near cell is the padding, v1 again: up = U mip U^T.  Every product below is exact in fp32.  An upsample that gave the last
+    row the cells (1, 0) as near and far instead would repeat row 2 there."""
+    mip = np.array([[[0, 16], [32, 64]]], F32)
+    want = np.array([[0, 4, 12, 16, 16],
+                     [8, 13, 23, 28, 28],
+                     [24, 31, 45, 52, 52],
+                     [32, 40, 56, 64, 64],
+                     [32, 40, 56, 64, 64]], F32)
+    U = np.array([[1, 0], [0.75, 0.25], [0.25, 0.75], [0, 1], [0, 1]], np.float64)
+    assert np.array_equal(want, U @ mip[0].astype(np.float64) @ U.T)
+    kd = np.full((1, 5, 5), -1, F32)
+    mask = np.zeros((5, 5), bool)
+    mask[1, 3] = mask[4, 4] = True                  # covered texels keep their own value
+    got, m = G._push(kd, mask, mip, np.ones((2, 2), bool))
+    want[1, 3] = want[4, 4] = -1
+    assert np.array_equal(got[0], want) and m is mask
+    # the pull drops the odd last row / column, as avg_pool2d does
+    k5 = np.arange(25, dtype=F32).reshape(1, 5, 5)
+    k, a = G._pull(k5, np.ones((5, 5), bool))
+    assert np.array_equal(k[0], np.array([[3, 5], [13, 15]], F32)) and a.shape == (2, 2) and a.all()

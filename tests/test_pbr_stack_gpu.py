@@ -1,6 +1,6 @@
 """The 9-channel (PBR stack) bake on the GPU: fixture G67s through NVDiffRendererInverse.infer against the reference's own outputs, bit-identity of the
-9-channel path against the 3-channel path per channel group (the 3-channel kernels are the yardstick), the new entry points alone, view sharding, the
-PBR TexturedMesh and its GLB, and the refusals."""
+9-channel path against the 3-channel path per channel group, the post-processing stages at C channels against their thread-per-texel instantiation
+(C = 3) and against the numpy restatement, the new entry points alone, view sharding, the PBR TexturedMesh and its GLB, and the refusals."""
 import ctypes as C
 import math
 import os
@@ -210,7 +210,7 @@ def _post_inputs(Hh, Ww, seed):
 @pytest.mark.parametrize("size", [(96, 160), (250, 131)])
 def test_c_channel_post_processing_equals_the_three_channel_kernels_per_group(Cc, size):
     """ragged C is padded by repeating channels: C-channel input channel c holds base channel (c % 7) of a 7-channel base, and every group of three of the
-    result (the last one padded by repeating) must equal the 3-channel kernel's result on those three channels"""
+    result (the last one padded by repeating) must equal the C = 3 result (the thread-per-texel instantiation) on those three channels"""
     from unitex_amd.texturetools import ops
     Hh, Ww = size
     winner, rast2d, seam, _, pos = _post_inputs(Hh, Ww, 11 + Cc)
@@ -227,15 +227,15 @@ def test_c_channel_post_processing_equals_the_three_channel_kernels_per_group(Cc
             yield ch
     # nn fill
     filled = src.clone()
-    idx = ops.nn_fill_c(filled, winner, rast2d, pos)
+    idx = ops.nn_fill(filled, winner, rast2d, pos, want_index=True)
     for ch in groups():
         a3 = src[..., ch].contiguous()
         idx3 = ops.nn_fill(a3, winner, rast2d, pos, want_index=True)
         assert torch.equal(filled[..., ch], a3) and torch.equal(idx, idx3)
     assert not torch.equal(filled, src)
     # the two blurs
-    lens = ops.lens_blur_seam_c(filled, seam)
-    gauss = {k: ops.gaussian_blur_seam_c(filled, seam, k) for k in (5, 7, 31)}
+    lens = ops.lens_blur_seam(filled, seam)
+    gauss = {k: ops.gaussian_blur_seam(filled, seam, k) for k in (5, 7, 31)}
     for ch in groups():
         f3 = filled[..., ch].contiguous()
         assert torch.equal(lens[..., ch], ops.lens_blur_seam(f3, seam))
@@ -243,17 +243,67 @@ def test_c_channel_post_processing_equals_the_three_channel_kernels_per_group(Cc
             assert torch.equal(gauss[k][..., ch], ops.gaussian_blur_seam(f3, seam, k)), "gaussian %d" % k
     assert not torch.equal(lens, filled) and not torch.equal(gauss[5], lens)
     # pull-push
-    pp = ops.pull_push_c(lens, mask)
+    pp = ops.pull_push(lens, mask)
     for ch in groups():
         assert torch.equal(pp[..., ch], ops.pull_push(lens[..., ch].contiguous(), mask))
     assert not torch.equal(pp, lens)
+
+
+@pytest.mark.parametrize("Cc", [1, 9, 16])
+@pytest.mark.parametrize("size", [(96, 160), (250, 131)])
+def test_c_channel_post_processing_equals_the_numpy_restatement(Cc, size):
+    """the two instantiations of a stage share one body, so the C-channel results are also held against oracle/geom_ref.py, at the tolerances the 3-channel
+    chain has in test_geometry_gpu.py and test_reproject_variants_gpu.py: NN fill and pull-push exact, lens blur 2e-6 (libm's powf against the device's),
+    Gaussian blur 1e-6 from the fp64 sum"""
+    from oracle import geom_ref as G
+    from tests import test_reproject_variants_cpu as RV
+    from unitex_amd.texturetools import ops
+    Hh, Ww = size
+    winner, rast2d, seam, _, pos = _post_inputs(Hh, Ww, 11 + Cc)
+    src = torch.rand(Hh, Ww, Cc, generator=torch.Generator().manual_seed(200 + Cc)).cuda() * (winner >= 0)[..., None]
+    mask = (rast2d[..., 3] > 0).to(torch.uint8).contiguous()
+    unseen = (winner < 0) & (mask > 0)
+    assert seam.any() and unseen.any() and (mask == 0).any()
+    w_np, r_np, pos_np, seam_np, src_np = winner.cpu().numpy(), rast2d.cpu().numpy(), pos.cpu().numpy(), seam.cpu().numpy().astype(bool), src.cpu().numpy()
+    # nn fill: the brute-force search takes three channels at a time
+    filled = src.clone()
+    idx = ops.nn_fill(filled, winner, rast2d, pos, want_index=True).cpu().numpy().reshape(Hh, Ww)
+    filled_np = filled.cpu().numpy()
+    for c0 in range(0, Cc, 3):
+        ch = [min(c0 + j, Cc - 1) for j in range(3)]
+        ref, idx_ref = G.nn_fill_brute(np.ascontiguousarray(src_np[..., ch]), w_np, r_np, pos_np)
+        assert np.array_equal(idx, idx_ref) and np.array_equal(filled_np[..., ch], ref)
+    assert (idx[unseen.cpu().numpy()] >= 0).all() and not np.array_equal(filled_np, src_np)
+    # the two blurs
+    lens = ops.lens_blur_seam(filled, seam)
+    err = np.abs(lens.cpu().numpy() - G.lens_blur_collapsed(filled_np, seam_np)).max()
+    print("C %d %s lens: max |d| %.3g" % (Cc, size, err))
+    assert err < 2e-6
+    for k in (5, 7, 31):
+        err = np.abs(ops.gaussian_blur_seam(filled, seam, k).cpu().numpy() - RV.gaussian_blur_fp64(filled_np, k, seam_np)).max()
+        print("C %d %s gaussian %d: max |d| %.3g" % (Cc, size, k, err))
+        assert err <= 1e-6
+    # pull-push, with holes over the last rows and columns as well: at an odd size the last row / column of a level lies past the last coarse cell, and the
+    # push writes there only where that level is uncovered
+    pp_mask = mask.clone()
+    pp_mask[-6:, :] = 0
+    pp_mask[:, -5:] = 0
+    m0 = pp_mask.cpu().numpy().astype(bool)
+    lens_np = np.ascontiguousarray(lens.cpu().numpy().transpose(2, 0, 1))
+    _, m1 = G._pull(lens_np, m0)
+    for m in (m0, m1):          # levels 0 and 1: 250 x 131 and 125 x 65
+        assert not m[-1].any() and not m[:, -1].any()
+    assert m0.any()
+    pp = ops.pull_push(lens, pp_mask).cpu().numpy()
+    pp_ref = G.pull_push(lens_np, m0).transpose(1, 2, 0)
+    assert np.array_equal(pp, pp_ref) and not np.array_equal(pp, lens.cpu().numpy())
 
 
 def test_pull_push_c_below_the_first_level_is_a_copy():
     from unitex_amd.texturetools import ops
     kd = torch.rand(7, 6, 9).cuda()
     mask = (torch.rand(7, 6) > 0.5).to(torch.uint8).cuda()
-    assert torch.equal(ops.pull_push_c(kd, mask), kd)
+    assert torch.equal(ops.pull_push(kd, mask), kd)
 
 
 # ------------------------------------------------------------------------------------------------ 4. view sharding
@@ -406,4 +456,4 @@ def test_refusals():
     assert lib.utx_backproject_vis(h, C.byref(d), None, 0, s["bvh"].handle, st) == 0
     torch.cuda.synchronize()
     with pytest.raises(RuntimeError, match="utx_lens_blur_seam_c"):
-        ops.lens_blur_seam_c(torch.zeros(Hh, Ww, 17, device="cuda"), seam)
+        ops.lens_blur_seam(torch.zeros(Hh, Ww, 17, device="cuda"), seam)

@@ -2,7 +2,7 @@
 """Cost of the 9-channel (PBR stack) bake against the 3-channel path, in one process, interleaved, with HIP events around the whole infer() enqueue
 and around every stage (NVDiffRendererInverse.stage_events), tree cached:
   (a) one 9-channel infer;  (b) three 3-channel infers on the channel groups;  (c) one 3-channel infer.
-(b) and (c) run the 3-channel kernels and are the baseline.  Prints one JSON line, the per-stage table and the ratios (a)/(b), (a)/(c), and the peak
+(b) and (c) run the thread-per-texel (C = 3) instantiation of the post-processing kernels and are the baseline.  Prints one JSON line, the per-stage table and the ratios (a)/(b), (a)/(c), and the peak
 device memory of (a) and (b).
 usage: python tools/bench_backproject_stack.py [--faces 50000] [--view 1024] [--atlas 2048] [--rounds 10] [--blur lens|gaussian]"""
 import argparse

@@ -461,21 +461,21 @@ long utx_nn_fill_workspace_bytes(long T) { return (long)utx_nn_fill_workspace_by
 int utx_nn_fill(utx_ctx* ctx, const float* pos, const void* winner, const float* rast2d, long T, float* atlas, int* nn_index,
                 void* work, long work_bytes, utx_stream stream) {
     if (!pos || !winner || !rast2d || !atlas || !work) return fail(ctx, -2, "utx_nn_fill");
-    UTX_CALL(ctx, "utx_nn_fill", utx_launch_nn_fill(pos, winner, rast2d, T, atlas, nn_index, work, (size_t)work_bytes, (hipStream_t)stream));
+    UTX_CALL(ctx, "utx_nn_fill", utx_launch_nn_fill(pos, winner, rast2d, T, 3, atlas, nn_index, work, (size_t)work_bytes, (hipStream_t)stream));
 }
 int utx_lens_blur_seam(utx_ctx* ctx, const float* src, const void* seam, int H, int W, const float* k49_host, float* dst, utx_stream stream) {
     if (!src || !seam || !k49_host || !dst) return fail(ctx, -2, "utx_lens_blur_seam");
-    UTX_CALL(ctx, "utx_lens_blur_seam", utx_launch_lens_blur_seam(src, seam, H, W, k49_host, dst, (hipStream_t)stream));
+    UTX_CALL(ctx, "utx_lens_blur_seam", utx_launch_lens_blur_seam(src, seam, H, W, 3, k49_host, dst, (hipStream_t)stream));
 }
 int utx_gaussian_blur_seam(utx_ctx* ctx, const float* src, const void* seam, int H, int W, int ksize, const float* w1_host, float* dst, utx_stream stream) {
     if (!src || !seam || !w1_host || !dst || H <= 0 || W <= 0 || ksize < 1 || ksize > 31 || (ksize & 1) == 0 || ksize / 2 >= H || ksize / 2 >= W)
         return fail(ctx, -2, "utx_gaussian_blur_seam");
-    UTX_CALL(ctx, "utx_gaussian_blur_seam", utx_launch_gaussian_blur_seam(src, seam, H, W, ksize, w1_host, dst, (hipStream_t)stream));
+    UTX_CALL(ctx, "utx_gaussian_blur_seam", utx_launch_gaussian_blur_seam(src, seam, H, W, 3, ksize, w1_host, dst, (hipStream_t)stream));
 }
-long utx_pull_push_workspace_bytes(int H, int W) { return (long)utx_pull_push_workspace_bytes_impl(H, W); }
+long utx_pull_push_workspace_bytes(int H, int W) { return (long)utx_pull_push_workspace_bytes_impl(H, W, 3); }
 int utx_pull_push(utx_ctx* ctx, const float* kd, const void* mask, int H, int W, float* out, void* work, utx_stream stream) {
     if (!kd || !mask || !out || !work) return fail(ctx, -2, "utx_pull_push");
-    UTX_CALL(ctx, "utx_pull_push", utx_launch_pull_push(kd, mask, H, W, out, work, (hipStream_t)stream));
+    UTX_CALL(ctx, "utx_pull_push", utx_launch_pull_push(kd, mask, H, W, 3, out, work, (hipStream_t)stream));
 }
 /* ---- the C-channel (PBR stack) bake: visibility and winner without colour, one gather from the winning view, C-channel post-processing ---- */
 int utx_backproject_vis(utx_ctx* ctx, const utx_backproject_desc* d, const float* eyes, int sample_mode, utx_bvh* bvh, utx_stream stream) {
@@ -497,21 +497,21 @@ int utx_gather_winner(utx_ctx* ctx, const float* rast2d, const int* faces, const
 int utx_nn_fill_c(utx_ctx* ctx, const float* pos, const void* winner, const float* rast2d, long T, int C, float* atlas, int* nn_index,
                   void* work, long work_bytes, utx_stream stream) {
     if (!pos || !winner || !rast2d || !atlas || !nn_index || !work || C < 1 || C > 16) return fail(ctx, -2, "utx_nn_fill_c");
-    UTX_CALL(ctx, "utx_nn_fill_c", utx_launch_nn_fill_c(pos, winner, rast2d, T, C, atlas, nn_index, work, (size_t)work_bytes, (hipStream_t)stream));
+    UTX_CALL(ctx, "utx_nn_fill_c", utx_launch_nn_fill(pos, winner, rast2d, T, C, atlas, nn_index, work, (size_t)work_bytes, (hipStream_t)stream));
 }
 int utx_lens_blur_seam_c(utx_ctx* ctx, const float* src, const void* seam, int H, int W, int C, const float* k49_host, float* dst, utx_stream stream) {
     if (!src || !seam || !k49_host || !dst || C < 1 || C > 16) return fail(ctx, -2, "utx_lens_blur_seam_c");
-    UTX_CALL(ctx, "utx_lens_blur_seam_c", utx_launch_lens_blur_seam_c(src, seam, H, W, C, k49_host, dst, (hipStream_t)stream));
+    UTX_CALL(ctx, "utx_lens_blur_seam_c", utx_launch_lens_blur_seam(src, seam, H, W, C, k49_host, dst, (hipStream_t)stream));
 }
 int utx_gaussian_blur_seam_c(utx_ctx* ctx, const float* src, const void* seam, int H, int W, int C, int ksize, const float* w1_host, float* dst, utx_stream stream) {
     if (!src || !seam || !w1_host || !dst || C < 1 || C > 16 || H <= 0 || W <= 0 || ksize < 1 || ksize > 31 || (ksize & 1) == 0 || ksize / 2 >= H || ksize / 2 >= W)
         return fail(ctx, -2, "utx_gaussian_blur_seam_c");
-    UTX_CALL(ctx, "utx_gaussian_blur_seam_c", utx_launch_gaussian_blur_seam_c(src, seam, H, W, C, ksize, w1_host, dst, (hipStream_t)stream));
+    UTX_CALL(ctx, "utx_gaussian_blur_seam_c", utx_launch_gaussian_blur_seam(src, seam, H, W, C, ksize, w1_host, dst, (hipStream_t)stream));
 }
-long utx_pull_push_workspace_bytes_c(int H, int W, int C) { return (long)utx_pull_push_workspace_bytes_c_impl(H, W, C); }
+long utx_pull_push_workspace_bytes_c(int H, int W, int C) { return (long)utx_pull_push_workspace_bytes_impl(H, W, C); }
 int utx_pull_push_c(utx_ctx* ctx, const float* kd, const void* mask, int H, int W, int C, float* out, void* work, utx_stream stream) {
     if (!kd || !mask || !out || !work || C < 1 || C > 16) return fail(ctx, -2, "utx_pull_push_c");
-    UTX_CALL(ctx, "utx_pull_push_c", utx_launch_pull_push_c(kd, mask, H, W, C, out, work, (hipStream_t)stream));
+    UTX_CALL(ctx, "utx_pull_push_c", utx_launch_pull_push(kd, mask, H, W, C, out, work, (hipStream_t)stream));
 }
 int utx_chart_flood(utx_ctx* ctx, const int* adj, const int* bucket, int F, int* chart, int* flag, utx_stream stream) {
     if (!adj || !bucket || !chart || !flag) return fail(ctx, -2, "utx_chart_flood");

@@ -150,21 +150,16 @@ int utx_launch_backproject(const utx_backproject_desc* p, const float* eyes, int
 int utx_launch_backproject_vis(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_composite_winner(const void* vis, int n_views, const int* order, int n_order, long T, void* winner, hipStream_t stream);
 int utx_launch_gather_winner(const float* rast2d, const int* faces, const float* vndc, const float* images, const void* winner, long T, int V, int n_views, int H, int W, int C, int sample, float* atlas, hipStream_t stream);
-int utx_launch_nn_fill_c(const float* pos, const void* winner, const float* rast2d, long T, int C, float* atlas, int* nn_index, void* work, size_t work_bytes, hipStream_t stream);
-int utx_launch_lens_blur_seam_c(const float* src, const void* seam, int Hh, int Ww, int C, const float* k49_host, float* dst, hipStream_t stream);
-int utx_launch_gaussian_blur_seam_c(const float* src, const void* seam, int Hh, int Ww, int C, int ksize, const float* w1_host, float* dst, hipStream_t stream);
-size_t utx_pull_push_workspace_bytes_c_impl(int Hh, int Ww, int C);
-int utx_launch_pull_push_c(const float* kd, const void* mask, int Hh, int Ww, int C, float* out, void* work, hipStream_t stream);
 int utx_launch_dilate_visibility(const void* rayvis, const void* alphaok, const void* rast2d, int n_views, int Hh, int Ww, void* tmp, void* vis_out, hipStream_t stream);
 int utx_launch_composite(const float* colors, const void* vis, const int* order, int n_order, long T, float* atlas, void* winner, hipStream_t stream);
 int utx_launch_seam_mask(const void* winner, const float* rast2d, int Hh, int Ww, void* tmp, void* seam, hipStream_t stream);
 int utx_launch_seam_mask_sized(const void* winner, const float* rast2d, int Hh, int Ww, int k_boundary, int k_boundary_blur, void* tmp, void* seam, hipStream_t stream);
 size_t utx_nn_fill_workspace_bytes_impl(long T);
-int utx_launch_nn_fill(const float* pos, const void* winner, const float* rast2d, long T, float* atlas, int* nn_index, void* work, size_t work_bytes, hipStream_t stream);
-int utx_launch_lens_blur_seam(const float* src, const void* seam, int Hh, int Ww, const float* k49_host, float* dst, hipStream_t stream);
-int utx_launch_gaussian_blur_seam(const float* src, const void* seam, int Hh, int Ww, int ksize, const float* w1_host, float* dst, hipStream_t stream);
-size_t utx_pull_push_workspace_bytes_impl(int Hh, int Ww);
-int utx_launch_pull_push(const float* kd, const void* mask, int Hh, int Ww, float* out, void* work, hipStream_t stream);
+int utx_launch_nn_fill(const float* pos, const void* winner, const float* rast2d, long T, int C, float* atlas, int* nn_index, void* work, size_t work_bytes, hipStream_t stream);
+int utx_launch_lens_blur_seam(const float* src, const void* seam, int Hh, int Ww, int C, const float* k49_host, float* dst, hipStream_t stream);
+int utx_launch_gaussian_blur_seam(const float* src, const void* seam, int Hh, int Ww, int C, int ksize, const float* w1_host, float* dst, hipStream_t stream);
+size_t utx_pull_push_workspace_bytes_impl(int Hh, int Ww, int C);
+int utx_launch_pull_push(const float* kd, const void* mask, int Hh, int Ww, int C, float* out, void* work, hipStream_t stream);
 int utx_launch_chart_flood(const int* adj, const int* bucket, int F, int* chart, int* flag, hipStream_t stream);
 int utx_launch_to_u8(const float* src, long n_rows, long row_elems, int flip, void* dst, hipStream_t stream);
 }

@@ -163,7 +163,7 @@ __global__ __launch_bounds__(256) void nn_bounds_kernel(const unsigned* keys, co
     const int j = vals[i];
     spos[i] = make_float4(pos[3 * (long)j], pos[3 * (long)j + 1], pos[3 * (long)j + 2], __int_as_float(j));
 }
-// COPY3 false (utx_nn_fill_c): the search alone -- nn_index is the result, the C-channel copy is nn_copy_c_kernel's
+// COPY3 false (C != 3): the search alone -- nn_index is the result, the C-channel copy is nn_copy_c_kernel's
 template <bool COPY3>
 __global__ __launch_bounds__(256) void nn_query_kernel(const float* pos, const signed char* winner, const float4* rast2d, long T,
                                                        const float4* __restrict__ spos, const int* __restrict__ cell_start, const int* __restrict__ cell_end,
@@ -244,10 +244,10 @@ __global__ __launch_bounds__(256) void nn_copy_c_kernel(const int* nn_index, lon
     if (bi >= 0) atlas[i] = atlas[(long)bi * C + (i - t * C)];
 }
 
-// C == 0: the 3-channel fill (the copy inside the query kernel); C >= 1: search once into nn_index (required), then the C-channel copy
-static int nn_fill_any(const float* pos, const void* winner, const float* rast2d, long T, int C, float* atlas, int* nn_index,
-                       void* work, size_t work_bytes, hipStream_t stream) {
-    if (T <= 0) return -2;
+// C == 3: the copy inside the query kernel (nn_index optional); any other C: search into nn_index (required), then nn_copy_c_kernel
+extern "C" int utx_launch_nn_fill(const float* pos, const void* winner, const float* rast2d, long T, int C, float* atlas, int* nn_index,
+                                  void* work, size_t work_bytes, hipStream_t stream) {
+    if (T <= 0 || C < 1 || C > 16 || (C != 3 && !nn_index)) return -2;
     if (work_bytes < utx_nn_fill_workspace_bytes_impl(T)) return -2;
     const int NN_G = nn_grid(T);
     unsigned* keys = (unsigned*)work; unsigned* keys_s = keys + T;
@@ -262,7 +262,7 @@ static int nn_fill_any(const float* pos, const void* winner, const float* rast2d
     hipLaunchKernelGGL(nn_keys_kernel, dim3(nb), dim3(256), 0, stream, pos, (const signed char*)winner, T, keys, vals, NN_G);
     if (rocprim::radix_sort_pairs(tmp, tmp_bytes, keys, keys_s, vals, vals_s, (size_t)T, 0, 32, stream) != hipSuccess) return -7;
     hipLaunchKernelGGL(nn_bounds_kernel, dim3(nb), dim3(256), 0, stream, keys_s, vals_s, pos, T, cell_start, cell_end, spos);
-    if (C == 0) {
+    if (C == 3) {
         hipLaunchKernelGGL(nn_query_kernel<true>, dim3(nb), dim3(256), 0, stream, pos, (const signed char*)winner, (const float4*)rast2d, T, spos,
                            cell_start, cell_end, atlas, nn_index, NN_G);
     } else {
@@ -272,15 +272,26 @@ static int nn_fill_any(const float* pos, const void* winner, const float* rast2d
     }
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
-extern "C" int utx_launch_nn_fill(const float* pos, const void* winner, const float* rast2d, long T, float* atlas, int* nn_index,
-                                  void* work, size_t work_bytes, hipStream_t stream) {
-    return nn_fill_any(pos, winner, rast2d, T, 0, atlas, nn_index, work, work_bytes, stream);
+
+// ---------------------------------------------------------------------------------------------
+// The stages below work on images interleaved [H][W][C] f32, 1 <= C <= 16, every channel on its own (depthwise, as the reference's convolutions with
+// groups = channels).  Each stage's per-channel arithmetic is ONE device function; its kernel template <CPT> gives a thread CPT consecutive channels of
+// one texel.  CPT = 3 exactly when C == 3 (one thread per texel: seam / mask / index math once, three adjacent floats per tap), CPT = 1 otherwise (one
+// thread per float).  So a channel's result does not depend on C or on which channel of the image it is.  The device functions take the thread's CPT
+// channels and loop over them inside each tap: called once per channel, their tap loops stay apart after inlining (three passes over the taps per
+// texel in the Gaussian blur, 120 VGPRs in the lens blur).
+// ---------------------------------------------------------------------------------------------
+// this thread's texel t and first channel c0; false when the thread is past the image of T texels
+template <int CPT> __device__ __forceinline__ bool pp_owned(long T, int C, long& t, int& c0) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if constexpr (CPT == 1) { t = i / C; c0 = (int)(i - t * C); return i < T * C; }
+    else { t = i; c0 = 0; return i < T; }
 }
-extern "C" int utx_launch_nn_fill_c(const float* pos, const void* winner, const float* rast2d, long T, int C, float* atlas, int* nn_index,
-                                    void* work, size_t work_bytes, hipStream_t stream) {
-    if (C < 1 || C > 16 || !nn_index) return -2;
-    return nn_fill_any(pos, winner, rast2d, T, C, atlas, nn_index, work, work_bytes, stream);
-}
+#define PP_LAUNCH(kernel, T, C, stream, ...)                                                                                          \
+    do {                                                                                                                             \
+        if ((C) == 3) hipLaunchKernelGGL(kernel<3>, dim3((unsigned)(((T) + 255) / 256)), dim3(256), 0, stream, __VA_ARGS__);          \
+        else hipLaunchKernelGGL(kernel<1>, dim3((unsigned)(((T) * (C) + 255) / 256)), dim3(256), 0, stream, __VA_ARGS__);             \
+    } while (0)
 
 // ---------------------------------------------------------------------------------------------
 // lens blur, evaluated only where it is consumed (the seam mask).  lens_blur_torch is linear between the
@@ -289,63 +300,40 @@ extern "C" int utx_launch_nn_fill_c(const float* pos, const void* winner, const 
 // out = clamp( max(sum K * x^5, 0)^(1/5), 0, 1 ), zero padding, x^5 = ((x*x)*(x*x))*x.
 // ---------------------------------------------------------------------------------------------
 struct BlurK { float k[49]; };
-__global__ __launch_bounds__(256) void lens_blur_seam_kernel(const float* src, const unsigned char* seam, int Hh, int Ww, BlurK K, float* dst) {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)Hh * Ww) return;
-    float o0 = src[3 * t], o1 = src[3 * t + 1], o2 = src[3 * t + 2];
+template <int CPT>
+__device__ __forceinline__ void lens_blur_values(const float* src, int Hh, int Ww, int C, int y, int x, int ch, const BlurK& K, float (&o)[CPT]) {
+    float a[CPT];
+    for (int j = 0; j < CPT; ++j) a[j] = 0.f;
+    for (int dy = -3; dy <= 3; ++dy) for (int dx = -3; dx <= 3; ++dx) {
+        const int yy = y + dy, xx = x + dx;
+        if (yy < 0 || yy >= Hh || xx < 0 || xx >= Ww) continue;
+        const float kk = K.k[(dy + 3) * 7 + (dx + 3)];
+        const float* c = src + ((long)yy * Ww + xx) * C + ch;
+        for (int j = 0; j < CPT; ++j) { const float c0 = c[j]; a[j] = a[j] + kk * (((c0 * c0) * (c0 * c0)) * c0); }
+    }
+    // every per-channel loop here has the constant trip count CPT and is unrolled without being asked; this one alone carries the pragma, because the
+    // three powf expansions are then scheduled as the 3-channel kernel always had them (28 VGPRs at CPT = 3; 31 without it)
+#pragma unroll
+    for (int j = 0; j < CPT; ++j) o[j] = fminf(fmaxf(powf(fmaxf(a[j], 0.f), 0.2f), 0.f), 1.f);
+}
+template <int CPT>
+__global__ __launch_bounds__(256) void lens_blur_seam_kernel(const float* src, const unsigned char* seam, int Hh, int Ww, int C_, BlurK K, float* dst) {
+    const int C = CPT == 1 ? C_ : CPT;
+    long t; int c0;
+    if (!pp_owned<CPT>((long)Hh * Ww, C, t, c0)) return;
+    const long i = t * C + c0;
+    float o[CPT];
+    for (int j = 0; j < CPT; ++j) o[j] = src[i + j];
     if (seam[t]) {
         const int y = (int)(t / Ww), x = (int)(t % Ww);
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-        for (int dy = -3; dy <= 3; ++dy) for (int dx = -3; dx <= 3; ++dx) {
-            const int yy = y + dy, xx = x + dx;
-            if (yy < 0 || yy >= Hh || xx < 0 || xx >= Ww) continue;
-            const float kk = K.k[(dy + 3) * 7 + (dx + 3)];
-            const float* c = src + 3 * ((long)yy * Ww + xx);
-            const float c0 = c[0], c1 = c[1], c2 = c[2];
-            a0 = a0 + kk * (((c0 * c0) * (c0 * c0)) * c0);
-            a1 = a1 + kk * (((c1 * c1) * (c1 * c1)) * c1);
-            a2 = a2 + kk * (((c2 * c2) * (c2 * c2)) * c2);
-        }
-        o0 = fminf(fmaxf(powf(fmaxf(a0, 0.f), 0.2f), 0.f), 1.f);
-        o1 = fminf(fmaxf(powf(fmaxf(a1, 0.f), 0.2f), 0.f), 1.f);
-        o2 = fminf(fmaxf(powf(fmaxf(a2, 0.f), 0.2f), 0.f), 1.f);
+        lens_blur_values<CPT>(src, Hh, Ww, C, y, x, c0, K, o);
     }
-    dst[3 * t] = o0; dst[3 * t + 1] = o1; dst[3 * t + 2] = o2;
+    for (int j = 0; j < CPT; ++j) dst[i + j] = o[j];
 }
-extern "C" int utx_launch_lens_blur_seam(const float* src, const void* seam, int Hh, int Ww, const float* k49_host, float* dst, hipStream_t stream) {
-    const long T = (long)Hh * Ww;
-    if (T <= 0 || !k49_host) return -2;
-    BlurK K; for (int i = 0; i < 49; ++i) K.k[i] = k49_host[i];
-    hipLaunchKernelGGL(lens_blur_seam_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, stream, src, (const unsigned char*)seam, Hh, Ww, K, dst);
-    return hipGetLastError() == hipSuccess ? 0 : -4;
-}
-
-// C channels, one thread per float of src / dst [H][W][C] (depthwise, as lens_blur_torch: groups = channels): the per-channel expression is the one above
-__global__ __launch_bounds__(256) void lens_blur_seam_c_kernel(const float* src, const unsigned char* seam, int Hh, int Ww, int C, BlurK K, float* dst) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)Hh * Ww * C) return;
-    const long t = i / C;
-    const int ch = (int)(i - t * C);
-    float o = src[i];
-    if (seam[t]) {
-        const int y = (int)(t / Ww), x = (int)(t % Ww);
-        float a = 0.f;
-        for (int dy = -3; dy <= 3; ++dy) for (int dx = -3; dx <= 3; ++dx) {
-            const int yy = y + dy, xx = x + dx;
-            if (yy < 0 || yy >= Hh || xx < 0 || xx >= Ww) continue;
-            const float kk = K.k[(dy + 3) * 7 + (dx + 3)];
-            const float c0 = src[((long)yy * Ww + xx) * C + ch];
-            a = a + kk * (((c0 * c0) * (c0 * c0)) * c0);
-        }
-        o = fminf(fmaxf(powf(fmaxf(a, 0.f), 0.2f), 0.f), 1.f);
-    }
-    dst[i] = o;
-}
-extern "C" int utx_launch_lens_blur_seam_c(const float* src, const void* seam, int Hh, int Ww, int C, const float* k49_host, float* dst, hipStream_t stream) {
-    const long n = (long)Hh * Ww * C;
+extern "C" int utx_launch_lens_blur_seam(const float* src, const void* seam, int Hh, int Ww, int C, const float* k49_host, float* dst, hipStream_t stream) {
     if (Hh <= 0 || Ww <= 0 || C < 1 || C > 16 || !k49_host) return -2;
     BlurK K; for (int i = 0; i < 49; ++i) K.k[i] = k49_host[i];
-    hipLaunchKernelGGL(lens_blur_seam_c_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, src, (const unsigned char*)seam, Hh, Ww, C, K, dst);
+    PP_LAUNCH(lens_blur_seam_kernel, (long)Hh * Ww, C, stream, src, (const unsigned char*)seam, Hh, Ww, C, K, dst);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
@@ -362,207 +350,112 @@ __device__ __forceinline__ int reflect_idx(int i, int n) {
     if (i >= n) i = 2 * (n - 1) - i;
     return i;
 }
-__global__ __launch_bounds__(256) void gaussian_blur_seam_kernel(const float* src, const unsigned char* seam, int Hh, int Ww, int r, GaussK K, float* dst) {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)Hh * Ww) return;
-    float o0 = src[3 * t], o1 = src[3 * t + 1], o2 = src[3 * t + 2];
+template <int CPT>
+__device__ __forceinline__ void gaussian_blur_values(const float* src, int Hh, int Ww, int C, int y, int x, int ch, int r, const GaussK& K, float (&o)[CPT]) {
+    double a[CPT];
+    for (int j = 0; j < CPT; ++j) a[j] = 0.0;
+    for (int dy = -r; dy <= r; ++dy) {
+        const int yy = reflect_idx(y + dy, Hh);
+        const float wy = K.w[dy + r];
+        for (int dx = -r; dx <= r; ++dx) {
+            const int xx = reflect_idx(x + dx, Ww);
+            const double kk = (double)(wy * K.w[dx + r]);
+            const float* c = src + ((long)yy * Ww + xx) * C + ch;
+            for (int j = 0; j < CPT; ++j) a[j] = a[j] + kk * (double)c[j];
+        }
+    }
+    for (int j = 0; j < CPT; ++j) o[j] = (float)a[j];
+}
+template <int CPT>
+__global__ __launch_bounds__(256) void gaussian_blur_seam_kernel(const float* src, const unsigned char* seam, int Hh, int Ww, int C_, int r, GaussK K, float* dst) {
+    const int C = CPT == 1 ? C_ : CPT;
+    long t; int c0;
+    if (!pp_owned<CPT>((long)Hh * Ww, C, t, c0)) return;
+    const long i = t * C + c0;
+    float o[CPT];
+    for (int j = 0; j < CPT; ++j) o[j] = src[i + j];
     if (seam[t]) {
         const int y = (int)(t / Ww), x = (int)(t % Ww);
-        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
-        for (int dy = -r; dy <= r; ++dy) {
-            const int yy = reflect_idx(y + dy, Hh);
-            const float wy = K.w[dy + r];
-            for (int dx = -r; dx <= r; ++dx) {
-                const int xx = reflect_idx(x + dx, Ww);
-                const double kk = (double)(wy * K.w[dx + r]);
-                const float* c = src + 3 * ((long)yy * Ww + xx);
-                a0 = a0 + kk * (double)c[0];
-                a1 = a1 + kk * (double)c[1];
-                a2 = a2 + kk * (double)c[2];
-            }
-        }
-        o0 = (float)a0; o1 = (float)a1; o2 = (float)a2;
+        gaussian_blur_values<CPT>(src, Hh, Ww, C, y, x, c0, r, K, o);
     }
-    dst[3 * t] = o0; dst[3 * t + 1] = o1; dst[3 * t + 2] = o2;
+    for (int j = 0; j < CPT; ++j) dst[i + j] = o[j];
 }
-extern "C" int utx_launch_gaussian_blur_seam(const float* src, const void* seam, int Hh, int Ww, int ksize, const float* w1_host, float* dst, hipStream_t stream) {
-    const long T = (long)Hh * Ww;
-    if (T <= 0 || Hh <= 0 || Ww <= 0 || !w1_host || ksize < 1 || ksize > 31 || (ksize & 1) == 0) return -2;
-    const int r = ksize / 2;
-    if (r >= Hh || r >= Ww) return -2;
-    GaussK K;
-    for (int i = 0; i < 31; ++i) K.w[i] = i < ksize ? w1_host[i] : 0.f;
-    hipLaunchKernelGGL(gaussian_blur_seam_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, stream, src, (const unsigned char*)seam, Hh, Ww, r, K, dst);
-    return hipGetLastError() == hipSuccess ? 0 : -4;
-}
-
-// C channels, one thread per float (depthwise, as gaussian_blur): the same taps, weights and fp64 sum per channel
-__global__ __launch_bounds__(256) void gaussian_blur_seam_c_kernel(const float* src, const unsigned char* seam, int Hh, int Ww, int C, int r, GaussK K, float* dst) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)Hh * Ww * C) return;
-    const long t = i / C;
-    const int ch = (int)(i - t * C);
-    float o = src[i];
-    if (seam[t]) {
-        const int y = (int)(t / Ww), x = (int)(t % Ww);
-        double a = 0.0;
-        for (int dy = -r; dy <= r; ++dy) {
-            const int yy = reflect_idx(y + dy, Hh);
-            const float wy = K.w[dy + r];
-            for (int dx = -r; dx <= r; ++dx) {
-                const int xx = reflect_idx(x + dx, Ww);
-                const double kk = (double)(wy * K.w[dx + r]);
-                a = a + kk * (double)src[((long)yy * Ww + xx) * C + ch];
-            }
-        }
-        o = (float)a;
-    }
-    dst[i] = o;
-}
-extern "C" int utx_launch_gaussian_blur_seam_c(const float* src, const void* seam, int Hh, int Ww, int C, int ksize, const float* w1_host, float* dst, hipStream_t stream) {
+extern "C" int utx_launch_gaussian_blur_seam(const float* src, const void* seam, int Hh, int Ww, int C, int ksize, const float* w1_host, float* dst, hipStream_t stream) {
     if (Hh <= 0 || Ww <= 0 || C < 1 || C > 16 || !w1_host || ksize < 1 || ksize > 31 || (ksize & 1) == 0) return -2;
     const int r = ksize / 2;
     if (r >= Hh || r >= Ww) return -2;
-    const long n = (long)Hh * Ww * C;
     GaussK K;
     for (int i = 0; i < 31; ++i) K.w[i] = i < ksize ? w1_host[i] : 0.f;
-    hipLaunchKernelGGL(gaussian_blur_seam_c_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, src, (const unsigned char*)seam, Hh, Ww, C, r, K, dst);
+    PP_LAUNCH(gaussian_blur_seam_kernel, (long)Hh * Ww, C, stream, src, (const unsigned char*)seam, Hh, Ww, C, r, K, dst);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
 // ---------------------------------------------------------------------------------------------
-// pull-push (mip.py:51-95).  Level l has size (H>>l, W>>l); colour interleaved [h][w][3] f32, mask u8.
+// pull-push (mip.py:51-95).  Level l has size (H>>l, W>>l); colour interleaved [h][w][C] f32, mask u8.
 // ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void pp_pull_kernel(const float* kd, const unsigned char* mask, int Hh, int Ww, int zero_outside,
+// channels [c, c + CPT) of texel (y, x) of the next coarser level into k; returns that texel's coverage
+template <int CPT>
+__device__ __forceinline__ float pp_pull_values(const float* kd, const unsigned char* mask, int Ww, int C, int zero_outside, int y, int x, int c, float (&k)[CPT]) {
+    float a = 0.f;
+    for (int j = 0; j < CPT; ++j) k[j] = 0.f;
+    for (int dy = 0; dy < 2; ++dy) for (int dx = 0; dx < 2; ++dx) {
+        const long q = (long)(2 * y + dy) * Ww + (2 * x + dx);
+        const float m = mask[q] ? 1.0f : 0.0f;
+        a = a + m;
+        for (int j = 0; j < CPT; ++j) { const float vv = (zero_outside && !mask[q]) ? 0.f : kd[q * C + c + j]; k[j] = k[j] + vv; }
+    }
+    a = a * 0.25f;
+    for (int j = 0; j < CPT; ++j) k[j] = k[j] * 0.25f;
+    if (a > 0.f && a < 1.f) for (int j = 0; j < CPT; ++j) k[j] = k[j] / a;
+    return a;
+}
+template <int CPT>
+__global__ __launch_bounds__(256) void pp_pull_kernel(const float* kd, const unsigned char* mask, int Hh, int Ww, int C_, int zero_outside,
                                                       float* kd_mip, unsigned char* mask_mip) {
+    const int C = CPT == 1 ? C_ : CPT;
     const int h2 = Hh / 2, w2 = Ww / 2;
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)h2 * w2) return;
-    const int y = (int)(t / w2), x = (int)(t % w2);
-    float a = 0.f, k[3] = {0.f, 0.f, 0.f};
-    for (int dy = 0; dy < 2; ++dy) for (int dx = 0; dx < 2; ++dx) {
-        const long q = (long)(2 * y + dy) * Ww + (2 * x + dx);
-        const float m = mask[q] ? 1.0f : 0.0f;
-        a = a + m;
-        for (int c = 0; c < 3; ++c) { const float vv = (zero_outside && !mask[q]) ? 0.f : kd[3 * q + c]; k[c] = k[c] + vv; }
-    }
-    a = a * 0.25f;
-    for (int c = 0; c < 3; ++c) k[c] = k[c] * 0.25f;
-    if (a > 0.f && a < 1.f) for (int c = 0; c < 3; ++c) k[c] = k[c] / a;
-    for (int c = 0; c < 3; ++c) kd_mip[3 * t + c] = k[c];
-    mask_mip[t] = a > 0.f ? 1 : 0;
+    long t; int c0;
+    if (!pp_owned<CPT>((long)h2 * w2, C, t, c0)) return;
+    float k[CPT];
+    const float a = pp_pull_values<CPT>(kd, mask, Ww, C, zero_outside, (int)(t / w2), (int)(t % w2), c0, k);
+    for (int j = 0; j < CPT; ++j) kd_mip[t * C + c0 + j] = k[j];
+    if (c0 == 0) mask_mip[t] = a > 0.f ? 1 : 0;
 }
-// out(fine) = mask ? kd : bilinear_up(kd_mip)  (replicate padding; tap order = the reference's conv2d kernels)
-__global__ __launch_bounds__(256) void pp_push_kernel(const float* kd, const unsigned char* mask, int Hh, int Ww, int zero_outside,
-                                                      const float* kd_mip, float* out) {
-    const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long)Hh * Ww) return;
-    const int y = (int)(t / Ww), x = (int)(t % Ww);
-    if (mask[t]) { for (int c = 0; c < 3; ++c) out[3 * t + c] = kd[3 * t + c]; return; }
-    (void)zero_outside;
-    const int h2 = Hh / 2, w2 = Ww / 2;
-    const int i = y >> 1, j = x >> 1, py = y & 1, px = x & 1;
-    const int iy = py ? min(i + 1, h2 - 1) : max(i - 1, 0);
-    const int jx = px ? min(j + 1, w2 - 1) : max(j - 1, 0);
-    const float* c_ = kd_mip + 3 * ((long)i * w2 + j);
-    const float* cx = kd_mip + 3 * ((long)i * w2 + jx);
-    const float* cy = kd_mip + 3 * ((long)iy * w2 + j);
-    const float* cxy = kd_mip + 3 * ((long)iy * w2 + jx);
+// channels [c, c + CPT) of the bilinear upsampling of kd_mip [h2][w2][C] at fine texel (y, x)  (replicate padding; tap order = the reference's conv2d kernels).
+// The last row / column of an odd fine size has the padding cell (y >> 1 == h2) as its near cell, so both its near and its far cell are the last coarse cell.
+template <int CPT>
+__device__ __forceinline__ void pp_push_values(const float* kd_mip, int h2, int w2, int C, int y, int x, int c, float* out) {
+    const int py = y & 1, px = x & 1;
+    const int i = min(y >> 1, h2 - 1), j = min(x >> 1, w2 - 1);
+    const int iy = py ? min((y >> 1) + 1, h2 - 1) : max((y >> 1) - 1, 0);
+    const int jx = px ? min((x >> 1) + 1, w2 - 1) : max((x >> 1) - 1, 0);
+    const float* c_ = kd_mip + ((long)i * w2 + j) * C + c;
+    const float* cx = kd_mip + ((long)i * w2 + jx) * C + c;
+    const float* cy = kd_mip + ((long)iy * w2 + j) * C + c;
+    const float* cxy = kd_mip + ((long)iy * w2 + jx) * C + c;
     const float w9 = 0.5625f, w3 = 0.1875f, w1 = 0.0625f;
-    for (int c = 0; c < 3; ++c) {
+    for (int k = 0; k < CPT; ++k) {
+        const float v_ = c_[k], vx = cx[k], vy = cy[k], vxy = cxy[k];
         float r;
-        if (!py && !px) r = ((cxy[c] * w1 + cy[c] * w3) + cx[c] * w3) + c_[c] * w9;
-        else if (!py && px) r = ((cy[c] * w3 + cxy[c] * w1) + c_[c] * w9) + cx[c] * w3;
-        else if (py && !px) r = ((cx[c] * w3 + c_[c] * w9) + cxy[c] * w1) + cy[c] * w3;
-        else r = ((c_[c] * w9 + cx[c] * w3) + cy[c] * w3) + cxy[c] * w1;
-        out[3 * t + c] = r;
+        if (!py && !px) r = ((vxy * w1 + vy * w3) + vx * w3) + v_ * w9;
+        else if (!py && px) r = ((vy * w3 + vxy * w1) + v_ * w9) + vx * w3;
+        else if (py && !px) r = ((vx * w3 + v_ * w9) + vxy * w1) + vy * w3;
+        else r = ((v_ * w9 + vx * w3) + vy * w3) + vxy * w1;
+        out[k] = r;
     }
+}
+// out(fine) = mask ? kd : bilinear_up(kd_mip)
+template <int CPT>
+__global__ __launch_bounds__(256) void pp_push_kernel(const float* kd, const unsigned char* mask, int Hh, int Ww, int C_, const float* kd_mip, float* out) {
+    const int C = CPT == 1 ? C_ : CPT;
+    long t; int c0;
+    if (!pp_owned<CPT>((long)Hh * Ww, C, t, c0)) return;
+    const long i = t * C + c0;
+    if (mask[t]) { for (int j = 0; j < CPT; ++j) out[i + j] = kd[i + j]; return; }
+    pp_push_values<CPT>(kd_mip, Hh / 2, Ww / 2, C, (int)(t / Ww), (int)(t % Ww), c0, out + i);
 }
 
-extern "C" size_t utx_pull_push_workspace_bytes_impl(int Hh, int Ww) {
-    size_t tot = 0;
-    int h = Hh, w = Ww;
-    for (int l = 0; l < 32 && h >= 2 && w >= 2; ++l) { h /= 2; w /= 2; tot += (size_t)h * w * (2 * 12 + 1) + 64; }
-    return tot + 256;
-}
-
-extern "C" int utx_launch_pull_push(const float* kd, const void* mask, int Hh, int Ww, float* out, void* work, hipStream_t stream) {
-    int n = 0;
-    { int lh = 0, lw = 0; while ((1 << (lh + 1)) <= Hh) ++lh; while ((1 << (lw + 1)) <= Ww) ++lw; n = (lh < lw ? lh : lw) - 2; if (n < 0) n = 0; }
-    const long T = (long)Hh * Ww;
-    if (n == 0) { return hipMemcpyAsync(out, kd, T * 12, hipMemcpyDeviceToDevice, stream) == hipSuccess ? 0 : -7; }
-    if (n > 16) return -2;
-    float* kds[17]; float* fill[17]; unsigned char* ms[17]; int hs[17], wsz[17];
-    char* p = (char*)work;
-    hs[0] = Hh; wsz[0] = Ww; kds[0] = (float*)kd; ms[0] = (unsigned char*)mask; fill[0] = out;
-    for (int l = 1; l <= n; ++l) {
-        hs[l] = hs[l - 1] / 2; wsz[l] = wsz[l - 1] / 2;
-        const size_t px = (size_t)hs[l] * wsz[l];
-        kds[l] = (float*)p; p += px * 12;
-        fill[l] = (float*)p; p += px * 12;
-        ms[l] = (unsigned char*)p; p += (px + 63) & ~(size_t)63;
-    }
-    for (int l = 1; l <= n; ++l) {
-        const long px = (long)hs[l] * wsz[l];
-        hipLaunchKernelGGL(pp_pull_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, stream, kds[l - 1], ms[l - 1], hs[l - 1], wsz[l - 1],
-                           l == 1 ? 1 : 0, kds[l], ms[l]);
-    }
-    // coarsest level is its own fill; push down to level 0
-    const float* cur = kds[n];
-    for (int l = n - 1; l >= 0; --l) {
-        const long px = (long)hs[l] * wsz[l];
-        hipLaunchKernelGGL(pp_push_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, stream, kds[l], ms[l], hs[l], wsz[l], l == 0 ? 1 : 0, cur, fill[l]);
-        cur = fill[l];
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -4;
-}
-
-// C channels, colour interleaved [h][w][C], one thread per float (depthwise, as the reference's pull_push); per channel the expressions of the two kernels above.
-__global__ __launch_bounds__(256) void pp_pull_c_kernel(const float* kd, const unsigned char* mask, int Hh, int Ww, int C, int zero_outside,
-                                                        float* kd_mip, unsigned char* mask_mip) {
-    const int h2 = Hh / 2, w2 = Ww / 2;
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)h2 * w2 * C) return;
-    const long t = i / C;
-    const int c = (int)(i - t * C);
-    const int y = (int)(t / w2), x = (int)(t % w2);
-    float a = 0.f, k = 0.f;
-    for (int dy = 0; dy < 2; ++dy) for (int dx = 0; dx < 2; ++dx) {
-        const long q = (long)(2 * y + dy) * Ww + (2 * x + dx);
-        const float m = mask[q] ? 1.0f : 0.0f;
-        a = a + m;
-        const float vv = (zero_outside && !mask[q]) ? 0.f : kd[q * C + c];
-        k = k + vv;
-    }
-    a = a * 0.25f;
-    k = k * 0.25f;
-    if (a > 0.f && a < 1.f) k = k / a;
-    kd_mip[i] = k;
-    if (c == 0) mask_mip[t] = a > 0.f ? 1 : 0;
-}
-__global__ __launch_bounds__(256) void pp_push_c_kernel(const float* kd, const unsigned char* mask, int Hh, int Ww, int C, const float* kd_mip, float* out) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long)Hh * Ww * C) return;
-    const long t = i / C;
-    const int c = (int)(i - t * C);
-    if (mask[t]) { out[i] = kd[i]; return; }
-    const int y = (int)(t / Ww), x = (int)(t % Ww);
-    const int h2 = Hh / 2, w2 = Ww / 2;
-    const int ii = y >> 1, j = x >> 1, py = y & 1, px = x & 1;
-    const int iy = py ? min(ii + 1, h2 - 1) : max(ii - 1, 0);
-    const int jx = px ? min(j + 1, w2 - 1) : max(j - 1, 0);
-    const float c_ = kd_mip[((long)ii * w2 + j) * C + c], cx = kd_mip[((long)ii * w2 + jx) * C + c];
-    const float cy = kd_mip[((long)iy * w2 + j) * C + c], cxy = kd_mip[((long)iy * w2 + jx) * C + c];
-    const float w9 = 0.5625f, w3 = 0.1875f, w1 = 0.0625f;
-    float r;
-    if (!py && !px) r = ((cxy * w1 + cy * w3) + cx * w3) + c_ * w9;
-    else if (!py && px) r = ((cy * w3 + cxy * w1) + c_ * w9) + cx * w3;
-    else if (py && !px) r = ((cx * w3 + c_ * w9) + cxy * w1) + cy * w3;
-    else r = ((c_ * w9 + cx * w3) + cy * w3) + cxy * w1;
-    out[i] = r;
-}
-
-extern "C" size_t utx_pull_push_workspace_bytes_c_impl(int Hh, int Ww, int C) {
+extern "C" size_t utx_pull_push_workspace_bytes_impl(int Hh, int Ww, int C) {
     if (C < 1 || C > 16) return 0;
     size_t tot = 0;
     int h = Hh, w = Ww;
@@ -570,7 +463,7 @@ extern "C" size_t utx_pull_push_workspace_bytes_c_impl(int Hh, int Ww, int C) {
     return tot + 256;
 }
 
-extern "C" int utx_launch_pull_push_c(const float* kd, const void* mask, int Hh, int Ww, int C, float* out, void* work, hipStream_t stream) {
+extern "C" int utx_launch_pull_push(const float* kd, const void* mask, int Hh, int Ww, int C, float* out, void* work, hipStream_t stream) {
     if (Hh <= 0 || Ww <= 0 || C < 1 || C > 16) return -2;
     int n = 0;
     { int lh = 0, lw = 0; while ((1 << (lh + 1)) <= Hh) ++lh; while ((1 << (lw + 1)) <= Ww) ++lw; n = (lh < lw ? lh : lw) - 2; if (n < 0) n = 0; }
@@ -587,15 +480,12 @@ extern "C" int utx_launch_pull_push_c(const float* kd, const void* mask, int Hh,
         fill[l] = (float*)p; p += px * 4 * C;
         ms[l] = (unsigned char*)p; p += (px + 63) & ~(size_t)63;
     }
-    for (int l = 1; l <= n; ++l) {
-        const long px = (long)hs[l] * wsz[l] * C;
-        hipLaunchKernelGGL(pp_pull_c_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, stream, kds[l - 1], ms[l - 1], hs[l - 1], wsz[l - 1], C,
-                           l == 1 ? 1 : 0, kds[l], ms[l]);
-    }
+    for (int l = 1; l <= n; ++l)
+        PP_LAUNCH(pp_pull_kernel, (long)hs[l] * wsz[l], C, stream, kds[l - 1], ms[l - 1], hs[l - 1], wsz[l - 1], C, l == 1 ? 1 : 0, kds[l], ms[l]);
+    // coarsest level is its own fill; push down to level 0
     const float* cur = kds[n];
     for (int l = n - 1; l >= 0; --l) {
-        const long px = (long)hs[l] * wsz[l] * C;
-        hipLaunchKernelGGL(pp_push_c_kernel, dim3((unsigned)((px + 255) / 256)), dim3(256), 0, stream, kds[l], ms[l], hs[l], wsz[l], C, cur, fill[l]);
+        PP_LAUNCH(pp_push_kernel, (long)hs[l] * wsz[l], C, stream, kds[l], ms[l], hs[l], wsz[l], C, cur, fill[l]);
         cur = fill[l];
     }
     return hipGetLastError() == hipSuccess ? 0 : -4;

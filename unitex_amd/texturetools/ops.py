@@ -348,16 +348,25 @@ def knn_gather(src_pos, dst_pos, k, src_attr=None, src_mask=None, dst_mask=None,
     return out
 
 
+# ---- atlas post-processing.  Every image is interleaved [H,W,C] f32, 1 <= C <= CHANNELS_MAX, each channel on its own: a channel's result does not depend on
+# C or on where in the image it sits.  C == 3 goes through the 3-channel entries of the C ABI, any other C through the *_c entries (one library routine behind both).
+CHANNELS_MAX = 16
+
+
 def nn_fill(atlas, winner, rast2d, pos, want_index=False):
-    """in place on atlas [H,W,3]"""
+    """in place on atlas [H,W,C]; want_index: returns the search's nn_index [H*W] i32 (-1 where the texel was not filled)"""
     ctx = get_ctx(atlas.device.index)
     H, W = winner.shape
     T = H * W
+    Cc = atlas.shape[-1]
     wb = ctx.lib.utx_nn_fill_workspace_bytes(T)
     work = torch.empty(wb, dtype=U8, device=atlas.device)
-    idx = torch.empty(T, dtype=I32, device=atlas.device) if want_index else None
-    ctx.check(ctx.lib.utx_nn_fill(ctx.handle, ptr(_f(pos)), ptr(winner), ptr(_f(rast2d)), T, ptr(_f(atlas)), ptr(idx), ptr(work), wb, ctx.stream()))
-    return idx
+    idx = torch.empty(T, dtype=I32, device=atlas.device) if (want_index or Cc != 3) else None      # utx_nn_fill_c copies from the index
+    if Cc == 3:
+        ctx.check(ctx.lib.utx_nn_fill(ctx.handle, ptr(_f(pos)), ptr(winner), ptr(_f(rast2d)), T, ptr(_f(atlas)), ptr(idx), ptr(work), wb, ctx.stream()))
+    else:
+        ctx.check(ctx.lib.utx_nn_fill_c(ctx.handle, ptr(_f(pos)), ptr(winner), ptr(_f(rast2d)), T, Cc, ptr(_f(atlas)), ptr(idx), ptr(work), wb, ctx.stream()))
+    return idx if want_index else None
 
 
 def lens_blur_kernel49(radius=3.0):
@@ -386,13 +395,18 @@ def lens_blur_kernel49(radius=3.0):
 
 
 def lens_blur_seam(src, seam, k49=None):
+    """src [H,W,C] f32, seam [H,W] u8 -> dst: the collapsed lens blur where seam is set, src elsewhere"""
     ctx = get_ctx(src.device.index)
     H, W = seam.shape
     if k49 is None:
         k49 = lens_blur_kernel49()
     arr = (C.c_float * 49)(*[float(x) for x in np.asarray(k49, dtype=np.float32).reshape(-1)])
     dst = torch.empty_like(src)
-    ctx.check(ctx.lib.utx_lens_blur_seam(ctx.handle, ptr(_f(src)), ptr(seam), H, W, arr, ptr(dst), ctx.stream()))
+    Cc = src.shape[-1]
+    if Cc == 3:
+        ctx.check(ctx.lib.utx_lens_blur_seam(ctx.handle, ptr(_f(src)), ptr(seam), H, W, arr, ptr(dst), ctx.stream()))
+    else:
+        ctx.check(ctx.lib.utx_lens_blur_seam_c(ctx.handle, ptr(_f(src)), ptr(seam), H, W, Cc, arr, ptr(dst), ctx.stream()))
     return dst
 
 
@@ -407,31 +421,37 @@ def gaussian_kernel1d(ksize):
 
 
 def gaussian_blur_seam(src, seam, ksize=5):
-    """src [H,W,3] f32, seam [H,W] u8 -> dst: torchvision's gaussian_blur(src, (ksize, ksize)) (reflect padding) where seam is set, src
+    """src [H,W,C] f32, seam [H,W] u8 -> dst: torchvision's gaussian_blur(src, (ksize, ksize)) (reflect padding) where seam is set, src
     elsewhere (bake_mv_to_uv_reproject_blur(method='gaussian'), :618-625).  ksize odd, 1..31, ksize // 2 < min(H, W)."""
     ctx = get_ctx(src.device.index)
     H, W = seam.shape
     w1 = gaussian_kernel1d(int(ksize))
     arr = (C.c_float * int(ksize))(*[float(x) for x in w1.numpy()])
     dst = torch.empty_like(src)
-    ctx.check(ctx.lib.utx_gaussian_blur_seam(ctx.handle, ptr(_f(src)), ptr(seam), H, W, int(ksize), arr, ptr(dst), ctx.stream()))
+    Cc = src.shape[-1]
+    if Cc == 3:
+        ctx.check(ctx.lib.utx_gaussian_blur_seam(ctx.handle, ptr(_f(src)), ptr(seam), H, W, int(ksize), arr, ptr(dst), ctx.stream()))
+    else:
+        ctx.check(ctx.lib.utx_gaussian_blur_seam_c(ctx.handle, ptr(_f(src)), ptr(seam), H, W, Cc, int(ksize), arr, ptr(dst), ctx.stream()))
     return dst
 
 
 def pull_push(kd, mask):
-    """kd [H,W,3] f32, mask [H,W] u8 -> [H,W,3]"""
+    """kd [H,W,C] f32, mask [H,W] u8 -> [H,W,C]"""
     ctx = get_ctx(kd.device.index)
     H, W = mask.shape
-    wb = ctx.lib.utx_pull_push_workspace_bytes(H, W)
-    work = torch.empty(wb, dtype=U8, device=kd.device)
+    Cc = kd.shape[-1]
+    wb = ctx.lib.utx_pull_push_workspace_bytes(H, W) if Cc == 3 else ctx.lib.utx_pull_push_workspace_bytes_c(H, W, Cc)
+    work = torch.empty(max(wb, 1), dtype=U8, device=kd.device)
     out = torch.empty_like(kd)
-    ctx.check(ctx.lib.utx_pull_push(ctx.handle, ptr(_f(kd)), ptr(mask), H, W, ptr(out), ptr(work), ctx.stream()))
+    if Cc == 3:
+        ctx.check(ctx.lib.utx_pull_push(ctx.handle, ptr(_f(kd)), ptr(mask), H, W, ptr(out), ptr(work), ctx.stream()))
+    else:
+        ctx.check(ctx.lib.utx_pull_push_c(ctx.handle, ptr(_f(kd)), ptr(mask), H, W, Cc, ptr(out), ptr(work), ctx.stream()))
     return out
 
 
-# ---- the C-channel (PBR stack) bake: visibility and winner without colour, one gather from the winning view, C-channel post-processing.
-# Every image is interleaved [..., C] f32, 1 <= C <= CHANNELS_MAX; channels [3g, 3g+3) of a result equal the 3-channel function's result on that group.
-CHANNELS_MAX = 16
+# ---- the C-channel (PBR stack) bake: visibility and winner without colour, one gather from the winning view (images interleaved [..., C] f32, 1 <= C <= CHANNELS_MAX)
 
 
 def backproject_vis(rast2d, verts, faces, fnormal, vndc, dirs, alpha, bvh, angle_deg=100.0, view_begin=0, view_count=None, out=None, eyes=None,
@@ -487,54 +507,6 @@ def gather_winner(rast2d, faces, vndc, images, winner, sample="grid"):
     ctx.check(ctx.lib.utx_gather_winner(ctx.handle, ptr(_f(rast2d)), ptr(_i(faces)), ptr(_f(vndc)), ptr(_f(images)), ptr(winner), Th * Tw, vndc.shape[1], n,
                                         H, W, Cc, 1 if sample == "nvdiff" else 0, ptr(atlas), ctx.stream()))
     return atlas
-
-
-def nn_fill_c(atlas, winner, rast2d, pos):
-    """nn_fill() in place on atlas [H,W,C]; returns the search's nn_index [H*W] i32"""
-    ctx = get_ctx(atlas.device.index)
-    H, W = winner.shape
-    T = H * W
-    wb = ctx.lib.utx_nn_fill_workspace_bytes(T)
-    work = torch.empty(wb, dtype=U8, device=atlas.device)
-    idx = torch.empty(T, dtype=I32, device=atlas.device)
-    ctx.check(ctx.lib.utx_nn_fill_c(ctx.handle, ptr(_f(pos)), ptr(winner), ptr(_f(rast2d)), T, atlas.shape[-1], ptr(_f(atlas)), ptr(idx), ptr(work), wb,
-                                    ctx.stream()))
-    return idx
-
-
-def lens_blur_seam_c(src, seam, k49=None):
-    """lens_blur_seam() on src [H,W,C]"""
-    ctx = get_ctx(src.device.index)
-    H, W = seam.shape
-    if k49 is None:
-        k49 = lens_blur_kernel49()
-    arr = (C.c_float * 49)(*[float(x) for x in np.asarray(k49, dtype=np.float32).reshape(-1)])
-    dst = torch.empty_like(src)
-    ctx.check(ctx.lib.utx_lens_blur_seam_c(ctx.handle, ptr(_f(src)), ptr(seam), H, W, src.shape[-1], arr, ptr(dst), ctx.stream()))
-    return dst
-
-
-def gaussian_blur_seam_c(src, seam, ksize=5):
-    """gaussian_blur_seam() on src [H,W,C]"""
-    ctx = get_ctx(src.device.index)
-    H, W = seam.shape
-    w1 = gaussian_kernel1d(int(ksize))
-    arr = (C.c_float * int(ksize))(*[float(x) for x in w1.numpy()])
-    dst = torch.empty_like(src)
-    ctx.check(ctx.lib.utx_gaussian_blur_seam_c(ctx.handle, ptr(_f(src)), ptr(seam), H, W, src.shape[-1], int(ksize), arr, ptr(dst), ctx.stream()))
-    return dst
-
-
-def pull_push_c(kd, mask):
-    """pull_push() on kd [H,W,C]"""
-    ctx = get_ctx(kd.device.index)
-    H, W = mask.shape
-    Cc = kd.shape[-1]
-    wb = ctx.lib.utx_pull_push_workspace_bytes_c(H, W, Cc)
-    work = torch.empty(max(wb, 1), dtype=U8, device=kd.device)
-    out = torch.empty_like(kd)
-    ctx.check(ctx.lib.utx_pull_push_c(ctx.handle, ptr(_f(kd)), ptr(mask), H, W, Cc, ptr(out), ptr(work), ctx.stream()))
-    return out
 
 
 def to_u8(img, flip=False):

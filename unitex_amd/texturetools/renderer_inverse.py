@@ -360,30 +360,17 @@ class NVDiffRendererInverse:
                     color, vis = self._gather_layers(color, vis, per, n)
         mask_u8 = (rast2d[..., 3] > 0).to(torch.uint8).contiguous()
         winner = seam = None
-        if stack:
+        if method == "reproject":
             with self._stage("composite"):
-                winner = ops.composite_winner(vis, self.index)
-            with self._stage("seam_mask"):
-                seam = ops.seam_mask(winner, rast2d, reproject_kernel_size_boundary, reproject_kernel_size_boundary_blur)
-            with self._stage("gather_winner"):
-                atlas = ops.gather_winner(rast2d, m.faces, vndc, image_attrs.contiguous(), winner, sample=sample)
-            with self._stage("nn_fill"):
-                pos = ops.interpolate(m.vertices, rast2d, m.faces)
-                if reproject_inpainting:
-                    self._fill_unseen(atlas, (winner >= 0).to(torch.uint8), rast2d[..., 3] > 0, pos, True)
+                if stack:
+                    winner = ops.composite_winner(vis, self.index)
                 else:
-                    ops.nn_fill_c(atlas, winner, rast2d, pos)
-            if reproject_method == "gaussian":
-                with self._stage("gaussian_blur_seam"):
-                    baked = ops.gaussian_blur_seam_c(atlas, seam, reproject_kernel_size_blur)
-            else:
-                with self._stage("lens_blur_seam"):
-                    baked = ops.lens_blur_seam_c(atlas, seam)
-        elif method == "reproject":
-            with self._stage("composite"):
-                atlas, winner = ops.composite(color, vis, self.index)
+                    atlas, winner = ops.composite(color, vis, self.index)
             with self._stage("seam_mask"):
                 seam = ops.seam_mask(winner, rast2d, reproject_kernel_size_boundary, reproject_kernel_size_boundary_blur)
+            if stack:
+                with self._stage("gather_winner"):
+                    atlas = ops.gather_winner(rast2d, m.faces, vndc, image_attrs.contiguous(), winner, sample=sample)
             with self._stage("nn_fill"):
                 pos = ops.interpolate(m.vertices, rast2d, m.faces)
                 if reproject_inpainting:
@@ -403,12 +390,7 @@ class NVDiffRendererInverse:
                                           kdtree_method, kdtree_n_neighbors, kdtree_n_neighbors_visiable, kdtree_n_neighbors_invisiable,
                                           kdtree_inpainting)
         with self._stage("pull_push"):
-            if baked.shape[-1] == 3:
-                color_2d = ops.pull_push(baked, mask_u8)
-            elif stack:
-                color_2d = ops.pull_push_c(baked, mask_u8)
-            else:   # PBR stack: three rgb groups through the same 3-channel kernel
-                color_2d = torch.cat([ops.pull_push(baked[..., c:c + 3].contiguous(), mask_u8) for c in range(0, baked.shape[-1], 3)], dim=-1)
+            color_2d = ops.pull_push(baked, mask_u8)
         with self._stage("to_u8"):
             # tensor_to_image + FLIP_TOP_BOTTOM (link_pbr_to_mesh.py:17 / :46-48); nine channels: albedo 0:3, metallic-roughness 3:6, bump 6:9 (:716-721)
             texs = [ops.to_u8(color_2d[..., c:c + 3].contiguous(), flip=True) for c in range(0, color_2d.shape[-1], 3)]
