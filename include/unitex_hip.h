@@ -478,6 +478,35 @@ typedef struct utx_knn_desc {
 long utx_knn_workspace_bytes(long N);
 int utx_knn(utx_ctx* ctx, const utx_knn_desc* d, void* work, long work_bytes, utx_stream stream);
 
+/* ---- geometry sampling for the field stage (pipeline.py:363-407 sampling_on_mesh; TextureTools/texturetools/geometry/sampling/) ---- */
+
+/* exact farthest-point sampling (replaces fpsample.bucket_fps_kdline_sampling [3p], pipeline.py:390,401, and the thinning of the atlas texels,
+ * pipeline.py:507-514).  pos [N][3] f32 (16-byte aligned), mask [N] u8 (optional) -> out_idx [M] i32, out_d2 [M] f32 (optional): the pick's squared
+ * distance to the set chosen before it, +inf for the first pick.  d2 = (dx*dx + dy*dy) + dz*dz in float32.  A point that is masked out or has a
+ * non-finite coordinate is never a candidate; each pick is the candidate farthest from the chosen set, ties -> lower index, and leaves the candidate
+ * set (coincident points are picked later with d2 = 0, no index twice); when the candidates run out the rest of out_idx and out_d2 is -1.
+ * start >= 0: the first pick (a start that is no candidate counts as -1); start = -1: the lowest candidate index.
+ * 0 < M, 0 < N < 2^31, -1 <= start < N, else -2.  One kernel launch per pick on `stream`, M + 1 launches, no synchronisation; work: utx_fps_workspace_bytes(N)
+ * bytes, 16-byte aligned, owned by the call until the stream has run it. */
+long utx_fps_workspace_bytes(long N);
+int utx_fps(utx_ctx* ctx, const float* pos, const void* mask, long N, int M, int start, int* out_idx, float* out_d2, void* work, long work_bytes,
+            utx_stream stream);
+/* sample_on_edges_v2 (edge_sampling.py:102-119): N equally spaced samples along the selected edges laid end to end.  verts [V][3] f32, edges [E][2] i32
+ * (the selected edges), edge_ids [E] i32 (optional: each one's index in the full edge list, else 0..E-1), start [E] f32 (length before each edge, start[0] = 0),
+ * length [E] f32, total = their sum.  Sample i: t = linspace(0, total, N)[i] (torch's formula: step = total / (N - 1); lower half step * i, upper half
+ * total - step * (N - 1 - i)); e = searchsorted(start[1:], t), lower bound; w = (t - start[e]) / length[e], 0.5 when non-finite; point = w * v0 + (1 - w) * v1.
+ * One step beyond the reference: w is then clamped to [0, 1].  start[] holds ROUNDED running sums, so t can pass start[e] + length[e] by half a float32 step of the
+ * running length and the unclamped point would lie past the end of the edge it reports; where the sums are exact the clamp changes nothing.
+ * -> samples [N][3] f32, edge_index [N] i32 (optional), edge_t [N] f32 (optional). */
+int utx_sample_edges_equal_steps(utx_ctx* ctx, const float* verts, const int* edges, const int* edge_ids, const float* start, const float* length, int E,
+                                 float total, long N, float* samples, int* edge_index, float* edge_t, utx_stream stream);
+/* sample_surface (surface_sampling.py:24-35).  cum [F] f32: running sum of the face weights |cross(v1 - v0, v2 - v0)|.  The reference draws from the CUDA
+ * generator; here the stream is defined: Philox4x32-10, key (seed & 0xffffffff, seed >> 32), counter (i, 0, 0, 0) for sample i, a word x -> (x >> 8) * 2^-24.
+ * Word 0: face = min(searchsorted(cum, u0 * cum[F - 1]), F - 1), lower bound; words 1, 2: (u, v), folded as the reference does (u + v > 1: both minus 1, then
+ * absolute values), w = 1 - (u + v); point = (v0 * u + v1 * v) + v2 * w.  -> samples [N][3] f32, face_index [N] i32 (optional), uvw [N][3] f32 (optional). */
+int utx_sample_surface(utx_ctx* ctx, const float* verts, const int* faces, const float* cum, int F, long N, unsigned long long seed, float* samples,
+                       int* face_index, float* uvw, utx_stream stream);
+
 /* lens blur consumed on the seam only (image/lens_blur.py:260-280; renderer_inverse.py:620-624).
  * k49_host: HOST array, the collapsed real 7x7 kernel. src/dst [H][W][3] f32. */
 int utx_lens_blur_seam(utx_ctx* ctx, const float* src, const void* seam, int H, int W, const float* k49_host, float* dst, utx_stream stream);

@@ -201,6 +201,10 @@ SYMBOLS = {
                                           c_void_p, c_void_p, c_void_p, c_void_p]),
     "utx_knn_workspace_bytes": (c_long, [c_long]),
     "utx_knn": (c_int, [c_void_p, C.POINTER(KnnDesc), c_void_p, c_long, c_void_p]),
+    "utx_fps_workspace_bytes": (c_long, [c_long]),
+    "utx_fps": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
+    "utx_sample_edges_equal_steps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "utx_sample_surface": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, C.c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p]),
     "utx_nn_fill_workspace_bytes": (c_long, [c_long]),
     "utx_nn_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "utx_lens_blur_seam": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, C.POINTER(c_float), c_void_p, c_void_p]),

@@ -45,6 +45,7 @@ GEOM = [
     ("backproject.hip", ["-ffp-contract=off"] + NO_PK),
     ("texture_post.hip", ["-ffp-contract=off"] + NO_PK),
     ("knn.hip", ["-ffp-contract=off"]),
+    ("sampling.hip", ["-ffp-contract=off"]),
     ("unwrap.hip", []),
 ]
 for s in GEOM:

@@ -457,6 +457,22 @@ int utx_knn(utx_ctx* ctx, const utx_knn_desc* d, void* work, long work_bytes, ut
     if (!d || !d->src_pos || !d->dst_pos || !work) return fail(ctx, -2, "utx_knn");
     UTX_CALL(ctx, "utx_knn", utx_launch_knn(d, work, (size_t)work_bytes, (hipStream_t)stream));
 }
+long utx_fps_workspace_bytes(long N) { return (long)utx_fps_workspace_bytes_impl(N); }
+int utx_fps(utx_ctx* ctx, const float* pos, const void* mask, long N, int M, int start, int* out_idx, float* out_d2, void* work, long work_bytes,
+            utx_stream stream) {
+    if (!pos || !out_idx || !work || work_bytes < 0) return fail(ctx, -2, "utx_fps");
+    UTX_CALL(ctx, "utx_fps", utx_launch_fps(pos, (const unsigned char*)mask, N, M, start, out_idx, out_d2, work, (size_t)work_bytes, (hipStream_t)stream));
+}
+int utx_sample_edges_equal_steps(utx_ctx* ctx, const float* verts, const int* edges, const int* edge_ids, const float* start, const float* length, int E,
+                                 float total, long N, float* samples, int* edge_index, float* edge_t, utx_stream stream) {
+    if (!verts || !edges || !start || !length || !samples) return fail(ctx, -2, "utx_sample_edges_equal_steps");
+    UTX_CALL(ctx, "utx_sample_edges_equal_steps", utx_launch_sample_edges(verts, edges, edge_ids, start, length, E, total, N, samples, edge_index, edge_t, (hipStream_t)stream));
+}
+int utx_sample_surface(utx_ctx* ctx, const float* verts, const int* faces, const float* cum, int F, long N, unsigned long long seed, float* samples,
+                       int* face_index, float* uvw, utx_stream stream) {
+    if (!verts || !faces || !cum || !samples) return fail(ctx, -2, "utx_sample_surface");
+    UTX_CALL(ctx, "utx_sample_surface", utx_launch_sample_surface(verts, faces, cum, F, N, seed, samples, face_index, uvw, (hipStream_t)stream));
+}
 long utx_nn_fill_workspace_bytes(long T) { return (long)utx_nn_fill_workspace_bytes_impl(T); }
 int utx_nn_fill(utx_ctx* ctx, const float* pos, const void* winner, const float* rast2d, long T, float* atlas, int* nn_index,
                 void* work, long work_bytes, utx_stream stream) {

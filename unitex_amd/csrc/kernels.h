@@ -135,6 +135,12 @@ int utx_launch_view_visibility(const float* attr6, const float* rast, const floa
                                float grad_thr, float cos_thr, int radius, void* tmp, void* vis, float* alpha, hipStream_t stream);
 size_t utx_knn_workspace_bytes_impl(long N);
 int utx_launch_knn(const KnnParams* p, void* work, size_t work_bytes, hipStream_t stream);
+size_t utx_fps_workspace_bytes_impl(long N);      // sampling.hip
+int utx_launch_fps(const float* pos, const unsigned char* mask, long N, int M, int start, int* out_idx, float* out_d2, void* work, size_t work_bytes, hipStream_t stream);
+int utx_launch_sample_edges(const float* verts, const int* edges, const int* edge_ids, const float* start, const float* length, int E, float total, long N,
+                            float* samples, int* edge_index, float* edge_t, hipStream_t stream);
+int utx_launch_sample_surface(const float* verts, const int* faces, const float* cum, int F, long N, unsigned long long seed, float* samples, int* face_index,
+                              float* uvw, hipStream_t stream);
 int utx_launch_texture_shade(const float* rast, const float* uv, const int* tri, const float* tex, int Ht, int Wt, const float* bg3_host, long npix, void* out, hipStream_t stream);
 int utx_launch_gbuffer_shade(int mode, const float* rast, const int* tri, const float* attr, int stride, const float* scale2, int ndc, int composite, const float* bg3_host, long npix, void* out_u8, float* out_rgba, hipStream_t stream);
 int utx_launch_gbuffer_range(int mode, const float* rast, const int* tri, const float* attr, int stride, long npix, float* scale2, int* empty, hipStream_t stream);

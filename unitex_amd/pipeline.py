@@ -208,6 +208,27 @@ class RGBTextureFullPipelineBase:
                                                video_type="rgb", save_frames=False, save_grid=False, save_cover=False,
                                                save_camera=False, rename_with_euler=False)
 
+    @CPUTimer("sampling_on_mesh")
+    def sampling_on_mesh(self, save_dir, input_mesh_path, scale=1.0, N=200000, N_fps=32768, angle=15.0):
+        """reference pipeline.py:363-407, the geometry input of the field stage: N points on the sharp and non-manifold edges of the mesh and N points on its
+        surface (sharp_pcd.ply, coarse_pcd.ply), each thinned to N_fps points by farthest-point sampling (sharp_pcd_fps.ply, coarse_pcd_fps.ply).  A mesh
+        without such edges gives N_fps x (1, 1, 1); non-finite coordinates become 1.  The reference thins with fpsample.bucket_fps_kdline_sampling [3p],
+        whose start point is not pinned (the package is absent); here the thinning is exact farthest-point sampling started at index 0.
+        Not part of any step sequence, as in the reference."""
+        from .texturetools import meshes, sampling
+        paths = {k: os.path.join(save_dir, k + ".ply") for k in ("sharp_pcd", "coarse_pcd", "sharp_pcd_fps", "coarse_pcd_fps")}
+        device = str(self.inverse_renderer.device) if getattr(self, "inverse_renderer", None) is not None else "cuda:0"
+        sampling.geometry_sampling(input_mesh_path, paths["sharp_pcd"], paths["coarse_pcd"], scale=scale, N=N, angle_threhold_deg=angle,
+                                   method="equal_steps", merge_close_vertices=True, device=device)
+        for key in ("sharp_pcd", "coarse_pcd"):
+            cloud = meshes.load_ply(paths[key], faces_required=False)[0]
+            if cloud.shape[0] > 0:
+                idx = sampling.farthest_point_sampling(cloud, N_fps, start_idx=0, device=device)
+                thinned = np.nan_to_num(cloud[idx[idx >= 0]], copy=False, nan=1.0, posinf=1.0, neginf=1.0)
+            else:
+                thinned = np.full((N_fps, 3), fill_value=1.0, dtype=np.float32)
+            meshes.save_ply(paths[key + "_fps"], thinned)
+
     @CPUTimer("reproject_and_query_field")
     def reproject_and_query_field(self, save_dir, input_mesh_path, input_mv_image_path, camera_info_path, four_or_six=False,
                                   flatten=False, method="reproject", inpainting=False):

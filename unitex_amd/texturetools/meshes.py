@@ -424,10 +424,32 @@ def _fan(polys):
     return np.asarray(out, dtype=np.int32).reshape(-1, 3)
 
 
-def load_ply(path):
+def save_ply(path, vertices, colors_u8=None):
+    """point cloud as binary_little_endian PLY: element `vertex` only (float x y z, optional uchar red green blue), what trimesh writes for a Trimesh without
+    faces (pipeline.py:395-396).  vertices [N,3] (stored as float32), colors_u8 [N,3] uint8.  load_ply(path, faces_required=False) reads it back."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    head = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % len(v)
+    if colors_u8 is not None:
+        c = np.asarray(colors_u8)
+        if c.dtype != np.uint8 or c.shape != v.shape:
+            raise ValueError("colors_u8 must be uint8 of shape %s, got %s %s" % (v.shape, c.dtype, c.shape))
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        head += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    rec = np.empty(len(v), dtype=np.dtype(fields))
+    rec["x"], rec["y"], rec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if colors_u8 is not None:
+        rec["red"], rec["green"], rec["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    with open(path, "wb") as f:
+        f.write((head + "end_header\n").encode("ascii"))
+        f.write(rec.tobytes())
+
+
+def load_ply(path, faces_required=True):
     """Stanford PLY, ascii / binary_little_endian / binary_big_endian: element `vertex` (x y z, optional s t | u v | texture_u texture_v; any other property is
     skipped) and element `face` (a list property vertex_indices | vertex_index; other properties skipped; polygons fanned).  Other elements before / between are
-    skipped by their declared layout.  Returns (verts f32 [V,3], faces i32 [F,3], uvs f32 [V,2] | None)."""
+    skipped by their declared layout.  Returns (verts f32 [V,3], faces i32 [F,3], uvs f32 [V,2] | None).  A file without faces is refused unless
+    faces_required=False (point clouds: save_ply), which returns faces [0,3]."""
     with open(path, "rb") as f:
         blob = f.read()
     end = blob.find(b"end_header")
@@ -530,7 +552,7 @@ def load_ply(path):
         faces = polys.astype(np.int32)
     else:
         faces = _fan([list(p_) for p_ in polys])
-    if len(faces) == 0:
+    if len(faces) == 0 and faces_required:
         raise ValueError("%s holds no faces (a point cloud cannot be textured)" % path)
     return verts, faces, uvs
 

@@ -348,6 +348,59 @@ def knn_gather(src_pos, dst_pos, k, src_attr=None, src_mask=None, dst_mask=None,
     return out
 
 
+def fps(pos, n_samples, mask=None, start=0, want_d2=False):
+    """exact farthest-point sampling (utx_fps): pos [N,3] f32, mask [N] (optional) -> idx [n_samples] i32 (-1 behind the last candidate); want_d2: also each
+    pick's squared distance to the set chosen before it (+inf for the first, -1 behind the last candidate).  start: first pick, -1 = lowest valid index."""
+    ctx = get_ctx(pos.device.index)
+    pos = _f(pos).reshape(-1, 3)
+    if pos.data_ptr() % 16:
+        pos = pos.clone()
+    N, M, start = pos.shape[0], int(n_samples), int(start)
+    if M <= 0:
+        raise ValueError("farthest-point sampling needs n_samples > 0, got %d" % M)
+    if not 0 < N < 2 ** 31:
+        raise ValueError("farthest-point sampling takes 0 < N < 2^31 points, got %d" % N)
+    if not -1 <= start < N:
+        raise ValueError("start index %d is outside [-1, %d)" % (start, N))
+    if mask is not None:
+        mask = mask.reshape(-1).to(U8).contiguous()
+        assert mask.numel() == N
+    idx = torch.empty(M, dtype=I32, device=pos.device)
+    d2 = torch.empty(M, dtype=F32, device=pos.device) if want_d2 else None
+    wb = ctx.lib.utx_fps_workspace_bytes(N)
+    work = torch.empty(wb, dtype=U8, device=pos.device)
+    ctx.check(ctx.lib.utx_fps(ctx.handle, ptr(pos), ptr(mask), N, M, start, ptr(idx), ptr(d2), ptr(work), wb, ctx.stream()))
+    return (idx, d2) if want_d2 else idx
+
+
+def sample_edges_equal_steps(verts, edges, start, length, total, N, edge_ids=None):
+    """sample_on_edges_v2's sampling (utx_sample_edges_equal_steps): verts [V,3] f32, edges [E,2] i32 (selected), start / length [E] f32, total float
+    -> samples [N,3] f32, edge_index [N] i32 (edge_ids[e] when given, else e), edge_t [N] f32."""
+    ctx = get_ctx(verts.device.index)
+    E, N = edges.shape[0], int(N)
+    assert start.shape == (E,) and length.shape == (E,) and (edge_ids is None or edge_ids.shape == (E,))
+    samples = torch.empty(N, 3, dtype=F32, device=verts.device)
+    eidx = torch.empty(N, dtype=I32, device=verts.device)
+    et = torch.empty(N, dtype=F32, device=verts.device)
+    ctx.check(ctx.lib.utx_sample_edges_equal_steps(ctx.handle, ptr(_f(verts)), ptr(_i(edges)), ptr(_i(edge_ids) if edge_ids is not None else None), ptr(_f(start)),
+                                                   ptr(_f(length)), E, float(total), N, ptr(samples), ptr(eidx), ptr(et), ctx.stream()))
+    return samples, eidx, et
+
+
+def sample_surface(verts, faces, cum, N, seed):
+    """sample_surface's sampling on the defined Philox4x32-10 stream (utx_sample_surface): verts [V,3] f32, faces [F,3] i32, cum [F] f32 running face weights
+    -> samples [N,3] f32, face_index [N] i32, uvw [N,3] f32."""
+    ctx = get_ctx(verts.device.index)
+    F, N = faces.shape[0], int(N)
+    assert cum.shape == (F,)
+    samples = torch.empty(N, 3, dtype=F32, device=verts.device)
+    fidx = torch.empty(N, dtype=I32, device=verts.device)
+    uvw = torch.empty(N, 3, dtype=F32, device=verts.device)
+    ctx.check(ctx.lib.utx_sample_surface(ctx.handle, ptr(_f(verts)), ptr(_i(faces)), ptr(_f(cum)), F, N, int(seed) & (2 ** 64 - 1), ptr(samples), ptr(fidx), ptr(uvw),
+                                         ctx.stream()))
+    return samples, fidx, uvw
+
+
 # ---- atlas post-processing.  Every image is interleaved [H,W,C] f32, 1 <= C <= CHANNELS_MAX, each channel on its own: a channel's result does not depend on
 # C or on where in the image it sits.  C == 3 goes through the 3-channel entries of the C ABI, any other C through the *_c entries (one library routine behind both).
 CHANNELS_MAX = 16
