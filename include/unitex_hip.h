@@ -382,6 +382,66 @@ int utx_gbuffer_range(utx_ctx* ctx, int mode, const float* rast, const int* tri,
  * out [n_views][V][3] = F.normalize(nrm @ c2ws[:3,:3]) with the fixed order (n0*R0j + n1*R1j) + n2*R2j. */
 int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws, int n_views, float* out, utx_stream stream);
 
+/* Image-based PBR shading of the turntable: PBRModel (texture/pbr/pbr.py:18-49, 91-130), NVDiffRendererPBR.render_base / render_pbr
+ * (render/nvdiffrast/renderer_pbr.py:19-94) and the environment-light prefilters of the renderutils plugin (texture/pbr/renderutils/ops.py:398-465,
+ * c_src/cubemap.cu:12-139, 174-298).  Cubemaps are [6][N][N][3] fp32; face s and its in-face coordinates (fx, fy) in [-1, 1] follow cube_to_dir:
+ * 0 (1, -fy, -fx)  1 (-1, -fy, fx)  2 (fx, 1, fy)  3 (fx, -1, -fy)  4 (fx, -fy, 1)  5 (-fx, -fy, -1); texel i has its centre at f = 2 (i + 0.5) / N - 1.
+ * Everything is fp32 data, stream-ordered, without host synchronisation; a bad size returns -2.
+ *
+ * Cube lookup rule (utx_cube_sample, utx_pbr_forward, utx_pbr_shade; this library's own -- nvdiffrast's boundary_mode='cube' is third-party):
+ *   1. face = the component of largest magnitude, ties to x, then y (a zero vector looks up the centre of face 0); (fx, fy) = the other two
+ *      components over that magnitude;
+ *   2. t = (f + 1) * N / 2 - 0.5, base = floor(t), fraction = t - base; a fraction within N * 2^-21 of a texel centre snaps to it (four times
+ *      the fp32 uncertainty of t), so a texel-centre direction returns that texel exactly;
+ *   3. the four taps (base + {0, 1})^2 blend as a + f (b - a), along x first;
+ *   4. a tap that left the face along one axis is taken from the texel that holds its own direction on the neighbouring face (the edge texel
+ *      of the same row);
+ *   5. a tap that left along both axes is the mean ((t1 + t2) + t3) / 3 of the three texels that meet at that cube corner.
+ *   The value is continuous across edges and corners. */
+
+/* HOST tables of a cubemap size, computed in fp64 and rounded once: texels_host [6][N][N][4] = (unit direction of the texel centre, pixel_area of
+ * cubemap.cu:17-30); tiles_host_or_null [6][nt][nt][4], nt = ceil(N / 16) = (unit axis, cosine bound) of every 16^2 texel tile for the lobe
+ * of costheta_cutoff (utx_cubemap_specular culls with it).  N must be even (pixel_area halves it in integers), 2 <= N <= 8192.  Upload both 16-byte aligned. */
+int utx_cubemap_table(int N, float costheta_cutoff, float* texels_host, float* tiles_host_or_null);
+
+/* latlong_to_cubemap (pbr.py:28-49): latlong [Hi][Wi][3] -> out [6][N][N][3]; tu = atan2(vx, -vz) / 2pi + 0.5, tv = acos(vy) / pi, bilinear fetch
+ * with wrap addressing in both axes.  Coordinates and blend are carried in fp64 and rounded once. */
+int utx_latlong_to_cubemap(utx_ctx* ctx, const float* latlong, int Hi, int Wi, int N, float* out, utx_stream stream);
+
+/* diffuse prefilter (cubemap.cu:110-139): out(n) = sum over all 6 N^2 texels of c * clamp(n.L, 0, 0.999) * pixel_area / 3.141592 (the reference's
+ * constants).  texels_dev: utx_cubemap_table's texels on the device.  Fixed reduction order (run-to-run identical).  Odd N is refused. */
+int utx_cubemap_diffuse(utx_ctx* ctx, const float* cube, int N, const float* texels_dev, float* out, utx_stream stream);
+
+/* specular prefilter (cubemap.cu:174-179, 246-298 and the division of ops.py:465): over the texels with L.V >= costheta_cutoff,
+ * w = max(L.V, 0) * ndfGGX(roughness^4, max(V.H, 0)) * pixel_area / 4; out = sum(c w) / sum(w).  tiles_dev (built for the same cutoff) only culls: the
+ * accepted set is the cutoff test's.  A cubemap of ones returns exactly 1.0f, a lobe of one texel that texel exactly (the weights are carried relative to the first accepted texel's). */
+int utx_cubemap_specular(utx_ctx* ctx, const float* cube, int N, const float* texels_dev, const float* tiles_dev, float roughness, float costheta_cutoff,
+                         float* out, utx_stream stream);
+
+/* split-sum scale / bias table out [R][R][2] at cos(theta) = (column + 0.5) / R, roughness = (row + 0.5) / R: GGX importance sampling over the
+ * n_samples-point Hammersley set, height-correlated Smith GGX visibility (alpha = roughness^2), Schlick's (1 - V.H)^5. */
+int utx_dfg_lut(utx_ctx* ctx, int R, int n_samples, float* out, utx_stream stream);
+
+/* the cube lookup alone: dirs [n][3] (any length) -> out [n][3]. */
+int utx_cube_sample(utx_ctx* ctx, const float* cube, int N, const float* dirs, long n, float* out, utx_stream stream);
+
+/* PBRModel.forward (pbr.py:110-130) on dense buffers: view_pos [npix][3] (view_stride 3) or one [3] (view_stride 0), world_pos / world_nrm
+ * [npix][3], kd [npix][kd_stride >= 3], ks [npix][3] = (-, roughness, metallic), fg_lut [R][R][2] indexed (x = cos, y = roughness, clamp)
+ * -> out_diffuse, out_specular [npix][3]. */
+int utx_pbr_forward(utx_ctx* ctx, const float* view_pos, int view_stride, const float* world_pos, const float* world_nrm, const float* kd, int kd_stride,
+                    const float* ks, const float* light_diffuse, int Nd, const float* light_specular, int Ns, const float* fg_lut, int R, long npix,
+                    float* out_diffuse, float* out_specular, utx_stream stream);
+
+/* one fused PBR frame (renderer_pbr.py:19-94): rast [npix][4]; position, normal and uv interpolate as utx_interpolate does, kd [Hk][Wk][3] and
+ * ks_or_null [Hs][Ws][3] fetch as utx_texture_shade does (NULL = the reference's constant [1, 1, 0], bit-identical to that texture at kd's size);
+ * PBRModel.forward; rgb = lambda_diffuse * diffuse + lambda_specular * specular; background bg3_host where empty (alpha = coverage);
+ * out_u8 [npix][3] = clamp(0, 1) * 255 truncated; out_rgba_or_null [npix][4] fp32, alpha fourth.  eye3_host, bg3_host: HOST arrays of 3 floats.
+ * rast and out_rgba_or_null must be 16-byte aligned.  The bump texture is not applied: the shading normal is the interpolated vertex normal. */
+int utx_pbr_shade(utx_ctx* ctx, const float* rast, const int* tri, const float* v_pos, const float* v_nrm, const float* v_uv, const float* kd, int Hk, int Wk,
+                  const float* ks_or_null, int Hs, int Ws, const float* eye3_host, const float* light_diffuse, int Nd, const float* light_specular, int Ns,
+                  const float* fg_lut, int R, float lambda_diffuse, float lambda_specular, const float* bg3_host, long npix, void* out_u8,
+                  float* out_rgba_or_null, utx_stream stream);
+
 /* LBVH ray-mesh intersector (raytracing/__init__.py:12-83 RayTracing / rt_aprmis APRMISRayTracing; the build the
  * reference runs per mesh: raytracing/rt_aprmis/bvhhelpers.py:20-84).  verts/faces are borrowed and must stay alive while
  * the handle is used.

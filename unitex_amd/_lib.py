@@ -180,6 +180,16 @@ SYMBOLS = {
     "utx_gbuffer_shade": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, C.POINTER(c_float), c_long, c_void_p, c_void_p, c_void_p]),
     "utx_gbuffer_range": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p]),
     "utx_camera_normals": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "utx_cubemap_table": (c_int, [c_int, c_float, c_void_p, c_void_p]),
+    "utx_latlong_to_cubemap": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "utx_cubemap_diffuse": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "utx_cubemap_specular": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_float, c_float, c_void_p, c_void_p]),
+    "utx_dfg_lut": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "utx_cube_sample": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p, c_void_p]),
+    "utx_pbr_forward": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_long,
+                                c_void_p, c_void_p, c_void_p]),
+    "utx_pbr_shade": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, C.POINTER(c_float),
+                              c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_float, c_float, C.POINTER(c_float), c_long, c_void_p, c_void_p, c_void_p]),
     "utx_bvh_build": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, C.POINTER(c_void_p), c_void_p]),
     "utx_bvh_workspace_bytes": (C.c_size_t, [c_int]),
     "utx_bvh_build_ws": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, C.c_size_t, C.POINTER(c_void_p), c_void_p]),

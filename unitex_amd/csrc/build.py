@@ -41,6 +41,7 @@ SOURCES = [
 ]
 GEOM = [
     ("raster.hip", ["-ffp-contract=off"]),
+    ("pbr.hip", ["-ffp-contract=off"] + NO_PK),
     ("bvh.hip", ["-ffp-contract=off"] + NO_PK),
     ("backproject.hip", ["-ffp-contract=off"] + NO_PK),
     ("texture_post.hip", ["-ffp-contract=off"] + NO_PK),

@@ -376,6 +376,50 @@ int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws,
     UTX_CALL(ctx, "utx_camera_normals", utx_launch_camera_normals(nrm, V, c2ws, n_views, out, (hipStream_t)stream));
 }
 
+// ---- image-based PBR shading (pbr.hip) ----
+int utx_cubemap_table(int N, float costheta_cutoff, float* texels_host, float* tiles_host_or_null) {
+    return utx_cubemap_table_impl(N, costheta_cutoff, texels_host, tiles_host_or_null);
+}
+int utx_latlong_to_cubemap(utx_ctx* ctx, const float* latlong, int Hi, int Wi, int N, float* out, utx_stream stream) {
+    if (!latlong || !out) return fail(ctx, -2, "utx_latlong_to_cubemap");
+    UTX_CALL(ctx, "utx_latlong_to_cubemap", utx_launch_latlong_to_cubemap(latlong, Hi, Wi, N, out, (hipStream_t)stream));
+}
+int utx_cubemap_diffuse(utx_ctx* ctx, const float* cube, int N, const float* texels_dev, float* out, utx_stream stream) {
+    if (!cube || !texels_dev || !out || ((uintptr_t)texels_dev & 15)) return fail(ctx, -2, "utx_cubemap_diffuse");      // the table is read as float4
+    UTX_CALL(ctx, "utx_cubemap_diffuse", utx_launch_cubemap_diffuse(cube, N, texels_dev, out, (hipStream_t)stream));
+}
+int utx_cubemap_specular(utx_ctx* ctx, const float* cube, int N, const float* texels_dev, const float* tiles_dev, float roughness, float costheta_cutoff,
+                         float* out, utx_stream stream) {
+    if (!cube || !texels_dev || !tiles_dev || !out || ((uintptr_t)texels_dev & 15) || ((uintptr_t)tiles_dev & 15)) return fail(ctx, -2, "utx_cubemap_specular");
+    UTX_CALL(ctx, "utx_cubemap_specular", utx_launch_cubemap_specular(cube, N, texels_dev, tiles_dev, roughness, costheta_cutoff, out, (hipStream_t)stream));
+}
+int utx_dfg_lut(utx_ctx* ctx, int R, int n_samples, float* out, utx_stream stream) {
+    if (!out) return fail(ctx, -2, "utx_dfg_lut");
+    UTX_CALL(ctx, "utx_dfg_lut", utx_launch_dfg_lut(R, n_samples, out, (hipStream_t)stream));
+}
+int utx_cube_sample(utx_ctx* ctx, const float* cube, int N, const float* dirs, long n, float* out, utx_stream stream) {
+    if (!cube || !dirs || !out) return fail(ctx, -2, "utx_cube_sample");
+    UTX_CALL(ctx, "utx_cube_sample", utx_launch_cube_sample(cube, N, dirs, n, out, (hipStream_t)stream));
+}
+int utx_pbr_forward(utx_ctx* ctx, const float* view_pos, int view_stride, const float* world_pos, const float* world_nrm, const float* kd, int kd_stride,
+                    const float* ks, const float* light_diffuse, int Nd, const float* light_specular, int Ns, const float* fg_lut, int R, long npix,
+                    float* out_diffuse, float* out_specular, utx_stream stream) {
+    if (!view_pos || !world_pos || !world_nrm || !kd || !ks || !light_diffuse || !light_specular || !fg_lut || !out_diffuse || !out_specular)
+        return fail(ctx, -2, "utx_pbr_forward");
+    UTX_CALL(ctx, "utx_pbr_forward", utx_launch_pbr_forward(view_pos, view_stride, world_pos, world_nrm, kd, kd_stride, ks, light_diffuse, Nd, light_specular, Ns,
+                                                            fg_lut, R, npix, out_diffuse, out_specular, (hipStream_t)stream));
+}
+int utx_pbr_shade(utx_ctx* ctx, const float* rast, const int* tri, const float* v_pos, const float* v_nrm, const float* v_uv, const float* kd, int Hk, int Wk,
+                  const float* ks_or_null, int Hs, int Ws, const float* eye3_host, const float* light_diffuse, int Nd, const float* light_specular, int Ns,
+                  const float* fg_lut, int R, float lambda_diffuse, float lambda_specular, const float* bg3_host, long npix, void* out_u8,
+                  float* out_rgba_or_null, utx_stream stream) {
+    if (!rast || !tri || !v_pos || !v_nrm || !v_uv || !kd || !eye3_host || !light_diffuse || !light_specular || !fg_lut || !bg3_host || !out_u8)
+        return fail(ctx, -2, "utx_pbr_shade");
+    if (((uintptr_t)rast & 15) || ((uintptr_t)out_rgba_or_null & 15)) return fail(ctx, -2, "utx_pbr_shade");      // read / stored as float4
+    UTX_CALL(ctx, "utx_pbr_shade", utx_launch_pbr_shade(rast, tri, v_pos, v_nrm, v_uv, kd, Hk, Wk, ks_or_null, Hs, Ws, eye3_host, light_diffuse, Nd, light_specular, Ns,
+                                                        fg_lut, R, lambda_diffuse, lambda_specular, bg3_host, npix, out_u8, out_rgba_or_null, (hipStream_t)stream));
+}
+
 int utx_condition_shade(utx_ctx* ctx, const float* rast, const float* nrm, const float* pos, const float* bg3_host, long npix,
                         void* out_normal, void* out_ccm, void* out_alpha, utx_stream stream) {
     if (!rast || !nrm || !pos || !bg3_host || !out_normal || !out_ccm || !out_alpha) return fail(ctx, -2, "utx_condition_shade");

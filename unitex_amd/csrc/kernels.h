@@ -145,6 +145,18 @@ int utx_launch_texture_shade(const float* rast, const float* uv, const int* tri,
 int utx_launch_gbuffer_shade(int mode, const float* rast, const int* tri, const float* attr, int stride, const float* scale2, int ndc, int composite, const float* bg3_host, long npix, void* out_u8, float* out_rgba, hipStream_t stream);
 int utx_launch_gbuffer_range(int mode, const float* rast, const int* tri, const float* attr, int stride, long npix, float* scale2, int* empty, hipStream_t stream);
 int utx_launch_camera_normals(const float* nrm, int V, const float* c2ws, int n_views, float* out, hipStream_t stream);
+// pbr.hip
+int utx_cubemap_table_impl(int N, float costheta_cutoff, float* texels_host, float* tiles_host);
+int utx_launch_latlong_to_cubemap(const float* lat, int Hi, int Wi, int N, float* out, hipStream_t stream);
+int utx_launch_cubemap_diffuse(const float* cube, int N, const float* texels, float* out, hipStream_t stream);
+int utx_launch_cubemap_specular(const float* cube, int N, const float* texels, const float* tiles, float roughness, float costheta_cutoff, float* out, hipStream_t stream);
+int utx_launch_dfg_lut(int R, int nsamples, float* out, hipStream_t stream);
+int utx_launch_cube_sample(const float* cube, int N, const float* dirs, long n, float* out, hipStream_t stream);
+int utx_launch_pbr_forward(const float* eye, int eye_stride, const float* pos, const float* nrm, const float* kd, int kd_stride, const float* ks, const float* light_diffuse, int Nd,
+                           const float* light_specular, int Ns, const float* lut, int R, long npix, float* out_diffuse, float* out_specular, hipStream_t stream);
+int utx_launch_pbr_shade(const float* rast, const int* tri, const float* vpos, const float* vnrm, const float* vuv, const float* kd, int Hk, int Wk, const float* ks, int Hs, int Ws,
+                         const float* eye3_host, const float* light_diffuse, int Nd, const float* light_specular, int Ns, const float* lut, int R, float lambda_diffuse,
+                         float lambda_specular, const float* bg3_host, long npix, void* out_u8, float* out_rgba, hipStream_t stream);
 int utx_bvh_build_impl(const float* verts, int V, const int* faces, int F, utx_bvh** out, hipStream_t stream);
 size_t utx_bvh_workspace_bytes_impl(int F);
 int utx_bvh_build_ws_impl(const float* verts, int V, const int* faces, int F, void* work, size_t work_bytes, utx_bvh** out, hipStream_t stream);

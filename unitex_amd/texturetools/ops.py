@@ -142,6 +142,102 @@ def camera_normals(nrm, c2ws):
     return out
 
 
+def cubemap_tables(N, costheta_cutoff=None, device="cuda"):
+    """utx_cubemap_table: (texels [6,N,N,4] = unit direction + pixel_area, tiles [6,nt,nt,4] or None) on `device`, built on the host in fp64.
+    Runs without a GPU when device is 'cpu' (the tests' oracle reads the same table)."""
+    from .._lib import load_library
+    lib = load_library()
+    tex = np.empty((6, N, N, 4), np.float32)
+    nt = (N + 15) // 16
+    tiles = np.empty((6, nt, nt, 4), np.float32) if costheta_cutoff is not None else None
+    rc = lib.utx_cubemap_table(int(N), float(costheta_cutoff if costheta_cutoff is not None else 1.0), tex.ctypes.data_as(C.c_void_p),
+                               tiles.ctypes.data_as(C.c_void_p) if tiles is not None else None)
+    if rc != 0:
+        raise ValueError("utx_cubemap_table(N=%d) -> %d: N must be even, 2 <= N <= 8192" % (N, rc))
+    return torch.from_numpy(tex).to(device), (torch.from_numpy(tiles).to(device) if tiles is not None else None)
+
+
+def latlong_to_cubemap(latlong, N):
+    """latlong [Hi,Wi,3] -> cubemap [6,N,N,3] (utx_latlong_to_cubemap)"""
+    ctx = get_ctx(latlong.device.index)
+    out = torch.empty(6, N, N, 3, dtype=F32, device=latlong.device)
+    ctx.check(ctx.lib.utx_latlong_to_cubemap(ctx.handle, ptr(_f(latlong)), latlong.shape[0], latlong.shape[1], N, ptr(out), ctx.stream()))
+    return out
+
+
+def cubemap_diffuse(cube, texels=None):
+    """cube [6,N,N,3] -> the cosine-convolved cubemap (utx_cubemap_diffuse); texels: cubemap_tables(N)[0], built if None"""
+    ctx = get_ctx(cube.device.index)
+    N = cube.shape[1]
+    assert cube.shape == (6, N, N, 3)
+    if texels is None:
+        texels, _ = cubemap_tables(N, None, cube.device)
+    out = torch.empty_like(cube)
+    ctx.check(ctx.lib.utx_cubemap_diffuse(ctx.handle, ptr(_f(cube)), N, ptr(_f(texels)), ptr(out), ctx.stream()))
+    return out
+
+
+def cubemap_specular(cube, roughness, costheta_cutoff, texels=None, tiles=None):
+    """cube [6,N,N,3] -> the GGX-prefiltered cubemap over the lobe L.V >= costheta_cutoff (utx_cubemap_specular)"""
+    ctx = get_ctx(cube.device.index)
+    N = cube.shape[1]
+    assert cube.shape == (6, N, N, 3)
+    if texels is None or tiles is None:
+        texels, tiles = cubemap_tables(N, costheta_cutoff, cube.device)
+    out = torch.empty_like(cube)
+    ctx.check(ctx.lib.utx_cubemap_specular(ctx.handle, ptr(_f(cube)), N, ptr(_f(texels)), ptr(_f(tiles)), float(roughness), float(costheta_cutoff), ptr(out),
+                                           ctx.stream()))
+    return out
+
+
+def dfg_lut(R=256, n_samples=1024, device="cuda"):
+    """split-sum table [R,R,2] (utx_dfg_lut), indexed (x = cos, y = roughness)"""
+    device = torch.device(device if device != "cuda" else "cuda:%d" % torch.cuda.current_device())
+    ctx = get_ctx(device.index)
+    out = torch.empty(R, R, 2, dtype=F32, device=device)
+    ctx.check(ctx.lib.utx_dfg_lut(ctx.handle, R, n_samples, ptr(out), ctx.stream()))
+    return out
+
+
+def cube_sample(cube, dirs):
+    """cube [6,N,N,3], dirs [...,3] -> [...,3] by the library's cube lookup rule (include/unitex_hip.h)"""
+    ctx = get_ctx(cube.device.index)
+    d = _f(dirs.reshape(-1, 3))
+    out = torch.empty_like(d)
+    ctx.check(ctx.lib.utx_cube_sample(ctx.handle, ptr(_f(cube)), cube.shape[1], ptr(d), d.shape[0], ptr(out), ctx.stream()))
+    return out.reshape(dirs.shape)
+
+
+def pbr_forward(view_pos, world_pos, world_nrm, kd, ks, light_diffuse, light_specular, fg_lut):
+    """dense PBRModel.forward (utx_pbr_forward): view_pos [3] or [npix,3], world_pos / world_nrm [npix,3], kd [npix,>=3], ks [npix,3]
+    -> (diffuse, specular) [npix,3]"""
+    ctx = get_ctx(world_pos.device.index)
+    npix = world_pos.shape[0]
+    d = torch.empty(npix, 3, dtype=F32, device=world_pos.device)
+    s = torch.empty_like(d)
+    ctx.check(ctx.lib.utx_pbr_forward(ctx.handle, ptr(_f(view_pos)), 0 if view_pos.numel() == 3 else 3, ptr(_f(world_pos)), ptr(_f(world_nrm)), ptr(_f(kd)),
+                                      kd.shape[1], ptr(_f(ks)), ptr(_f(light_diffuse)), light_diffuse.shape[1], ptr(_f(light_specular)),
+                                      light_specular.shape[1], ptr(_f(fg_lut)), fg_lut.shape[0], npix, ptr(d), ptr(s), ctx.stream()))
+    return d, s
+
+
+def pbr_shade(rast, tri, v_pos, v_nrm, v_uv, kd, ks, eye, light_diffuse, light_specular, fg_lut, lambda_diffuse=1.0, lambda_specular=1.0,
+              bg=(1.0, 1.0, 1.0), want_rgba=False):
+    """one PBR frame (utx_pbr_shade): rast [H,W,4], kd [Hk,Wk,3] / ks [Hs,Ws,3] or None in UV-raster orientation, eye = 3 floats
+    -> uint8 RGB [H,W,3] (, float RGBA [H,W,4])"""
+    ctx = get_ctx(rast.device.index)
+    H, W = rast.shape[:2]
+    out = torch.empty(H, W, 3, dtype=U8, device=rast.device)
+    rgba = torch.empty(H, W, 4, dtype=F32, device=rast.device) if want_rgba else None
+    ev = (C.c_float * 3)(*[float(e) for e in eye])
+    bgv = (C.c_float * 3)(*[float(b) for b in bg])
+    ctx.check(ctx.lib.utx_pbr_shade(ctx.handle, ptr(_f(rast)), ptr(_i(tri)), ptr(_f(v_pos)), ptr(_f(v_nrm)), ptr(_f(v_uv)), ptr(_f(kd)), kd.shape[0], kd.shape[1],
+                                    ptr(_f(ks) if ks is not None else None), ks.shape[0] if ks is not None else 0, ks.shape[1] if ks is not None else 0, ev,
+                                    ptr(_f(light_diffuse)), light_diffuse.shape[1], ptr(_f(light_specular)), light_specular.shape[1], ptr(_f(fg_lut)),
+                                    fg_lut.shape[0], float(lambda_diffuse), float(lambda_specular), bgv, H * W, ptr(out), ptr(rgba), ctx.stream()))
+    return (out, rgba) if want_rgba else out
+
+
 class BVH:
     """utx_bvh handle (RayTracing / APRMISRayTracing of the reference)."""
 

@@ -137,29 +137,37 @@ class VideoExporter:
 
     def export_orbit_video(self, mesh_obj, video_path, n_frames=120, enhance_mode=None, perspective=True, video_type="rgb",
                            save_frames=False, save_grid=False, save_cover=False, save_camera=False, rename_with_euler=False,
-                           render_size=1024, fps=15, return_frames=False):
+                           render_size=1024, fps=15, return_frames=False, pbr_model=None):
         """turntable of a textured mesh on a white background.  mesh_obj: path to a textured .glb, a TexturedMesh
         (renderer_inverse.py) or (verts, faces, uvs01, texture_u8_top_down[, vertex_normals]).
         video_type: 'rgb' or a geometry buffer of the same mesh ('world_normal', 'camera_normal', 'world_position', 'camera_position',
         'z_depth', 'distance'; export_nvdiffrast_video.py:157-175): normals / positions mapped x*0.5+0.5, depths normalised with the (min, max) of
         the FIRST frame's covered pixels (later frames may leave [0, 1] and are clamped in the file).  Vertex normals are
         _vertex_normals(self.normal_weighting) unless the mesh tuple brings its own.
-        return_frames: True -> the uint8 frames, 'rgba' -> the float RGBA frames of export_video (geometry types only)."""
+        return_frames: True -> the uint8 frames, 'rgba' -> the float RGBA frames of export_video (geometry types only).
+        pbr_model: a pbr.PBRModel -> the 'rgb' frames are lit by its environment (utx_pbr_shade: NVDiffRendererPBR.render_base / render_pbr,
+        render/nvdiffrast/renderer_pbr.py:19-94, alpha = coverage) instead of the unlit texture fetch.  map_Ks = (-, roughness, metallic) is the mesh's
+        .metallic_roughness (a TexturedMesh of the 9-channel bake; glTF's G / B channels) or a sixth tuple element (uint8, top-down like the texture), else
+        the reference's default [1, 1, 0].  The bump texture is not applied (no tangent-space normal maps).  None: the unlit path, unchanged."""
         ext = os.path.splitext(video_path)[1]
         assert ext in [".mp4", ".gif"]
         assert video_type in ["rgb", "albedo", "world_normal", "camera_normal", "world_position", "camera_position", "z_depth", "distance"]
         if video_type == "albedo":       # uv_rendering has no render_albedo: the reference's render_result['albedo'] raises (export_video :103)
             raise KeyError("albedo")
         assert return_frames != "rgba" or video_type != "rgb", "return_frames='rgba' is for the geometry video types"
-        vnrm = None
+        if pbr_model is not None and video_type != "rgb":
+            raise ValueError("pbr_model lights the 'rgb' video only, not video_type=%r" % (video_type,))
+        vnrm, tex_ks = None, None
         if isinstance(mesh_obj, str):
             verts, faces, uvs, tex = meshes.load_mesh(mesh_obj)
             verts = meshes.normalise_to_bbox(verts, 1.0)              # texture.mesh.scale_to_bbox() (:178)
         elif isinstance(mesh_obj, (tuple, list)):
             verts, faces, uvs, tex = mesh_obj[:4]
             vnrm = mesh_obj[4] if len(mesh_obj) > 4 else None
+            tex_ks = mesh_obj[5] if len(mesh_obj) > 5 else None
         else:
             verts, faces, uvs, tex = mesh_obj.vertices, mesh_obj.faces, mesh_obj.uv, mesh_obj.texture
+            tex_ks = getattr(mesh_obj, "metallic_roughness", None)
         assert uvs is not None and tex is not None, "missing map_Kd in texture"
         if enhance_mode is None:
             c2ws = camera.generate_orbit_views_c2ws(n_frames + 1, radius=2.8, height=0.0, theta_0=0.0, degree=True)[:n_frames]
@@ -185,7 +193,17 @@ class VideoExporter:
         mvp = torch.matmul(camera.intr_to_proj(intrinsics, perspective=perspective), camera.c2w_to_w2c(c2ws)).to(dev).contiguous()
         clip, _ = ops.transform_points(vd, mvp, want_ndc=False)
         frames, rgba = [], []
-        if video_type == "rgb":
+        if pbr_model is not None:
+            to_tex = lambda t: torch.from_numpy(np.ascontiguousarray(np.asarray(t)[::-1, :, :3]).astype(np.float32) / np.float32(255.0)).to(dev).contiguous()
+            ksd = to_tex(tex_ks) if tex_ks is not None else None
+            nd = (torch.as_tensor(np.asarray(vnrm), dtype=torch.float32) if vnrm is not None
+                  else _vertex_normals(torch.as_tensor(np.asarray(verts), dtype=torch.float32), torch.as_tensor(np.asarray(faces)), self.normal_weighting))
+            nd = nd.to(dev).contiguous()
+            for i in range(c2ws.shape[0]):
+                rast = ops.rasterize(clip[i].contiguous(), fd, render_size, render_size)
+                frames.append(ops.pbr_shade(rast, fd, vd, nd, uvd, texd, ksd, c2ws[i, :3, 3].tolist(), pbr_model.light_diffuse, pbr_model.light_specular,
+                                            pbr_model.FG_LUT[0], bg=(1.0, 1.0, 1.0)).cpu().numpy())
+        elif video_type == "rgb":
             for i in range(c2ws.shape[0]):
                 rast = ops.rasterize(clip[i].contiguous(), fd, render_size, render_size)
                 frames.append(ops.texture_shade(rast, uvd, fd, texd, bg=(1.0, 1.0, 1.0)).cpu().numpy())
