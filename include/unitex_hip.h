@@ -388,7 +388,7 @@ int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws,
  * 0 (1, -fy, -fx)  1 (-1, -fy, fx)  2 (fx, 1, fy)  3 (fx, -1, -fy)  4 (fx, -fy, 1)  5 (-fx, -fy, -1); texel i has its centre at f = 2 (i + 0.5) / N - 1.
  * Everything is fp32 data, stream-ordered, without host synchronisation; a bad size returns -2.
  *
- * Cube lookup rule (utx_cube_sample, utx_pbr_forward, utx_pbr_shade; this library's own -- nvdiffrast's boundary_mode='cube' is third-party):
+ * Cube lookup rule (utx_cube_sample, utx_pbr_forward, utx_pbr_shade, utx_pbr_shade_nm; this library's own -- nvdiffrast's boundary_mode='cube' is third-party):
  *   1. face = the component of largest magnitude, ties to x, then y (a zero vector looks up the centre of face 0); (fx, fy) = the other two
  *      components over that magnitude;
  *   2. t = (f + 1) * N / 2 - 0.5, base = floor(t), fraction = t - base; a fraction within N * 2^-21 of a texel centre snaps to it (four times
@@ -436,11 +436,35 @@ int utx_pbr_forward(utx_ctx* ctx, const float* view_pos, int view_stride, const 
  * ks_or_null [Hs][Ws][3] fetch as utx_texture_shade does (NULL = the reference's constant [1, 1, 0], bit-identical to that texture at kd's size);
  * PBRModel.forward; rgb = lambda_diffuse * diffuse + lambda_specular * specular; background bg3_host where empty (alpha = coverage);
  * out_u8 [npix][3] = clamp(0, 1) * 255 truncated; out_rgba_or_null [npix][4] fp32, alpha fourth.  eye3_host, bg3_host: HOST arrays of 3 floats.
- * rast and out_rgba_or_null must be 16-byte aligned.  The bump texture is not applied: the shading normal is the interpolated vertex normal. */
+ * rast and out_rgba_or_null must be 16-byte aligned.  The shading normal is the interpolated vertex normal; utx_pbr_shade_nm applies a normal map. */
 int utx_pbr_shade(utx_ctx* ctx, const float* rast, const int* tri, const float* v_pos, const float* v_nrm, const float* v_uv, const float* kd, int Hk, int Wk,
                   const float* ks_or_null, int Hs, int Ws, const float* eye3_host, const float* light_diffuse, int Nd, const float* light_specular, int Ns,
                   const float* fg_lut, int R, float lambda_diffuse, float lambda_specular, const float* bg3_host, long npix, void* out_u8,
                   float* out_rgba_or_null, utx_stream stream);
+
+/* tangent-space normal map: bsdf_prepare_shading_normal (texture/pbr/renderutils/bsdf.py:28-51) with two_sided_shading = True and opengl = True
+ * (glTF's convention), on dense buffers: view_pos [npix][3] (view_stride 3) or one [3] (view_stride 0); world_pos, perturbed_nrm (the decoded map value,
+ * not normalised), smooth_nrm, smooth_tng, geom_nrm [npix][3] -> out [npix][3].  fp32, every sum in a fixed order; normalize(x) = x / max(|x|, 1e-12):
+ *   sn = normalize(smooth_nrm);  st = normalize(smooth_tng);  vv = normalize(view_pos - world_pos);  b = normalize(cross(st, sn))
+ *   s  = normalize((st * p.x - b * p.y) + sn * max(p.z, 0))
+ *   dot(geom_nrm, vv) > 0 ? (s, g) = (s, geom_nrm) : (s, g) = (-s, -geom_nrm)
+ *   t  = clamp(dot(vv, s) / 0.1, 0, 1);  out = g + t * (s - g)
+ * out is not normalised (utx_pbr_forward normalises its normal).  A zero tangent, a tangent parallel to the normal, a zero perturbation and a negative
+ * p.z give finite values (the floors turn a zero vector into a zero vector; s = 0 gives out = g).  Mirrored UV charts (handedness -1) are not handled,
+ * as in the reference: the bitangent is always cross(tangent, normal).
+ * Returns -2 for a null pointer, npix <= 0 or a view_stride other than 0 and 3. */
+int utx_pbr_shading_normal(utx_ctx* ctx, const float* view_pos, int view_stride, const float* world_pos, const float* perturbed_nrm, const float* smooth_nrm,
+                           const float* smooth_tng, const float* geom_nrm, long npix, float* out, utx_stream stream);
+
+/* utx_pbr_shade with a tangent-space normal map.  As utx_pbr_shade, plus: v_tng [V][3] (per-vertex tangents, interpolated exactly as v_nrm is), f_nrm [F][3]
+ * (utx_face_normals' output, indexed by the pixel's triangle: the geometric normal) and nm [Hn][Wn][3] fp32 in UV-raster orientation, fetched as kd is and
+ * decoded as p = 2 * texel - 1 without normalisation.  The rule of utx_pbr_shading_normal with (interpolated position, p, interpolated normal, interpolated
+ * tangent, f_nrm[triangle]) gives the normal that PBRModel.forward shades with; everything after that is utx_pbr_shade's.
+ * Returns -2 for a null pointer (ks_or_null and out_rgba_or_null excepted), a non-positive size, or rast / out_rgba_or_null off a 16-byte boundary. */
+int utx_pbr_shade_nm(utx_ctx* ctx, const float* rast, const int* tri, const float* v_pos, const float* v_nrm, const float* v_tng, const float* f_nrm, const float* v_uv,
+                     const float* kd, int Hk, int Wk, const float* ks_or_null, int Hs, int Ws, const float* nm, int Hn, int Wn, const float* eye3_host,
+                     const float* light_diffuse, int Nd, const float* light_specular, int Ns, const float* fg_lut, int R, float lambda_diffuse, float lambda_specular,
+                     const float* bg3_host, long npix, void* out_u8, float* out_rgba_or_null, utx_stream stream);
 
 /* LBVH ray-mesh intersector (raytracing/__init__.py:12-83 RayTracing / rt_aprmis APRMISRayTracing; the build the
  * reference runs per mesh: raytracing/rt_aprmis/bvhhelpers.py:20-84).  verts/faces are borrowed and must stay alive while

@@ -190,6 +190,10 @@ SYMBOLS = {
                                 c_void_p, c_void_p, c_void_p]),
     "utx_pbr_shade": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, C.POINTER(c_float),
                               c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_float, c_float, C.POINTER(c_float), c_long, c_void_p, c_void_p, c_void_p]),
+    "utx_pbr_shading_normal": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p]),
+    "utx_pbr_shade_nm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
+                                 c_void_p, c_int, c_int, C.POINTER(c_float), c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_float, c_float, C.POINTER(c_float),
+                                 c_long, c_void_p, c_void_p, c_void_p]),
     "utx_bvh_build": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, C.POINTER(c_void_p), c_void_p]),
     "utx_bvh_workspace_bytes": (C.c_size_t, [c_int]),
     "utx_bvh_build_ws": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, C.c_size_t, C.POINTER(c_void_p), c_void_p]),

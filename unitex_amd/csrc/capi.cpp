@@ -419,6 +419,23 @@ int utx_pbr_shade(utx_ctx* ctx, const float* rast, const int* tri, const float* 
     UTX_CALL(ctx, "utx_pbr_shade", utx_launch_pbr_shade(rast, tri, v_pos, v_nrm, v_uv, kd, Hk, Wk, ks_or_null, Hs, Ws, eye3_host, light_diffuse, Nd, light_specular, Ns,
                                                         fg_lut, R, lambda_diffuse, lambda_specular, bg3_host, npix, out_u8, out_rgba_or_null, (hipStream_t)stream));
 }
+int utx_pbr_shading_normal(utx_ctx* ctx, const float* view_pos, int view_stride, const float* world_pos, const float* perturbed_nrm, const float* smooth_nrm,
+                           const float* smooth_tng, const float* geom_nrm, long npix, float* out, utx_stream stream) {
+    if (!view_pos || !world_pos || !perturbed_nrm || !smooth_nrm || !smooth_tng || !geom_nrm || !out) return fail(ctx, -2, "utx_pbr_shading_normal");
+    UTX_CALL(ctx, "utx_pbr_shading_normal", utx_launch_pbr_shading_normal(view_pos, view_stride, world_pos, perturbed_nrm, smooth_nrm, smooth_tng, geom_nrm, npix, out,
+                                                                          (hipStream_t)stream));
+}
+int utx_pbr_shade_nm(utx_ctx* ctx, const float* rast, const int* tri, const float* v_pos, const float* v_nrm, const float* v_tng, const float* f_nrm, const float* v_uv,
+                     const float* kd, int Hk, int Wk, const float* ks_or_null, int Hs, int Ws, const float* nm, int Hn, int Wn, const float* eye3_host,
+                     const float* light_diffuse, int Nd, const float* light_specular, int Ns, const float* fg_lut, int R, float lambda_diffuse, float lambda_specular,
+                     const float* bg3_host, long npix, void* out_u8, float* out_rgba_or_null, utx_stream stream) {
+    if (!rast || !tri || !v_pos || !v_nrm || !v_tng || !f_nrm || !v_uv || !kd || !nm || !eye3_host || !light_diffuse || !light_specular || !fg_lut || !bg3_host || !out_u8)
+        return fail(ctx, -2, "utx_pbr_shade_nm");
+    if (((uintptr_t)rast & 15) || ((uintptr_t)out_rgba_or_null & 15)) return fail(ctx, -2, "utx_pbr_shade_nm");      // read / stored as float4
+    UTX_CALL(ctx, "utx_pbr_shade_nm", utx_launch_pbr_shade_nm(rast, tri, v_pos, v_nrm, v_tng, f_nrm, v_uv, kd, Hk, Wk, ks_or_null, Hs, Ws, nm, Hn, Wn, eye3_host,
+                                                              light_diffuse, Nd, light_specular, Ns, fg_lut, R, lambda_diffuse, lambda_specular, bg3_host, npix, out_u8,
+                                                              out_rgba_or_null, (hipStream_t)stream));
+}
 
 int utx_condition_shade(utx_ctx* ctx, const float* rast, const float* nrm, const float* pos, const float* bg3_host, long npix,
                         void* out_normal, void* out_ccm, void* out_alpha, utx_stream stream) {

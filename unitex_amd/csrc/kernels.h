@@ -157,6 +157,12 @@ int utx_launch_pbr_forward(const float* eye, int eye_stride, const float* pos, c
 int utx_launch_pbr_shade(const float* rast, const int* tri, const float* vpos, const float* vnrm, const float* vuv, const float* kd, int Hk, int Wk, const float* ks, int Hs, int Ws,
                          const float* eye3_host, const float* light_diffuse, int Nd, const float* light_specular, int Ns, const float* lut, int R, float lambda_diffuse,
                          float lambda_specular, const float* bg3_host, long npix, void* out_u8, float* out_rgba, hipStream_t stream);
+int utx_launch_pbr_shading_normal(const float* eye, int eye_stride, const float* pos, const float* pert, const float* snrm, const float* stng, const float* gnrm, long npix,
+                                  float* out, hipStream_t stream);
+int utx_launch_pbr_shade_nm(const float* rast, const int* tri, const float* vpos, const float* vnrm, const float* vtng, const float* fnrm, const float* vuv, const float* kd, int Hk,
+                            int Wk, const float* ks, int Hs, int Ws, const float* nm, int Hn, int Wn, const float* eye3_host, const float* light_diffuse, int Nd,
+                            const float* light_specular, int Ns, const float* lut, int R, float lambda_diffuse, float lambda_specular, const float* bg3_host, long npix,
+                            void* out_u8, float* out_rgba, hipStream_t stream);
 int utx_bvh_build_impl(const float* verts, int V, const int* faces, int F, utx_bvh** out, hipStream_t stream);
 size_t utx_bvh_workspace_bytes_impl(int F);
 int utx_bvh_build_ws_impl(const float* verts, int V, const int* faces, int F, void* work, size_t work_bytes, utx_bvh** out, hipStream_t stream);

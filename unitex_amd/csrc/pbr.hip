@@ -472,6 +472,60 @@ extern "C" int utx_launch_pbr_forward(const float* eye, int eye_stride, const fl
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- tangent-space normal map
+// bsdf_prepare_shading_normal (texture/pbr/renderutils/bsdf.py:28-51) with two_sided_shading = True and opengl = True (glTF's convention) on one pixel,
+// every sum in a fixed order; normalize is F.normalize (x / max(|x|, 1e-12), pbr_normalize):
+//   sn = normalize(smooth_nrm);  st = normalize(smooth_tng);  vv = normalize(eye - pos);  b = normalize(cross(st, sn))
+//   s = normalize((st p.x - b p.y) + sn max(p.z, 0))
+//   dot(geom_nrm, vv) > 0 ? (s, g) = (s, geom_nrm) : (-s, -geom_nrm)
+//   t = clamp(dot(vv, s) / 0.1, 0, 1);  out = g + t (s - g)
+// out is not normalised (pbr_eval normalises its input).  A zero tangent, a tangent parallel to the normal, a zero perturbation and a negative p.z all
+// stay finite: the 1e-12 floors turn a zero vector into a zero vector, and s = 0 gives t = 0, out = g.
+__device__ __forceinline__ void pbr_shading_normal(const float eye[3], const float pos[3], const float p[3], const float smooth_nrm[3], const float smooth_tng[3],
+                                                   const float geom_nrm[3], float out[3]) {
+    float sn[3] = {smooth_nrm[0], smooth_nrm[1], smooth_nrm[2]}, st[3] = {smooth_tng[0], smooth_tng[1], smooth_tng[2]};
+    float vv[3] = {eye[0] - pos[0], eye[1] - pos[1], eye[2] - pos[2]};
+    pbr_normalize(sn);
+    pbr_normalize(st);
+    pbr_normalize(vv);
+    float b[3] = {st[1] * sn[2] - st[2] * sn[1], st[2] * sn[0] - st[0] * sn[2], st[0] * sn[1] - st[1] * sn[0]};
+    pbr_normalize(b);
+    const float pz = fmaxf(p[2], 0.0f);
+    float s[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) s[k] = (st[k] * p[0] - b[k] * p[1]) + sn[k] * pz;
+    pbr_normalize(s);
+    const bool front = pbr_dot3(geom_nrm, vv) > 0.0f;
+    float g[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { s[k] = front ? s[k] : -s[k]; g[k] = front ? geom_nrm[k] : -geom_nrm[k]; }
+    const float t = fminf(fmaxf(pbr_dot3(vv, s) / 0.1f, 0.0f), 1.0f);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[k] = g[k] + t * (s[k] - g[k]);
+}
+
+// dense form, the counterpart of pbr_forward_kernel: eye [npix][3] or one [3] (eye_stride 0), everything else [npix][3]
+__global__ __launch_bounds__(256) void pbr_shading_normal_kernel(const float* eye, int eye_stride, const float* pos, const float* pert, const float* snrm,
+                                                                 const float* stng, const float* gnrm, long npix, float* out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const float* e = eye + (long)eye_stride * i;
+    const float ev[3] = {e[0], e[1], e[2]}, p[3] = {pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]}, pt[3] = {pert[3 * i], pert[3 * i + 1], pert[3 * i + 2]};
+    const float n[3] = {snrm[3 * i], snrm[3 * i + 1], snrm[3 * i + 2]}, t[3] = {stng[3 * i], stng[3 * i + 1], stng[3 * i + 2]};
+    const float g[3] = {gnrm[3 * i], gnrm[3 * i + 1], gnrm[3 * i + 2]};
+    float o[3];
+    pbr_shading_normal(ev, p, pt, n, t, g, o);
+    out[3 * i] = o[0]; out[3 * i + 1] = o[1]; out[3 * i + 2] = o[2];
+}
+
+extern "C" int utx_launch_pbr_shading_normal(const float* eye, int eye_stride, const float* pos, const float* pert, const float* snrm, const float* stng,
+                                             const float* gnrm, long npix, float* out, hipStream_t stream) {
+    if (npix <= 0 || (eye_stride != 0 && eye_stride != 3)) return -2;
+    hipLaunchKernelGGL(pbr_shading_normal_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, eye, eye_stride, pos, pert, snrm, stng, gnrm, npix,
+                       out);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
 // ---------------------------------------------------------------------------------------------------------------- fused frame
 // NVDiffRendererPBR.render_base + render_pbr (renderer_pbr.py:19-94) for one frame: position, normal and uv interpolate as utx_interpolate does (same
 // operations, same order); Kd / Ks fetch as utx_texture_shade does (bilinear, wrap, t00 (1 - fx) + t01 fx); PBRModel.forward; rgb = ld diffuse + ls specular;
@@ -495,9 +549,15 @@ __device__ __forceinline__ void pbr_tex_fetch(const float* tex, int Ht, int Wt, 
     }
 }
 
-__global__ __launch_bounds__(256) void pbr_shade_kernel(PbrLights L, const float4* rast, const int* tri, const float* vpos, const float* vnrm, const float* vuv,
-                                                        const float* kd, int Hk, int Wk, const float* ks, int Hs, int Ws, float e0, float e1, float e2,
-                                                        float lam_d, float lam_s, float bg0, float bg1, float bg2, long npix, unsigned char* out_u8,
+// NM = true (utx_pbr_shade_nm): the tangent interpolates as the normal does, the map fetches as Kd does and decodes as p = 2 texel - 1 (not normalised),
+// pbr_shading_normal with the triangle's face normal as the geometric one replaces the interpolated normal in front of pbr_eval.  NM = false is
+// utx_pbr_shade: none of that is compiled in and its arithmetic is what it was.
+struct PbrNormalMap { const float* vtng; const float* fnrm; const float* nm; int Hn, Wn; };
+
+template <bool NM>
+__global__ __launch_bounds__(256) void pbr_shade_kernel(PbrLights L, PbrNormalMap M, const float4* rast, const int* tri, const float* vpos, const float* vnrm,
+                                                        const float* vuv, const float* kd, int Hk, int Wk, const float* ks, int Hs, int Ws, float e0, float e1,
+                                                        float e2, float lam_d, float lam_s, float bg0, float bg1, float bg2, long npix, unsigned char* out_u8,
                                                         float4* out_rgba) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= npix) return;
@@ -520,6 +580,16 @@ __global__ __launch_bounds__(256) void pbr_shade_kernel(PbrLights L, const float
         pbr_tex_fetch(kd, Hk, Wk, uv[0], uv[1], 0.f, 0.f, 0.f, al);
         pbr_tex_fetch(ks, ks ? Hs : Hk, ks ? Ws : Wk, uv[0], uv[1], 1.0f, 1.0f, 0.0f, arm);
         const float eye[3] = {e0, e1, e2};
+        if constexpr (NM) {
+            float tg[3], tx[3];
+#pragma unroll
+            for (int k = 0; k < 3; ++k) tg[k] = (M.vtng[3 * i0 + k] * u + M.vtng[3 * i1 + k] * v) + M.vtng[3 * i2 + k] * w;
+            pbr_tex_fetch(M.nm, M.Hn, M.Wn, uv[0], uv[1], 0.f, 0.f, 0.f, tx);
+            const float pt[3] = {2.0f * tx[0] - 1.0f, 2.0f * tx[1] - 1.0f, 2.0f * tx[2] - 1.0f};
+            const float g[3] = {M.fnrm[3 * (long)id], M.fnrm[3 * (long)id + 1], M.fnrm[3 * (long)id + 2]};
+            const float sm[3] = {n[0], n[1], n[2]};
+            pbr_shading_normal(eye, p, pt, sm, tg, g, n);
+        }
         float d[3], s[3];
         pbr_eval(L, eye, p, n, al, arm[1], arm[2], d, s);
 #pragma unroll
@@ -530,15 +600,41 @@ __global__ __launch_bounds__(256) void pbr_shade_kernel(PbrLights L, const float
     if (out_rgba) out_rgba[i] = make_float4(c[0], c[1], c[2], a);
 }
 
+static int pbr_shade_launch(const PbrNormalMap* M, const float* rast, const int* tri, const float* vpos, const float* vnrm, const float* vuv, const float* kd, int Hk,
+                            int Wk, const float* ks, int Hs, int Ws, const float* eye3_host, const float* light_diffuse, int Nd, const float* light_specular,
+                            int Ns, const float* lut, int R, float lambda_diffuse, float lambda_specular, const float* bg3_host, long npix, void* out_u8,
+                            float* out_rgba, hipStream_t stream) {
+    if (npix <= 0 || Hk <= 0 || Wk <= 0 || (ks && (Hs <= 0 || Ws <= 0)) || Nd <= 0 || Ns <= 0 || R <= 0 || Nd > 8192 || Ns > 8192 || !eye3_host || !bg3_host)
+        return -2;
+    const PbrLights L = {light_diffuse, Nd, light_specular, Ns, lut, R};
+    const PbrNormalMap none = {nullptr, nullptr, nullptr, 0, 0};
+    const dim3 grid((unsigned)((npix + 255) / 256));
+    if (M) {
+        hipLaunchKernelGGL(pbr_shade_kernel<true>, grid, dim3(256), 0, stream, L, *M, (const float4*)rast, tri, vpos, vnrm, vuv, kd, Hk, Wk, ks, Hs, Ws, eye3_host[0],
+                           eye3_host[1], eye3_host[2], lambda_diffuse, lambda_specular, bg3_host[0], bg3_host[1], bg3_host[2], npix, (unsigned char*)out_u8,
+                           (float4*)out_rgba);
+    } else {
+        hipLaunchKernelGGL(pbr_shade_kernel<false>, grid, dim3(256), 0, stream, L, none, (const float4*)rast, tri, vpos, vnrm, vuv, kd, Hk, Wk, ks, Hs, Ws, eye3_host[0],
+                           eye3_host[1], eye3_host[2], lambda_diffuse, lambda_specular, bg3_host[0], bg3_host[1], bg3_host[2], npix, (unsigned char*)out_u8,
+                           (float4*)out_rgba);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
 extern "C" int utx_launch_pbr_shade(const float* rast, const int* tri, const float* vpos, const float* vnrm, const float* vuv, const float* kd, int Hk, int Wk,
                                     const float* ks, int Hs, int Ws, const float* eye3_host, const float* light_diffuse, int Nd,
                                     const float* light_specular, int Ns, const float* lut, int R, float lambda_diffuse, float lambda_specular,
                                     const float* bg3_host, long npix, void* out_u8, float* out_rgba, hipStream_t stream) {
-    if (npix <= 0 || Hk <= 0 || Wk <= 0 || (ks && (Hs <= 0 || Ws <= 0)) || Nd <= 0 || Ns <= 0 || R <= 0 || Nd > 8192 || Ns > 8192 || !eye3_host || !bg3_host)
-        return -2;
-    const PbrLights L = {light_diffuse, Nd, light_specular, Ns, lut, R};
-    hipLaunchKernelGGL(pbr_shade_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, L, (const float4*)rast, tri, vpos, vnrm, vuv, kd, Hk, Wk,
-                       ks, Hs, Ws, eye3_host[0], eye3_host[1], eye3_host[2], lambda_diffuse, lambda_specular, bg3_host[0], bg3_host[1], bg3_host[2], npix,
-                       (unsigned char*)out_u8, (float4*)out_rgba);
-    return hipGetLastError() == hipSuccess ? 0 : -4;
+    return pbr_shade_launch(nullptr, rast, tri, vpos, vnrm, vuv, kd, Hk, Wk, ks, Hs, Ws, eye3_host, light_diffuse, Nd, light_specular, Ns, lut, R, lambda_diffuse,
+                            lambda_specular, bg3_host, npix, out_u8, out_rgba, stream);
+}
+
+extern "C" int utx_launch_pbr_shade_nm(const float* rast, const int* tri, const float* vpos, const float* vnrm, const float* vtng, const float* fnrm, const float* vuv,
+                                       const float* kd, int Hk, int Wk, const float* ks, int Hs, int Ws, const float* nm, int Hn, int Wn, const float* eye3_host,
+                                       const float* light_diffuse, int Nd, const float* light_specular, int Ns, const float* lut, int R, float lambda_diffuse,
+                                       float lambda_specular, const float* bg3_host, long npix, void* out_u8, float* out_rgba, hipStream_t stream) {
+    if (!vtng || !fnrm || !nm || Hn <= 0 || Wn <= 0) return -2;
+    const PbrNormalMap M = {vtng, fnrm, nm, Hn, Wn};
+    return pbr_shade_launch(&M, rast, tri, vpos, vnrm, vuv, kd, Hk, Wk, ks, Hs, Ws, eye3_host, light_diffuse, Nd, light_specular, Ns, lut, R, lambda_diffuse,
+                            lambda_specular, bg3_host, npix, out_u8, out_rgba, stream);
 }

@@ -945,6 +945,39 @@ def normalise_to_bbox(verts, scale):
     return ((verts - 0.5 * (lo + hi)) / ((hi - lo).max() / (2.0 * scale))).astype(np.float32)
 
 
+def vertex_tangents(verts, faces, uvs, normals):
+    """per-vertex unit tangents (the direction in which u grows) for tangent-space normal maps, float64 on the host (mesh preparation, like
+    video._vertex_normals) -> float32 tensor [V,3], unit length and orthogonal to the vertex normal.  verts [V,3], faces [F,3], uvs [V,2], normals [V,3]
+    (arrays or tensors; the normals need not be unit).
+
+    Per face, with the edges e1, e2 and the UV edges d1, d2 from corner 0: T = (e1 d2.v - e2 d1.v) / det, det = d1.u d2.v - d1.v d2.u; a face with
+    |det| < 1e-12 (no UV area) contributes nothing.  T is added to the face's three vertices in face order, then t = T - (T.n) n, normalised.  A vertex
+    whose t is shorter than 1e-12 (unreferenced, only degenerate faces, or T parallel to n) gets normalize(cross(n, e_k)), e_k the coordinate axis on
+    which |n| is smallest ((1, 0, 0) if the normal itself is zero).
+    Mirrored UV charts (handedness -1) are not handled, as in the reference: the shader's bitangent is always cross(tangent, normal), so a chart whose
+    v runs the other way shades with a flipped bitangent."""
+    import torch
+    as64 = lambda a: torch.as_tensor(np.asarray(a.cpu() if torch.is_tensor(a) else a)).double()
+    v, uv, f = as64(verts), as64(uvs), torch.as_tensor(np.asarray(faces.cpu() if torch.is_tensor(faces) else faces)).long()
+    n = torch.nn.functional.normalize(as64(normals), dim=-1)
+    e1, e2 = v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]]
+    d1, d2 = uv[f[:, 1]] - uv[f[:, 0]], uv[f[:, 2]] - uv[f[:, 0]]
+    det = d1[:, 0] * d2[:, 1] - d1[:, 1] * d2[:, 0]
+    ok = det.abs() >= 1e-12
+    T = (e1 * d2[:, 1:2] - e2 * d1[:, 1:2]) / torch.where(ok, det, torch.ones_like(det))[:, None]
+    T = torch.where(ok[:, None], T, torch.zeros_like(T))
+    acc = torch.zeros_like(v)
+    for k in range(3):
+        acc.index_add_(0, f[:, k], T)
+    t = acc - (acc * n).sum(-1, keepdim=True) * n
+    tl = t.norm(dim=-1, keepdim=True)
+    axis = torch.eye(3, dtype=n.dtype)[n.abs().argmin(-1)]
+    fb = torch.linalg.cross(n, axis, dim=-1)
+    fl = fb.norm(dim=-1, keepdim=True)
+    fb = torch.where(fl >= 1e-12, fb / fl.clamp_min(1e-300), torch.tensor([1.0, 0.0, 0.0], dtype=n.dtype))
+    return torch.where(tl >= 1e-12, t / tl.clamp_min(1e-300), fb).float().contiguous()
+
+
 def prepare_blank_mesh(path, min_faces=20_000, max_faces=200_000, scale=1.0, atlas=2048, gutter=4.0, unwrap="grid", device="cuda:0"):
     """preprocess_blank_mesh_o3d (uv_atlas.py:131-175) with the host-side equivalents above: rescale to the bbox;
     a mesh that already has UVs passes through; otherwise clean, bring the face count into [min_faces, max_faces],

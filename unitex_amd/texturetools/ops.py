@@ -221,20 +221,43 @@ def pbr_forward(view_pos, world_pos, world_nrm, kd, ks, light_diffuse, light_spe
     return d, s
 
 
+def pbr_shading_normal(view_pos, world_pos, perturbed_nrm, smooth_nrm, smooth_tng, geom_nrm):
+    """the shading normal of a tangent-space normal map (utx_pbr_shading_normal: bsdf_prepare_shading_normal, two-sided, OpenGL convention): view_pos [3] or
+    [npix,3], the rest [npix,3] (perturbed_nrm = the decoded map value) -> [npix,3], not normalised"""
+    ctx = get_ctx(world_pos.device.index)
+    npix = world_pos.shape[0]
+    out = torch.empty(npix, 3, dtype=F32, device=world_pos.device)
+    ctx.check(ctx.lib.utx_pbr_shading_normal(ctx.handle, ptr(_f(view_pos)), 0 if view_pos.numel() == 3 else 3, ptr(_f(world_pos)), ptr(_f(perturbed_nrm)),
+                                             ptr(_f(smooth_nrm)), ptr(_f(smooth_tng)), ptr(_f(geom_nrm)), npix, ptr(out), ctx.stream()))
+    return out
+
+
 def pbr_shade(rast, tri, v_pos, v_nrm, v_uv, kd, ks, eye, light_diffuse, light_specular, fg_lut, lambda_diffuse=1.0, lambda_specular=1.0,
-              bg=(1.0, 1.0, 1.0), want_rgba=False):
+              bg=(1.0, 1.0, 1.0), want_rgba=False, v_tng=None, f_nrm=None, normal_map=None):
     """one PBR frame (utx_pbr_shade): rast [H,W,4], kd [Hk,Wk,3] / ks [Hs,Ws,3] or None in UV-raster orientation, eye = 3 floats
-    -> uint8 RGB [H,W,3] (, float RGBA [H,W,4])"""
+    -> uint8 RGB [H,W,3] (, float RGBA [H,W,4]).
+    v_tng [V,3] (meshes.vertex_tangents), f_nrm [F,3] (face_normals) and normal_map [Hn,Wn,3] (fp32, UV-raster orientation), all three or none: the frame is
+    shaded with the map's normal (utx_pbr_shade_nm)."""
+    nm_args = (v_tng, f_nrm, normal_map)
+    if any(a is not None for a in nm_args) and any(a is None for a in nm_args):
+        raise ValueError("pbr_shade: v_tng, f_nrm and normal_map go together (all three or none)")
     ctx = get_ctx(rast.device.index)
     H, W = rast.shape[:2]
     out = torch.empty(H, W, 3, dtype=U8, device=rast.device)
     rgba = torch.empty(H, W, 4, dtype=F32, device=rast.device) if want_rgba else None
     ev = (C.c_float * 3)(*[float(e) for e in eye])
     bgv = (C.c_float * 3)(*[float(b) for b in bg])
-    ctx.check(ctx.lib.utx_pbr_shade(ctx.handle, ptr(_f(rast)), ptr(_i(tri)), ptr(_f(v_pos)), ptr(_f(v_nrm)), ptr(_f(v_uv)), ptr(_f(kd)), kd.shape[0], kd.shape[1],
-                                    ptr(_f(ks) if ks is not None else None), ks.shape[0] if ks is not None else 0, ks.shape[1] if ks is not None else 0, ev,
-                                    ptr(_f(light_diffuse)), light_diffuse.shape[1], ptr(_f(light_specular)), light_specular.shape[1], ptr(_f(fg_lut)),
-                                    fg_lut.shape[0], float(lambda_diffuse), float(lambda_specular), bgv, H * W, ptr(out), ptr(rgba), ctx.stream()))
+    ksp, Hs, Ws = ptr(_f(ks) if ks is not None else None), ks.shape[0] if ks is not None else 0, ks.shape[1] if ks is not None else 0
+    lights = (ptr(_f(light_diffuse)), light_diffuse.shape[1], ptr(_f(light_specular)), light_specular.shape[1], ptr(_f(fg_lut)), fg_lut.shape[0],
+              float(lambda_diffuse), float(lambda_specular), bgv, H * W, ptr(out), ptr(rgba), ctx.stream())
+    if normal_map is None:
+        ctx.check(ctx.lib.utx_pbr_shade(ctx.handle, ptr(_f(rast)), ptr(_i(tri)), ptr(_f(v_pos)), ptr(_f(v_nrm)), ptr(_f(v_uv)), ptr(_f(kd)), kd.shape[0], kd.shape[1],
+                                        ksp, Hs, Ws, ev, *lights))
+    else:
+        assert v_tng.shape == v_nrm.shape and f_nrm.shape == tri.shape and normal_map.dim() == 3 and normal_map.shape[2] == 3
+        ctx.check(ctx.lib.utx_pbr_shade_nm(ctx.handle, ptr(_f(rast)), ptr(_i(tri)), ptr(_f(v_pos)), ptr(_f(v_nrm)), ptr(_f(v_tng)), ptr(_f(f_nrm)), ptr(_f(v_uv)),
+                                           ptr(_f(kd)), kd.shape[0], kd.shape[1], ksp, Hs, Ws, ptr(_f(normal_map)), normal_map.shape[0], normal_map.shape[1], ev,
+                                           *lights))
     return (out, rgba) if want_rgba else out
 
 

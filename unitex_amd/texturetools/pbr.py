@@ -6,8 +6,11 @@ its two prefilters (texture/pbr/renderutils/ops.py:398-465), on the HIP kernels 
 
 Colour order: the reference reads its map with cv2.imread and hands the BGR array to the shader as it is; here the map stays RGB (read_hdr and PIL both
 return RGB), which is what the file means.
-Not built (the reference's render_pbr has them or nvdiffrast does): tangent-space normal maps -- the bump texture is not applied, the shading normal is
-the interpolated vertex normal --, dr.antialias, backward passes, and render_pbr's lambda_* knobs other than lambda_diffuse / lambda_specular."""
+Tangent-space normal maps (the bump texture of the 9-channel bake, glTF's normalTexture): export_orbit_video(normal_map=...) shades with
+bsdf_prepare_shading_normal's normal (renderutils/bsdf.py:28-51, two-sided, OpenGL convention; ops.pbr_shading_normal, ops.pbr_shade(normal_map=...));
+mirrored UV charts (tangent handedness -1) are not handled, as in the reference.
+Not built (the reference's render_pbr has them or nvdiffrast does): dr.antialias, backward passes, and render_pbr's lambda_* knobs other than
+lambda_diffuse / lambda_specular."""
 import re
 
 import numpy as np

@@ -137,7 +137,7 @@ class VideoExporter:
 
     def export_orbit_video(self, mesh_obj, video_path, n_frames=120, enhance_mode=None, perspective=True, video_type="rgb",
                            save_frames=False, save_grid=False, save_cover=False, save_camera=False, rename_with_euler=False,
-                           render_size=1024, fps=15, return_frames=False, pbr_model=None):
+                           render_size=1024, fps=15, return_frames=False, pbr_model=None, normal_map=None):
         """turntable of a textured mesh on a white background.  mesh_obj: path to a textured .glb, a TexturedMesh
         (renderer_inverse.py) or (verts, faces, uvs01, texture_u8_top_down[, vertex_normals]).
         video_type: 'rgb' or a geometry buffer of the same mesh ('world_normal', 'camera_normal', 'world_position', 'camera_position',
@@ -148,7 +148,11 @@ class VideoExporter:
         pbr_model: a pbr.PBRModel -> the 'rgb' frames are lit by its environment (utx_pbr_shade: NVDiffRendererPBR.render_base / render_pbr,
         render/nvdiffrast/renderer_pbr.py:19-94, alpha = coverage) instead of the unlit texture fetch.  map_Ks = (-, roughness, metallic) is the mesh's
         .metallic_roughness (a TexturedMesh of the 9-channel bake; glTF's G / B channels) or a sixth tuple element (uint8, top-down like the texture), else
-        the reference's default [1, 1, 0].  The bump texture is not applied (no tangent-space normal maps).  None: the unlit path, unchanged."""
+        the reference's default [1, 1, 0].  None: the unlit path, unchanged.
+        normal_map (with pbr_model only): a tangent-space normal map (uint8, top-down like the texture; glTF's normalTexture, OpenGL convention) perturbs the
+        shading normal (utx_pbr_shade_nm: bsdf_prepare_shading_normal, two-sided, bent towards the face normal at grazing angles; tangents from
+        meshes.vertex_tangents, mirrored UV charts not handled).  True takes the mesh's own map: a TexturedMesh's .bump, a seventh tuple element or, for a
+        .glb path, the material's normalTexture; an array is used as the map.  None: the interpolated vertex normal shades, as before."""
         ext = os.path.splitext(video_path)[1]
         assert ext in [".mp4", ".gif"]
         assert video_type in ["rgb", "albedo", "world_normal", "camera_normal", "world_position", "camera_position", "z_depth", "distance"]
@@ -157,17 +161,30 @@ class VideoExporter:
         assert return_frames != "rgba" or video_type != "rgb", "return_frames='rgba' is for the geometry video types"
         if pbr_model is not None and video_type != "rgb":
             raise ValueError("pbr_model lights the 'rgb' video only, not video_type=%r" % (video_type,))
-        vnrm, tex_ks = None, None
+        if normal_map is not None and pbr_model is None:
+            raise ValueError("normal_map perturbs the shading normal of the lit video: it needs pbr_model")
+        vnrm, tex_ks, tex_nm = None, None, None
         if isinstance(mesh_obj, str):
+            if normal_map is True and not mesh_obj.lower().endswith(".glb"):
+                raise ValueError("normal_map=True reads the normalTexture of a .glb, not of %r" % (mesh_obj,))
             verts, faces, uvs, tex = meshes.load_mesh(mesh_obj)
             verts = meshes.normalise_to_bbox(verts, 1.0)              # texture.mesh.scale_to_bbox() (:178)
+            if normal_map is True:
+                tex_nm = meshes.load_material_textures(mesh_obj)["normal"]
         elif isinstance(mesh_obj, (tuple, list)):
             verts, faces, uvs, tex = mesh_obj[:4]
             vnrm = mesh_obj[4] if len(mesh_obj) > 4 else None
             tex_ks = mesh_obj[5] if len(mesh_obj) > 5 else None
+            tex_nm = mesh_obj[6] if len(mesh_obj) > 6 else None
         else:
             verts, faces, uvs, tex = mesh_obj.vertices, mesh_obj.faces, mesh_obj.uv, mesh_obj.texture
             tex_ks = getattr(mesh_obj, "metallic_roughness", None)
+            tex_nm = getattr(mesh_obj, "bump", None)
+        if normal_map is True:
+            if tex_nm is None:
+                raise ValueError("normal_map=True, but the mesh brings no normal map")
+        else:
+            tex_nm = normal_map
         assert uvs is not None and tex is not None, "missing map_Kd in texture"
         if enhance_mode is None:
             c2ws = camera.generate_orbit_views_c2ws(n_frames + 1, radius=2.8, height=0.0, theta_0=0.0, degree=True)[:n_frames]
@@ -198,11 +215,14 @@ class VideoExporter:
             ksd = to_tex(tex_ks) if tex_ks is not None else None
             nd = (torch.as_tensor(np.asarray(vnrm), dtype=torch.float32) if vnrm is not None
                   else _vertex_normals(torch.as_tensor(np.asarray(verts), dtype=torch.float32), torch.as_tensor(np.asarray(faces)), self.normal_weighting))
+            nm_args = {}
+            if tex_nm is not None:      # tangents (host, fp64) and face normals once per mesh
+                nm_args = dict(v_tng=meshes.vertex_tangents(verts, faces, uvs, nd).to(dev).contiguous(), f_nrm=ops.face_normals(vd, fd), normal_map=to_tex(tex_nm))
             nd = nd.to(dev).contiguous()
             for i in range(c2ws.shape[0]):
                 rast = ops.rasterize(clip[i].contiguous(), fd, render_size, render_size)
                 frames.append(ops.pbr_shade(rast, fd, vd, nd, uvd, texd, ksd, c2ws[i, :3, 3].tolist(), pbr_model.light_diffuse, pbr_model.light_specular,
-                                            pbr_model.FG_LUT[0], bg=(1.0, 1.0, 1.0)).cpu().numpy())
+                                            pbr_model.FG_LUT[0], bg=(1.0, 1.0, 1.0), **nm_args).cpu().numpy())
         elif video_type == "rgb":
             for i in range(c2ws.shape[0]):
                 rast = ops.rasterize(clip[i].contiguous(), fd, render_size, render_size)
