@@ -382,6 +382,43 @@ int utx_gbuffer_range(utx_ctx* ctx, int mode, const float* rast, const int* tri,
  * out [n_views][V][3] = F.normalize(nrm @ c2ws[:3,:3]) with the fixed order (n0*R0j + n1*R1j) + n2*R2j. */
 int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws, int n_views, float* out, utx_stream stream);
 
+/* Atlas-space geometry buffers: NVDiffRendererBase.simple_inverse_rendering (render/nvdiffrast/renderer_base.py:352-489) with alpha = coverage
+ * (no dr.antialias).  ONE launch for a whole request: rast2d [H2D][W2D][4] is the UV raster (utx_rasterize of the uvs as clip xy; 16-byte
+ * aligned); faces [F][3]; v_pos, v_nrm [V][3]; for B >= 0 cameras v_pos_cam [B][V][3] (xyz of utx_transform_points with M = w2c, packed to
+ * three floats per vertex) and v_nrm_cam [B][V][3] (utx_camera_normals): the per-vertex arrays the reference hands to dr.interpolate.  `want`
+ * is the OR of the requested buffers; outs_host is a HOST array of UTX_UVGB_COUNT device pointers, entry k belonging to bit k (entries of
+ * buffers that were not requested are not read, and nothing is written through them).  m = rast.w > 0, lerp(bg, x, m) is a select:
+ *   bit  buffer            layout                covered texel                                         bg
+ *   0    MASK              u8  [H2D][W2D]        1                                                      0
+ *   1    ALPHA             f32 [H2D][W2D][1]     1                                                      0
+ *   2    WORLD_NORMAL      f32 [1][H2D][W2D][3]  normalize(interp(v_nrm))                              -1
+ *   3    WORLD_POSITION    f32 [1][H2D][W2D][3]  interp(v_pos)                                         -1
+ *   4    CAMERA_NORMAL     f32 [B][H2D][W2D][3]  normalize(interp(v_nrm_cam[b]))                       -1
+ *   5    CAMERA_POSITION   f32 [B][H2D][W2D][3]  interp(v_pos_cam[b])                                   0
+ *   6    DISTANCE          f32 [B][H2D][W2D][1]  |interp(v_pos_cam[b])|                                 0
+ *   7    Z_DEPTH           f32 [B][H2D][W2D][1]  interp(v_pos_cam[b]).z                                 0
+ *   8    RAY_DIRECTION     f32 [B][H2D][W2D][3]  normalize(interp(v_pos_cam[b]))                       -1
+ *   9    COS_RAY_NORMAL    f32 [B][H2D][W2D][1]  dot(camera_normal[b], ray_direction[b])               -1
+ * interp is utx_interpolate's expression, bit for bit; normalize(x) = x / max(|x|, 1e-12); |x| = sqrt((x*x + y*y) + z*z); the dot product is
+ * (a.x*b.x + a.y*b.y) + a.z*b.z.  Stream-ordered, no workspace, no host synchronisation.
+ * Returns -2 for a null rast2d / faces / outs_host, a rast2d off a 16-byte boundary, H2D, W2D or V <= 0, B < 0, want == 0 or with unknown bits,
+ * a null output pointer of a requested buffer, a null v_pos / v_nrm that a requested buffer reads, and B > 0 with a camera-dependent buffer
+ * requested but its per-view array null.  With B == 0 the camera-dependent buffers are empty and nothing is written to them. */
+#define UTX_UVGB_MASK 1
+#define UTX_UVGB_ALPHA 2
+#define UTX_UVGB_WORLD_NORMAL 4
+#define UTX_UVGB_WORLD_POSITION 8
+#define UTX_UVGB_CAMERA_NORMAL 16
+#define UTX_UVGB_CAMERA_POSITION 32
+#define UTX_UVGB_DISTANCE 64
+#define UTX_UVGB_Z_DEPTH 128
+#define UTX_UVGB_RAY_DIRECTION 256
+#define UTX_UVGB_COS_RAY_NORMAL 512
+#define UTX_UVGB_COUNT 10
+#define UTX_UVGB_ALL 1023
+int utx_uv_gbuffer(utx_ctx* ctx, const float* rast2d, const int* faces, const float* v_pos, const float* v_nrm, const float* v_pos_cam,
+                   const float* v_nrm_cam, int V, int B, int H2D, int W2D, unsigned want, void* const* outs_host, utx_stream stream);
+
 /* Image-based PBR shading of the turntable: PBRModel (texture/pbr/pbr.py:18-49, 91-130), NVDiffRendererPBR.render_base / render_pbr
  * (render/nvdiffrast/renderer_pbr.py:19-94) and the environment-light prefilters of the renderutils plugin (texture/pbr/renderutils/ops.py:398-465,
  * c_src/cubemap.cu:12-139, 174-298).  Cubemaps are [6][N][N][3] fp32; face s and its in-face coordinates (fx, fy) in [-1, 1] follow cube_to_dir:

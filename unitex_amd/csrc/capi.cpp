@@ -371,6 +371,19 @@ int utx_gbuffer_range(utx_ctx* ctx, int mode, const float* rast, const int* tri,
     if (attr_stride < (mode == UTX_GBUF_Z_DEPTH ? 1 : 3)) return fail(ctx, -2, "utx_gbuffer_range");
     UTX_CALL(ctx, "utx_gbuffer_range", utx_launch_gbuffer_range(mode, rast, tri, attr, attr_stride, npix, scale2_dev, empty_flag_dev, (hipStream_t)stream));
 }
+int utx_uv_gbuffer(utx_ctx* ctx, const float* rast2d, const int* faces, const float* v_pos, const float* v_nrm, const float* v_pos_cam,
+                   const float* v_nrm_cam, int V, int B, int H2D, int W2D, unsigned want, void* const* outs_host, utx_stream stream) {
+    const unsigned need_nrm_cam = UTX_UVGB_CAMERA_NORMAL | UTX_UVGB_COS_RAY_NORMAL;
+    const unsigned need_pos_cam = UTX_UVGB_CAMERA_POSITION | UTX_UVGB_DISTANCE | UTX_UVGB_Z_DEPTH | UTX_UVGB_RAY_DIRECTION | UTX_UVGB_COS_RAY_NORMAL;
+    if (!rast2d || !faces || !outs_host || ((uintptr_t)rast2d & 15)) return fail(ctx, -2, "utx_uv_gbuffer");      // rast2d is read as float4
+    if (H2D <= 0 || W2D <= 0 || V <= 0 || B < 0 || want == 0 || (want & ~(unsigned)UTX_UVGB_ALL)) return fail(ctx, -2, "utx_uv_gbuffer");
+    for (int k = 0; k < UTX_UVGB_COUNT; ++k)
+        if (((want >> k) & 1u) && !outs_host[k]) return fail(ctx, -2, "utx_uv_gbuffer");
+    if (((want & UTX_UVGB_WORLD_POSITION) && !v_pos) || ((want & UTX_UVGB_WORLD_NORMAL) && !v_nrm)) return fail(ctx, -2, "utx_uv_gbuffer");
+    if (B > 0 && (((want & need_nrm_cam) && !v_nrm_cam) || ((want & need_pos_cam) && !v_pos_cam))) return fail(ctx, -2, "utx_uv_gbuffer");
+    UTX_CALL(ctx, "utx_uv_gbuffer", utx_launch_uv_gbuffer(rast2d, faces, v_pos, v_nrm, v_pos_cam, v_nrm_cam, V, B, H2D, W2D, want, outs_host,
+                                                          (hipStream_t)stream));
+}
 int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws, int n_views, float* out, utx_stream stream) {
     if (!nrm || !c2ws || !out) return fail(ctx, -2, "utx_camera_normals");
     UTX_CALL(ctx, "utx_camera_normals", utx_launch_camera_normals(nrm, V, c2ws, n_views, out, (hipStream_t)stream));

@@ -16,6 +16,7 @@
 // Compiled with -ffp-contract=off.
 #include "common.h"
 #include "kernels.h"
+#include "gbuffer_device.h"
 
 #define SUBPIX 256
 #define BIG_BBOX 2048  // bbox area (pixels) above which a triangle goes to the cooperative path
@@ -303,16 +304,8 @@ extern "C" int utx_launch_texture_shade(const float* rast, const float* uv, cons
 // torch.lerp(fill, v, alpha) with alpha in {0, 1} returns v or fill exactly, so it is a select here.
 enum { GB_NORMAL = 0, GB_POSITION = 1, GB_DEPTH = 2, GB_DISTANCE = 3 };
 
-// keeps each product a scalar of its own: left alone, hipcc pairs two products of a sum into one packed multiply and adds its halves with a
-// cross-half packed add, the instruction pair tests/test_asm_hazards_cpu.py bans from every listing (unitex_amd/csrc/build.py, NO_PK).  No code is emitted.
-// Why not NO_PK on this file, the project's usual answer: the flag is per translation unit and would regenerate the rasteriser, utx_interpolate and
-// texture_shade_kernel, whose listings are clean today and whose speed and bit-exact results other tests and the rgb turntable rest on; the new
-// kernels belong in this file (they share its interpolation and its -ffp-contract=off).  The audit reads every listing on every run, so a compiler
-// that stops honouring the barrier is caught there, and NO_PK for the file remains the fallback.
-__device__ __forceinline__ float gb_scalar(float x) { asm volatile("" : "+v"(x)); return x; }
-__device__ __forceinline__ float gb_dot3(float x0, float y0, float x1, float y1, float x2, float y2) {
-    return (gb_scalar(x0 * y0) + gb_scalar(x1 * y1)) + gb_scalar(x2 * y2);
-}
+// gb_scalar / gb_dot3 (each product a scalar of its own: no cross-half packed pair in this file's listing), the interpolation and the normalisation
+// live in gbuffer_device.h, which the atlas-space buffers (uv_gbuffer.hip) share.
 
 template <int MODE>
 __device__ __forceinline__ bool gbuffer_value(const float4 r, const int* tri, const float* attr, int stride, float fill, float v3[3]) {
@@ -326,13 +319,11 @@ __device__ __forceinline__ bool gbuffer_value(const float4 r, const int* tri, co
         v3[0] = v3[1] = v3[2] = gb_dot3(a0[0], u, a1[0], v, a2[0], w);
     } else {
         float p[3];
-#pragma unroll
-        for (int c = 0; c < 3; ++c) p[c] = gb_dot3(a0[c], u, a1[c], v, a2[c], w);
+        gb_interp3(a0, a1, a2, u, v, w, p);
         if constexpr (MODE == GB_NORMAL) {
-            const float len = fmaxf(sqrtf(gb_dot3(p[0], p[0], p[1], p[1], p[2], p[2])), 1e-12f);
-            v3[0] = p[0] / len; v3[1] = p[1] / len; v3[2] = p[2] / len;
+            gb_normalize3(p, gb_length3(p), v3);
         } else if constexpr (MODE == GB_DISTANCE) {
-            v3[0] = v3[1] = v3[2] = sqrtf(gb_dot3(p[0], p[0], p[1], p[1], p[2], p[2]));
+            v3[0] = v3[1] = v3[2] = gb_length3(p);
         } else {
             v3[0] = p[0]; v3[1] = p[1]; v3[2] = p[2];
         }

@@ -142,6 +142,71 @@ def camera_normals(nrm, c2ws):
     return out
 
 
+# name -> (bit of utx_uv_gbuffer's `want`, channels, one layer per camera); the order is the header's UTX_UVGB_* bits
+UV_GBUFFERS = {"mask": (0, 1, False), "alpha": (1, 1, False), "world_normal": (2, 3, False), "world_position": (3, 3, False),
+               "camera_normal": (4, 3, True), "camera_position": (5, 3, True), "distance": (6, 1, True), "z_depth": (7, 1, True),
+               "ray_direction": (8, 3, True), "cos_ray_normal": (9, 1, True)}
+UV_GBUFFERS_POS_CAM = ("camera_position", "distance", "z_depth", "ray_direction", "cos_ray_normal")      # read v_pos_cam
+UV_GBUFFERS_NRM_CAM = ("camera_normal", "cos_ray_normal")                                                # read v_nrm_cam
+
+
+def uv_gbuffer(rast2d, faces, v_pos, v_nrm, c2ws=None, want=("mask", "alpha", "world_normal", "world_position"), v_pos_cam=None, v_nrm_cam=None):
+    """The atlas-space geometry buffers of simple_inverse_rendering in one launch (utx_uv_gbuffer): rast2d [H2D,W2D,4] (the UV raster), faces [F,3]
+    int32, v_pos / v_nrm [V,3] (v_nrm may be None when no normal buffer is requested), c2ws [B,4,4] or None -> dict of the buffers named in
+    `want` (UV_GBUFFERS): mask uint8 [H2D,W2D], alpha [H2D,W2D,1], world_* [1,H2D,W2D,3], the camera-dependent ones [B,H2D,W2D,C].  The per-view per-vertex arrays are built here with the existing kernels
+    (transform_points with M = w2c, camera_normals), as the reference builds them in front of dr.interpolate; a caller that holds them already
+    (e.g. the reference's own, in the parity tests) passes v_pos_cam / v_nrm_cam [B,V,3] and c2ws is then not read."""
+    want = tuple(want)
+    for k in want:
+        if k not in UV_GBUFFERS:
+            raise KeyError("uv_gbuffer: unknown buffer %r (known: %s)" % (k, ", ".join(UV_GBUFFERS)))
+    if not want:
+        raise ValueError("uv_gbuffer: no buffer requested")
+    need_pos, need_nrm = any(k in UV_GBUFFERS_POS_CAM for k in want), any(k in UV_GBUFFERS_NRM_CAM for k in want)
+    if (need_pos and v_pos_cam is None or need_nrm and v_nrm_cam is None) and c2ws is None:
+        raise ValueError("uv_gbuffer: %s depend on the cameras: c2ws is required" % ", ".join(k for k in want if UV_GBUFFERS[k][2]))
+    ctx = get_ctx(rast2d.device.index)
+    dev = rast2d.device
+    H, W = rast2d.shape[:2]
+    V = v_pos.shape[0]
+    if c2ws is not None:
+        c2ws = torch.as_tensor(c2ws, dtype=F32)
+    if c2ws is not None and c2ws.shape[0] > 0:
+        if need_pos and v_pos_cam is None:
+            from . import camera
+            w2c = camera.c2w_to_w2c(c2ws.cpu()).to(dev, F32).contiguous()
+            v_pos_cam = transform_points(v_pos, w2c, want_ndc=False)[0][..., :3].contiguous()
+        if need_nrm and v_nrm_cam is None:
+            v_nrm_cam = camera_normals(v_nrm, c2ws.to(dev).contiguous())
+    per_view = [a for a in (v_pos_cam, v_nrm_cam) if a is not None]
+    B = per_view[0].shape[0] if per_view else (c2ws.shape[0] if c2ws is not None else 0)
+    for a in per_view:
+        assert tuple(a.shape) == (B, V, 3), "per-view vertex arrays are [B, V, 3]"
+    assert faces.shape[1] == 3 and rast2d.shape[2] == 4 and tuple(v_pos.shape) == (V, 3)
+    if "world_normal" in want or (need_nrm and v_nrm_cam is None):
+        assert v_nrm is not None and tuple(v_nrm.shape) == (V, 3), "v_nrm [V, 3] is required by the normal buffers"
+    out, bits = {}, 0
+    ptrs = (C.c_void_p * len(UV_GBUFFERS))()
+    for k in want:
+        bit, ch, per = UV_GBUFFERS[k]
+        if k == "mask":
+            out[k] = torch.empty(H, W, dtype=U8, device=dev)
+        elif k == "alpha":
+            out[k] = torch.empty(H, W, 1, dtype=F32, device=dev)
+        else:
+            out[k] = torch.empty(B if per else 1, H, W, ch, dtype=F32, device=dev)
+        ptrs[bit] = out[k].data_ptr() or None
+        bits |= 1 << bit
+    if B == 0:      # no camera: the camera-dependent buffers are empty, and an empty tensor has no address to hand over
+        bits &= ~sum(1 << UV_GBUFFERS[k][0] for k in want if UV_GBUFFERS[k][2])
+        if bits == 0:
+            return out
+    ctx.check(ctx.lib.utx_uv_gbuffer(ctx.handle, ptr(_f(rast2d)), ptr(_i(faces)), ptr(_f(v_pos)), ptr(_f(v_nrm) if v_nrm is not None else None),
+                                     ptr(_f(v_pos_cam) if v_pos_cam is not None and B else None), ptr(_f(v_nrm_cam) if v_nrm_cam is not None and B else None),
+                                     V, B, H, W, bits, ptrs, ctx.stream()))
+    return out
+
+
 def cubemap_tables(N, costheta_cutoff=None, device="cuda"):
     """utx_cubemap_table: (texels [6,N,N,4] = unit direction + pixel_area, tiles [6,nt,nt,4] or None) on `device`, built on the host in fp64.
     Runs without a GPU when device is 'cpu' (the tests' oracle reads the same table)."""

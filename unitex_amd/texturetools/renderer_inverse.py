@@ -77,6 +77,13 @@ class DeviceMesh:
             self._vertex_normals = _vertex_normals(self.vertices.cpu(), self.faces.cpu(), weighting="area").to(self.device)
         return self._vertex_normals
 
+    def set_vertex_normals(self, normals):
+        """per-vertex normals [V,3] of the caller's own (e.g. the file's, or analytic ones) in place of the area-weighted ones; they need not be unit"""
+        n = torch.as_tensor(normals, dtype=torch.float32).to(self.device).contiguous()
+        assert tuple(n.shape) == tuple(self.vertices.shape), "one normal per vertex"
+        self._vertex_normals = n
+        return self
+
     @property
     def optix(self):
         if self._bvh is None:
@@ -272,6 +279,70 @@ class NVDiffRendererInverse:
             raise NotImplementedError("method %s is not supported" % method)
         return atlas
 
+    def _uv_raster(self, H2D, W2D):
+        """UV-space raster [H2D,W2D,4]: uv in [-1,1] used directly as clip xy, z = 0, w = 1 (renderer_inverse.py:268-274, renderer_base.py:377-384)"""
+        m = self.pbr_mesh
+        uvclip = torch.cat([m.uvs_2d, torch.zeros_like(m.uvs_2d[:, :1]), torch.ones_like(m.uvs_2d[:, :1])], dim=-1).contiguous()
+        with self._stage("uv_raster"):
+            return ops.rasterize(uvclip, m.faces, H2D, W2D)
+
+    # flag of simple_inverse_rendering -> key of the returned dict, camera-independent first
+    _UV_FLAGS = ("world_normal", "world_position", "camera_normal", "camera_position", "distance", "z_depth", "ray_direction", "cos_ray_normal")
+    _UV_FLAGS_UNBUILT = ("render_voxel_attr", "render_v_attr", "render_uv", "render_map_attr", "render_all_point_cloud", "render_visible_point_cloud")
+
+    def simple_inverse_rendering(self, c2ws=None, texture_size=2048, render_world_normal=False, render_world_position=False,
+                                 render_camera_normal=False, render_camera_position=False, render_distance=False, render_z_depth=False,
+                                 render_ray_direction=False, render_cos_ray_normal=False, enable_antialis=True, **kwargs):
+        """NVDiffRendererBase.simple_inverse_rendering (render/nvdiffrast/renderer_base.py:352-489) on the mesh of update_from_file: the geometry
+        buffers rendered into the UV atlas instead of onto a screen, all of them in one kernel launch (ops.uv_gbuffer).  Returns the reference's
+        dict: 'mask' bool [1,H,W,1], 'alpha' float32 [1,H,W,1] and, per flag, 'world_normal' / 'world_position' [1,H,W,3] and, per camera of
+        c2ws [B,4,4], 'camera_normal' / 'camera_position' / 'ray_direction' [B,H,W,3], 'distance' / 'z_depth' / 'cos_ray_normal' [B,H,W,1].
+        texture_size: int or (H, W).  Row 0 is v = 0 (the raster's orientation; TexturedMesh.texture is the flipped one).  Only c2ws enters: the
+        function never projects, so it takes no intrinsics.  Vertex normals are pbr_mesh.vertex_normals.
+        enable_antialis is accepted and has no effect: alpha is the coverage mask (no dr.antialias in this build, as on the turntable).
+        A camera-dependent flag without c2ws raises ValueError; render_voxel_attr, render_v_attr, render_uv, render_map_attr,
+        render_all_point_cloud and render_visible_point_cloud are not built and raise NotImplementedError when set; any other keyword is a TypeError."""
+        for k_, v_ in kwargs.items():
+            if k_ not in self._UV_FLAGS_UNBUILT:
+                raise TypeError("simple_inverse_rendering() got an unexpected keyword argument %r" % k_)
+            if v_:
+                raise NotImplementedError("simple_inverse_rendering(%s=%r) is not built" % (k_, v_))
+        flags = dict(world_normal=render_world_normal, world_position=render_world_position, camera_normal=render_camera_normal,
+                     camera_position=render_camera_position, distance=render_distance, z_depth=render_z_depth,
+                     ray_direction=render_ray_direction, cos_ray_normal=render_cos_ray_normal)
+        want = [k for k in self._UV_FLAGS if flags[k]]
+        per_view = [k for k in want if ops.UV_GBUFFERS[k][2]]
+        if per_view and c2ws is None:
+            raise ValueError("simple_inverse_rendering(render_%s=True) depends on the cameras: c2ws is required" % per_view[0])
+        H2D, W2D = (texture_size, texture_size) if isinstance(texture_size, int) else texture_size
+        m = self.pbr_mesh
+        assert m is not None, "update_from_file first"
+        rast2d = self._uv_raster(int(H2D), int(W2D))
+        with self._stage("uv_gbuffer"):
+            need_nrm = any(k in ("world_normal",) + ops.UV_GBUFFERS_NRM_CAM for k in want)      # the normals are built lazily, on the host
+            out = ops.uv_gbuffer(rast2d, m.faces, m.vertices, m.vertex_normals if need_nrm else None, c2ws=c2ws, want=["mask", "alpha"] + want)
+        out["mask"] = out["mask"].bool()[None, ..., None]
+        out["alpha"] = out["alpha"][None]
+        return out
+
+    def compute_uv_mask(self, texture_size=2048):
+        """Mesh.compute_uv_mask (mesh/structure.py:786-799): the atlas coverage, bool [H,W,1]"""
+        return self.simple_inverse_rendering(None, texture_size, enable_antialis=False)["mask"][0]
+
+    def export_uv_maps(self, save_dir, texture_size=2048):
+        """uv_mask.png (L), uv_position.png and uv_normal.png (x * 0.5 + 0.5, background -1 -> 0) of the atlas, rows flipped so that the images
+        lie like the baked texture (TexturedMesh.texture: row 0 is v = 1).  Returns the three paths."""
+        from PIL import Image
+        out = self.simple_inverse_rendering(None, texture_size, render_world_normal=True, render_world_position=True)
+        os.makedirs(save_dir, exist_ok=True)
+        level = int(os.environ.get("UTX_PNG_LEVEL", "1"))
+        paths = [os.path.join(save_dir, n) for n in ("uv_mask.png", "uv_position.png", "uv_normal.png")]
+        Image.fromarray(out["mask"][0, ..., 0].flip(0).to(torch.uint8).mul(255).cpu().numpy()).save(paths[0], compress_level=level)
+        for key, path in (("world_position", paths[1]), ("world_normal", paths[2])):
+            ndc = (out[key][0] * 0.5 + 0.5).contiguous()
+            Image.fromarray(ops.to_u8(ndc, flip=True).cpu().numpy()).save(path, compress_level=level)
+        return paths
+
     def infer(self, blank_mesh, c2ws, intrinsics, image_attrs, H=512, W=512, H2D=2048, W2D=2048, perspective=True,
               grad_norm_threhold=0.20, ray_normal_angle_threhold=115.0, grid_interpolate_mode="torch", method="reproject",
               kdtree_n_neighbors=32, kdtree_n_neighbors_visiable=1, kdtree_n_neighbors_invisiable=32, kdtree_method="order_mean",
@@ -324,10 +395,7 @@ class NVDiffRendererInverse:
         # ray model per view (uv_to_pcd, :279-284): perspective -- from the camera centre to each texel's surface point; orthographic -- along -z of the camera
         eyes = c2ws_cpu[:, :3, 3].contiguous().to(dev) if perspective else None
         dirs = None if perspective else (-c2ws_cpu[:, :3, 2]).contiguous().to(dev)
-        # UV-space raster: uv in [-1,1] used directly as clip xy, z = 0, w = 1 (renderer_inverse.py:268-274)
-        uvclip = torch.cat([m.uvs_2d, torch.zeros_like(m.uvs_2d[:, :1]), torch.ones_like(m.uvs_2d[:, :1])], dim=-1).contiguous()
-        with self._stage("uv_raster"):
-            rast2d = ops.rasterize(uvclip, m.faces, H2D, W2D)
+        rast2d = self._uv_raster(H2D, W2D)
         from .distributed import view_range
         rank, world = self.view_shard
         v0, v1, per = view_range(rank, world, n)
