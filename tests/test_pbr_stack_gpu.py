@@ -2,6 +2,7 @@
 9-channel path against the 3-channel path per channel group, the post-processing stages at C channels against their thread-per-texel instantiation
 (C = 3) and against the numpy restatement, the new entry points alone, view sharding, the PBR TexturedMesh and its GLB, and the refusals."""
 import ctypes as C
+import functools
 import math
 import os
 import sys
@@ -126,12 +127,13 @@ def _scene(persp, n_faces=20000, px=128, Tt=256):
     mv = inv.mv_to_pcd(c2ws, intr, (px, px), perspective=persp, filt_gradient_points=True)
     m = inv.pbr_mesh
     uvclip = torch.cat([m.uvs_2d, torch.zeros_like(m.uvs_2d[:, :1]), torch.ones_like(m.uvs_2d[:, :1])], dim=-1).contiguous()
-    rast2d = ops.rasterize(uvclip, m.faces, Tt, Tt)
+    rast2d = ops.rasterize(uvclip, m.faces, *((Tt, Tt) if isinstance(Tt, int) else Tt))
     c2 = torch.as_tensor(c2ws, dtype=torch.float32)
     eyes = c2[:, :3, 3].contiguous().cuda() if persp else None
     dirs = None if persp else (-c2[:, :3, 2]).contiguous().cuda()
     rgb = torch.from_numpy(smooth_views(6, px, px)).cuda()
-    return dict(m=m, rast2d=rast2d, vndc=mv["ndc"].contiguous(), alpha=mv["alpha"].contiguous(), eyes=eyes, dirs=dirs, rgb=rgb, bvh=m.optix)
+    return dict(m=m, rast2d=rast2d, vndc=mv["ndc"].contiguous(), alpha=mv["alpha"].contiguous(), eyes=eyes, dirs=dirs, rgb=rgb, bvh=m.optix,
+                view_dirs=(-c2[:, :3, 2]).contiguous())
 
 
 @pytest.mark.parametrize("persp", [False, True])
@@ -192,6 +194,55 @@ def test_gather_winner_at_three_channels_equals_composite_of_backproject(persp, 
     assert torch.equal(ops.composite_winner(vis, order), w3)
     assert torch.equal(w3 != winner, vis.sum(0) > 1)
     assert torch.equal(ops.gather_winner(s["rast2d"], m.faces, s["vndc"], s["rgb"].contiguous(), w3, sample=sample), a3)
+
+
+@functools.lru_cache(maxsize=None)
+def _border_scene(persp):
+    """a 2 000-face sphere, six 64 x 64 views, an atlas of 80 rows x 96 columns, and every view's vertex NDC multiplied by 1.6: part of the surface projects
+    outside the view, so the zero-padded taps of the grid mode and the wrap of the nvdiff mode run.  Built once per camera model, never written to."""
+    s = _scene(persp, n_faces=2000, px=64, Tt=(80, 96))
+    s["vndc"] = (s["vndc"] * 1.6).contiguous()
+    return s
+
+
+@pytest.mark.parametrize("persp", [False, True])
+@pytest.mark.parametrize("sample", ["grid", "nvdiff"])
+def test_the_three_sampling_kernels_agree_where_the_surface_leaves_the_view(persp, sample):
+    """backproject, backproject_vis and gather_winner share one statement of each sampling mode; the scenes of the tests above keep the whole mesh inside
+    every view, this one does not.  Everything bit for bit; the grid mode also against the oracle's gather (its rays are orthographic, so the perspective
+    case compares the ray-independent outputs, as test_perspective_gpu.py does)."""
+    from oracle import geom_ref as G
+    from unitex_amd.texturetools import ops
+    from unitex_amd.texturetools.renderer_inverse import PRIORITY
+    s = _border_scene(persp)
+    m = s["m"]
+    assert tuple(s["rast2d"].shape) == (80, 96, 4)
+    # the guard: covered texels project both outside and inside the view
+    covered = s["rast2d"][..., 3] > 0
+    reach = torch.stack([ops.interpolate(s["vndc"][v].contiguous(), s["rast2d"], m.faces).abs().amax(-1) for v in range(6)])
+    outside, inside = (reach > 1)[:, covered], (reach < 1)[:, covered]
+    print("covered texel-views with |ndc| > 1: %d, with |ndc| < 1: %d" % (int(outside.sum()), int(inside.sum())))
+    assert bool(outside.any()) and bool(inside.any())
+    images4 = torch.cat([s["rgb"], s["alpha"][..., None]], -1).contiguous()
+    col, rv, ao = ops.backproject(s["rast2d"], m.vertices, m.faces, m.normals, s["vndc"], s["dirs"], images4, s["bvh"], eyes=s["eyes"], sample=sample)
+    rv2, ao2 = ops.backproject_vis(s["rast2d"], m.vertices, m.faces, m.normals, s["vndc"], s["dirs"], s["alpha"], s["bvh"], eyes=s["eyes"], sample=sample)
+    assert torch.equal(rv, rv2) and torch.equal(ao, ao2)
+    assert rv.any() and not rv.all() and ao.any() and not ao.all()
+    vis = ops.dilate_visibility(rv, ao, s["rast2d"])
+    atlas, winner = ops.composite(col, vis, PRIORITY)
+    assert torch.equal(ops.composite_winner(vis, PRIORITY), winner)
+    assert (winner >= 0).any() and (winner < 0).any() and atlas.abs().sum() > 0
+    for Cc in (3, 1, 9):
+        idx = [c % 3 for c in range(Cc)]
+        got = ops.gather_winner(s["rast2d"], m.faces, s["vndc"], s["rgb"][..., idx].contiguous(), winner, sample=sample)
+        assert torch.equal(got, atlas[..., idx]), "gather_winner at C = %d" % Cc
+    if sample == "grid":
+        verts, faces = m.vertices.cpu().numpy(), m.faces.cpu().numpy()
+        col_ref, rv_ref, ao_ref = G.backproject(s["rast2d"].cpu().numpy(), verts, faces, m.normals.cpu().numpy(), s["vndc"].cpu().numpy(),
+                                                s["view_dirs"].numpy(), images4.cpu().numpy(), G.BVH(verts, faces))
+        assert np.array_equal(col.cpu().numpy(), col_ref) and np.array_equal(ao.cpu().numpy(), ao_ref)
+        if not persp:
+            assert np.array_equal(rv.cpu().numpy(), rv_ref)
 
 
 def _post_inputs(Hh, Ww, seed):

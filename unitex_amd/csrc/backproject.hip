@@ -12,41 +12,36 @@
 #include "common.h"
 #include "kernels.h"
 #include "bvh_device.h"
+#include "shade_device.h"
 
-__device__ __forceinline__ float4 tap4(const float4* img, int H, int W, int x, int y) {
-    if (x < 0 || x >= W || y < 0 || y >= H) return make_float4(0.f, 0.f, 0.f, 0.f);
-    return img[(long)y * W + x];
+// The two lookups of a view image.  Each has ONE function for its taps and weights and ONE blend, templated on the tap type: float4 for the colour
+// kernel (rgb + alpha, one 16-byte load per tap), float for the alpha plane and for one channel of a [H][W][C] image (taps `stride` = C floats apart).
+//
+// grid_sample(bilinear, zero padding, align_corners=False): the four tap offsets in pixels (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), -1 for a
+// tap outside the view (it reads as zero), and their weights
+__device__ __forceinline__ void grid_taps(int H, int W, float gx, float gy, long o[4], float w[4]) {
+    const float ix = ((gx + 1.0f) * (float)W - 1.0f) * 0.5f;
+    const float iy = ((gy + 1.0f) * (float)H - 1.0f) * 0.5f;
+    const float fx = floorf(ix), fy = floorf(iy);
+    const int x0 = (int)fx, y0 = (int)fy;
+    const float tx = ix - fx, ty = iy - fy;
+    w[0] = (1.0f - tx) * (1.0f - ty); w[1] = tx * (1.0f - ty); w[2] = (1.0f - tx) * ty; w[3] = tx * ty;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = x0 + (k & 1), y = y0 + (k >> 1);
+        o[k] = (x < 0 || x >= W || y < 0 || y >= H) ? -1 : (long)y * W + x;
+    }
 }
+template <class T>
+__device__ __forceinline__ T grid_tap(const T* img, long stride, long o) { return o < 0 ? T{} : img[o * stride]; }
+template <class T>
+__device__ __forceinline__ T grid_blend(T a, T b, T c, T e, const float w[4]) { return ((a * w[0] + b * w[1]) + c * w[2]) + e * w[3]; }
 
 // nvdiffrast's 2-D linear lookup with the wrap boundary (indexTextureLinear + bilerp, restated): uv = ndc * 0.5 + 0.5 (two roundings, as
 // ndc_2d.mul(0.5).add(0.5)), u -= floor(u), u = u * W - 0.5, i0 = floor(u), i1 = i0 + 1, f = u - i0, indices wrapped into [0, W) (the same along v with H),
 // out = lerp(lerp(t00, t10, fu), lerp(t01, t11, fu), fv) with lerp(a, b, t) = a + t * (b - a).  For a finite u, u - floor(u) lies in [0, 1], so i0 lies in
 // [-1, W - 1] and i1 in [0, W]: after the wrap every tap is inside the view.
-__device__ __forceinline__ float lerp_nv(float a, float b, float t) { return a + t * (b - a); }
-__device__ __forceinline__ float4 tex_wrap_linear(const float4* img, int H, int W, float gx, float gy) {
-    if (!isfinite(gx) || !isfinite(gy)) return make_float4(0.f, 0.f, 0.f, 0.f);
-    float su = gx * 0.5f + 0.5f, sv = gy * 0.5f + 0.5f;
-    su = su - floorf(su); sv = sv - floorf(sv);
-    su = su * (float)W - 0.5f; sv = sv * (float)H - 0.5f;
-    const float fu0 = floorf(su), fv0 = floorf(sv);
-    int iu0 = (int)fu0, iv0 = (int)fv0, iu1 = iu0 + 1, iv1 = iv0 + 1;
-    const float fu = su - fu0, fv = sv - fv0;
-    if (iu0 < 0) iu0 += W;
-    if (iv0 < 0) iv0 += H;
-    if (iu1 >= W) iu1 -= W;
-    if (iv1 >= H) iv1 -= H;
-    const float4 t00 = img[(long)iv0 * W + iu0], t10 = img[(long)iv0 * W + iu1];
-    const float4 t01 = img[(long)iv1 * W + iu0], t11 = img[(long)iv1 * W + iu1];
-    return make_float4(lerp_nv(lerp_nv(t00.x, t10.x, fu), lerp_nv(t01.x, t11.x, fu), fv), lerp_nv(lerp_nv(t00.y, t10.y, fu), lerp_nv(t01.y, t11.y, fu), fv),
-                       lerp_nv(lerp_nv(t00.z, t10.z, fu), lerp_nv(t01.z, t11.z, fu), fv), lerp_nv(lerp_nv(t00.w, t10.w, fu), lerp_nv(t01.w, t11.w, fu), fv));
-}
-
-// the same two lookups on a one-channel plane [H][W] f32 (the visibility-only kernel's alpha): same taps, same weights, same order
-__device__ __forceinline__ float tap1(const float* img, int H, int W, int x, int y) {
-    if (x < 0 || x >= W || y < 0 || y >= H) return 0.f;
-    return img[(long)y * W + x];
-}
-// the wrap-mode taps of tex_wrap_linear for any channel count: the four tap offsets (in pixels) and the two lerp fractions; false for a non-finite coordinate
+// wrap_taps: the four tap offsets (in pixels) and the two lerp fractions; false for a non-finite coordinate (it samples zero)
 __device__ __forceinline__ bool wrap_taps(int H, int W, float gx, float gy, long& o00, long& o10, long& o01, long& o11, float& fu, float& fv) {
     if (!isfinite(gx) || !isfinite(gy)) return false;
     float su = gx * 0.5f + 0.5f, sv = gy * 0.5f + 0.5f;
@@ -62,6 +57,29 @@ __device__ __forceinline__ bool wrap_taps(int H, int W, float gx, float gy, long
     o00 = (long)iv0 * W + iu0; o10 = (long)iv0 * W + iu1; o01 = (long)iv1 * W + iu0; o11 = (long)iv1 * W + iu1;
     return true;
 }
+template <class T>
+__device__ __forceinline__ T lerp_nv(T a, T b, float t) { return a + (b - a) * t; }
+template <class T>
+__device__ __forceinline__ T wrap_blend(T t00, T t10, T t01, T t11, float fu, float fv) { return lerp_nv(lerp_nv(t00, t10, fu), lerp_nv(t01, t11, fu), fv); }
+
+// SAMPLE 0: grid_sample, 1: the wrap lookup, of img [H][W] texels of type T, `stride` T's apart, at the NDC (gx, gy)
+template <int SAMPLE, class T>
+__device__ __forceinline__ T sample_view(const T* img, long stride, int H, int W, float gx, float gy) {
+    if constexpr (SAMPLE == 0) {
+        long o[4]; float w[4];
+        grid_taps(H, W, gx, gy, o, w);
+        return grid_blend(grid_tap(img, stride, o[0]), grid_tap(img, stride, o[1]), grid_tap(img, stride, o[2]), grid_tap(img, stride, o[3]), w);
+    } else {
+        long o00, o10, o01, o11; float fu, fv;
+        if (!wrap_taps(H, W, gx, gy, o00, o10, o01, o11, fu, fv)) return T{};
+        return wrap_blend(img[o00 * stride], img[o10 * stride], img[o01 * stride], img[o11 * stride], fu, fv);
+    }
+}
+
+// the NDC of a texel in view `nd` [V][2]: the triangle's three vertex NDCs at the texel's barycentrics, as utx_interpolate would
+__device__ __forceinline__ void texel_ndc(const float* nd, int f0, int f1, int f2, float u, float v, float w, float g[2]) {
+    sd_interp<2>(nd + 2 * (long)f0, nd + 2 * (long)f1, nd + 2 * (long)f2, u, v, w, g);
+}
 
 // MODE 1: stackless thread-per-ray walk over the packed tree (bvh_device.h); MODE 0: the reference's 64-entry stack walk, kept for trees deeper than
 // UTX_BVH_PACKED_MAX_DEPTH (where the reference's stack overflow quirk could matter) and for A/B tests; MODE 2 (round 4, the default): a wave owns an
@@ -70,7 +88,7 @@ __device__ __forceinline__ bool wrap_taps(int H, int W, float gx, float gy, long
 // PERSP (renderer_inverse.py:279-281, perspective=True): every ray of view v starts at the camera centre eyes[v] = c2w[v][:3, 3] and points at the texel's
 // surface point, d = (pos - eye) / max(|pos - eye|, 1e-12); the orthographic arm (one direction per view, origin 2 sqrt(3) behind the point) is unchanged.
 // SAMPLE (renderer_inverse.py:290-305, grid_interpolate_mode): 0 = grid_sample(bilinear, zero padding, align_corners=False); 1 = dr.texture(uv = ndc * 0.5 + 0.5,
-// filter_mode='linear') with nvdiffrast's default wrap boundary (its indexTextureLinear + bilerp restated below); a non-finite coordinate samples zero.
+// filter_mode='linear') with nvdiffrast's default wrap boundary (its indexTextureLinear + bilerp restated above); a non-finite coordinate samples zero.
 // VIS (utx_backproject_vis, the 9-channel bake): visibility only -- p.images is the alpha plane [n][H][W] f32, p.color is not touched; the alpha expression, the ray
 // and the walk are the ones of the colour kernel, so rayvis / alphaok come out bit-identical.
 template <int MODE, bool PERSP, int SAMPLE, bool VIS = false>
@@ -109,18 +127,17 @@ __global__ __launch_bounds__(256) void backproject_kernel(utx_backproject_desc p
     } else if (id < 0) { if constexpr (!VIS) { oc[0] = 0.f; oc[1] = 0.f; oc[2] = 0.f; } *rv = 0; *ao = 0; return; }
     const float* vert = (const float*)p.verts;
     const int* faces = (const int*)p.faces;
-    const float u = r.x, v = r.y, w = (1.0f - u) - v;
+    const float u = r.x, v = r.y, w = sd_bary_w(u, v);
     const int f0 = faces[3 * (long)id], f1 = faces[3 * (long)id + 1], f2 = faces[3 * (long)id + 2];
     float pos[3];
-#pragma unroll
-    for (int a = 0; a < 3; ++a) pos[a] = (vert[3 * (long)f0 + a] * u + vert[3 * (long)f1 + a] * v) + vert[3 * (long)f2 + a] * w;
+    sd_interp<3>(vert + 3 * (long)f0, vert + 3 * (long)f1, vert + 3 * (long)f2, u, v, w, pos);
     float ro[3], d[3];
     if constexpr (PERSP) {
         const float* e = eyes + 3 * vw;
         ro[0] = e[0]; ro[1] = e[1]; ro[2] = e[2];
-        const float dx = pos[0] - e[0], dy = pos[1] - e[1], dz = pos[2] - e[2];
-        float dn = sqrtf((dx * dx + dy * dy) + dz * dz); if (dn < 1e-12f) dn = 1e-12f;
-        d[0] = dx / dn; d[1] = dy / dn; d[2] = dz / dn;
+        const float dv[3] = {pos[0] - e[0], pos[1] - e[1], pos[2] - e[2]};
+        float dn = sd_length3(dv); if (dn < 1e-12f) dn = 1e-12f;      // a compare, as the oracle's: a NaN length stays NaN (sd_normalize3's fmaxf would floor it)
+        d[0] = dv[0] / dn; d[1] = dv[1] / dn; d[2] = dv[2] / dn;
     } else {
         const float* d_in = (const float*)p.dirs + 3 * vw;
         const float two_sqrt3 = p.two_sqrt3;
@@ -134,46 +151,18 @@ __global__ __launch_bounds__(256) void backproject_kernel(utx_backproject_desc p
     float ln = sqrtf(dot3(nn, nn)); if (ln < 1e-8f) ln = 1e-8f;
     const float cs = dot3(d, nn) / (ld * ln);
     const float* nd = (const float*)p.vndc + (long)vw * p.V * 2;
-    const float gx = (nd[2 * (long)f0] * u + nd[2 * (long)f1] * v) + nd[2 * (long)f2] * w;
-    const float gy = (nd[2 * (long)f0 + 1] * u + nd[2 * (long)f1 + 1] * v) + nd[2 * (long)f2 + 1] * w;
+    float g[2];
+    texel_ndc(nd, f0, f1, f2, u, v, w, g);
     const int H = p.H, W = p.W;
+    float sa;
     if constexpr (VIS) {
-        const float* img = (const float*)p.images + (long)vw * H * W;
-        float sa;
-        if constexpr (SAMPLE == 0) {
-            const float ix = ((gx + 1.0f) * (float)W - 1.0f) * 0.5f;
-            const float iy = ((gy + 1.0f) * (float)H - 1.0f) * 0.5f;
-            const float fx = floorf(ix), fy = floorf(iy);
-            const int x0 = (int)fx, y0 = (int)fy;
-            const float tx = ix - fx, ty = iy - fy;
-            const float w00 = (1.0f - tx) * (1.0f - ty), w01 = tx * (1.0f - ty), w10 = (1.0f - tx) * ty, w11 = tx * ty;
-            const float a = tap1(img, H, W, x0, y0), b = tap1(img, H, W, x0 + 1, y0), c = tap1(img, H, W, x0, y0 + 1), e = tap1(img, H, W, x0 + 1, y0 + 1);
-            sa = ((a * w00 + b * w01) + c * w10) + e * w11;
-        } else {
-            long o00, o10, o01, o11; float fu, fv;
-            sa = wrap_taps(H, W, gx, gy, o00, o10, o01, o11, fu, fv) ? lerp_nv(lerp_nv(img[o00], img[o10], fu), lerp_nv(img[o01], img[o11], fu), fv) : 0.f;
-        }
-        *ao = sa > 0.999f ? 1 : 0;
-    } else if constexpr (SAMPLE == 0) {
-        const float ix = ((gx + 1.0f) * (float)W - 1.0f) * 0.5f;
-        const float iy = ((gy + 1.0f) * (float)H - 1.0f) * 0.5f;
-        const float fx = floorf(ix), fy = floorf(iy);
-        const int x0 = (int)fx, y0 = (int)fy;
-        const float tx = ix - fx, ty = iy - fy;
-        const float w00 = (1.0f - tx) * (1.0f - ty), w01 = tx * (1.0f - ty), w10 = (1.0f - tx) * ty, w11 = tx * ty;
-        const float4* img = (const float4*)p.images + (long)vw * H * W;
-        const float4 a = tap4(img, H, W, x0, y0), b = tap4(img, H, W, x0 + 1, y0);
-        const float4 c = tap4(img, H, W, x0, y0 + 1), e = tap4(img, H, W, x0 + 1, y0 + 1);
-        oc[0] = ((a.x * w00 + b.x * w01) + c.x * w10) + e.x * w11;
-        oc[1] = ((a.y * w00 + b.y * w01) + c.y * w10) + e.y * w11;
-        oc[2] = ((a.z * w00 + b.z * w01) + c.z * w10) + e.z * w11;
-        const float sa = ((a.w * w00 + b.w * w01) + c.w * w10) + e.w * w11;
-        *ao = sa > 0.999f ? 1 : 0;
+        sa = sample_view<SAMPLE>((const float*)p.images + (long)vw * H * W, 1, H, W, g[0], g[1]);
     } else {
-        const float4 s = tex_wrap_linear((const float4*)p.images + (long)vw * H * W, H, W, gx, gy);
+        const float4 s = sample_view<SAMPLE>((const float4*)p.images + (long)vw * H * W, 1, H, W, g[0], g[1]);
         oc[0] = s.x; oc[1] = s.y; oc[2] = s.z;
-        *ao = s.w > 0.999f ? 1 : 0;
+        sa = s.w;
     }
+    *ao = sa > 0.999f ? 1 : 0;
     const int hit = MODE == 2 ? bvh_trace_packet(nodes, tris, ro, d, true, pstack + (threadIdx.x >> 6) * 192, nullptr)
                   : MODE == 1 ? bvh_trace_packed(nodes, tris, ro, d, nullptr) : bvh_trace_one(info, aabb, vert, faces, ro, d);
     *rv = (hit == id && hit != -1 && cs < p.cos_thresh) ? 1 : 0;
@@ -194,36 +183,32 @@ static void launch_backproject(const utx_backproject_desc& p, const float* eyes,
 
 // eyes == nullptr: orthographic rays along p.dirs; otherwise [n_views][3] camera centres (perspective), p.dirs / p.two_sqrt3 unused.
 // sample: 0 = grid_sample (zero padding), 1 = nvdiffrast linear filtering with wrap
-extern "C" int utx_launch_backproject(const utx_backproject_desc* hp, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream) {
-    utx_backproject_desc p = *hp;
-    if (!bvh || p.T_h <= 0 || p.T_w <= 0 || p.view_count <= 0 || (sample != 0 && sample != 1)) return -2;
-    if (sample == 1 && (p.H <= 0 || p.W <= 0)) return -2;      // the wrap needs a non-empty view
+template <bool VIS>
+static int dispatch_backproject(const utx_backproject_desc& p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream) {
     const int depth = utx_bvh_depth_impl(const_cast<utx_bvh*>(bvh));      // first use after a build: waits for the build's depth word
     if (depth < 0) return -7;
     if (sample == 0) {
-        if (eyes) launch_backproject<true, 0>(p, eyes, bvh, depth, stream);
-        else launch_backproject<false, 0>(p, nullptr, bvh, depth, stream);
+        if (eyes) launch_backproject<true, 0, VIS>(p, eyes, bvh, depth, stream);
+        else launch_backproject<false, 0, VIS>(p, nullptr, bvh, depth, stream);
     } else {
-        if (eyes) launch_backproject<true, 1>(p, eyes, bvh, depth, stream);
-        else launch_backproject<false, 1>(p, nullptr, bvh, depth, stream);
+        if (eyes) launch_backproject<true, 1, VIS>(p, eyes, bvh, depth, stream);
+        else launch_backproject<false, 1, VIS>(p, nullptr, bvh, depth, stream);
     }
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
+extern "C" int utx_launch_backproject(const utx_backproject_desc* hp, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream) {
+    const utx_backproject_desc p = *hp;
+    if (!bvh || p.T_h <= 0 || p.T_w <= 0 || p.view_count <= 0 || (sample != 0 && sample != 1)) return -2;
+    if (sample == 1 && (p.H <= 0 || p.W <= 0)) return -2;      // the wrap needs a non-empty view
+    return dispatch_backproject<false>(p, eyes, sample, bvh, stream);
+}
+
 // visibility only (the 9-channel bake): p.images = alpha [n][H][W] f32, p.color unused.  Same traversal choice, same options.
 extern "C" int utx_launch_backproject_vis(const utx_backproject_desc* hp, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream) {
-    utx_backproject_desc p = *hp;
+    const utx_backproject_desc p = *hp;
     if (!bvh || p.T_h <= 0 || p.T_w <= 0 || p.view_count <= 0 || p.H <= 0 || p.W <= 0 || (sample != 0 && sample != 1)) return -2;
-    const int depth = utx_bvh_depth_impl(const_cast<utx_bvh*>(bvh));
-    if (depth < 0) return -7;
-    if (sample == 0) {
-        if (eyes) launch_backproject<true, 0, true>(p, eyes, bvh, depth, stream);
-        else launch_backproject<false, 0, true>(p, nullptr, bvh, depth, stream);
-    } else {
-        if (eyes) launch_backproject<true, 1, true>(p, eyes, bvh, depth, stream);
-        else launch_backproject<false, 1, true>(p, nullptr, bvh, depth, stream);
-    }
-    return hipGetLastError() == hipSuccess ? 0 : -4;
+    return dispatch_backproject<true>(p, eyes, sample, bvh, stream);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -276,12 +261,23 @@ extern "C" int utx_launch_dilate_visibility(const void* rayvis, const void* alph
 // ---------------------------------------------------------------------------------------------
 struct OrderArg { int v[8]; int n; };
 
+// order [n_order <= 8] of view indices -> the kernel argument
+static OrderArg order_arg(const int* order, int n_order) {
+    OrderArg o; o.n = n_order;
+    for (int i = 0; i < 8; ++i) o.v[i] = i < n_order ? order[i] : 0;
+    return o;
+}
+
+__device__ __forceinline__ int first_visible(const unsigned char* vis, const OrderArg& ord, long T, long t) {
+    for (int i = 0; i < ord.n; ++i) { const int vw = ord.v[i]; if (vis[(long)vw * T + t]) return vw; }
+    return -1;
+}
+
 __global__ __launch_bounds__(256) void composite_kernel(const float* colors, const unsigned char* vis, OrderArg ord, long T,
                                                         float* atlas, signed char* winner) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= T) return;
-    int wv = -1;
-    for (int i = 0; i < ord.n; ++i) { const int vw = ord.v[i]; if (vis[(long)vw * T + t]) { wv = vw; break; } }
+    const int wv = first_visible(vis, ord, T, t);
     float c0 = 0.f, c1 = 0.f, c2 = 0.f;
     if (wv >= 0) { const float* c = colors + ((long)wv * T + t) * 3; c0 = c[0]; c1 = c[1]; c2 = c[2]; }
     atlas[3 * t] = c0; atlas[3 * t + 1] = c1; atlas[3 * t + 2] = c2;
@@ -291,8 +287,7 @@ __global__ __launch_bounds__(256) void composite_kernel(const float* colors, con
 extern "C" int utx_launch_composite(const float* colors, const void* vis, const int* order, int n_order, long T, float* atlas,
                                     void* winner, hipStream_t stream) {
     if (n_order <= 0 || n_order > 8 || T <= 0) return -2;
-    OrderArg o; o.n = n_order;
-    for (int i = 0; i < 8; ++i) o.v[i] = i < n_order ? order[i] : 0;
+    const OrderArg o = order_arg(order, n_order);
     hipLaunchKernelGGL(composite_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, stream, colors, (const unsigned char*)vis, o, T,
                        atlas, (signed char*)winner);
     return hipGetLastError() == hipSuccess ? 0 : -4;
@@ -302,15 +297,12 @@ extern "C" int utx_launch_composite(const float* colors, const void* vis, const 
 __global__ __launch_bounds__(256) void composite_winner_kernel(const unsigned char* vis, OrderArg ord, long T, signed char* winner) {
     const long t = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= T) return;
-    int wv = -1;
-    for (int i = 0; i < ord.n; ++i) { const int vw = ord.v[i]; if (vis[(long)vw * T + t]) { wv = vw; break; } }
-    winner[t] = (signed char)wv;
+    winner[t] = (signed char)first_visible(vis, ord, T, t);
 }
 
 extern "C" int utx_launch_composite_winner(const void* vis, int n_views, const int* order, int n_order, long T, void* winner, hipStream_t stream) {
     if (n_order <= 0 || n_order > 8 || T <= 0 || n_views <= 0) return -2;
-    OrderArg o; o.n = n_order;
-    for (int i = 0; i < 8; ++i) o.v[i] = i < n_order ? order[i] : 0;
+    const OrderArg o = order_arg(order, n_order);
     for (int i = 0; i < n_order; ++i) if (o.v[i] < 0 || o.v[i] >= n_views) return -2;
     hipLaunchKernelGGL(composite_winner_kernel, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, stream, (const unsigned char*)vis, o, T, (signed char*)winner);
     return hipGetLastError() == hipSuccess ? 0 : -4;
@@ -335,27 +327,11 @@ __global__ __launch_bounds__(256) void gather_winner_kernel(const float4* rast2d
     const float4 r = rast2d[t];
     const int id = (int)r.w - 1;
     if (vw >= 0 && vw < n_views && id >= 0) {
-        const float u = r.x, v = r.y, w = (1.0f - u) - v;
+        const float u = r.x, v = r.y, w = sd_bary_w(u, v);
         const int f0 = faces[3 * (long)id], f1 = faces[3 * (long)id + 1], f2 = faces[3 * (long)id + 2];
-        const float* nd = vndc + (long)vw * V * 2;
-        const float gx = (nd[2 * (long)f0] * u + nd[2 * (long)f1] * v) + nd[2 * (long)f2] * w;
-        const float gy = (nd[2 * (long)f0 + 1] * u + nd[2 * (long)f1 + 1] * v) + nd[2 * (long)f2 + 1] * w;
-        const float* img = images + (long)vw * H * W * C + ch;
-        if constexpr (SAMPLE == 0) {
-            const float ix = ((gx + 1.0f) * (float)W - 1.0f) * 0.5f;
-            const float iy = ((gy + 1.0f) * (float)H - 1.0f) * 0.5f;
-            const float fx = floorf(ix), fy = floorf(iy);
-            const int x0 = (int)fx, y0 = (int)fy;
-            const float tx = ix - fx, ty = iy - fy;
-            const float w00 = (1.0f - tx) * (1.0f - ty), w01 = tx * (1.0f - ty), w10 = (1.0f - tx) * ty, w11 = tx * ty;
-            auto tap = [&](int x, int y) -> float { return (x < 0 || x >= W || y < 0 || y >= H) ? 0.f : img[((long)y * W + x) * C]; };
-            const float a = tap(x0, y0), b = tap(x0 + 1, y0), c = tap(x0, y0 + 1), e = tap(x0 + 1, y0 + 1);
-            o = ((a * w00 + b * w01) + c * w10) + e * w11;
-        } else {
-            long o00, o10, o01, o11; float fu, fv;
-            if (wrap_taps(H, W, gx, gy, o00, o10, o01, o11, fu, fv))
-                o = lerp_nv(lerp_nv(img[o00 * C], img[o10 * C], fu), lerp_nv(img[o01 * C], img[o11 * C], fu), fv);
-        }
+        float g[2];
+        texel_ndc(vndc + (long)vw * V * 2, f0, f1, f2, u, v, w, g);
+        o = sample_view<SAMPLE>(images + (long)vw * H * W * C + ch, C, H, W, g[0], g[1]);
     }
     atlas[i] = o;
 }

@@ -41,7 +41,7 @@ SOURCES = [
 ]
 GEOM = [
     ("raster.hip", ["-ffp-contract=off"]),
-    ("uv_gbuffer.hip", ["-ffp-contract=off"] + NO_PK),      # NO_PK is what its UTX_TU_NO_PACKED_FP32 promises gbuffer_device.h
+    ("gbuffer.hip", ["-ffp-contract=off"] + NO_PK),      # screen- and atlas-space geometry buffers: sums of products that would form the packed pair
     ("pbr.hip", ["-ffp-contract=off"] + NO_PK),
     ("bvh.hip", ["-ffp-contract=off"] + NO_PK),
     ("backproject.hip", ["-ffp-contract=off"] + NO_PK),

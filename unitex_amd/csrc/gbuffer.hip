@@ -1,0 +1,277 @@
+// Geometry buffers (gfx950): the screen-space ones of the orbit video (utx_gbuffer_shade, utx_gbuffer_range, utx_camera_normals) and the atlas-space
+// ones of simple_inverse_rendering (utx_uv_gbuffer).  Both interpolate with shade_device.h's sd_interp, utx_interpolate's (a0*u + a1*v) + a2*w, and
+// normalise with its F.normalize, so a covered pixel's value is bit-identical to interpolate_kernel's wherever it is computed.
+//
+// HBM-bound.  Plain vector loads and stores, no LDS, no scratch, no inline assembly; atomics only in the range reduction.  Built with -ffp-contract=off
+// (every operation one correctly rounded fp32 operation) and without packed fp32 (csrc/build.py NO_PK): the sums of products below are exactly what hipcc
+// would otherwise turn into the cross-half packed pair that tests/test_asm_hazards_cpu.py bans from every listing.
+#include "common.h"
+#include "kernels.h"
+#include "shade_device.h"
+
+// ---- geometry-buffer shading of the orbit video (VideoExporter.export_orbit_video(video_type=...) -> export_video,
+// video/export_nvdiffrast_video.py:37-139, on simple_rendering, render/nvdiffrast/renderer_base.py:153-241, with alpha = coverage):
+// one thread per pixel interpolates the triangle's three vertex attributes, then, per MODE,
+//   NORMAL    v = n / max(sqrt((nx*nx + ny*ny) + nz*nz), 1e-12), background -1   (world_normal :160-166; camera_normal :168-176 with the
+//             per-view, per-vertex re-normalised camera_normals_kernel output as attribute)
+//   POSITION  v = p, background -1 (world_position :178-188) or 0 (camera_position :228-235: `fill`)
+//   DEPTH     v = the one interpolated channel (clip w), background 0, repeated to three (z_depth :153-158, export_video :107-108)
+//   DISTANCE  v = sqrt((px*px + py*py) + pz*pz) of the interpolated camera-space position, background 0, repeated (:236-241)
+// then export_video :120-131 in its order: covered pixels (v - lo) / (hi - lo) if scale2 = {lo, hi} is given; v * 0.5 + 0.5 if ndc;
+// v * alpha + bg * (1 - alpha) if composite; RGBA float frame (alpha fourth) and clamp(0, 1) * 255 truncated to uint8.
+// torch.lerp(fill, v, alpha) with alpha in {0, 1} returns v or fill exactly, so it is a select here.
+enum { GB_NORMAL = 0, GB_POSITION = 1, GB_DEPTH = 2, GB_DISTANCE = 3 };
+
+template <int MODE>
+__device__ __forceinline__ bool gbuffer_value(const float4 r, const int* tri, const float* attr, int stride, float fill, float v3[3]) {
+    const int id = (int)r.w - 1;
+    if (id < 0) { v3[0] = v3[1] = v3[2] = fill; return false; }
+    const float u = r.x, v = r.y, w = sd_bary_w(u, v);
+    const float* a0 = attr + (long)stride * tri[3 * id + 0];
+    const float* a1 = attr + (long)stride * tri[3 * id + 1];
+    const float* a2 = attr + (long)stride * tri[3 * id + 2];
+    if constexpr (MODE == GB_DEPTH) {
+        v3[0] = v3[1] = v3[2] = sd_interp1(a0[0], a1[0], a2[0], u, v, w);
+    } else {
+        float p[3];
+        sd_interp<3>(a0, a1, a2, u, v, w, p);
+        if constexpr (MODE == GB_NORMAL) {
+            sd_normalize3(p, sd_length3(p), v3);
+        } else if constexpr (MODE == GB_DISTANCE) {
+            v3[0] = v3[1] = v3[2] = sd_length3(p);
+        } else {
+            v3[0] = p[0]; v3[1] = p[1]; v3[2] = p[2];
+        }
+    }
+    return true;
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void gbuffer_shade_kernel(const float4* rast, const int* tri, const float* attr, int stride, float fill,
+                                                            const float* scale2, int ndc, int composite, float bg0, float bg1, float bg2,
+                                                            long npix, unsigned char* out_u8, float4* out_rgba) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    float c[3];
+    const bool covered = gbuffer_value<MODE>(rast[i], tri, attr, stride, fill, c);
+    const float a = covered ? 1.0f : 0.0f;
+    if (scale2 && covered) {
+        const float lo = scale2[0], hi = scale2[1];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) c[k] = (c[k] - lo) / (hi - lo);
+    }
+    const float bg[3] = {bg0, bg1, bg2};
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        if (ndc) c[k] = c[k] * 0.5f + 0.5f;
+        if (composite) c[k] = c[k] * a + bg[k] * (1.0f - a);
+        out_u8[3 * i + k] = sd_to_u8(c[k]);
+    }
+    if (out_rgba) out_rgba[i] = make_float4(c[0], c[1], c[2], a);
+}
+
+// mode of the ABI (unitex_hip.h UTX_GBUF_*) -> kernel arm, background fill of the buffer, vertex stride is the caller's
+extern "C" int utx_launch_gbuffer_shade(int mode, const float* rast, const int* tri, const float* attr, int stride, const float* scale2,
+                                        int ndc, int composite, const float* bg3_host, long npix, void* out_u8, float* out_rgba,
+                                        hipStream_t stream) {
+    if (npix <= 0 || stride <= 0 || !bg3_host) return -2;
+    const dim3 g((unsigned)((npix + 255) / 256)), b(256);
+#define GB_LAUNCH(M, FILL) hipLaunchKernelGGL(gbuffer_shade_kernel<M>, g, b, 0, stream, (const float4*)rast, tri, attr, stride, FILL, scale2, \
+                                              ndc, composite, bg3_host[0], bg3_host[1], bg3_host[2], npix, (unsigned char*)out_u8, (float4*)out_rgba)
+    switch (mode) {
+        case 0: case 1: GB_LAUNCH(GB_NORMAL, -1.0f); break;     // world_normal, camera_normal
+        case 2: GB_LAUNCH(GB_POSITION, -1.0f); break;           // world_position
+        case 3: GB_LAUNCH(GB_POSITION, 0.0f); break;            // camera_position
+        case 4: GB_LAUNCH(GB_DEPTH, 0.0f); break;               // z_depth
+        case 5: GB_LAUNCH(GB_DISTANCE, 0.0f); break;            // distance
+        default: return -2;
+    }
+#undef GB_LAUNCH
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// (lo, hi) of the buffer over the covered pixels of one frame (export_video :120-125 rgb_sel.min() / .max(), taken on the first frame only):
+// per-wave shuffle reduction, one atomic pair per wave.  Floats are ordered through their bit patterns (non-negative: as signed ints,
+// negative: reversed as unsigned), so the result is the exact min / max whatever the order.  empty stays 1 if no pixel is covered.
+__global__ void gbuffer_range_init_kernel(float* scale2, int* empty) {
+    scale2[0] = __int_as_float(0x7f800000); scale2[1] = __int_as_float(0xff800000); *empty = 1;
+}
+
+__device__ __forceinline__ void atomic_min_float(float* addr, float v) {
+    if (v >= 0.f) atomicMin((int*)addr, __float_as_int(v)); else atomicMax((unsigned int*)addr, __float_as_uint(v));
+}
+__device__ __forceinline__ void atomic_max_float(float* addr, float v) {
+    if (v >= 0.f) atomicMax((int*)addr, __float_as_int(v)); else atomicMin((unsigned int*)addr, __float_as_uint(v));
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void gbuffer_range_kernel(const float4* rast, const int* tri, const float* attr, int stride, long npix,
+                                                            float* scale2, int* empty) {
+    float lo = __int_as_float(0x7f800000), hi = __int_as_float(0xff800000);
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (long)gridDim.x * blockDim.x) {
+        float c[3];
+        if (gbuffer_value<MODE>(rast[i], tri, attr, stride, 0.f, c))
+            for (int k = 0; k < 3; ++k) { lo = fminf(lo, c[k]); hi = fmaxf(hi, c[k]); }
+    }
+    for (int off = warpSize / 2; off > 0; off >>= 1) {
+        lo = fminf(lo, __shfl_down(lo, off));
+        hi = fmaxf(hi, __shfl_down(hi, off));
+    }
+    if ((threadIdx.x & (warpSize - 1)) == 0 && lo <= hi) {
+        atomic_min_float(scale2, lo + 0.0f);      // + 0.0f canonicalises -0
+        atomic_max_float(scale2 + 1, hi + 0.0f);
+        atomicAnd(empty, 0);
+    }
+}
+
+extern "C" int utx_launch_gbuffer_range(int mode, const float* rast, const int* tri, const float* attr, int stride, long npix, float* scale2,
+                                        int* empty, hipStream_t stream) {
+    if (npix <= 0 || stride <= 0) return -2;
+    long nb = (npix + 255) / 256; if (nb > 1024) nb = 1024;
+    const dim3 g((unsigned)nb), b(256);
+    hipLaunchKernelGGL(gbuffer_range_init_kernel, dim3(1), dim3(1), 0, stream, scale2, empty);
+#define GB_RANGE(M) hipLaunchKernelGGL(gbuffer_range_kernel<M>, g, b, 0, stream, (const float4*)rast, tri, attr, stride, npix, scale2, empty)
+    switch (mode) {
+        case 0: case 1: GB_RANGE(GB_NORMAL); break;
+        case 2: case 3: GB_RANGE(GB_POSITION); break;
+        case 4: GB_RANGE(GB_DEPTH); break;
+        case 5: GB_RANGE(GB_DISTANCE); break;
+        default: return -2;
+    }
+#undef GB_RANGE
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// per-view, per-vertex camera-space normals of render_camera_normal (renderer_base.py:169-170): out[n][v] = normalize(nrm[v] @ c2ws[n][:3,:3]),
+// out_j = (n0*R0j + n1*R1j) + n2*R2j, F.normalize eps 1e-12
+__global__ __launch_bounds__(256) void camera_normals_kernel(const float* nrm, int V, const float* c2ws, float* out) {
+    const int v = blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= V) return;
+    const float* m = c2ws + 16 * blockIdx.y;
+    const float n[3] = {nrm[3 * v], nrm[3 * v + 1], nrm[3 * v + 2]};
+    float c[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float col[3] = {m[j], m[4 + j], m[8 + j]};
+        c[j] = sd_dot3(n, col);
+    }
+    sd_normalize3(c);
+    float* o = out + 3 * ((long)blockIdx.y * V + v);
+    o[0] = c[0]; o[1] = c[1]; o[2] = c[2];
+}
+
+extern "C" int utx_launch_camera_normals(const float* nrm, int V, const float* c2ws, int n_views, float* out, hipStream_t stream) {
+    if (V <= 0 || n_views <= 0) return -2;
+    hipLaunchKernelGGL(camera_normals_kernel, dim3((V + 255) / 256, n_views), dim3(256), 0, stream, nrm, V, c2ws, out);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// ---- atlas-space geometry buffers: NVDiffRendererBase.simple_inverse_rendering of the reference
+// (TextureTools/texturetools/render/nvdiffrast/renderer_base.py:352-489) with alpha = coverage (no dr.antialias), every requested buffer of
+// every camera in ONE launch.
+//
+// One thread per texel of the UV raster, x fastest.  The thread reads its raster record (u, v, z/w, id + 1) and the triangle's three vertex
+// indices once, forms w = (1 - u) - v once, and then loops over the views itself: per view two gathers of three vertices (camera-space position and
+// normal), the interpolation and the table below.  torch.lerp(bg, x, alpha) with alpha in {0, 1} returns x or bg exactly, so it is a select.
+//
+//   buffer               covered texel                                         background
+//   world_normal         normalize(interp(v_nrm))                              -1     (:401-407)
+//   world_position       interp(v_pos)                                         -1     (:419-429)
+//   camera_normal[b]     normalize(interp(v_nrm_cam[b]))                       -1     (:409-417)
+//   camera_position[b]   interp(v_pos_cam[b])                                   0     (:445-455)
+//   distance[b]          sqrt((x*x + y*y) + z*z) of camera_position             0     (:456-461)
+//   z_depth[b]           camera_position.z                                      0     (:462-467)
+//   ray_direction[b]     normalize(camera_position)                            -1     (:468-473)
+//   cos_ray_normal[b]    (cn.x*rd.x + cn.y*rd.y) + cn.z*rd.z, both as above    -1     (:475-489)
+//   normalize(x) = x / max(|x|, 1e-12), |x| = sqrt((x*x + y*y) + z*z)
+//
+// 16 B read and up to 29 + 48 B written per texel and view; the vertex gathers hit L2 (neighbouring texels share a triangle).
+struct UvGbufferOut {
+    unsigned char* mask;
+    float *alpha, *world_normal, *world_position, *camera_normal, *camera_position, *distance, *z_depth, *ray_direction, *cos_ray_normal;
+};
+
+__device__ __forceinline__ void uvgb_store3(float* base, long texel, const float v[3]) {
+    float* o = base + 3 * texel;
+    o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
+}
+
+__global__ __launch_bounds__(256) void uv_gbuffer_kernel(const float4* __restrict__ rast, const int* __restrict__ tri, const float* __restrict__ v_pos,
+                                                         const float* __restrict__ v_nrm, const float* __restrict__ v_pos_cam,
+                                                         const float* __restrict__ v_nrm_cam, long V, int B, long npix, UvGbufferOut o) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const float4 r = rast[i];
+    const int id = (int)r.w - 1;
+    const bool covered = id >= 0;
+    const float u = r.x, v = r.y, w = sd_bary_w(u, v);
+    long i0 = 0, i1 = 0, i2 = 0;
+    if (covered) { i0 = tri[3 * id + 0]; i1 = tri[3 * id + 1]; i2 = tri[3 * id + 2]; }
+    if (o.mask) o.mask[i] = covered ? 1 : 0;
+    if (o.alpha) o.alpha[i] = covered ? 1.0f : 0.0f;
+    if (o.world_normal) {
+        float n[3] = {-1.0f, -1.0f, -1.0f};
+        if (covered) {
+            float p[3];
+            sd_interp<3>(v_nrm + 3 * i0, v_nrm + 3 * i1, v_nrm + 3 * i2, u, v, w, p);
+            sd_normalize3(p, sd_length3(p), n);
+        }
+        uvgb_store3(o.world_normal, i, n);
+    }
+    if (o.world_position) {
+        float p[3] = {-1.0f, -1.0f, -1.0f};
+        if (covered) sd_interp<3>(v_pos + 3 * i0, v_pos + 3 * i1, v_pos + 3 * i2, u, v, w, p);
+        uvgb_store3(o.world_position, i, p);
+    }
+    const bool want_cn = o.camera_normal || o.cos_ray_normal;
+    const bool want_cp = o.camera_position || o.distance || o.z_depth || o.ray_direction || o.cos_ray_normal;
+    for (int b = 0; b < B; ++b) {
+        const long t = (long)b * npix + i;
+        float cn[3] = {-1.0f, -1.0f, -1.0f}, cp[3] = {0.0f, 0.0f, 0.0f}, rd[3] = {-1.0f, -1.0f, -1.0f};
+        float dist = 0.0f, cosv = -1.0f;
+        if (covered) {
+            if (want_cn) {
+                float p[3];
+                const float* a = v_nrm_cam + 3 * V * b;
+                sd_interp<3>(a + 3 * i0, a + 3 * i1, a + 3 * i2, u, v, w, p);
+                sd_normalize3(p, sd_length3(p), cn);
+            }
+            if (want_cp) {
+                const float* a = v_pos_cam + 3 * V * b;
+                sd_interp<3>(a + 3 * i0, a + 3 * i1, a + 3 * i2, u, v, w, cp);
+                dist = sd_length3(cp);
+                sd_normalize3(cp, dist, rd);
+            }
+            if (o.cos_ray_normal) cosv = sd_dot3(cn, rd);
+        }
+        if (o.camera_normal) uvgb_store3(o.camera_normal, t, cn);
+        if (o.camera_position) uvgb_store3(o.camera_position, t, cp);
+        if (o.distance) o.distance[t] = dist;
+        if (o.z_depth) o.z_depth[t] = cp[2];
+        if (o.ray_direction) uvgb_store3(o.ray_direction, t, rd);
+        if (o.cos_ray_normal) o.cos_ray_normal[t] = cosv;
+    }
+}
+
+// outs_host[k] is the buffer of bit k of `want` (unitex_hip.h UTX_UVGB_*); pointers of buffers that were not requested are never read
+extern "C" int utx_launch_uv_gbuffer(const float* rast, const int* tri, const float* v_pos, const float* v_nrm, const float* v_pos_cam,
+                                     const float* v_nrm_cam, int V, int B, int H2D, int W2D, unsigned want, void* const* outs_host,
+                                     hipStream_t stream) {
+    if (H2D <= 0 || W2D <= 0 || B < 0 || V <= 0 || !outs_host) return -2;
+    const long npix = (long)H2D * W2D;
+    auto out = [&](int bit) -> void* { return (want >> bit) & 1u ? outs_host[bit] : nullptr; };
+    UvGbufferOut o;
+    o.mask = (unsigned char*)out(0);
+    o.alpha = (float*)out(1);
+    o.world_normal = (float*)out(2);
+    o.world_position = (float*)out(3);
+    o.camera_normal = (float*)out(4);
+    o.camera_position = (float*)out(5);
+    o.distance = (float*)out(6);
+    o.z_depth = (float*)out(7);
+    o.ray_direction = (float*)out(8);
+    o.cos_ray_normal = (float*)out(9);
+    hipLaunchKernelGGL(uv_gbuffer_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, (const float4*)rast, tri, v_pos, v_nrm,
+                       v_pos_cam, v_nrm_cam, (long)V, B, npix, o);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}

@@ -142,10 +142,10 @@ int utx_launch_sample_edges(const float* verts, const int* edges, const int* edg
 int utx_launch_sample_surface(const float* verts, const int* faces, const float* cum, int F, long N, unsigned long long seed, float* samples, int* face_index,
                               float* uvw, hipStream_t stream);
 int utx_launch_texture_shade(const float* rast, const float* uv, const int* tri, const float* tex, int Ht, int Wt, const float* bg3_host, long npix, void* out, hipStream_t stream);
+// gbuffer.hip
 int utx_launch_gbuffer_shade(int mode, const float* rast, const int* tri, const float* attr, int stride, const float* scale2, int ndc, int composite, const float* bg3_host, long npix, void* out_u8, float* out_rgba, hipStream_t stream);
 int utx_launch_gbuffer_range(int mode, const float* rast, const int* tri, const float* attr, int stride, long npix, float* scale2, int* empty, hipStream_t stream);
 int utx_launch_camera_normals(const float* nrm, int V, const float* c2ws, int n_views, float* out, hipStream_t stream);
-// uv_gbuffer.hip
 int utx_launch_uv_gbuffer(const float* rast, const int* tri, const float* v_pos, const float* v_nrm, const float* v_pos_cam, const float* v_nrm_cam, int V, int B, int H2D, int W2D,
                           unsigned want, void* const* outs_host, hipStream_t stream);
 // pbr.hip

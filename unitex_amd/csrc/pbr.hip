@@ -21,17 +21,41 @@
 #include <math.h>
 #include "common.h"
 #include "kernels.h"
+#include "shade_device.h"
+
+// ---------------------------------------------------------------------------------------------------------------- the cube's faces, stated once
+// face s, in-face coordinates (a, b), depth d -> the vector (cube_to_dir before normalisation): fp64 with d = 1 for the tables and the lat-long resampling,
+// integers in units of 1 / N with d = N for the taps that leave a face
+template <class T>
+__host__ __device__ inline void pbr_face_vec(int s, T a, T b, T d, T v[3]) {
+    switch (s) {
+        case 0: v[0] = d; v[1] = -b; v[2] = -a; break;
+        case 1: v[0] = -d; v[1] = -b; v[2] = a; break;
+        case 2: v[0] = a; v[1] = d; v[2] = b; break;
+        case 3: v[0] = a; v[1] = -d; v[2] = -b; break;
+        case 4: v[0] = a; v[1] = -b; v[2] = d; break;
+        default: v[0] = -a; v[1] = -b; v[2] = -d; break;
+    }
+}
+
+// vector -> its face (the component of largest magnitude, ties to x, then y) and the in-face numerators (cx, cy) over the denominator cz = that magnitude
+// (dir_to_side of cubemap.cu:48-60): fp32 for a direction, integers for a tap's centre
+__device__ __forceinline__ float pbr_abs(float x) { return fabsf(x); }
+__device__ __forceinline__ int pbr_abs(int x) { return abs(x); }
+template <class T>
+__device__ __forceinline__ int pbr_vec_face(T v0, T v1, T v2, T& cx, T& cy, T& cz) {
+    const T a0 = pbr_abs(v0), a1 = pbr_abs(v1), a2 = pbr_abs(v2);
+    int s;
+    if (a0 >= a1 && a0 >= a2) { s = v0 >= (T)0 ? 0 : 1; cx = s == 0 ? -v2 : v2; cy = -v1; cz = a0; }
+    else if (a1 >= a2) { s = v1 >= (T)0 ? 2 : 3; cx = v0; cy = s == 2 ? v2 : -v2; cz = a1; }
+    else { s = v2 >= (T)0 ? 4 : 5; cx = s == 4 ? v0 : -v0; cy = -v1; cz = a2; }
+    return s;
+}
 
 // ---------------------------------------------------------------------------------------------------------------- host tables (fp64, rounded once)
-static void pbr_cube_dir(int s, double fx, double fy, double v[3]) {
-    switch (s) {
-        case 0: v[0] = 1; v[1] = -fy; v[2] = -fx; break;
-        case 1: v[0] = -1; v[1] = -fy; v[2] = fx; break;
-        case 2: v[0] = fx; v[1] = 1; v[2] = fy; break;
-        case 3: v[0] = fx; v[1] = -1; v[2] = -fy; break;
-        case 4: v[0] = fx; v[1] = -fy; v[2] = 1; break;
-        default: v[0] = -fx; v[1] = -fy; v[2] = -1; break;
-    }
+// unit direction of (fx, fy) on face s
+__host__ __device__ inline void pbr_cube_dir(int s, double fx, double fy, double v[3]) {
+    pbr_face_vec(s, fx, fy, 1.0, v);
     const double l = sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
     v[0] /= l; v[1] /= l; v[2] /= l;
 }
@@ -81,41 +105,27 @@ extern "C" int utx_cubemap_table_impl(int N, float costheta_cutoff, float* texel
 // latlong_to_cubemap (pbr.py:28-49): v = normalize(cube_to_dir(s, gx, gy)), tu = atan2(vx, -vz) / 2pi + 0.5, tv = acos(clamp(vy)) / pi, bilinear fetch with
 // wrap addressing in both axes (texel centres at +0.5).  The texture coordinates, the fractions and the blend are carried in fp64 and rounded once:
 // a fp32 tu times Wi already moves the fraction by more than the result may differ from the fp64 statement (one-time work, 6 N^2 texels).
-__device__ __forceinline__ int pbr_wrapi(long i, int n) { i %= n; return (int)(i < 0 ? i + n : i); }
-
 __global__ __launch_bounds__(256) void latlong_to_cubemap_kernel(const float* lat, int Hi, int Wi, int N, float* out) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 6L * N * N) return;
     const int x = (int)(i % N), y = (int)((i / N) % N), s = (int)(i / ((long)N * N));
     const double fx = 2.0 * ((x + 0.5) / N) - 1.0, fy = 2.0 * ((y + 0.5) / N) - 1.0;
-    double v0, v1, v2;
-    switch (s) {
-        case 0: v0 = 1; v1 = -fy; v2 = -fx; break;
-        case 1: v0 = -1; v1 = -fy; v2 = fx; break;
-        case 2: v0 = fx; v1 = 1; v2 = fy; break;
-        case 3: v0 = fx; v1 = -1; v2 = -fy; break;
-        case 4: v0 = fx; v1 = -fy; v2 = 1; break;
-        default: v0 = -fx; v1 = -fy; v2 = -1; break;
-    }
-    const double l = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
-    v0 /= l; v1 /= l; v2 /= l;
+    double vd[3];
+    pbr_cube_dir(s, fx, fy, vd);
+    const double v0 = vd[0], v1 = vd[1], v2 = vd[2];
     const double kPi = 3.14159265358979323846;
     const double tu = atan2(v0, -v2) / (2.0 * kPi) + 0.5;
     const double tv = acos(fmin(fmax(v1, -1.0), 1.0)) / kPi;
     const double px = tu * Wi - 0.5, py = tv * Hi - 0.5;
     const double bx = floor(px), by = floor(py);
     const double wx = px - bx, wy = py - by;
-    const int x0 = pbr_wrapi((long)bx, Wi), x1 = pbr_wrapi((long)bx + 1, Wi);
-    const int y0 = pbr_wrapi((long)by, Hi), y1 = pbr_wrapi((long)by + 1, Hi);
+    const int x0 = sd_wrapi((long)bx, Wi), x1 = sd_wrapi((long)bx + 1, Wi);
+    const int y0 = sd_wrapi((long)by, Hi), y1 = sd_wrapi((long)by + 1, Hi);
     const float* t00 = lat + 3 * ((long)y0 * Wi + x0);
     const float* t01 = lat + 3 * ((long)y0 * Wi + x1);
     const float* t10 = lat + 3 * ((long)y1 * Wi + x0);
     const float* t11 = lat + 3 * ((long)y1 * Wi + x1);
-    for (int k = 0; k < 3; ++k) {
-        const double top = (double)t00[k] * (1.0 - wx) + (double)t01[k] * wx;
-        const double bot = (double)t10[k] * (1.0 - wx) + (double)t11[k] * wx;
-        out[3 * i + k] = (float)(top * (1.0 - wy) + bot * wy);
-    }
+    for (int k = 0; k < 3; ++k) out[3 * i + k] = (float)sd_bilerp((double)t00[k], (double)t01[k], (double)t10[k], (double)t11[k], wx, wy);
 }
 
 extern "C" int utx_launch_latlong_to_cubemap(const float* lat, int Hi, int Wi, int N, float* out, hipStream_t stream) {
@@ -299,34 +309,19 @@ extern "C" int utx_launch_dfg_lut(int R, int nsamples, float* out, hipStream_t s
 }
 
 // ---------------------------------------------------------------------------------------------------------------- lookups
-// face and in-face coordinates of a direction (dir_to_side of cubemap.cu:48-60, over the major magnitude)
+// face and in-face coordinates of a direction, over the major magnitude
 __device__ __forceinline__ int pbr_dir_face(float dx, float dy, float dz, float& fx, float& fy) {
-    const float ax = fabsf(dx), ay = fabsf(dy), az = fabsf(dz);
-    int s; float cx, cy, cz;
-    if (ax >= ay && ax >= az) { s = dx >= 0.f ? 0 : 1; cx = s == 0 ? -dz : dz; cy = -dy; cz = ax; }
-    else if (ay >= az) { s = dy >= 0.f ? 2 : 3; cx = dx; cy = s == 2 ? dz : -dz; cz = ay; }
-    else { s = dz >= 0.f ? 4 : 5; cx = s == 4 ? dx : -dx; cy = -dy; cz = az; }
+    float cx, cy, cz;
+    const int s = pbr_vec_face(dx, dy, dz, cx, cy, cz);
     if (cz > 0.f) { fx = cx / cz; fy = cy / cz; } else { fx = fy = 0.f; }
     return s;
 }
 
 // texel of a tap that left face s along one axis: its centre on the plane of s, in integer units of 1 / N ((a, b) odd, depth N), seen from the neighbour
 __device__ __forceinline__ long pbr_out_tap(int N, int s, int x, int y) {
-    const int a = 2 * x + 1 - N, b = 2 * y + 1 - N;
-    int v0, v1, v2;
-    switch (s) {
-        case 0: v0 = N; v1 = -b; v2 = -a; break;
-        case 1: v0 = -N; v1 = -b; v2 = a; break;
-        case 2: v0 = a; v1 = N; v2 = b; break;
-        case 3: v0 = a; v1 = -N; v2 = -b; break;
-        case 4: v0 = a; v1 = -b; v2 = N; break;
-        default: v0 = -a; v1 = -b; v2 = -N; break;
-    }
-    const int a0 = abs(v0), a1 = abs(v1), a2 = abs(v2);
-    int s2, cx, cy, cz;
-    if (a0 >= a1 && a0 >= a2) { s2 = v0 >= 0 ? 0 : 1; cx = s2 == 0 ? -v2 : v2; cy = -v1; cz = a0; }
-    else if (a1 >= a2) { s2 = v1 >= 0 ? 2 : 3; cx = v0; cy = s2 == 2 ? v2 : -v2; cz = a1; }
-    else { s2 = v2 >= 0 ? 4 : 5; cx = s2 == 4 ? v0 : -v0; cy = -v1; cz = a2; }
+    int v[3], cx, cy, cz;
+    pbr_face_vec(s, 2 * x + 1 - N, 2 * y + 1 - N, N, v);
+    const int s2 = pbr_vec_face(v[0], v[1], v[2], cx, cy, cz);
     int ix = (int)(((long)(cx + cz) * N) / (2L * cz)), iy = (int)(((long)(cy + cz) * N) / (2L * cz));
     ix = min(max(ix, 0), N - 1); iy = min(max(iy, 0), N - 1);
     return ((long)s2 * N + iy) * N + ix;
@@ -417,23 +412,17 @@ extern "C" int utx_launch_cube_sample(const float* cube, int N, const float* dir
 //   diffuse = kd * light_diffuse[nrm];  specular = (ks * FG[c, roughness].x + FG[c, roughness].y) * light_specular[wi]
 struct PbrLights { const float* diff; int Nd; const float* spec; int Ns; const float* lut; int R; };
 
-__device__ __forceinline__ float pbr_dot3(const float a[3], const float b[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-__device__ __forceinline__ void pbr_normalize(float v[3]) {
-    const float l = fmaxf(sqrtf(pbr_dot3(v, v)), 1e-12f);
-    v[0] /= l; v[1] /= l; v[2] /= l;
-}
-
 __device__ __forceinline__ void pbr_eval(const PbrLights& L, const float eye[3], const float p[3], const float n_in[3], const float albedo[3], float rough,
                                          float metal, float diffuse[3], float specular[3]) {
     float nrm[3] = {n_in[0], n_in[1], n_in[2]};
-    pbr_normalize(nrm);
+    sd_normalize3(nrm);
     float wo[3] = {eye[0] - p[0], eye[1] - p[1], eye[2] - p[2]};
-    pbr_normalize(wo);
-    const float dn = pbr_dot3(wo, nrm);
+    sd_normalize3(wo);
+    const float dn = sd_dot3(wo, nrm);
     float wi[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) wi[k] = (2.0f * dn) * nrm[k] - wo[k];
-    pbr_normalize(wi);
+    sd_normalize3(wi);
     const float c = fminf(fmaxf(dn, 0.0f), 1.0f);
     float ld[3], ls[3], fg0, fg1;
     pbr_cube_lookup(L.diff, L.Nd, nrm[0], nrm[1], nrm[2], ld);
@@ -474,7 +463,7 @@ extern "C" int utx_launch_pbr_forward(const float* eye, int eye_stride, const fl
 
 // ---------------------------------------------------------------------------------------------------------------- tangent-space normal map
 // bsdf_prepare_shading_normal (texture/pbr/renderutils/bsdf.py:28-51) with two_sided_shading = True and opengl = True (glTF's convention) on one pixel,
-// every sum in a fixed order; normalize is F.normalize (x / max(|x|, 1e-12), pbr_normalize):
+// every sum in a fixed order; normalize is F.normalize (x / max(|x|, 1e-12), sd_normalize3):
 //   sn = normalize(smooth_nrm);  st = normalize(smooth_tng);  vv = normalize(eye - pos);  b = normalize(cross(st, sn))
 //   s = normalize((st p.x - b p.y) + sn max(p.z, 0))
 //   dot(geom_nrm, vv) > 0 ? (s, g) = (s, geom_nrm) : (-s, -geom_nrm)
@@ -485,21 +474,21 @@ __device__ __forceinline__ void pbr_shading_normal(const float eye[3], const flo
                                                    const float geom_nrm[3], float out[3]) {
     float sn[3] = {smooth_nrm[0], smooth_nrm[1], smooth_nrm[2]}, st[3] = {smooth_tng[0], smooth_tng[1], smooth_tng[2]};
     float vv[3] = {eye[0] - pos[0], eye[1] - pos[1], eye[2] - pos[2]};
-    pbr_normalize(sn);
-    pbr_normalize(st);
-    pbr_normalize(vv);
+    sd_normalize3(sn);
+    sd_normalize3(st);
+    sd_normalize3(vv);
     float b[3] = {st[1] * sn[2] - st[2] * sn[1], st[2] * sn[0] - st[0] * sn[2], st[0] * sn[1] - st[1] * sn[0]};
-    pbr_normalize(b);
+    sd_normalize3(b);
     const float pz = fmaxf(p[2], 0.0f);
     float s[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) s[k] = (st[k] * p[0] - b[k] * p[1]) + sn[k] * pz;
-    pbr_normalize(s);
-    const bool front = pbr_dot3(geom_nrm, vv) > 0.0f;
+    sd_normalize3(s);
+    const bool front = sd_dot3(geom_nrm, vv) > 0.0f;
     float g[3];
 #pragma unroll
     for (int k = 0; k < 3; ++k) { s[k] = front ? s[k] : -s[k]; g[k] = front ? geom_nrm[k] : -geom_nrm[k]; }
-    const float t = fminf(fmaxf(pbr_dot3(vv, s) / 0.1f, 0.0f), 1.0f);
+    const float t = fminf(fmaxf(sd_dot3(vv, s) / 0.1f, 0.0f), 1.0f);
 #pragma unroll
     for (int k = 0; k < 3; ++k) out[k] = g[k] + t * (s[k] - g[k]);
 }
@@ -528,27 +517,9 @@ extern "C" int utx_launch_pbr_shading_normal(const float* eye, int eye_stride, c
 
 // ---------------------------------------------------------------------------------------------------------------- fused frame
 // NVDiffRendererPBR.render_base + render_pbr (renderer_pbr.py:19-94) for one frame: position, normal and uv interpolate as utx_interpolate does (same
-// operations, same order); Kd / Ks fetch as utx_texture_shade does (bilinear, wrap, t00 (1 - fx) + t01 fx); PBRModel.forward; rgb = ld diffuse + ls specular;
+// operations, same order: sd_interp); Kd / Ks fetch as utx_texture_shade does (sd_tex3_wrap: bilinear, wrap, t00 (1 - fx) + t01 fx); PBRModel.forward; rgb = ld diffuse + ls specular;
 // torch.lerp(bg, rgb, alpha) with alpha = coverage in {0, 1} is a select; uint8 = clamp * 255 truncated.  ks == nullptr: the reference's default
-// [1, 1, 0] expanded to Kd's size (renderer_pbr.py:24-26), sent through the SAME blend arithmetic so that it is bit-identical to that constant texture.
-__device__ __forceinline__ void pbr_tex_fetch(const float* tex, int Ht, int Wt, float tu, float tv, float k0, float k1, float k2, float o[3]) {
-    const float x = tu * (float)Wt - 0.5f, y = tv * (float)Ht - 0.5f;
-    const float x0 = floorf(x), y0 = floorf(y);
-    const float fx = x - x0, fy = y - y0;
-    const int ix0 = pbr_wrapi((long)(int)x0, Wt), ix1 = pbr_wrapi((long)(int)x0 + 1, Wt);
-    const int iy0 = pbr_wrapi((long)(int)y0, Ht), iy1 = pbr_wrapi((long)(int)y0 + 1, Ht);
-    const long o00 = 3 * ((long)iy0 * Wt + ix0), o01 = 3 * ((long)iy0 * Wt + ix1), o10 = 3 * ((long)iy1 * Wt + ix0), o11 = 3 * ((long)iy1 * Wt + ix1);
-    const float cst[3] = {k0, k1, k2};      // tex == nullptr: the constant texture (k0, k1, k2), same arithmetic
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const float t00 = tex ? tex[o00 + k] : cst[k], t01 = tex ? tex[o01 + k] : cst[k];
-        const float t10 = tex ? tex[o10 + k] : cst[k], t11 = tex ? tex[o11 + k] : cst[k];
-        const float top = t00 * (1.0f - fx) + t01 * fx;
-        const float bot = t10 * (1.0f - fx) + t11 * fx;
-        o[k] = top * (1.0f - fy) + bot * fy;
-    }
-}
-
+// [1, 1, 0] expanded to Kd's size (renderer_pbr.py:24-26): sd_tex3_wrap_const, bit-identical to that constant texture.
 // NM = true (utx_pbr_shade_nm): the tangent interpolates as the normal does, the map fetches as Kd does and decodes as p = 2 texel - 1 (not normalised),
 // pbr_shading_normal with the triangle's face normal as the geometric one replaces the interpolated normal in front of pbr_eval.  NM = false is
 // utx_pbr_shade: none of that is compiled in and its arithmetic is what it was.
@@ -566,25 +537,22 @@ __global__ __launch_bounds__(256) void pbr_shade_kernel(PbrLights L, PbrNormalMa
     float c[3] = {bg0, bg1, bg2};
     const float a = id >= 0 ? 1.0f : 0.0f;
     if (id >= 0) {
-        const float u = r.x, v = r.y, w = (1.0f - u) - v;
+        const float u = r.x, v = r.y, w = sd_bary_w(u, v);
         const long i0 = tri[3 * id + 0], i1 = tri[3 * id + 1], i2 = tri[3 * id + 2];
         float p[3], n[3], uv[2];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            p[k] = (vpos[3 * i0 + k] * u + vpos[3 * i1 + k] * v) + vpos[3 * i2 + k] * w;
-            n[k] = (vnrm[3 * i0 + k] * u + vnrm[3 * i1 + k] * v) + vnrm[3 * i2 + k] * w;
-        }
-#pragma unroll
-        for (int k = 0; k < 2; ++k) uv[k] = (vuv[2 * i0 + k] * u + vuv[2 * i1 + k] * v) + vuv[2 * i2 + k] * w;
+        sd_interp<3>(vpos + 3 * i0, vpos + 3 * i1, vpos + 3 * i2, u, v, w, p);
+        sd_interp<3>(vnrm + 3 * i0, vnrm + 3 * i1, vnrm + 3 * i2, u, v, w, n);
+        sd_interp<2>(vuv + 2 * i0, vuv + 2 * i1, vuv + 2 * i2, u, v, w, uv);
         float al[3], arm[3];
-        pbr_tex_fetch(kd, Hk, Wk, uv[0], uv[1], 0.f, 0.f, 0.f, al);
-        pbr_tex_fetch(ks, ks ? Hs : Hk, ks ? Ws : Wk, uv[0], uv[1], 1.0f, 1.0f, 0.0f, arm);
+        sd_tex3_wrap(kd, Hk, Wk, uv[0], uv[1], al);
+        const float ks_default[3] = {1.0f, 1.0f, 0.0f};
+        if (ks) sd_tex3_wrap(ks, Hs, Ws, uv[0], uv[1], arm);
+        else sd_tex3_wrap_const(ks_default, Hk, Wk, uv[0], uv[1], arm);
         const float eye[3] = {e0, e1, e2};
         if constexpr (NM) {
             float tg[3], tx[3];
-#pragma unroll
-            for (int k = 0; k < 3; ++k) tg[k] = (M.vtng[3 * i0 + k] * u + M.vtng[3 * i1 + k] * v) + M.vtng[3 * i2 + k] * w;
-            pbr_tex_fetch(M.nm, M.Hn, M.Wn, uv[0], uv[1], 0.f, 0.f, 0.f, tx);
+            sd_interp<3>(M.vtng + 3 * i0, M.vtng + 3 * i1, M.vtng + 3 * i2, u, v, w, tg);
+            sd_tex3_wrap(M.nm, M.Hn, M.Wn, uv[0], uv[1], tx);
             const float pt[3] = {2.0f * tx[0] - 1.0f, 2.0f * tx[1] - 1.0f, 2.0f * tx[2] - 1.0f};
             const float g[3] = {M.fnrm[3 * (long)id], M.fnrm[3 * (long)id + 1], M.fnrm[3 * (long)id + 2]};
             const float sm[3] = {n[0], n[1], n[2]};
@@ -596,7 +564,7 @@ __global__ __launch_bounds__(256) void pbr_shade_kernel(PbrLights L, PbrNormalMa
         for (int k = 0; k < 3; ++k) c[k] = lam_d * d[k] + lam_s * s[k];
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) out_u8[3 * i + k] = (unsigned char)(fminf(fmaxf(c[k], 0.f), 1.f) * 255.0f);
+    for (int k = 0; k < 3; ++k) out_u8[3 * i + k] = sd_to_u8(c[k]);
     if (out_rgba) out_rgba[i] = make_float4(c[0], c[1], c[2], a);
 }
 
@@ -609,15 +577,10 @@ static int pbr_shade_launch(const PbrNormalMap* M, const float* rast, const int*
     const PbrLights L = {light_diffuse, Nd, light_specular, Ns, lut, R};
     const PbrNormalMap none = {nullptr, nullptr, nullptr, 0, 0};
     const dim3 grid((unsigned)((npix + 255) / 256));
-    if (M) {
-        hipLaunchKernelGGL(pbr_shade_kernel<true>, grid, dim3(256), 0, stream, L, *M, (const float4*)rast, tri, vpos, vnrm, vuv, kd, Hk, Wk, ks, Hs, Ws, eye3_host[0],
-                           eye3_host[1], eye3_host[2], lambda_diffuse, lambda_specular, bg3_host[0], bg3_host[1], bg3_host[2], npix, (unsigned char*)out_u8,
-                           (float4*)out_rgba);
-    } else {
-        hipLaunchKernelGGL(pbr_shade_kernel<false>, grid, dim3(256), 0, stream, L, none, (const float4*)rast, tri, vpos, vnrm, vuv, kd, Hk, Wk, ks, Hs, Ws, eye3_host[0],
-                           eye3_host[1], eye3_host[2], lambda_diffuse, lambda_specular, bg3_host[0], bg3_host[1], bg3_host[2], npix, (unsigned char*)out_u8,
-                           (float4*)out_rgba);
-    }
+    const auto kernel = M ? pbr_shade_kernel<true> : pbr_shade_kernel<false>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, stream, L, M ? *M : none, (const float4*)rast, tri, vpos, vnrm, vuv,
+                       kd, Hk, Wk, ks, Hs, Ws, eye3_host[0], eye3_host[1], eye3_host[2], lambda_diffuse, lambda_specular, bg3_host[0], bg3_host[1], bg3_host[2], npix,
+                       (unsigned char*)out_u8, (float4*)out_rgba);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

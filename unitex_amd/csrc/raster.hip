@@ -13,10 +13,11 @@
 // HBM-bound integer/byte work: one thread per triangle scans its bounding box (triangles of a 50k-200k
 // face mesh on a 2048^2 atlas cover ~15-80 texels each); large triangles are queued and scanned by a
 // whole workgroup.  A resolve pass turns the depth/id buffer into the (u, v, z/w, id+1) record.
-// Compiled with -ffp-contract=off.
+// Also here: the clip-space transform, the condition and texture shaders of the turntable, the per-face normals and the view-space visibility
+// filter; the geometry-buffer shaders live in gbuffer.hip.  Compiled with -ffp-contract=off; the per-pixel expressions are shade_device.h's.
 #include "common.h"
 #include "kernels.h"
-#include "gbuffer_device.h"
+#include "shade_device.h"
 
 #define SUBPIX 256
 #define BIG_BBOX 2048  // bbox area (pixels) above which a triangle goes to the cooperative path
@@ -170,11 +171,11 @@ __global__ __launch_bounds__(256) void interpolate_kernel(const float* attr, int
     const int id = (int)r.w - 1;
     float* o = out + (long)C * i;
     if (id < 0) { for (int c = 0; c < C; ++c) o[c] = 0.f; return; }
-    const float u = r.x, v = r.y, w = (1.0f - u) - v;
+    const float u = r.x, v = r.y, w = sd_bary_w(u, v);
     const float* a0 = attr + (long)C * tri[3 * id + 0];
     const float* a1 = attr + (long)C * tri[3 * id + 1];
     const float* a2 = attr + (long)C * tri[3 * id + 2];
-    for (int c = 0; c < C; ++c) o[c] = (a0[c] * u + a1[c] * v) + a2[c] * w;
+    for (int c = 0; c < C; ++c) o[c] = sd_interp1(a0[c], a1[c], a2[c], u, v, w);
 }
 
 extern "C" int utx_launch_interpolate(const float* attr, int C, const float* rast, const int* tri, long npix, float* out,
@@ -219,16 +220,16 @@ __global__ __launch_bounds__(256) void condition_shade_kernel(const float4* rast
     if (i >= npix) return;
     const float a = rast[i].w > 0.f ? 1.0f : 0.0f;
     float n[3] = {nrm[3 * i], nrm[3 * i + 1], nrm[3 * i + 2]};
-    float len = sqrtf((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
-    if (len < 1e-12f) len = 1e-12f;
+    float len = sd_length3(n);
+    if (len < 1e-12f) len = 1e-12f;      // not sd_normalize3: this floor is a compare, which leaves a NaN length NaN where fmaxf would return the floor
     const float bg[3] = {bg0, bg1, bg2};
     for (int c = 0; c < 3; ++c) {
         const float nv = a > 0.f ? n[c] / len : -1.0f;
         const float pv = a > 0.f ? pos[3 * i + c] : -1.0f;
         const float ni = (nv * 0.5f + 0.5f) * a + bg[c] * (1.0f - a);
         const float pi = (pv * 0.5f + 0.5f) * a + bg[c] * (1.0f - a);
-        out_normal[3 * i + c] = (unsigned char)(fminf(fmaxf(ni, 0.f), 1.f) * 255.0f);
-        out_ccm[3 * i + c] = (unsigned char)(fminf(fmaxf(pi, 0.f), 1.f) * 255.0f);
+        out_normal[3 * i + c] = sd_to_u8(ni);
+        out_ccm[3 * i + c] = sd_to_u8(pi);
     }
     out_alpha[i] = (unsigned char)(a * 255.0f);
 }
@@ -245,41 +246,21 @@ extern "C" int utx_launch_condition_shade(const float* rast, const float* nrm, c
 // render/nvdiffrast/renderer_base.py:289-336): per pixel, interpolate the vertex UVs with the raster barycentrics,
 // fetch the base-colour map bilinearly (dr.texture filter 'linear', wrap addressing, texel centres at +0.5), composite
 // over the background with the coverage mask and convert to uint8 by truncation (clamp * 255 -> astype(uint8)).
-// tex is [Ht][Wt][3] fp32 in UV-raster orientation (row index grows with v).
-__device__ __forceinline__ int wrapi(int i, int n) { i %= n; return i < 0 ? i + n : i; }
-
+// tex is [Ht][Wt][3] fp32 in UV-raster orientation (row index grows with v).  Interpolation and fetch are shade_device.h's.
 __global__ __launch_bounds__(256) void texture_shade_kernel(const float4* rast, const float* uv, const int* tri, const float* tex, int Ht,
                                                             int Wt, float bg0, float bg1, float bg2, long npix, unsigned char* out) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= npix) return;
     const float4 r = rast[i];
     const int id = (int)r.w - 1;
-    const float bg[3] = {bg0, bg1, bg2};
     float c[3] = {bg0, bg1, bg2};
     if (id >= 0) {
-        const float u = r.x, v = r.y, w = (1.0f - u) - v;
-        const float* a0 = uv + 2 * (long)tri[3 * id + 0];
-        const float* a1 = uv + 2 * (long)tri[3 * id + 1];
-        const float* a2 = uv + 2 * (long)tri[3 * id + 2];
-        const float tu = (a0[0] * u + a1[0] * v) + a2[0] * w;
-        const float tv = (a0[1] * u + a1[1] * v) + a2[1] * w;
-        const float x = tu * (float)Wt - 0.5f, y = tv * (float)Ht - 0.5f;
-        const float x0 = floorf(x), y0 = floorf(y);
-        const float fx = x - x0, fy = y - y0;
-        const int ix0 = wrapi((int)x0, Wt), ix1 = wrapi((int)x0 + 1, Wt);
-        const int iy0 = wrapi((int)y0, Ht), iy1 = wrapi((int)y0 + 1, Ht);
-        const float* t00 = tex + 3 * ((long)iy0 * Wt + ix0);
-        const float* t01 = tex + 3 * ((long)iy0 * Wt + ix1);
-        const float* t10 = tex + 3 * ((long)iy1 * Wt + ix0);
-        const float* t11 = tex + 3 * ((long)iy1 * Wt + ix1);
-        for (int k = 0; k < 3; ++k) {
-            const float top = t00[k] * (1.0f - fx) + t01[k] * fx;
-            const float bot = t10[k] * (1.0f - fx) + t11[k] * fx;
-            c[k] = top * (1.0f - fy) + bot * fy;
-        }
+        const float u = r.x, v = r.y, w = sd_bary_w(u, v);
+        float t[2];
+        sd_interp<2>(uv + 2 * (long)tri[3 * id + 0], uv + 2 * (long)tri[3 * id + 1], uv + 2 * (long)tri[3 * id + 2], u, v, w, t);
+        sd_tex3_wrap(tex, Ht, Wt, t[0], t[1], c);
     }
-    (void)bg;
-    for (int k = 0; k < 3; ++k) out[3 * i + k] = (unsigned char)(fminf(fmaxf(c[k], 0.f), 1.f) * 255.0f);
+    for (int k = 0; k < 3; ++k) out[3 * i + k] = sd_to_u8(c[k]);
 }
 
 extern "C" int utx_launch_texture_shade(const float* rast, const float* uv, const int* tri, const float* tex, int Ht, int Wt,
@@ -287,164 +268,6 @@ extern "C" int utx_launch_texture_shade(const float* rast, const float* uv, cons
     if (npix <= 0 || Ht <= 0 || Wt <= 0 || !bg3_host) return -2;
     hipLaunchKernelGGL(texture_shade_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, (const float4*)rast, uv, tri, tex,
                        Ht, Wt, bg3_host[0], bg3_host[1], bg3_host[2], npix, (unsigned char*)out);
-    return hipGetLastError() == hipSuccess ? 0 : -4;
-}
-
-// ---- geometry-buffer shading of the orbit video (VideoExporter.export_orbit_video(video_type=...) -> export_video,
-// video/export_nvdiffrast_video.py:37-139, on simple_rendering, render/nvdiffrast/renderer_base.py:153-241, with alpha = coverage):
-// one thread per pixel interpolates the triangle's three vertex attributes exactly as interpolate_kernel does (same operations, same
-// order: the value is bit-identical to utx_interpolate's), then, per MODE,
-//   NORMAL    v = n / max(sqrt((nx*nx + ny*ny) + nz*nz), 1e-12), background -1   (world_normal :160-166; camera_normal :168-176 with the
-//             per-view, per-vertex re-normalised camera_normals_kernel output as attribute)
-//   POSITION  v = p, background -1 (world_position :178-188) or 0 (camera_position :228-235: `fill`)
-//   DEPTH     v = the one interpolated channel (clip w), background 0, repeated to three (z_depth :153-158, export_video :107-108)
-//   DISTANCE  v = sqrt((px*px + py*py) + pz*pz) of the interpolated camera-space position, background 0, repeated (:236-241)
-// then export_video :120-131 in its order: covered pixels (v - lo) / (hi - lo) if scale2 = {lo, hi} is given; v * 0.5 + 0.5 if ndc;
-// v * alpha + bg * (1 - alpha) if composite; RGBA float frame (alpha fourth) and clamp(0, 1) * 255 truncated to uint8.
-// torch.lerp(fill, v, alpha) with alpha in {0, 1} returns v or fill exactly, so it is a select here.
-enum { GB_NORMAL = 0, GB_POSITION = 1, GB_DEPTH = 2, GB_DISTANCE = 3 };
-
-// gb_scalar / gb_dot3 (each product a scalar of its own: no cross-half packed pair in this file's listing), the interpolation and the normalisation
-// live in gbuffer_device.h, which the atlas-space buffers (uv_gbuffer.hip) share.
-
-template <int MODE>
-__device__ __forceinline__ bool gbuffer_value(const float4 r, const int* tri, const float* attr, int stride, float fill, float v3[3]) {
-    const int id = (int)r.w - 1;
-    if (id < 0) { v3[0] = v3[1] = v3[2] = fill; return false; }
-    const float u = r.x, v = r.y, w = (1.0f - u) - v;
-    const float* a0 = attr + (long)stride * tri[3 * id + 0];
-    const float* a1 = attr + (long)stride * tri[3 * id + 1];
-    const float* a2 = attr + (long)stride * tri[3 * id + 2];
-    if constexpr (MODE == GB_DEPTH) {
-        v3[0] = v3[1] = v3[2] = gb_dot3(a0[0], u, a1[0], v, a2[0], w);
-    } else {
-        float p[3];
-        gb_interp3(a0, a1, a2, u, v, w, p);
-        if constexpr (MODE == GB_NORMAL) {
-            gb_normalize3(p, gb_length3(p), v3);
-        } else if constexpr (MODE == GB_DISTANCE) {
-            v3[0] = v3[1] = v3[2] = gb_length3(p);
-        } else {
-            v3[0] = p[0]; v3[1] = p[1]; v3[2] = p[2];
-        }
-    }
-    return true;
-}
-
-template <int MODE>
-__global__ __launch_bounds__(256) void gbuffer_shade_kernel(const float4* rast, const int* tri, const float* attr, int stride, float fill,
-                                                            const float* scale2, int ndc, int composite, float bg0, float bg1, float bg2,
-                                                            long npix, unsigned char* out_u8, float4* out_rgba) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npix) return;
-    float c[3];
-    const bool covered = gbuffer_value<MODE>(rast[i], tri, attr, stride, fill, c);
-    const float a = covered ? 1.0f : 0.0f;
-    if (scale2 && covered) {
-        const float lo = scale2[0], hi = scale2[1];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) c[k] = (c[k] - lo) / (hi - lo);
-    }
-    const float bg[3] = {bg0, bg1, bg2};
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        if (ndc) c[k] = c[k] * 0.5f + 0.5f;
-        if (composite) c[k] = gb_scalar(c[k] * a) + gb_scalar(bg[k] * (1.0f - a));
-        out_u8[3 * i + k] = (unsigned char)(fminf(fmaxf(c[k], 0.f), 1.f) * 255.0f);
-    }
-    if (out_rgba) out_rgba[i] = make_float4(c[0], c[1], c[2], a);
-}
-
-// mode of the ABI (unitex_hip.h UTX_GBUF_*) -> kernel arm, background fill of the buffer, vertex stride is the caller's
-extern "C" int utx_launch_gbuffer_shade(int mode, const float* rast, const int* tri, const float* attr, int stride, const float* scale2,
-                                        int ndc, int composite, const float* bg3_host, long npix, void* out_u8, float* out_rgba,
-                                        hipStream_t stream) {
-    if (npix <= 0 || stride <= 0 || !bg3_host) return -2;
-    const dim3 g((unsigned)((npix + 255) / 256)), b(256);
-#define GB_LAUNCH(M, FILL) hipLaunchKernelGGL(gbuffer_shade_kernel<M>, g, b, 0, stream, (const float4*)rast, tri, attr, stride, FILL, scale2, \
-                                              ndc, composite, bg3_host[0], bg3_host[1], bg3_host[2], npix, (unsigned char*)out_u8, (float4*)out_rgba)
-    switch (mode) {
-        case 0: case 1: GB_LAUNCH(GB_NORMAL, -1.0f); break;     // world_normal, camera_normal
-        case 2: GB_LAUNCH(GB_POSITION, -1.0f); break;           // world_position
-        case 3: GB_LAUNCH(GB_POSITION, 0.0f); break;            // camera_position
-        case 4: GB_LAUNCH(GB_DEPTH, 0.0f); break;               // z_depth
-        case 5: GB_LAUNCH(GB_DISTANCE, 0.0f); break;            // distance
-        default: return -2;
-    }
-#undef GB_LAUNCH
-    return hipGetLastError() == hipSuccess ? 0 : -4;
-}
-
-// (lo, hi) of the buffer over the covered pixels of one frame (export_video :120-125 rgb_sel.min() / .max(), taken on the first frame only):
-// per-wave shuffle reduction, one atomic pair per wave.  Floats are ordered through their bit patterns (non-negative: as signed ints,
-// negative: reversed as unsigned), so the result is the exact min / max whatever the order.  empty stays 1 if no pixel is covered.
-__global__ void gbuffer_range_init_kernel(float* scale2, int* empty) {
-    scale2[0] = __int_as_float(0x7f800000); scale2[1] = __int_as_float(0xff800000); *empty = 1;
-}
-
-__device__ __forceinline__ void atomic_min_float(float* addr, float v) {
-    if (v >= 0.f) atomicMin((int*)addr, __float_as_int(v)); else atomicMax((unsigned int*)addr, __float_as_uint(v));
-}
-__device__ __forceinline__ void atomic_max_float(float* addr, float v) {
-    if (v >= 0.f) atomicMax((int*)addr, __float_as_int(v)); else atomicMin((unsigned int*)addr, __float_as_uint(v));
-}
-
-template <int MODE>
-__global__ __launch_bounds__(256) void gbuffer_range_kernel(const float4* rast, const int* tri, const float* attr, int stride, long npix,
-                                                            float* scale2, int* empty) {
-    float lo = __int_as_float(0x7f800000), hi = __int_as_float(0xff800000);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < npix; i += (long)gridDim.x * blockDim.x) {
-        float c[3];
-        if (gbuffer_value<MODE>(rast[i], tri, attr, stride, 0.f, c))
-            for (int k = 0; k < 3; ++k) { lo = fminf(lo, c[k]); hi = fmaxf(hi, c[k]); }
-    }
-    for (int off = warpSize / 2; off > 0; off >>= 1) {
-        lo = fminf(lo, __shfl_down(lo, off));
-        hi = fmaxf(hi, __shfl_down(hi, off));
-    }
-    if ((threadIdx.x & (warpSize - 1)) == 0 && lo <= hi) {
-        atomic_min_float(scale2, lo + 0.0f);      // + 0.0f canonicalises -0
-        atomic_max_float(scale2 + 1, hi + 0.0f);
-        atomicAnd(empty, 0);
-    }
-}
-
-extern "C" int utx_launch_gbuffer_range(int mode, const float* rast, const int* tri, const float* attr, int stride, long npix, float* scale2,
-                                        int* empty, hipStream_t stream) {
-    if (npix <= 0 || stride <= 0) return -2;
-    long nb = (npix + 255) / 256; if (nb > 1024) nb = 1024;
-    const dim3 g((unsigned)nb), b(256);
-    hipLaunchKernelGGL(gbuffer_range_init_kernel, dim3(1), dim3(1), 0, stream, scale2, empty);
-#define GB_RANGE(M) hipLaunchKernelGGL(gbuffer_range_kernel<M>, g, b, 0, stream, (const float4*)rast, tri, attr, stride, npix, scale2, empty)
-    switch (mode) {
-        case 0: case 1: GB_RANGE(GB_NORMAL); break;
-        case 2: case 3: GB_RANGE(GB_POSITION); break;
-        case 4: GB_RANGE(GB_DEPTH); break;
-        case 5: GB_RANGE(GB_DISTANCE); break;
-        default: return -2;
-    }
-#undef GB_RANGE
-    return hipGetLastError() == hipSuccess ? 0 : -4;
-}
-
-// per-view, per-vertex camera-space normals of render_camera_normal (renderer_base.py:169-170): out[n][v] = normalize(nrm[v] @ c2ws[n][:3,:3]),
-// out_j = (n0*R0j + n1*R1j) + n2*R2j, F.normalize eps 1e-12
-__global__ __launch_bounds__(256) void camera_normals_kernel(const float* nrm, int V, const float* c2ws, float* out) {
-    const int v = blockIdx.x * blockDim.x + threadIdx.x;
-    if (v >= V) return;
-    const float* m = c2ws + 16 * blockIdx.y;
-    const float x = nrm[3 * v], y = nrm[3 * v + 1], z = nrm[3 * v + 2];
-    float c[3];
-#pragma unroll
-    for (int j = 0; j < 3; ++j) c[j] = gb_dot3(x, m[j], y, m[4 + j], z, m[8 + j]);
-    const float len = fmaxf(sqrtf(gb_dot3(c[0], c[0], c[1], c[1], c[2], c[2])), 1e-12f);
-    float* o = out + 3 * ((long)blockIdx.y * V + v);
-    o[0] = c[0] / len; o[1] = c[1] / len; o[2] = c[2] / len;
-}
-
-extern "C" int utx_launch_camera_normals(const float* nrm, int V, const float* c2ws, int n_views, float* out, hipStream_t stream) {
-    if (V <= 0 || n_views <= 0) return -2;
-    hipLaunchKernelGGL(camera_normals_kernel, dim3((V + 255) / 256, n_views), dim3(256), 0, stream, nrm, V, c2ws, out);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
@@ -459,9 +282,9 @@ __global__ __launch_bounds__(256) void face_normals_kernel(const float* verts, c
     const float a0 = v1[0] - v0[0], a1 = v1[1] - v0[1], a2 = v1[2] - v0[2];
     const float b0 = v2[0] - v0[0], b1 = v2[1] - v0[1], b2 = v2[2] - v0[2];
     const float c0 = a1 * b2 - a2 * b1, c1 = a2 * b0 - a0 * b2, c2 = a0 * b1 - a1 * b0;
-    float n = sqrtf((c0 * c0 + c1 * c1) + c2 * c2);
-    n = fmaxf(n, 1e-12f);
-    out[3 * f + 0] = c0 / n; out[3 * f + 1] = c1 / n; out[3 * f + 2] = c2 / n;
+    float c[3] = {c0, c1, c2};
+    sd_normalize3(c);
+    out[3 * f + 0] = c[0]; out[3 * f + 1] = c[1]; out[3 * f + 2] = c[2];
 }
 
 extern "C" int utx_launch_face_normals(const float* verts, const int* faces, int F, float* out, hipStream_t stream) {
@@ -500,14 +323,14 @@ __global__ __launch_bounds__(256) void mv_grad_kernel(const float* attr, const f
     float dp[3];
     if constexpr (PERSP) {
         const float* e = eyes + 3 * v;
-        const float dx = attr[6 * i] - e[0], dy = attr[6 * i + 1] - e[1], dz = attr[6 * i + 2] - e[2];
-        const float dl = fmaxf(sqrtf((dx * dx + dy * dy) + dz * dz), 1e-12f);
-        dp[0] = dx / dl; dp[1] = dy / dl; dp[2] = dz / dl;
+        dp[0] = attr[6 * i] - e[0]; dp[1] = attr[6 * i + 1] - e[1]; dp[2] = attr[6 * i + 2] - e[2];
+        sd_normalize3(dp);
     }
     const float* d = PERSP ? dp : dirs + 3 * v;
-    const float nd = fmaxf(sqrtf((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]), 1e-8f);
-    const float nn = fmaxf(sqrtf((fn[0] * fn[0] + fn[1] * fn[1]) + fn[2] * fn[2]), 1e-8f);
-    const float cs = ((d[0] * fn[0] + d[1] * fn[1]) + d[2] * fn[2]) / (nd * nn);
+    // the cosine floors each length at 1e-8, not at F.normalize's 1e-12: kept apart from sd_normalize3
+    const float nd = fmaxf(sd_length3(d), 1e-8f);
+    const float nn = fmaxf(sd_length3(fn), 1e-8f);
+    const float cs = sd_dot3(d, fn) / (nd * nn);
     facing[i] = (unsigned char)(cs < cos_thr);
 }
 __global__ __launch_bounds__(256) void mv_visible_kernel(const unsigned char* smooth, const unsigned char* facing, const float4* rast,
