@@ -44,7 +44,7 @@ const char* utx_last_error(utx_ctx* ctx);
  * tail-split switches (UTX_ATTN_TAILSPLIT, UTX_GEMM_TAILSPLIT, UTX_GEMM_STREAMK) change the fp32 summation order inside the tiles
  * they split -- the same result up to rounding, deterministic from launch to launch.  The first utx_init reads the environment
  * variables of the same names once; later changes go through utx_set_option only (no getenv on the launch path).  Names:
- * UTX_ATTN_GLDS, UTX_ATTN_FAST, UTX_ATTN_Q64, UTX_ATTN_TPB, UTX_ATTN_TAILSPLIT, UTX_GEMM_GROUP_M, UTX_GEMM_TILE, UTX_GEMM_TAILSPLIT,
+ * UTX_ATTN_Q64, UTX_ATTN_TAILSPLIT, UTX_GEMM_GROUP_M, UTX_GEMM_TILE, UTX_GEMM_TAILSPLIT,
  * UTX_GEMM_STREAMK, UTX_GEMM_PERS_GRID, UTX_GEMM_PERS_SCHED, UTX_BVH_STACK_WALK, UTX_BVH_PACKET, UTX_ATTN_PEEL, UTX_ATTN8_PEEL, UTX_NN_GRID.  UTX_ATTN_Q64 (default 1: the
  * 4 x 64 attention kernel for the launches it takes) keeps the bits wherever the 8 x 32 kernel does not re-centre its running maximum behind the first 32 keys; where it does, the two
  * kernels return two roundings of the same softmax.  The timing-ablation switches that compute wrong

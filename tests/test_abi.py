@@ -52,7 +52,13 @@ def test_product_library_has_no_wrong_result_switches():
     # sees exactly the options it can read -- a name missing here would be a switch tests could leak unnoticed
     import re
     table = re.findall(r'\{"(UTX_[A-Z0-9_]+)",\s*&UtxOptions::\w+,\s*(true|false)\}', open(os.path.join(ROOT, "unitex_amd", "csrc", "capi.cpp")).read())
-    assert len(table) >= 20 and {n for n, abl in table if abl == "false"} == set(_lib.OPTION_NAMES), sorted({n for n, abl in table if abl == "false"} ^ set(_lib.OPTION_NAMES))
+    assert len(_lib.OPTION_NAMES) == 14 and len(set(_lib.OPTION_NAMES)) == 14
+    assert len(table) == len(_lib.OPTION_NAMES) + 3 and {n for n, abl in table if abl == "false"} == set(_lib.OPTION_NAMES), sorted({n for n, abl in table if abl == "false"} ^ set(_lib.OPTION_NAMES))
+    # retired with the register-staged kernel and the two-tile ring: unknown names now
+    for n in ("UTX_ATTN_GLDS", "UTX_ATTN_FAST", "UTX_ATTN_TPB"):
+        v = C.c_int()
+        assert lib.utx_set_option(n.encode(), 1) == -2
+        assert lib.utx_get_option(n.encode(), C.byref(v)) == -2
     _lib.set_option("UTX_GEMM_TILE", 128)
     assert _lib.get_options()["UTX_GEMM_TILE"] == 128
     _lib.set_option("UTX_GEMM_TILE", 0)

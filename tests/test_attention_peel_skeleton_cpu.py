@@ -29,20 +29,18 @@ typedef std::vector<std::tuple<int, int, int, int>> Ev;
 #define AG_KVB 64
 constexpr int ABL = 0;      // the kernel's timing-ablation bits (ablation build only)
 #define AG_STAGE(t_, slot_) ev.push_back({0, (int)(t_), (int)(slot_), 0})
-#define AG_TILE_BODY { ev.push_back({1, t, gs + sub, 1}); }
+#define AG_TILE_BODY { ev.push_back({1, t, gs, 1}); }
 #define __syncthreads() ev.push_back({2, 0, 0, 0})
 #define AG_BARRIER() __syncthreads()
 #define AG_FAST_A(KB_) ev.push_back({3, u, gs, (int)(KB_)});
 #define AG_FAST_B(PF_) ev.push_back({4, u + 1, gs ^ 1, (PF_)});
 #define AG_LOAD_KFA(slot_) ev.push_back({5, -1, (int)(slot_), 0});
-template <bool FAST, int TPB, bool KBP = false>
+template <bool FAST, bool KBP = false>
 static Ev run(int Sk, P p) {
     const int tb = 0;      // first tile of this workgroup's key range (a key-split tail workgroup starts further in)
     Ev ev;
     const int nt = (Sk + AG_KVB - 1) / AG_KVB;
-    const int ngrp = (nt + TPB - 1) / TPB;
-    for (int i = 0; i < TPB; ++i)
-        if (i < nt) AG_STAGE(i, i);
+    if (0 < nt) AG_STAGE(0, 0);
     __syncthreads();
 %s
     return ev;
@@ -88,10 +86,10 @@ int main() {
     for (int Sk = 1; Sk <= 64 * 9; Sk += (Sk %% 64 == 0 ? 1 : 21)) {
         P p = {per ? 3.0f : (Sk %% 2 ? 0.0f : 3.0f), per};
         const bool general_everywhere = per && p.key_bias_log2 != 0.f;
-        Ev g = run<false, 1>(Sk, p);
+        Ev g = run<false>(Sk, p);
         discipline(g, Sk, 0, true);
         // the launcher: periodic key multiplicity -> the KBP instance of the fast kernel (key-multiplicity tiles through their own copy of the fast tile), else the plain one
-        Ev v = general_everywhere ? run<true, 1, true>(Sk, p) : run<true, 1, false>(Sk, p);
+        Ev v = general_everywhere ? run<true, true>(Sk, p) : run<true, false>(Sk, p);
         ++checked;
         discipline(v, Sk, 1, false, general_everywhere ? p.key_bias_period : 0);
     }
@@ -103,8 +101,8 @@ int main() {
 
 def _loop_source():
     lines = open(SRC).read().split("\n")
-    start = next(i for i, l in enumerate(lines) if l.lstrip().startswith("if (FAST && TPB == 1) {"))
-    end = next(i for i, l in enumerate(lines) if "this group fully read by every wave" in l)
+    start = next(i for i, l in enumerate(lines) if l.lstrip().startswith("if (FAST) {"))
+    end = next(i for i, l in enumerate(lines) if "this tile fully read by every wave" in l)
     assert 0 < start < end and lines[end + 1].strip() == "}", "the loop block of attention_glds.hip moved: update this test's markers"
     block = [l for l in lines[start:end + 2] if not l.lstrip().startswith("#pragma")]
     assert any("AG_FAST_A" in l for l in block) and any("AG_FAST_B(1)" in l for l in block)

@@ -491,6 +491,33 @@ def test_attention_on_block_strided_operands_equals_the_contiguous_call(P, H, S_
                                          None, 0, bad_rows, bs, bs, bs, ctx.stream()) != 0
 
 
+def test_attention_on_block_strided_operands_with_softmax_scale_matches_oracle():
+    """the block-strided instance with softmax_scale > 0 (Q not pre-scaled): no other test launches it.  H = 2, S = 320 in five blocks of one 64-key tile (tile 0, one
+    pair, an odd remainder; a block boundary behind every tile) against the oracle, with test_attention_matches_oracle's tolerance for this mode.  (Blocks are whole
+    tiles, so there is no ragged form of this launch.)"""
+    import ctypes as C
+    ops = _ops()
+    ctx = ops.get_ctx(0)
+    H, S, S_loc = 2, 320, 64
+    P, E = S // S_loc, S_loc * 128
+    q, k, v = _mk_attn_inputs(H, S, seed=S + H, spike=True)
+    ref = dit_ref.sdpa(q.float(), k.float(), v.float(), em=False)
+    buf = torch.empty(P, 3, H, E, dtype=BF, device="cuda")
+    buf[:, 0] = q.cuda().view(H, P, E).transpose(0, 1)
+    buf[:, 1] = k.cuda().view(H, P, E).transpose(0, 1)
+    buf[:, 2] = v.cuda().transpose(1, 2).contiguous().view(H, 128, P, S_loc).permute(2, 0, 1, 3).reshape(P, H, E)
+    out = torch.empty(S, H * 128, dtype=BF, device="cuda")
+    bs = 3 * H * E
+    rc = ctx.lib.utx_attn_fwd_bf16_blk(ctx.handle, C.c_void_p(buf[0, 0].data_ptr()), C.c_void_p(buf[0, 1].data_ptr()), C.c_void_p(buf[0, 2].data_ptr()),
+                                       C.c_void_p(out.data_ptr()), E, 128, E, 128, E, S_loc, out.stride(0), H, S, S, 1.0 / math.sqrt(128.0), 0.0, 0,
+                                       None, 0, S_loc, bs, bs, bs, ctx.stream())
+    assert rc == 0
+    torch.cuda.synchronize()
+    got = out.float().cpu().view(S, H, 128).permute(1, 0, 2)
+    err = (got - ref).abs().max().item()
+    assert torch.isfinite(got).all() and err < 3e-2, "block-strided attention with softmax_scale: max-abs err %g" % err
+
+
 @pytest.mark.parametrize("zero_copy", [False, True])
 def test_sequence_parallel_world1_through_rccl_collectives(monkeypatch, zero_copy):
     """RCCL on a one-GPU box: with UTX_SP_FORCE_A2A=1 a 1-rank NCCL group still issues every collective of the sequence-parallel plan -- per layer and

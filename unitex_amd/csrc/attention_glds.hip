@@ -1,17 +1,19 @@
-// bf16 MFMA flash-attention forward, LDS-DMA staged variant (gfx950).  Same contract, maths and block-pipelined
-// sum-checked softmax as attn_fwd_kernel<8, PRESC, 2> in attention.hip (see the header there); what differs is how the
-// K / Vt tiles reach LDS:
-//   attention.hip      global_load -> 8 staging VGPRs x 4 -> ds_write_b128 (padded rows, immediate fragment offsets)
-//   this file          global_load_lds (16 B / lane, no VGPRs, no ds_write): the LDS image of a wave-instruction is
-//                      lane-linear (1 KB = 4 K rows or 8 Vt rows), so rows cannot be padded; bank conflicts are
-//                      removed by an XOR swizzle applied on the SOURCE address (which 16-byte chunk a lane fetches)
-//                      and on the fragment read address:
-//                          K  tile [64 keys][256 B] : slot = chunk ^ (row & 15)
-//                          Vt tile [128 d ][128 B]  : slot = chunk ^ ((row >> 1) & 7)
-//                      both conflict-free for the ds_read_b128 lane groups {0-3,12-15,20-27} / {4-11,16-19,28-31}.
-// Why: round-1 ablation (profiles/r01_perf_attn_ablation.log) charges 2.9 of 27.8 ms per launch at S = 50 688 to the
-// register staging (a ds_write_b128 costs ~13 LDS cycles per wave-instruction, 4 per lane and tile) -- the kernel is
-// power/clock limited, so fewer instructions and less register traffic per tile is the lever that is left.
+// bf16 MFMA flash-attention forward, the 8 x 32 kernel (gfx950): 8 waves x 32 queries per workgroup, 64-key tiles staged by LDS-DMA.  The contract, the layouts and the
+// maths every attention kernel shares (swapped K Q^T with the kappa key permutation, the -m_run accumulator block, sum-checked softmax, defer-max) are in attention.hip's
+// header.  This file's own contract:
+//   * Q, K, V^T bases 16-byte aligned, rows of whole 16-byte chunks; K rows / V^T columns readable up to the next multiple of 64 past S.
+//   * softmax_scale > 0 (PRESC = 0) or Q pre-scaled by scale * log2(e) (PRESC = 1); Sq queries over S keys in either order of size; key multiplicity of tile 0 or of every
+//     key_bias_period-th tile; a key-split tail round with caller scratch; BLK: operands in blocks of blk_rows tokens; p.flags: the repair pass of the 4 x 64 kernel.
+//   * a tile is two 32-key blocks software-pipelined inside one wave: S0 QK(0) | S1 QK(1) || exp(0) | S2 PV(0) || exp(1) | S3 PV(1); a block whose lane row sum passes 2^13
+//     is redone against its true maximum (AG_SLOW) before anything of it was accumulated.
+//   * instances: the general loop (any tile may be first, ragged or a key-multiplicity tile), FAST and FAST + KBP (below), all bit-identical to each other.
+// Staging: global_load_lds (16 B / lane, no VGPRs, no ds_write).  The LDS image of a wave-instruction is lane-linear (1 KB = 4 K rows or 8 Vt rows), so rows cannot be
+// padded; bank conflicts are removed by an XOR swizzle applied on the SOURCE address (which 16-byte chunk a lane fetches) and on the fragment read address:
+//     K  tile [64 keys][256 B] : slot = chunk ^ (row & 15)
+//     Vt tile [128 d ][128 B]  : slot = chunk ^ ((row >> 1) & 7)
+// both conflict-free for the ds_read_b128 lane groups {0-3,12-15,20-27} / {4-11,16-19,28-31}.
+// Why LDS-DMA: round-1 ablation (profiles/r01_perf_attn_ablation.log) charged 2.9 of 27.8 ms per launch at S = 50 688 to staging through registers (a ds_write_b128 costs
+// ~13 LDS cycles per wave-instruction, 4 per lane and tile) -- the kernel is power/clock limited, so fewer instructions and less register traffic per tile is the lever that is left.
 // Ring: K and Vt 2-deep (64 KB); tile t+1 is requested at the top of tile t into the slot last read in tile t-1 (free
 // since the barrier that ended it) and retired by the explicit vmcnt(0) in front of that barrier (AG_BARRIER below).
 #include "common.h"
@@ -22,11 +24,11 @@
 #define AG_KVB 64
 #define AG_KTILE 16384
 #define AG_VTILE 16384
-#define AG_LDS(tpb) ((tpb) * 2 * (AG_KTILE + AG_VTILE))
+#define AG_LDS (2 * (AG_KTILE + AG_VTILE))      // K ring | V^T ring, two tiles each
 
 // The barrier that publishes a DMA'd tile: this wave's LDS-DMAs retire through vmcnt, and the wait for them must be WRITTEN -- hipcc does not owe a global_load_lds a
 // `vmcnt(0)` at __syncthreads() (cdna_hip_programming.md 5.7: "LDS-DMA data needs your own vmcnt(N), then a barrier, then the ds_read").  Until round 5 this file relied on
-// the `s_waitcnt vmcnt(0) lgkmcnt(0)` hipcc happened to emit at the fence; built with -mllvm -amdgpu-sched-strategy=max-memory-clause the first barrier of the two-tile loop
+// the `s_waitcnt vmcnt(0) lgkmcnt(0)` hipcc happened to emit at the fence; built with -mllvm -amdgpu-sched-strategy=max-memory-clause the first barrier of the then two-tile-per-barrier loop
 // came out with `lgkmcnt(0)` only and the fast loop returned run-to-run different results at full occupancy (profiles/r05_attn_lib_compare.log).  With the default
 // strategy the explicit wait is redundant (the listing shows both); tests/test_asm_hazards_cpu.py now requires a vmcnt(0) in front of every such barrier.
 #define AG_BARRIER() do { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); __syncthreads(); } while (0)
@@ -50,11 +52,11 @@ __device__ __forceinline__ float ag_mul_nofuse(float a, float b) {
 // instead of behind a relayout pass.  Token j = block j / blk_rows, row j % blk_rows; inside a block rows are q_ss / k_ss apart and V^T rows vt_ds (= blk_rows for
 // the exchange buffer).  The staging cursor below walks tiles in order, so the block term is two scalar adds per tile; same tiles, same order, same arithmetic
 // as the contiguous form: bit-identical results.
-template <int PRESC, int TPB, bool BLK = false, bool FAST = false, bool KBP = false>
+template <int PRESC, bool BLK = false, bool FAST = false, bool KBP = false>
 __global__ __launch_bounds__(512, 2) void attn_fwd_glds_kernel(AttnParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* const kring = smem;
-    char* const vring = smem + 2 * TPB * AG_KTILE;    // ring: 2 groups of TPB tiles, one barrier per group
+    char* const vring = smem + 2 * AG_KTILE;          // ring: 2 tiles, one barrier per tile
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -150,10 +152,7 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_glds_kernel(AttnParams p) {
     for (int r = 0; r < 16; ++r) negm[r] = 0.f;
 
     const int nt = (Sk + AG_KVB - 1) / AG_KVB;
-    const int ngrp = (nt + TPB - 1) / TPB;
-#pragma unroll
-    for (int i = 0; i < TPB; ++i)
-        if (i < nt) AG_STAGE(i, i);
+    if (0 < nt) AG_STAGE(0, 0);
     AG_BARRIER();
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) asm volatile("" : "+v"(qf[kk]));
@@ -197,8 +196,8 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_glds_kernel(AttnParams p) {
         }
 #define AG_TILE_BODY                                                                            \
         {                                                                                            \
-        const char* kb = kring + (gs + sub) * AG_KTILE;                                              \
-        const char* vb = vring + (gs + sub) * AG_VTILE;                                              \
+        const char* kb = kring + gs * AG_KTILE;                                                      \
+        const char* vb = vring + gs * AG_VTILE;                                                      \
         const bool ragged = (t == nt - 1) && (Sk & (AG_KVB - 1));                                      \
         const int lim = Sk - t * AG_KVB - 8 * lh;                                                    \
         f32x16 sa0, sa1;                                                                             \
@@ -343,12 +342,12 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_glds_kernel(AttnParams p) {
         }                                                                                            \
         __builtin_amdgcn_s_setprio(0);                                                               \
         }
-    if (FAST && TPB == 1) {      // (the launcher sends launches with periodic key multiplicity to the KBP instance)
+    if (FAST) {      // (the launcher sends launches with periodic key multiplicity to the KBP instance)
         const bool rag_ = (Sk & (AG_KVB - 1)) != 0;
         const int fast_end_ = rag_ ? nt - 1 : nt;                 // tiles [1, fast_end_) take the fast form
         bf16x8 kfa_n[8], vfb_n[8];
         {
-            const int gs = 0, sub = 0, t = 0;                     // tile 0: the general body, barrier at its end
+            const int gs = 0, t = 0;                              // tile 0: the general body, barrier at its end
             if (1 < nt) AG_STAGE(1, 1);
             AG_TILE_BODY
             AG_BARRIER();
@@ -393,22 +392,16 @@ __global__ __launch_bounds__(512, 2) void attn_fwd_glds_kernel(AttnParams p) {
             if (uu < fast_end_) AG_FAST_TILE_(uu, 1, false)
         }
         if (rag_ && nt > 1) {
-            const int gs = (nt - 1) & 1, sub = 0, t = nt - 1;     // its tile was requested two tiles ago and retired by the last barrier above (or by tile 0's)
+            const int gs = (nt - 1) & 1, t = nt - 1;              // its tile was requested two tiles ago and retired by the last barrier above (or by tile 0's)
             AG_TILE_BODY
             AG_BARRIER();
         }
     } else
-    for (int u = 0; u < ngrp; ++u) {
-      const int gs = (u & 1) * TPB;                      // first ring slot of this group
-#pragma unroll
-      for (int i = 0; i < TPB; ++i)
-          if ((u + 1) * TPB + i < nt) AG_STAGE((u + 1) * TPB + i, (gs ^ TPB) + i);
-      for (int sub = 0; sub < TPB; ++sub) {
-        const int t = u * TPB + sub;
-        if (t >= nt) break;
+    for (int t = 0; t < nt; ++t) {      // the general loop: one tile per barrier
+        const int gs = t & 1;              // ring slot of this tile
+        if (t + 1 < nt) AG_STAGE(t + 1, gs ^ 1);
         AG_TILE_BODY
-      }
-      AG_BARRIER();     // this group fully read by every wave; the next group (DMA) retired by the vmcnt(0) of this fence
+        AG_BARRIER();     // this tile fully read by every wave; the next one (DMA) retired by the vmcnt(0) of this fence
     }
 
     // ---- epilogue: lane (q, h) holds O[q][32db + 8a + 4h + c], r = 4a + c -- 8 bytes of a row per (db, a), the other half-wave the neighbouring 8.
@@ -522,48 +515,50 @@ extern "C" int utx_launch_attn_merge(const AttnParams* t, int n_items, hipStream
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-template <int PRESC, int TPB, bool BLK = false, bool FAST = false, bool KBP = false>
+template <int PRESC, bool BLK = false, bool FAST = false, bool KBP = false>
 static int launch_glds(AttnParams p, hipStream_t stream) {
     UTX_ONCE_PER_DEVICE(attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_glds_kernel<PRESC, TPB, BLK, FAST, KBP>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, AG_LDS(TPB)) != hipSuccess) return -3;
+        if (hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_glds_kernel<PRESC, BLK, FAST, KBP>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, AG_LDS) != hipSuccess) return -3;
         UTX_ONCE_DONE(attr_set);
     }
     p.nqb = ((p.Sq > 0 ? p.Sq : p.S) + 255) / 256;
     p.w_base = 0; p.nsplit = 1; p.tiles_per_split = 0; p.part_o = nullptr; p.part_lse = nullptr;
     int pl[4] = {p.nqb * p.H, 0, 1, 0};
-    if (TPB == 1 && !p.flags) utx_attn_split_plan_impl(p.H, p.Sq, p.S, utx_ncu(), pl);
+    if (!p.flags) utx_attn_split_plan_impl(p.H, p.Sq, p.S, utx_ncu(), pl);
     const int nwg = pl[0], nfull = pl[1], ns = pl[2], tps = pl[3], r = nwg - nfull;
     // the scratch of the split is CALLER-OWNED (utx_attn_fwd_bf16_ws; the legacy entry points pass the context's own buffer, grown outside of any
     // capture): nothing is allocated here, a launch whose scratch is missing or too small runs unsplit -- same result up to one bf16 rounding of the
     // tail rows, a fraction of a round slower
     const size_t rows = (size_t)r * ns * 256;
     if (ns <= 1 || !p.work || p.work_bytes < rows * (128 * sizeof(bf16_t) + sizeof(float))) {
-        hipLaunchKernelGGL((attn_fwd_glds_kernel<PRESC, TPB, BLK, FAST, KBP>), dim3(nwg), dim3(512), AG_LDS(TPB), stream, p);
+        hipLaunchKernelGGL((attn_fwd_glds_kernel<PRESC, BLK, FAST, KBP>), dim3(nwg), dim3(512), AG_LDS, stream, p);
         return hipGetLastError() == hipSuccess ? 0 : -4;
     }
-    hipLaunchKernelGGL((attn_fwd_glds_kernel<PRESC, TPB, BLK, FAST, KBP>), dim3(nfull), dim3(512), AG_LDS(TPB), stream, p);
+    hipLaunchKernelGGL((attn_fwd_glds_kernel<PRESC, BLK, FAST, KBP>), dim3(nfull), dim3(512), AG_LDS, stream, p);
     AttnParams t = p;
     t.w_base = nfull; t.nsplit = ns; t.tiles_per_split = tps;
     t.part_o = (bf16_t*)p.work; t.part_lse = (float*)((char*)p.work + rows * 128 * sizeof(bf16_t));
-    hipLaunchKernelGGL((attn_fwd_glds_kernel<PRESC, TPB, BLK, FAST, KBP>), dim3(r * ns), dim3(512), AG_LDS(TPB), stream, t);
+    hipLaunchKernelGGL((attn_fwd_glds_kernel<PRESC, BLK, FAST, KBP>), dim3(r * ns), dim3(512), AG_LDS, stream, t);
     const long mt = (long)r * 256 * 16;
     hipLaunchKernelGGL(attn_merge_kernel, dim3((unsigned)((mt + 255) / 256)), dim3(256), 0, stream, t, r);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-// UTX_ATTN_TPB: tiles per barrier (ring = 2 groups of TPB tiles): 1 -> 64 KB LDS, 2 -> 128 KB
+// The 8 x 32 instance of a launch (utx_launch_attn_fwd_blk validates and asks the 4 x 64 kernel first; that kernel's repair pass comes here with p->flags set):
+//   block-strided operands                             BLK      (general loop)
+//   pre-scaled Q, UTX_ATTN_PEEL != 0, periodic keys    FAST+KBP (a loop nest: a second copy of the fast tile for the key-multiplicity tiles INSIDE the loop made hipcc spill in
+//                                                                it -- 45 scratch accesses per trip with one tile per trip, 293 with two)
+//   pre-scaled Q, UTX_ATTN_PEEL != 0                   FAST     (what the DiT runs)
+//   everything else                                    general  (softmax_scale > 0; UTX_ATTN_PEEL=0: the default until round 5, A/B and the reference bits of the stress tests)
 extern "C" int utx_launch_attn_fwd_glds(const AttnParams* p, int presc, hipStream_t stream) {
-    const int tpb = g_utx_opt.attn_tpb;
     if (p->blk_rows > 0) {      // block-strided operands (the sequence-parallel receive buffer): whole 64-key tiles per block, whole blocks per sequence
-        if (tpb != 1 || p->flags || (p->blk_rows % AG_KVB) || (p->S % p->blk_rows) || ((p->q_bs | p->k_bs | p->vt_bs) & 7)) return -2;
-        return presc ? launch_glds<1, 1, true>(*p, stream) : launch_glds<0, 1, true>(*p, stream);
+        if (p->flags || (p->blk_rows % AG_KVB) || (p->S % p->blk_rows) || ((p->q_bs | p->k_bs | p->vt_bs) & 7)) return -2;
+        return presc ? launch_glds<1, true>(*p, stream) : launch_glds<0, true>(*p, stream);
     }
-    if (tpb == 2) return presc ? launch_glds<1, 2>(*p, stream) : launch_glds<0, 2>(*p, stream);
-    // the pre-scaled form the DiT uses: the fast loop (FAST above); UTX_ATTN_PEEL=0: the general loop, the default until round 5 (A/B and the reference bits of the stress tests)
-    // launches whose key-multiplicity tiles recur (key_bias_period > 0: sequence parallelism): the KBP instance (a loop nest: a second copy of the fast tile for those tiles INSIDE the
-    // loop made hipcc spill in it -- 45 scratch accesses per trip with one tile per trip, 293 with two)
-    if (presc && g_utx_opt.attn_peel != 0 && (p->key_bias_period > 0 && p->key_bias_log2 != 0.f)) return launch_glds<1, 1, false, true, true>(*p, stream);
-    if (presc && g_utx_opt.attn_peel != 0) return launch_glds<1, 1, false, true>(*p, stream);
-    return presc ? launch_glds<1, 1>(*p, stream) : launch_glds<0, 1>(*p, stream);
+    if (presc && g_utx_opt.attn_peel != 0) {
+        const bool periodic = p->key_bias_period > 0 && p->key_bias_log2 != 0.f;
+        return periodic ? launch_glds<1, false, true, true>(*p, stream) : launch_glds<1, false, true>(*p, stream);
+    }
+    return presc ? launch_glds<1>(*p, stream) : launch_glds<0>(*p, stream);
 }

@@ -13,13 +13,11 @@
 #include "kernels.h"
 #include "common.h"
 
-UtxOptions g_utx_opt = {1, 2, 1, 1, 1, 0, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 1, 1, 1, 0};      // (the last two: gemm_fastk, nn_grid)
+UtxOptions g_utx_opt;      // defaults: the member initialisers in kernels.h
 
 struct OptName { const char* name; int UtxOptions::*field; bool ablation; };
 static const OptName kOptions[] = {
-    {"UTX_ATTN_GLDS", &UtxOptions::attn_glds, false},       {"UTX_ATTN_FAST", &UtxOptions::attn_fast, false},
-    {"UTX_ATTN_Q64", &UtxOptions::attn_q64, false},         {"UTX_ATTN_TPB", &UtxOptions::attn_tpb, false},
-    {"UTX_ATTN_TAILSPLIT", &UtxOptions::attn_tailsplit, false},
+    {"UTX_ATTN_Q64", &UtxOptions::attn_q64, false},         {"UTX_ATTN_TAILSPLIT", &UtxOptions::attn_tailsplit, false},
     {"UTX_GEMM_GROUP_M", &UtxOptions::gemm_group_m, false}, {"UTX_GEMM_TILE", &UtxOptions::gemm_tile, false},
     {"UTX_GEMM_TAILSPLIT", &UtxOptions::gemm_tailsplit, false}, {"UTX_GEMM_PERS_GRID", &UtxOptions::gemm_pers_grid, false},
     {"UTX_GEMM_PERS_SCHED", &UtxOptions::gemm_pers_sched, false}, {"UTX_GEMM_STREAMK", &UtxOptions::gemm_streamk, false},

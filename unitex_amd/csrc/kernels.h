@@ -17,7 +17,7 @@ struct AttnParams {
     long q_hs, q_ss, k_hs, k_ss, vt_hs, vt_ds, o_ss;  // element strides
     int H, S, nqb;
     int Sq;            // query rows (0 = S): attention_glds.hip only
-    int dbg;           // perf ablation only (UTX_ATTN_DEBUG bits): 1 no staging, 2 no exp, 4 no barrier, 8 no PV, 16 no QK
+    int dbg;           // perf ablation only (UTX_ATTN_DEBUG; always 0 in the product library).  Its bits switched phases of the register-staged kernel off; no remaining kernel reads it
     float scale_log2;  // softmax_scale * log2(e)
     unsigned char* flags;  // per (head, 64-query group) overflow marks: written by the 4 x 64 kernel, read by the repair pass (else null)
     int flag_hs;           // flags per head
@@ -59,28 +59,26 @@ struct Attn8Params {
 // the first utx_init (UTX_ATTN_*, UTX_GEMM_* variables of the same names), afterwards changed only through utx_set_option.
 // The three `*_abl` fields switch timing ablations that compute WRONG results; they exist only in the UTX_ABLATION build
 // (libunitex_hip_ablate.so, used by tools/ -- never by the product, the tests or bench.py).
+// A field's default is written beside it; g_utx_opt (capi.cpp) is default-initialised.
 struct UtxOptions {
-    int attn_glds;        // 1 (default): LDS-DMA staged attention kernel; 0: register-staged variants
-    int attn_fast;        // register-staged kernel only: 2 block-pipelined sum-checked softmax, 1 sum-checked, 0 per-tile max
-    int attn_q64;         // 1 (default since round 6): launches the 4 x 64 kernel takes (attention_q64.hip: pre-scaled Q, whole 64-key tiles, contiguous operands, caller scratch) run it
-                          // + its repair pass; 0: the 8 x 32 kernel everywhere (A/B; bit-identical wherever the 8 x 32 kernel does not re-centre behind the first block)
-    int attn_tpb;         // tiles per barrier of the LDS-DMA kernel (1 | 2)
-    int attn_tailsplit;   // 1 (default): key-split tail round
-    int gemm_group_m;     // 0 = built-in GROUP_M
-    int gemm_tile;        // 0 auto, 128, 256 (per-tile 8-phase), 2560 (persistent), 2562 (2-barrier 256^2), 2564 (one wave per SIMD)
-    int gemm_tailsplit;   // 1: K-split tail round of the 8-phase GEMM (off by default)
-    int gemm_pers_grid;   // persistent GEMM: number of workgroups (0 = one per CU)
-    int gemm_pers_sched;  // persistent GEMM: DMA placement over the phases of a K-tile: 0 = by shape, 1 = force SCHED 0, 2 = force SCHED 1
-    int gemm_streamk;     // 1 (default): one-wave-per-SIMD GEMM balances the K loops of its last, partly filled round over all CUs (needs utx_gemm_desc.sk_work)
-    int bvh_stack_walk;   // 1: the reference's stack walk over the unpacked tree instead of the stackless packed walk (A/B; same results)
-    int attn_var_abl, attn_debug_abl, gemm_debug_abl;
-    int bvh_packet;       // 1 (default): back-projection rays walk the tree as wave-wide packets over 8 x 8 texel tiles (bvh_trace_packet); 0: one thread per ray (A/B; same results)
-    int attn_peel;        // 1 (default since round 5): the pre-scaled LDS-DMA attention launch runs its fast loop (attention_glds.hip, FAST: first / ragged tile outside the loop, the tile's
-                          // barrier between S2 and S3, next tile's first K fragments read under S3); 0: the general loop (the default until round 4).  Same bits either way.
-    int attn8_peel;       // 1 (default since round 5): MX fp8 attention with tile 0 / a ragged last tile outside the loop and the loop's exponentials in quarters under the PV MFMAs
-                          // (attn_fwd_fp8_kernel<1>, attention_fp8.hip); 0: the general loop.  Same bits either way.
-    int gemm_fastk;       // one-wave-per-SIMD GEMM (bf16): 1 (default since round 6: +2.3 ... +3.7 % on the FLUX shapes, profiles/r06_gemm_fastk_check_v0.log) = the steady-state K loop runs the generated instruction stream (gemm_w4_loop_asm.inc), 0 = hipcc's loop (round 2-5).  Same bits.
-    int nn_grid;          // 0 (default): the NN fill's cell grid follows the atlas size; 64 | 128 | 256 force one (A/B and the grid-independence test; same results)
+    int attn_q64 = 1;         // 1 (default since round 6): launches the 4 x 64 kernel takes (attention_q64.hip: pre-scaled Q, whole 64-key tiles, contiguous operands, caller scratch) run it
+                              // + its repair pass; 0: the 8 x 32 kernel everywhere (A/B; bit-identical wherever the 8 x 32 kernel does not re-centre behind the first block)
+    int attn_tailsplit = 1;   // 1 (default): key-split tail round
+    int gemm_group_m = 0;     // 0 = built-in GROUP_M
+    int gemm_tile = 0;        // 0 auto, 128, 256 (per-tile 8-phase), 2560 (persistent), 2562 (2-barrier 256^2), 2564 (one wave per SIMD)
+    int gemm_tailsplit = 0;   // 1: K-split tail round of the 8-phase GEMM (off by default)
+    int gemm_pers_grid = 0;   // persistent GEMM: number of workgroups (0 = one per CU)
+    int gemm_pers_sched = 0;  // persistent GEMM: DMA placement over the phases of a K-tile: 0 = by shape, 1 = force SCHED 0, 2 = force SCHED 1
+    int gemm_streamk = 1;     // 1 (default): one-wave-per-SIMD GEMM balances the K loops of its last, partly filled round over all CUs (needs utx_gemm_desc.sk_work)
+    int bvh_stack_walk = 0;   // 1: the reference's stack walk over the unpacked tree instead of the stackless packed walk (A/B; same results)
+    int attn_var_abl = 0, attn_debug_abl = 0, gemm_debug_abl = 0;
+    int bvh_packet = 1;       // 1 (default): back-projection rays walk the tree as wave-wide packets over 8 x 8 texel tiles (bvh_trace_packet); 0: one thread per ray (A/B; same results)
+    int attn_peel = 1;        // 1 (default since round 5): the pre-scaled 8 x 32 attention launch runs its fast loop (attention_glds.hip, FAST: first / ragged tile outside the loop, the tile's
+                              // barrier between S2 and S3, next tile's first K fragments read under S3); 0: the general loop (the default until round 4).  Same bits either way.
+    int attn8_peel = 1;       // 1 (default since round 5): MX fp8 attention with tile 0 / a ragged last tile outside the loop and the loop's exponentials in quarters under the PV MFMAs
+                              // (attn_fwd_fp8_kernel<1>, attention_fp8.hip); 0: the general loop.  Same bits either way.
+    int gemm_fastk = 1;       // one-wave-per-SIMD GEMM (bf16): 1 (default since round 6: +2.3 ... +3.7 % on the FLUX shapes, profiles/r06_gemm_fastk_check_v0.log) = the steady-state K loop runs the generated instruction stream (gemm_w4_loop_asm.inc), 0 = hipcc's loop (round 2-5).  Same bits.
+    int nn_grid = 0;          // 0 (default): the NN fill's cell grid follows the atlas size; 64 | 128 | 256 force one (A/B and the grid-independence test; same results)
 };
 extern UtxOptions g_utx_opt;
 
