@@ -419,6 +419,67 @@ int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws,
 int utx_uv_gbuffer(utx_ctx* ctx, const float* rast2d, const int* faces, const float* v_pos, const float* v_nrm, const float* v_pos_cam,
                    const float* v_nrm_cam, int V, int B, int H2D, int W2D, unsigned want, void* const* outs_host, utx_stream stream);
 
+/* Screen-space buffers of a camera batch: NVDiffRendererBase.simple_rendering (render/nvdiffrast/renderer_base.py:101-350) with alpha = coverage
+ * (no dr.antialias).  ONE launch for a whole request: rast [B][H][W][4] holds the B views' rasters (utx_rasterize per view; 16-byte aligned);
+ * faces [F][3]; per vertex v_pos, v_nrm [V][3], v_uv [V][2] in [-1, 1] (uv * 2 - 1), v_attr [V][Ca]; per view and vertex clip_w [B][V] (w of
+ * utx_transform_points with M = mvp), v_pos_cam [B][V][3] (xyz of utx_transform_points with M = w2c) and v_nrm_cam [B][V][3]
+ * (utx_camera_normals): the per-vertex arrays the reference hands to dr.interpolate.  maps_host is a HOST array of n_maps <= UTX_SGB_MAX_MAPS
+ * device pointers to fp32 maps [Ht_i][Wt_i][C_i]; map_dims_host is a HOST array {Ht_0, Wt_0, C_0, Ht_1, ...}.  `want` is the OR of the requested
+ * buffers; outs_host is a HOST array of UTX_SGB_COUNT device pointers, entry k belonging to bit k (entries of buffers that were not requested
+ * are not read, and nothing is written through them).  m = rast.w > 0, lerp(bg, x, m) is a select:
+ *   bit  buffer            layout              covered pixel                                   bg
+ *   0    MASK              u8  [B][H][W]       1                                                0
+ *   1    ALPHA             f32 [B][H][W][1]    1                                                0
+ *   2    WORLD_NORMAL      f32 [B][H][W][3]    normalize(interp(v_nrm))                        -1
+ *   3    CAMERA_NORMAL     f32 [B][H][W][3]    normalize(interp(v_nrm_cam[b]))                 -1
+ *   4    WORLD_POSITION    f32 [B][H][W][3]    interp(v_pos)                                   -1
+ *   5    CAMERA_POSITION   f32 [B][H][W][3]    interp(v_pos_cam[b])                             0
+ *   6    DISTANCE          f32 [B][H][W][1]    |interp(v_pos_cam[b])|                           0
+ *   7    RAY_DIRECTION     f32 [B][H][W][3]    normalize(interp(v_pos_cam[b]))                 -1
+ *   8    Z_DEPTH           f32 [B][H][W][1]    interp(clip_w[b])  (clip w, not camera z)        0
+ *   9    COS_RAY_NORMAL    f32 [B][H][W][1]    dot(camera_normal[b], ray_direction[b])         -1
+ *   10   V_ATTR            f32 [B][H][W][Ca]   interp(v_attr)                                  rule
+ *   11   UV                f32 [B][H][W][2]    interp(v_uv)                                    -1
+ *   12   MAP_ATTR          f32 [B][H][W][sum C_i]  the maps sampled at uv, concatenated        rule
+ * interp, normalize, |x| and the dot product as in utx_uv_gbuffer.  filter (UTX_SGB_FILTER_*): BILINEAR and NEAREST are F.grid_sample(map, uv,
+ * align_corners=False, padding_mode='zeros') (nearest rounds halves to even), NVDIFFRAST is dr.texture(uv * 0.5 + 0.5, filter_mode='linear') with
+ * its wrap boundary (the lookups of utx_backproject_sampled).  Background rule of V_ATTR and MAP_ATTR (bg_kind, UTX_SGB_BG_*): NONE leaves the
+ * computed value on every pixel (0 for V_ATTR, the maps' sample at uv = (-1, -1) for MAP_ATTR); SCALAR fills uncovered pixels with bg_scalar,
+ * VECTOR with bg_v_attr [Ca] / bg_map_attr [sum C_i], DENSE with the pixel's own entry of bg_v_attr [B][H][W][Ca] / bg_map_attr [B][H][W][sum C_i]
+ * (device pointers; each is read only if its buffer is requested).  Stream-ordered, no workspace, no host synchronisation.
+ * B * H * W == 0 or want == 0 does nothing and returns 0 -- except that B == 0 together with a buffer that reads a per-view vertex array (bits
+ * 3, 5-9) is refused, such an array having no address.  Returns -2 for a null rast / faces / outs_host, a rast off a 16-byte boundary, V <= 0, a
+ * negative B, H or W, unknown bits in want, a null output pointer of a requested buffer, a null vertex array that a requested buffer reads,
+ * Ca <= 0 with V_ATTR, and with MAP_ATTR: n_maps < 1 or > UTX_SGB_MAX_MAPS, a null maps_host / map_dims_host / map pointer, a map with a side
+ * or channel count <= 0; an unknown filter or bg_kind, and a VECTOR / DENSE background whose pointer for a requested buffer is null. */
+#define UTX_SGB_MASK 1
+#define UTX_SGB_ALPHA 2
+#define UTX_SGB_WORLD_NORMAL 4
+#define UTX_SGB_CAMERA_NORMAL 8
+#define UTX_SGB_WORLD_POSITION 16
+#define UTX_SGB_CAMERA_POSITION 32
+#define UTX_SGB_DISTANCE 64
+#define UTX_SGB_RAY_DIRECTION 128
+#define UTX_SGB_Z_DEPTH 256
+#define UTX_SGB_COS_RAY_NORMAL 512
+#define UTX_SGB_V_ATTR 1024
+#define UTX_SGB_UV 2048
+#define UTX_SGB_MAP_ATTR 4096
+#define UTX_SGB_COUNT 13
+#define UTX_SGB_ALL 8191
+#define UTX_SGB_MAX_MAPS 4
+#define UTX_SGB_FILTER_BILINEAR 0
+#define UTX_SGB_FILTER_NEAREST 1
+#define UTX_SGB_FILTER_NVDIFFRAST 2
+#define UTX_SGB_BG_NONE 0
+#define UTX_SGB_BG_SCALAR 1
+#define UTX_SGB_BG_VECTOR 2
+#define UTX_SGB_BG_DENSE 3
+int utx_screen_gbuffer(utx_ctx* ctx, const float* rast, const int* faces, const float* v_pos, const float* v_nrm, const float* v_uv,
+                       const float* v_attr, int Ca, const float* clip_w, const float* v_pos_cam, const float* v_nrm_cam, int V, int B, int H, int W,
+                       int n_maps, const float* const* maps_host, const int* map_dims_host, int filter, int bg_kind, float bg_scalar,
+                       const float* bg_v_attr, const float* bg_map_attr, unsigned want, void* const* outs_host, utx_stream stream);
+
 /* Image-based PBR shading of the turntable: PBRModel (texture/pbr/pbr.py:18-49, 91-130), NVDiffRendererPBR.render_base / render_pbr
  * (render/nvdiffrast/renderer_pbr.py:19-94) and the environment-light prefilters of the renderutils plugin (texture/pbr/renderutils/ops.py:398-465,
  * c_src/cubemap.cu:12-139, 174-298).  Cubemaps are [6][N][N][3] fp32; face s and its in-face coordinates (fx, fy) in [-1, 1] follow cube_to_dir:

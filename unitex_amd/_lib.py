@@ -181,6 +181,8 @@ SYMBOLS = {
     "utx_gbuffer_range": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_long, c_void_p, c_void_p, c_void_p]),
     "utx_camera_normals": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
     "utx_uv_gbuffer": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, C.c_uint, C.POINTER(c_void_p), c_void_p]),
+    "utx_screen_gbuffer": (c_int, [c_void_p] * 7 + [c_int] + [c_void_p] * 3 + [c_int] * 5 + [C.POINTER(c_void_p), C.POINTER(c_int), c_int, c_int, c_float, c_void_p, c_void_p,
+                                   C.c_uint, C.POINTER(c_void_p), c_void_p]),
     "utx_cubemap_table": (c_int, [c_int, c_float, c_void_p, c_void_p]),
     "utx_latlong_to_cubemap": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
     "utx_cubemap_diffuse": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),

@@ -382,6 +382,35 @@ int utx_uv_gbuffer(utx_ctx* ctx, const float* rast2d, const int* faces, const fl
     UTX_CALL(ctx, "utx_uv_gbuffer", utx_launch_uv_gbuffer(rast2d, faces, v_pos, v_nrm, v_pos_cam, v_nrm_cam, V, B, H2D, W2D, want, outs_host,
                                                           (hipStream_t)stream));
 }
+int utx_screen_gbuffer(utx_ctx* ctx, const float* rast, const int* faces, const float* v_pos, const float* v_nrm, const float* v_uv,
+                       const float* v_attr, int Ca, const float* clip_w, const float* v_pos_cam, const float* v_nrm_cam, int V, int B, int H, int W,
+                       int n_maps, const float* const* maps_host, const int* map_dims_host, int filter, int bg_kind, float bg_scalar,
+                       const float* bg_v_attr, const float* bg_map_attr, unsigned want, void* const* outs_host, utx_stream stream) {
+    const char* const me = "utx_screen_gbuffer";
+    const unsigned need_nrm_cam = UTX_SGB_CAMERA_NORMAL | UTX_SGB_COS_RAY_NORMAL;
+    const unsigned need_pos_cam = UTX_SGB_CAMERA_POSITION | UTX_SGB_DISTANCE | UTX_SGB_RAY_DIRECTION | UTX_SGB_COS_RAY_NORMAL;
+    if (!rast || !faces || !outs_host || ((uintptr_t)rast & 15)) return fail(ctx, -2, me);      // rast is read as float4
+    if (H < 0 || W < 0 || V <= 0 || B < 0 || (want & ~(unsigned)UTX_SGB_ALL)) return fail(ctx, -2, me);
+    if (filter < UTX_SGB_FILTER_BILINEAR || filter > UTX_SGB_FILTER_NVDIFFRAST || bg_kind < UTX_SGB_BG_NONE || bg_kind > UTX_SGB_BG_DENSE) return fail(ctx, -2, me);
+    for (int k = 0; k < UTX_SGB_COUNT; ++k)
+        if (((want >> k) & 1u) && !outs_host[k]) return fail(ctx, -2, me);
+    if (B == 0 && (want & (need_nrm_cam | need_pos_cam | UTX_SGB_Z_DEPTH))) return fail(ctx, -2, me);      // a per-view array of no view has no address
+    if (((want & UTX_SGB_WORLD_POSITION) && !v_pos) || ((want & UTX_SGB_WORLD_NORMAL) && !v_nrm)) return fail(ctx, -2, me);
+    if (((want & need_nrm_cam) && !v_nrm_cam) || ((want & need_pos_cam) && !v_pos_cam) || ((want & UTX_SGB_Z_DEPTH) && !clip_w)) return fail(ctx, -2, me);
+    if ((want & (UTX_SGB_UV | UTX_SGB_MAP_ATTR)) && !v_uv) return fail(ctx, -2, me);
+    const bool bg_ptr = bg_kind == UTX_SGB_BG_VECTOR || bg_kind == UTX_SGB_BG_DENSE;
+    if (want & UTX_SGB_V_ATTR) {
+        if (!v_attr || Ca <= 0 || (bg_ptr && !bg_v_attr)) return fail(ctx, -2, me);
+    }
+    if (want & UTX_SGB_MAP_ATTR) {
+        if (n_maps < 1 || n_maps > UTX_SGB_MAX_MAPS || !maps_host || !map_dims_host || (bg_ptr && !bg_map_attr)) return fail(ctx, -2, me);
+        for (int m = 0; m < n_maps; ++m)
+            if (!maps_host[m] || map_dims_host[3 * m] <= 0 || map_dims_host[3 * m + 1] <= 0 || map_dims_host[3 * m + 2] <= 0) return fail(ctx, -2, me);
+    }
+    UTX_CALL(ctx, me, utx_launch_screen_gbuffer(rast, faces, v_pos, v_nrm, v_uv, v_attr, Ca, clip_w, v_pos_cam, v_nrm_cam, V, B, H, W,
+                                                (want & UTX_SGB_MAP_ATTR) ? n_maps : 0, maps_host, map_dims_host, filter, bg_kind, bg_scalar, bg_v_attr,
+                                                bg_map_attr, want, outs_host, (hipStream_t)stream));
+}
 int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws, int n_views, float* out, utx_stream stream) {
     if (!nrm || !c2ws || !out) return fail(ctx, -2, "utx_camera_normals");
     UTX_CALL(ctx, "utx_camera_normals", utx_launch_camera_normals(nrm, V, c2ws, n_views, out, (hipStream_t)stream));

@@ -1,5 +1,5 @@
 // Geometry buffers (gfx950): the screen-space ones of the orbit video (utx_gbuffer_shade, utx_gbuffer_range, utx_camera_normals) and the atlas-space
-// ones of simple_inverse_rendering (utx_uv_gbuffer).  Both interpolate with shade_device.h's sd_interp, utx_interpolate's (a0*u + a1*v) + a2*w, and
+// ones of simple_inverse_rendering (utx_uv_gbuffer), and the screen-space buffers of a camera batch of simple_rendering (utx_screen_gbuffer).  All interpolate with shade_device.h's sd_interp, utx_interpolate's (a0*u + a1*v) + a2*w, and
 // normalise with its F.normalize, so a covered pixel's value is bit-identical to interpolate_kernel's wherever it is computed.
 //
 // HBM-bound.  Plain vector loads and stores, no LDS, no scratch, no inline assembly; atomics only in the range reduction.  Built with -ffp-contract=off
@@ -273,5 +273,199 @@ extern "C" int utx_launch_uv_gbuffer(const float* rast, const int* tri, const fl
     o.cos_ray_normal = (float*)out(9);
     hipLaunchKernelGGL(uv_gbuffer_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, (const float4*)rast, tri, v_pos, v_nrm,
                        v_pos_cam, v_nrm_cam, (long)V, B, npix, o);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// ---- screen-space buffers of a camera batch: NVDiffRendererBase.simple_rendering of the reference (render/nvdiffrast/renderer_base.py:101-350) with
+// alpha = coverage (no dr.antialias), every requested buffer of every camera in ONE launch.
+//
+// One thread per pixel of rast [B][H][W][4], x fastest.  The thread reads its raster record and the triangle's three vertex indices once, forms
+// w = (1 - u) - v once and writes every requested buffer.  torch.lerp(bg, x, alpha) with alpha in {0, 1} returns x or bg exactly, so it is a select.
+//
+//   buffer            covered pixel                                          background
+//   world_normal      normalize(interp(v_nrm))                               -1     (:172-178)
+//   camera_normal     normalize(interp(v_nrm_cam[b]))                        -1     (:180-188)
+//   world_position    interp(v_pos)                                          -1     (:190-200)
+//   camera_position   interp(v_pos_cam[b])                                    0     (:241-248)
+//   distance          sqrt((x*x + y*y) + z*z) of the interpolated position    0     (:249-254)
+//   ray_direction     normalize(interp(v_pos_cam[b]))                        -1     (:255-260)
+//   z_depth           interp(clip_w[b]): clip w, NOT camera z as on the atlas 0     (:165-170)
+//   cos_ray_normal    dot(camera_normal, ray_direction), both as above       -1     (:262-274)
+//   v_attr            interp(v_attr), Ca channels                            rule   (:276-287)
+//   uv                interp(v_uv), in [-1, 1]                               -1     (:289-303)
+//   map_attr          the maps sampled at uv, concatenated along channels    rule   (:305-336)
+// distance: with render_camera_position set the reference takes the norm of the ALREADY MASKED position (:245, :250), without it of the raw one and
+// masks afterwards (:251); with alpha = mask both give |p| on a covered pixel and 0 on the background, which is what is written here.
+// rule (:278-284, :327-333): without a background the value stays as computed on EVERY pixel -- dr.interpolate's 0 for v_attr, the maps' sample at the
+// background's uv = (-1, -1) for map_attr; with one (a scalar, a [C] vector or a dense [B][H][W][C] image) covered pixels keep the value and the rest
+// take the background.
+// FILTER of map_attr (grid_interpolate_mode): 0 'bilinear' / 1 'nearest' = F.grid_sample(align_corners=False, zero padding), 2 'nvdiffrast' =
+// dr.texture(uv * 0.5 + 0.5, filter_mode='linear') with its wrap boundary: shade_device.h's grid_taps / grid_nearest / wrap_taps, the taps of the
+// back-projection sampler, computed once per map and pixel and blended per channel.
+enum { SGB_BG_NONE = 0, SGB_BG_SCALAR = 1, SGB_BG_VECTOR = 2, SGB_BG_DENSE = 3 };
+
+struct ScreenGbufferArgs {
+    const float4* rast; const int* tri;
+    const float *v_pos, *v_nrm, *v_uv, *v_attr, *clip_w, *v_pos_cam, *v_nrm_cam;
+    const float* map[UTX_SGB_MAX_MAPS];
+    int map_h[UTX_SGB_MAX_MAPS], map_w[UTX_SGB_MAX_MAPS], map_c[UTX_SGB_MAX_MAPS];
+    int n_maps, Ca, Cm, bg_kind;
+    float bg_scalar;
+    const float *bg_v_attr, *bg_map_attr;
+    long V, npix, total;      // vertices, pixels of one view, pixels of all views
+    unsigned char* mask;
+    float *alpha, *world_normal, *camera_normal, *world_position, *camera_position, *distance, *ray_direction, *z_depth, *cos_ray_normal, *o_v_attr, *uv,
+        *map_attr;
+};
+
+__device__ __forceinline__ float sgb_background(const ScreenGbufferArgs& a, const float* bg, long pixel, int C, int c) {
+    return a.bg_kind == SGB_BG_SCALAR ? a.bg_scalar : a.bg_kind == SGB_BG_VECTOR ? bg[c] : bg[pixel * C + c];
+}
+
+// C channels of one map [Ht][Wt][C] at the NDC (gx, gy)
+template <int FILTER>
+__device__ __forceinline__ void sgb_sample_map(const float* tex, int Ht, int Wt, int C, float gx, float gy, float* out) {
+    if constexpr (FILTER == 0) {
+        long o[4]; float w[4];
+        grid_taps(Ht, Wt, gx, gy, o, w);
+        for (int c = 0; c < C; ++c)
+            out[c] = grid_blend(grid_tap(tex + c, (long)C, o[0]), grid_tap(tex + c, (long)C, o[1]), grid_tap(tex + c, (long)C, o[2]), grid_tap(tex + c, (long)C, o[3]), w);
+    } else if constexpr (FILTER == 1) {
+        const long o = grid_nearest(Ht, Wt, gx, gy);
+        for (int c = 0; c < C; ++c) out[c] = grid_tap(tex + c, (long)C, o);
+    } else {
+        long o00, o10, o01, o11; float fu, fv;
+        const bool finite = wrap_taps(Ht, Wt, gx, gy, o00, o10, o01, o11, fu, fv);
+        for (int c = 0; c < C; ++c)
+            out[c] = finite ? wrap_blend(tex[o00 * C + c], tex[o10 * C + c], tex[o01 * C + c], tex[o11 * C + c], fu, fv) : 0.0f;
+    }
+}
+
+template <int FILTER>
+__global__ __launch_bounds__(256) void screen_gbuffer_kernel(ScreenGbufferArgs a) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.total) return;
+    const long b = i / a.npix;
+    const float4 r = a.rast[i];
+    const int id = (int)r.w - 1;
+    const bool covered = id >= 0;
+    const float u = r.x, v = r.y, w = sd_bary_w(u, v);
+    long i0 = 0, i1 = 0, i2 = 0;
+    if (covered) { i0 = a.tri[3 * id + 0]; i1 = a.tri[3 * id + 1]; i2 = a.tri[3 * id + 2]; }
+    if (a.mask) a.mask[i] = covered ? 1 : 0;
+    if (a.alpha) a.alpha[i] = covered ? 1.0f : 0.0f;
+    if (a.world_normal) {
+        float n[3] = {-1.0f, -1.0f, -1.0f};
+        if (covered) {
+            float p[3];
+            sd_interp<3>(a.v_nrm + 3 * i0, a.v_nrm + 3 * i1, a.v_nrm + 3 * i2, u, v, w, p);
+            sd_normalize3(p, sd_length3(p), n);
+        }
+        uvgb_store3(a.world_normal, i, n);
+    }
+    if (a.world_position) {
+        float p[3] = {-1.0f, -1.0f, -1.0f};
+        if (covered) sd_interp<3>(a.v_pos + 3 * i0, a.v_pos + 3 * i1, a.v_pos + 3 * i2, u, v, w, p);
+        uvgb_store3(a.world_position, i, p);
+    }
+    if (a.z_depth) {
+        const float* cw = a.clip_w + a.V * b;
+        a.z_depth[i] = covered ? sd_interp1(cw[i0], cw[i1], cw[i2], u, v, w) : 0.0f;
+    }
+    const bool want_cn = a.camera_normal || a.cos_ray_normal;
+    const bool want_cp = a.camera_position || a.distance || a.ray_direction || a.cos_ray_normal;
+    if (want_cn || want_cp) {
+        float cn[3] = {-1.0f, -1.0f, -1.0f}, cp[3] = {0.0f, 0.0f, 0.0f}, rd[3] = {-1.0f, -1.0f, -1.0f};
+        float dist = 0.0f, cosv = -1.0f;
+        if (covered) {
+            if (want_cn) {
+                float p[3];
+                const float* n = a.v_nrm_cam + 3 * a.V * b;
+                sd_interp<3>(n + 3 * i0, n + 3 * i1, n + 3 * i2, u, v, w, p);
+                sd_normalize3(p, sd_length3(p), cn);
+            }
+            if (want_cp) {
+                const float* p = a.v_pos_cam + 3 * a.V * b;
+                sd_interp<3>(p + 3 * i0, p + 3 * i1, p + 3 * i2, u, v, w, cp);
+                dist = sd_length3(cp);
+                sd_normalize3(cp, dist, rd);
+            }
+            if (a.cos_ray_normal) cosv = sd_dot3(cn, rd);
+        }
+        if (a.camera_normal) uvgb_store3(a.camera_normal, i, cn);
+        if (a.camera_position) uvgb_store3(a.camera_position, i, cp);
+        if (a.distance) a.distance[i] = dist;
+        if (a.ray_direction) uvgb_store3(a.ray_direction, i, rd);
+        if (a.cos_ray_normal) a.cos_ray_normal[i] = cosv;
+    }
+    if (a.o_v_attr) {
+        float* o = a.o_v_attr + i * a.Ca;
+        const float *p0 = a.v_attr + i0 * a.Ca, *p1 = a.v_attr + i1 * a.Ca, *p2 = a.v_attr + i2 * a.Ca;
+        for (int c = 0; c < a.Ca; ++c) {
+            if (covered) o[c] = sd_interp1(p0[c], p1[c], p2[c], u, v, w);
+            else o[c] = a.bg_kind == SGB_BG_NONE ? 0.0f : sgb_background(a, a.bg_v_attr, i, a.Ca, c);
+        }
+    }
+    if (a.uv || a.map_attr) {
+        float g[2] = {-1.0f, -1.0f};
+        if (covered) sd_interp<2>(a.v_uv + 2 * i0, a.v_uv + 2 * i1, a.v_uv + 2 * i2, u, v, w, g);
+        if (a.uv) { a.uv[2 * i] = g[0]; a.uv[2 * i + 1] = g[1]; }
+        if (a.map_attr) {
+            float* o = a.map_attr + i * a.Cm;
+            if (!covered && a.bg_kind != SGB_BG_NONE) {
+                for (int c = 0; c < a.Cm; ++c) o[c] = sgb_background(a, a.bg_map_attr, i, a.Cm, c);
+            } else {
+#pragma unroll
+                for (int m = 0; m < UTX_SGB_MAX_MAPS; ++m) {
+                    if (m < a.n_maps) {
+                        sgb_sample_map<FILTER>(a.map[m], a.map_h[m], a.map_w[m], a.map_c[m], g[0], g[1], o);
+                        o += a.map_c[m];
+                    }
+                }
+            }
+        }
+    }
+}
+
+// outs_host[k] is the buffer of bit k of `want` (unitex_hip.h UTX_SGB_*); pointers of buffers that were not requested are never read.  The arguments
+// were checked by utx_screen_gbuffer (capi.cpp); B * H * W == 0 or want == 0 launches nothing.
+extern "C" int utx_launch_screen_gbuffer(const float* rast, const int* tri, const float* v_pos, const float* v_nrm, const float* v_uv, const float* v_attr,
+                                         int Ca, const float* clip_w, const float* v_pos_cam, const float* v_nrm_cam, int V, int B, int H, int W,
+                                         int n_maps, const float* const* maps_host, const int* map_dims_host, int filter, int bg_kind, float bg_scalar,
+                                         const float* bg_v_attr, const float* bg_map_attr, unsigned want, void* const* outs_host, hipStream_t stream) {
+    if (B < 0 || H < 0 || W < 0 || n_maps < 0 || n_maps > UTX_SGB_MAX_MAPS || filter < 0 || filter > 2) return -2;
+    ScreenGbufferArgs a = {};
+    a.npix = (long)H * W;
+    a.total = a.npix * B;
+    if (a.total == 0 || want == 0) return 0;
+    auto out = [&](int bit) -> void* { return (want >> bit) & 1u ? outs_host[bit] : nullptr; };
+    a.rast = (const float4*)rast; a.tri = tri;
+    a.v_pos = v_pos; a.v_nrm = v_nrm; a.v_uv = v_uv; a.v_attr = v_attr; a.clip_w = clip_w; a.v_pos_cam = v_pos_cam; a.v_nrm_cam = v_nrm_cam;
+    a.V = V; a.Ca = Ca; a.bg_kind = bg_kind; a.bg_scalar = bg_scalar; a.bg_v_attr = bg_v_attr; a.bg_map_attr = bg_map_attr;
+    a.mask = (unsigned char*)out(0);
+    a.alpha = (float*)out(1);
+    a.world_normal = (float*)out(2);
+    a.camera_normal = (float*)out(3);
+    a.world_position = (float*)out(4);
+    a.camera_position = (float*)out(5);
+    a.distance = (float*)out(6);
+    a.ray_direction = (float*)out(7);
+    a.z_depth = (float*)out(8);
+    a.cos_ray_normal = (float*)out(9);
+    a.o_v_attr = (float*)out(10);
+    a.uv = (float*)out(11);
+    a.map_attr = (float*)out(12);
+    if (a.map_attr) {
+        a.n_maps = n_maps;
+        for (int m = 0; m < n_maps; ++m) {
+            a.map[m] = maps_host[m];
+            a.map_h[m] = map_dims_host[3 * m]; a.map_w[m] = map_dims_host[3 * m + 1]; a.map_c[m] = map_dims_host[3 * m + 2];
+            a.Cm += a.map_c[m];
+        }
+    }
+    const dim3 g((unsigned)((a.total + 255) / 256)), blk(256);
+    if (filter == 0) hipLaunchKernelGGL(screen_gbuffer_kernel<0>, g, blk, 0, stream, a);
+    else if (filter == 1) hipLaunchKernelGGL(screen_gbuffer_kernel<1>, g, blk, 0, stream, a);
+    else hipLaunchKernelGGL(screen_gbuffer_kernel<2>, g, blk, 0, stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }

@@ -146,6 +146,9 @@ int utx_launch_gbuffer_range(int mode, const float* rast, const int* tri, const 
 int utx_launch_camera_normals(const float* nrm, int V, const float* c2ws, int n_views, float* out, hipStream_t stream);
 int utx_launch_uv_gbuffer(const float* rast, const int* tri, const float* v_pos, const float* v_nrm, const float* v_pos_cam, const float* v_nrm_cam, int V, int B, int H2D, int W2D,
                           unsigned want, void* const* outs_host, hipStream_t stream);
+int utx_launch_screen_gbuffer(const float* rast, const int* tri, const float* v_pos, const float* v_nrm, const float* v_uv, const float* v_attr, int Ca, const float* clip_w,
+                              const float* v_pos_cam, const float* v_nrm_cam, int V, int B, int H, int W, int n_maps, const float* const* maps_host, const int* map_dims_host,
+                              int filter, int bg_kind, float bg_scalar, const float* bg_v_attr, const float* bg_map_attr, unsigned want, void* const* outs_host, hipStream_t stream);
 // pbr.hip
 int utx_cubemap_table_impl(int N, float costheta_cutoff, float* texels_host, float* tiles_host);
 int utx_launch_latlong_to_cubemap(const float* lat, int Hi, int Wi, int N, float* out, hipStream_t stream);

@@ -1,6 +1,6 @@
 // Per-pixel device primitives of the geometry and shading kernels (raster.hip, gbuffer.hip, pbr.hip, backproject.hip): the barycentric
-// interpolation of utx_interpolate, the wrap-addressed bilinear texture fetch of utx_texture_shade, length / normalisation with F.normalize's
-// eps, and the float -> uint8 conversion.  These kernels are held to bit-exact parity with the oracle and with each other, so each expression
+// interpolation of utx_interpolate, the wrap-addressed bilinear texture fetch of utx_texture_shade, the grid_sample and nvdiffrast lookups of an
+// image at an NDC coordinate, length / normalisation with F.normalize's eps, and the float -> uint8 conversion.  These kernels are held to bit-exact parity with the oracle and with each other, so each expression
 // is written ONCE, here, with its sums in one fixed order.  Every translation unit that includes this header is compiled with
 // -ffp-contract=off: each operation below is one correctly rounded fp32 operation and a value is bit-identical wherever it is computed.
 #pragma once
@@ -66,6 +66,76 @@ __device__ __forceinline__ void sd_tex3_wrap(const float* tex, int Ht, int Wt, f
 __device__ __forceinline__ void sd_tex3_wrap_const(const float k[3], int Ht, int Wt, float tu, float tv, float o[3]) {
     const SdTexTaps t = sd_tex_taps(Ht, Wt, tu, tv);
     sd_tex3_blend(k, k, k, k, t.fx, t.fy, o);
+}
+
+// ---- the lookups of an image at an NDC coordinate in [-1, 1] (the views of the back-projection, the maps of utx_screen_gbuffer).
+// The two lookups of a view image.  Each has ONE function for its taps and weights and ONE blend, templated on the tap type: float4 for the colour
+// kernel (rgb + alpha, one 16-byte load per tap), float for the alpha plane and for one channel of a [H][W][C] image (taps `stride` = C floats apart).
+//
+// grid_sample(bilinear, zero padding, align_corners=False): the four tap offsets in pixels (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), -1 for a
+// tap outside the view (it reads as zero), and their weights
+__device__ __forceinline__ float grid_unnormalize(float g, int size) { return ((g + 1.0f) * (float)size - 1.0f) * 0.5f; }
+__device__ __forceinline__ void grid_taps(int H, int W, float gx, float gy, long o[4], float w[4]) {
+    const float ix = grid_unnormalize(gx, W), iy = grid_unnormalize(gy, H);
+    const float fx = floorf(ix), fy = floorf(iy);
+    const int x0 = (int)fx, y0 = (int)fy;
+    const float tx = ix - fx, ty = iy - fy;
+    w[0] = (1.0f - tx) * (1.0f - ty); w[1] = tx * (1.0f - ty); w[2] = (1.0f - tx) * ty; w[3] = tx * ty;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int x = x0 + (k & 1), y = y0 + (k >> 1);
+        o[k] = (x < 0 || x >= W || y < 0 || y >= H) ? -1 : (long)y * W + x;
+    }
+}
+// grid_sample(nearest, zero padding, align_corners=False): the offset of the one tap, the pixel nearest to the sample with halves rounded to even
+// (rintf, as torch's round), -1 outside the image
+__device__ __forceinline__ long grid_nearest(int H, int W, float gx, float gy) {
+    const float fx = rintf(grid_unnormalize(gx, W)), fy = rintf(grid_unnormalize(gy, H));
+    if (!(fx >= 0.0f && fx < (float)W && fy >= 0.0f && fy < (float)H)) return -1;      // (a NaN coordinate is outside)
+    return (long)(int)fy * W + (int)fx;
+}
+template <class T>
+__device__ __forceinline__ T grid_tap(const T* img, long stride, long o) { return o < 0 ? T{} : img[o * stride]; }
+template <class T>
+__device__ __forceinline__ T grid_blend(T a, T b, T c, T e, const float w[4]) { return ((a * w[0] + b * w[1]) + c * w[2]) + e * w[3]; }
+
+// nvdiffrast's 2-D linear lookup with the wrap boundary (indexTextureLinear + bilerp, restated): uv = ndc * 0.5 + 0.5 (two roundings, as
+// ndc_2d.mul(0.5).add(0.5)), u -= floor(u), u = u * W - 0.5, i0 = floor(u), i1 = i0 + 1, f = u - i0, indices wrapped into [0, W) (the same along v with H),
+// out = lerp(lerp(t00, t10, fu), lerp(t01, t11, fu), fv) with lerp(a, b, t) = a + t * (b - a).  For a finite u, u - floor(u) lies in [0, 1], so i0 lies in
+// [-1, W - 1] and i1 in [0, W]: after the wrap every tap is inside the view.
+// wrap_taps: the four tap offsets (in pixels) and the two lerp fractions; false for a non-finite coordinate (it samples zero)
+__device__ __forceinline__ bool wrap_taps(int H, int W, float gx, float gy, long& o00, long& o10, long& o01, long& o11, float& fu, float& fv) {
+    if (!isfinite(gx) || !isfinite(gy)) return false;
+    float su = gx * 0.5f + 0.5f, sv = gy * 0.5f + 0.5f;
+    su = su - floorf(su); sv = sv - floorf(sv);
+    su = su * (float)W - 0.5f; sv = sv * (float)H - 0.5f;
+    const float fu0 = floorf(su), fv0 = floorf(sv);
+    int iu0 = (int)fu0, iv0 = (int)fv0, iu1 = iu0 + 1, iv1 = iv0 + 1;
+    fu = su - fu0; fv = sv - fv0;
+    if (iu0 < 0) iu0 += W;
+    if (iv0 < 0) iv0 += H;
+    if (iu1 >= W) iu1 -= W;
+    if (iv1 >= H) iv1 -= H;
+    o00 = (long)iv0 * W + iu0; o10 = (long)iv0 * W + iu1; o01 = (long)iv1 * W + iu0; o11 = (long)iv1 * W + iu1;
+    return true;
+}
+template <class T>
+__device__ __forceinline__ T lerp_nv(T a, T b, float t) { return a + (b - a) * t; }
+template <class T>
+__device__ __forceinline__ T wrap_blend(T t00, T t10, T t01, T t11, float fu, float fv) { return lerp_nv(lerp_nv(t00, t10, fu), lerp_nv(t01, t11, fu), fv); }
+
+// SAMPLE 0: grid_sample, 1: the wrap lookup, of img [H][W] texels of type T, `stride` T's apart, at the NDC (gx, gy)
+template <int SAMPLE, class T>
+__device__ __forceinline__ T sample_view(const T* img, long stride, int H, int W, float gx, float gy) {
+    if constexpr (SAMPLE == 0) {
+        long o[4]; float w[4];
+        grid_taps(H, W, gx, gy, o, w);
+        return grid_blend(grid_tap(img, stride, o[0]), grid_tap(img, stride, o[1]), grid_tap(img, stride, o[2]), grid_tap(img, stride, o[3]), w);
+    } else {
+        long o00, o10, o01, o11; float fu, fv;
+        if (!wrap_taps(H, W, gx, gy, o00, o10, o01, o11, fu, fv)) return T{};
+        return wrap_blend(img[o00 * stride], img[o10 * stride], img[o01 * stride], img[o11 * stride], fu, fv);
+    }
 }
 
 // ---- float frame -> uint8: clamp(0, 1) * 255, truncated (astype(uint8))

@@ -207,6 +207,111 @@ def uv_gbuffer(rast2d, faces, v_pos, v_nrm, c2ws=None, want=("mask", "alpha", "w
     return out
 
 
+# name -> (bit of utx_screen_gbuffer's `want`, channels; None: the caller's); the order is the header's UTX_SGB_* bits
+SCREEN_GBUFFERS = {"mask": (0, 1), "alpha": (1, 1), "world_normal": (2, 3), "camera_normal": (3, 3), "world_position": (4, 3), "camera_position": (5, 3),
+                   "distance": (6, 1), "ray_direction": (7, 3), "z_depth": (8, 1), "cos_ray_normal": (9, 1), "v_attr": (10, None), "uv": (11, 2),
+                   "map_attr": (12, None)}
+SCREEN_GBUFFERS_POS_CAM = ("camera_position", "distance", "ray_direction", "cos_ray_normal")      # read v_pos_cam
+SCREEN_GBUFFERS_NRM_CAM = ("camera_normal", "cos_ray_normal")                                     # read v_nrm_cam
+SCREEN_FILTERS = {"bilinear": 0, "nearest": 1, "nvdiffrast": 2}                                   # UTX_SGB_FILTER_*
+SCREEN_MAX_MAPS = 4                                                                               # UTX_SGB_MAX_MAPS
+
+
+def screen_gbuffer(rast, faces, v_pos, v_nrm=None, v_uv=None, v_attr=None, maps=(), mvp=None, c2ws=None, want=("mask", "alpha"), background=None,
+                   filter="bilinear", clip_w=None, v_pos_cam=None, v_nrm_cam=None):
+    """The screen-space buffers of simple_rendering in one launch (utx_screen_gbuffer): rast [B,H,W,4] (one utx_rasterize per view), faces [F,3]
+    int32, v_pos [V,3], and whatever the requested buffers read: v_nrm [V,3], v_uv [V,2] in [-1,1], v_attr [V,Ca], maps = up to four [Ht,Wt,C]
+    tensors of their own sizes, mvp [B,4,4] (z_depth: clip w) and c2ws [B,4,4] (the camera-space buffers) -> dict of the buffers named in `want`
+    (SCREEN_GBUFFERS): mask uint8 [B,H,W], every other one float32 [B,H,W,C].  background (v_attr and map_attr only): None, a number, or a tensor
+    that broadcasts to [B,H,W,C]; filter: 'bilinear' | 'nearest' (grid_sample, zero padding, align_corners=False) | 'nvdiffrast' (linear, wrap).
+    The per-view per-vertex arrays are built here with the existing kernels only when a requested buffer reads them (transform_points with M = mvp
+    and M = w2c, camera_normals), as the reference builds them in front of dr.interpolate; a caller that holds them already passes clip_w [B,V],
+    v_pos_cam / v_nrm_cam [B,V,3], and mvp / c2ws are then not read."""
+    want = tuple(want)
+    for k in want:
+        if k not in SCREEN_GBUFFERS:
+            raise KeyError("screen_gbuffer: unknown buffer %r (known: %s)" % (k, ", ".join(SCREEN_GBUFFERS)))
+    if not want:
+        raise ValueError("screen_gbuffer: no buffer requested")
+    if filter not in SCREEN_FILTERS:
+        raise ValueError("screen_gbuffer: filter %r (known: %s)" % (filter, ", ".join(SCREEN_FILTERS)))
+    need_pos, need_nrm = any(k in SCREEN_GBUFFERS_POS_CAM for k in want), any(k in SCREEN_GBUFFERS_NRM_CAM for k in want)
+    need_w = "z_depth" in want
+    if (need_pos and v_pos_cam is None or need_nrm and v_nrm_cam is None) and c2ws is None:
+        raise ValueError("screen_gbuffer: %s depend on the cameras: c2ws is required" % ", ".join(k for k in want if k in SCREEN_GBUFFERS_POS_CAM + SCREEN_GBUFFERS_NRM_CAM))
+    if need_w and clip_w is None and mvp is None:
+        raise ValueError("screen_gbuffer: z_depth is the interpolated clip w: mvp (or clip_w) is required")
+    assert rast.dim() == 4 and rast.shape[3] == 4 and faces.shape[1] == 3, "rast is [B, H, W, 4], faces [F, 3]"
+    ctx = get_ctx(rast.device.index)
+    dev = rast.device
+    B, H, W = rast.shape[:3]
+    V = v_pos.shape[0]
+    assert tuple(v_pos.shape) == (V, 3)
+    if B > 0:
+        if need_w and clip_w is None:
+            clip_w = transform_points(v_pos, torch.as_tensor(mvp, dtype=F32).to(dev).contiguous(), want_ndc=False)[0][..., 3].contiguous()
+        if need_pos and v_pos_cam is None:
+            from . import camera
+            w2c = camera.c2w_to_w2c(torch.as_tensor(c2ws, dtype=F32).cpu()).to(dev, F32).contiguous()
+            v_pos_cam = transform_points(v_pos, w2c, want_ndc=False)[0][..., :3].contiguous()
+        if need_nrm and v_nrm_cam is None:
+            assert v_nrm is not None, "v_nrm [V, 3] is required by the normal buffers"
+            v_nrm_cam = camera_normals(v_nrm, torch.as_tensor(c2ws, dtype=F32).to(dev).contiguous())
+        for a, shp in ((clip_w, (B, V)), (v_pos_cam, (B, V, 3)), (v_nrm_cam, (B, V, 3))):
+            if a is not None and tuple(a.shape) != shp:
+                raise ValueError("screen_gbuffer: a per-view vertex array is %s, expected %s" % (tuple(a.shape), shp))
+    if "world_normal" in want and (v_nrm is None or tuple(v_nrm.shape) != (V, 3)):
+        raise ValueError("screen_gbuffer: world_normal reads v_nrm [V, 3]")
+    if ("uv" in want or "map_attr" in want) and (v_uv is None or tuple(v_uv.shape) != (V, 2)):
+        raise ValueError("screen_gbuffer: uv and map_attr read v_uv [V, 2]")
+    Ca = Cm = 0
+    if "v_attr" in want:
+        if v_attr is None or v_attr.dim() != 2 or v_attr.shape[0] != V or v_attr.shape[1] < 1:
+            raise ValueError("screen_gbuffer: v_attr is %s, expected [V = %d, Ca >= 1]" % (None if v_attr is None else tuple(v_attr.shape), V))
+        Ca = v_attr.shape[1]
+    maps = tuple(maps) if "map_attr" in want else ()
+    if "map_attr" in want:
+        if not 1 <= len(maps) <= SCREEN_MAX_MAPS:
+            raise ValueError("screen_gbuffer: map_attr samples 1 to %d maps, got %d" % (SCREEN_MAX_MAPS, len(maps)))
+        for m in maps:
+            if m.dim() != 3 or min(m.shape) < 1:
+                raise ValueError("screen_gbuffer: a map is %s, expected [Ht, Wt, C] with no empty side" % (tuple(m.shape),))
+        Cm = sum(m.shape[2] for m in maps)
+    # the background: None, a number, a [C] vector or a dense image, per buffer (the two channel counts may differ)
+    kind, scalar, bgs = 0, 0.0, {"v_attr": None, "map_attr": None}
+    if background is not None and ("v_attr" in want or "map_attr" in want):
+        if isinstance(background, (int, float)):
+            kind, scalar = 1, float(background)
+        elif isinstance(background, torch.Tensor):
+            bgt = background.to(dev, F32)
+            kind = 2 if bgt.dim() <= 1 else 3
+            for k, ch in (("v_attr", Ca), ("map_attr", Cm)):
+                if k in want:
+                    try:
+                        bgs[k] = bgt.expand(ch).contiguous() if kind == 2 else bgt.expand(B, H, W, ch).contiguous()
+                    except RuntimeError:
+                        raise ValueError("screen_gbuffer: background %s does not broadcast to %s of %s" % (tuple(bgt.shape), (B, H, W, ch), k))
+        else:
+            raise ValueError("screen_gbuffer: background is %r: expected None, a number or a tensor" % type(background))
+    out, bits = {}, 0
+    ptrs = (C.c_void_p * len(SCREEN_GBUFFERS))()
+    for k in want:
+        bit, ch = SCREEN_GBUFFERS[k]
+        ch = {"v_attr": Ca, "map_attr": Cm}.get(k, ch)
+        out[k] = torch.empty(B, H, W, dtype=U8, device=dev) if k == "mask" else torch.empty(B, H, W, ch, dtype=F32, device=dev)
+        ptrs[bit] = out[k].data_ptr() or None
+        bits |= 1 << bit
+    if B * H * W == 0:      # nothing to write, and an empty tensor has no address to hand over
+        return out
+    mptr = (C.c_void_p * SCREEN_MAX_MAPS)(*[_f(m).data_ptr() for m in maps])
+    mdim = (C.c_int * (3 * SCREEN_MAX_MAPS))(*[int(d) for m in maps for d in m.shape])
+    opt = lambda t: ptr(_f(t)) if t is not None else None
+    ctx.check(ctx.lib.utx_screen_gbuffer(ctx.handle, ptr(_f(rast)), ptr(_i(faces)), ptr(_f(v_pos)), opt(v_nrm), opt(v_uv), opt(v_attr if Ca else None), Ca,
+                                         opt(clip_w), opt(v_pos_cam), opt(v_nrm_cam), V, B, H, W, len(maps), mptr, mdim, SCREEN_FILTERS[filter], kind, scalar,
+                                         opt(bgs["v_attr"]), opt(bgs["map_attr"]), bits, ptrs, ctx.stream()))
+    return out
+
+
 def cubemap_tables(N, costheta_cutoff=None, device="cuda"):
     """utx_cubemap_table: (texels [6,N,N,4] = unit direction + pixel_area, tiles [6,nt,nt,4] or None) on `device`, built on the host in fp64.
     Runs without a GPU when device is 'cpu' (the tests' oracle reads the same table)."""

@@ -192,12 +192,9 @@ class NVDiffRendererInverse:
         mvp = torch.matmul(camera.intr_to_proj(intr, perspective=perspective), camera.c2w_to_w2c(c2ws))
         return mvp.to(self.device).contiguous(), c2ws
 
-    def mv_to_pcd(self, c2ws, intrinsics, render_size, perspective=True, grad_norm_threhold=0.20, ray_normal_angle_threhold=115.0,
-                  filt_gradient_points=False, want_points=False):
-        """view-space pass of the reference's mv_to_pcd (renderer_inverse.py:159-241), dense instead of compacted:
-          alpha [n,H,W] f32 = mask_visiable as float: plain coverage, or with filt_gradient_points=True coverage AND
-          back-facing-ray test AND the (row-wise, 31 wide) eroded gradient test (:189-209);
-          want_points: also pos [n,H,W,3] (interpolated vertex positions = the point cloud of :224-232) and the raster."""
+    def _view_raster(self, c2ws, intrinsics, render_size, perspective):
+        """the cameras' clip transform and one rasterisation per view (mv_to_pcd and simple_rendering share it):
+        (mvp [n,4,4], c2ws on the host, clip [n,V,4], ndc [n,V,2], rast [n,H,W,4])"""
         H, W = (render_size, render_size) if isinstance(render_size, int) else render_size
         m = self.pbr_mesh
         mvp, c2ws_cpu = self._mvp(c2ws, intrinsics, perspective)
@@ -206,6 +203,17 @@ class NVDiffRendererInverse:
         rast = torch.empty(n, H, W, 4, dtype=torch.float32, device=self.device)
         for v in range(n):
             rast[v] = ops.rasterize(clip[v].contiguous(), m.faces, H, W)
+        return mvp, c2ws_cpu, clip, ndc, rast
+
+    def mv_to_pcd(self, c2ws, intrinsics, render_size, perspective=True, grad_norm_threhold=0.20, ray_normal_angle_threhold=115.0,
+                  filt_gradient_points=False, want_points=False):
+        """view-space pass of the reference's mv_to_pcd (renderer_inverse.py:159-241), dense instead of compacted:
+          alpha [n,H,W] f32 = mask_visiable as float: plain coverage, or with filt_gradient_points=True coverage AND
+          back-facing-ray test AND the (row-wise, 31 wide) eroded gradient test (:189-209);
+          want_points: also pos [n,H,W,3] (interpolated vertex positions = the point cloud of :224-232) and the raster."""
+        m = self.pbr_mesh
+        mvp, c2ws_cpu, clip, ndc, rast = self._view_raster(c2ws, intrinsics, render_size, perspective)
+        n, H, W = rast.shape[:3]
         out = {"clip": clip, "ndc": ndc}
         attrs = None
         if filt_gradient_points or want_points:
@@ -288,11 +296,12 @@ class NVDiffRendererInverse:
 
     # flag of simple_inverse_rendering -> key of the returned dict, camera-independent first
     _UV_FLAGS = ("world_normal", "world_position", "camera_normal", "camera_position", "distance", "z_depth", "ray_direction", "cos_ray_normal")
-    _UV_FLAGS_UNBUILT = ("render_voxel_attr", "render_v_attr", "render_uv", "render_map_attr", "render_all_point_cloud", "render_visible_point_cloud")
+    _UV_FLAGS_UNBUILT = ("render_voxel_attr", "render_uv", "render_map_attr", "render_all_point_cloud", "render_visible_point_cloud")
 
     def simple_inverse_rendering(self, c2ws=None, texture_size=2048, render_world_normal=False, render_world_position=False,
                                  render_camera_normal=False, render_camera_position=False, render_distance=False, render_z_depth=False,
-                                 render_ray_direction=False, render_cos_ray_normal=False, enable_antialis=True, **kwargs):
+                                 render_ray_direction=False, render_cos_ray_normal=False, enable_antialis=True, render_v_attr=False, v_attr=None,
+                                 background=None, **kwargs):
         """NVDiffRendererBase.simple_inverse_rendering (render/nvdiffrast/renderer_base.py:352-489) on the mesh of update_from_file: the geometry
         buffers rendered into the UV atlas instead of onto a screen, all of them in one kernel launch (ops.uv_gbuffer).  Returns the reference's
         dict: 'mask' bool [1,H,W,1], 'alpha' float32 [1,H,W,1] and, per flag, 'world_normal' / 'world_position' [1,H,W,3] and, per camera of
@@ -300,13 +309,21 @@ class NVDiffRendererInverse:
         texture_size: int or (H, W).  Row 0 is v = 0 (the raster's orientation; TexturedMesh.texture is the flipped one).  Only c2ws enters: the
         function never projects, so it takes no intrinsics.  Vertex normals are pbr_mesh.vertex_normals.
         enable_antialis is accepted and has no effect: alpha is the coverage mask (no dr.antialias in this build, as on the turntable).
-        A camera-dependent flag without c2ws raises ValueError; render_voxel_attr, render_v_attr, render_uv, render_map_attr,
-        render_all_point_cloud and render_visible_point_cloud are not built and raise NotImplementedError when set; any other keyword is a TypeError."""
+        render_v_attr (:491-502) adds 'v_attr' [1,H,W,Ca]: the per-vertex attribute v_attr [V,Ca] interpolated into the atlas by the screen kernel
+        (ops.screen_gbuffer on the atlas raster as a batch of one), then the background rule of simple_rendering: None leaves the interpolated value
+        (0 outside the charts), a number or a tensor that broadcasts to [1,H,W,Ca] fills the uncovered texels.
+        A camera-dependent flag without c2ws raises ValueError, and so does a v_attr that is not [V,Ca]; render_v_attr with no v_attr at all is
+        refused like an unbuilt flag (NotImplementedError: the mesh has no attribute of its own to render); render_uv and render_map_attr
+        (they need Mesh.get_visible_faces and read a rebound batch_size, :446, :514; back-projection is this build's answer to them),
+        render_voxel_attr, render_all_point_cloud and render_visible_point_cloud are not built and raise NotImplementedError when set; any other
+        keyword is a TypeError."""
         for k_, v_ in kwargs.items():
             if k_ not in self._UV_FLAGS_UNBUILT:
                 raise TypeError("simple_inverse_rendering() got an unexpected keyword argument %r" % k_)
             if v_:
                 raise NotImplementedError("simple_inverse_rendering(%s=%r) is not built" % (k_, v_))
+        if render_v_attr and v_attr is None:      # the mesh carries no per-vertex attribute of its own that could stand in
+            raise NotImplementedError("simple_inverse_rendering(render_v_attr=True) without v_attr is not built: pass v_attr [V, Ca]")
         flags = dict(world_normal=render_world_normal, world_position=render_world_position, camera_normal=render_camera_normal,
                      camera_position=render_camera_position, distance=render_distance, z_depth=render_z_depth,
                      ray_direction=render_ray_direction, cos_ray_normal=render_cos_ray_normal)
@@ -317,12 +334,97 @@ class NVDiffRendererInverse:
         H2D, W2D = (texture_size, texture_size) if isinstance(texture_size, int) else texture_size
         m = self.pbr_mesh
         assert m is not None, "update_from_file first"
+        if render_v_attr:
+            v_attr = self._vertex_attr(v_attr, "simple_inverse_rendering")
         rast2d = self._uv_raster(int(H2D), int(W2D))
         with self._stage("uv_gbuffer"):
             need_nrm = any(k in ("world_normal",) + ops.UV_GBUFFERS_NRM_CAM for k in want)      # the normals are built lazily, on the host
             out = ops.uv_gbuffer(rast2d, m.faces, m.vertices, m.vertex_normals if need_nrm else None, c2ws=c2ws, want=["mask", "alpha"] + want)
+            if render_v_attr:
+                out["v_attr"] = ops.screen_gbuffer(rast2d[None], m.faces, m.vertices, v_attr=v_attr, want=("v_attr",), background=background)["v_attr"]
         out["mask"] = out["mask"].bool()[None, ..., None]
         out["alpha"] = out["alpha"][None]
+        return out
+
+    def _vertex_attr(self, v_attr, who):
+        """v_attr [V,Ca] of the caller -> contiguous float32 on the device, or ValueError"""
+        V = self.pbr_mesh.vertices.shape[0]
+        if v_attr is None:
+            raise ValueError("%s(render_v_attr=True) needs v_attr [V, Ca]" % who)
+        v_attr = torch.as_tensor(v_attr, dtype=torch.float32).to(self.device).contiguous()
+        if v_attr.dim() != 2 or v_attr.shape[0] != V or v_attr.shape[1] < 1:
+            raise ValueError("%s: v_attr is %s, the mesh has %d vertices: expected [%d, Ca >= 1]" % (who, tuple(v_attr.shape), V, V))
+        return v_attr
+
+    # flag of simple_rendering -> key of the returned dict, in the order the reference fills its dict
+    _SCREEN_FLAGS = ("z_depth", "world_normal", "camera_normal", "world_position", "camera_position", "distance", "ray_direction", "cos_ray_normal",
+                     "v_attr", "uv", "map_attr")
+    _SCREEN_FLAGS_UNBUILT = ("render_voxel_attr", "render_voxel_network", "render_all_point_cloud", "render_visible_point_cloud", "render_map_network")
+
+    def simple_rendering(self, c2ws, intrinsics, render_size, perspective=True, v_attr=None, map_attr=None, render_z_depth=False,
+                         render_distance=False, render_world_normal=False, render_camera_normal=False, render_world_position=False,
+                         render_camera_position=False, render_ray_direction=False, render_cos_ray_normal=False, render_v_attr=False,
+                         render_uv=False, render_map_attr=False, background=None, grid_interpolate_mode="bilinear", enable_antialis=True, **kwargs):
+        """NVDiffRendererBase.simple_rendering (render/nvdiffrast/renderer_base.py:101-350) on the mesh of update_from_file / update_from_arrays: the
+        buffers of a batch of cameras c2ws [B,4,4] / intrinsics [B,3,3] (normalised) on a screen of render_size (int or (H, W)).  One rasterisation
+        per view (the loop mv_to_pcd uses), then every requested buffer of every view in ONE kernel launch (ops.screen_gbuffer).  Returns the
+        reference's dict: 'mask' bool [B,H,W,1], 'alpha' float32 [B,H,W,1] and, per flag, 'world_normal' / 'camera_normal' / 'world_position' /
+        'camera_position' / 'ray_direction' [B,H,W,3], 'z_depth' (the interpolated clip w) / 'distance' / 'cos_ray_normal' [B,H,W,1], 'uv' [B,H,W,2]
+        in [-1,1], 'v_attr' [B,H,W,Ca] and 'map_attr' [B,H,W,sum C_i]; backgrounds as the reference fills them (-1 or 0).
+        perspective replaces the reference's enable_perspective() / enable_orthogonal() state, as in infer and mv_to_pcd.  Vertex normals are
+        pbr_mesh.vertex_normals, the vertex UVs the mesh's own.
+        v_attr [V,Ca]: any per-vertex attribute (render_v_attr).  map_attr (render_map_attr): one map [Ht,Wt,C] or [1,Ht,Wt,C], row 0 at v = 0, or a
+        tuple of up to four maps of sizes of their own, sampled at 'uv' and concatenated along the channels -- bit-identical to torch.cat of the
+        single-map calls.  grid_interpolate_mode: 'bilinear' | 'nearest' are F.grid_sample(align_corners=False, zero padding), 'nvdiffrast' is
+        dr.texture(uv * 0.5 + 0.5, filter_mode='linear') with its wrap boundary.  As in the reference, map_attr hangs under render_uv (:289-305):
+        render_map_attr without render_uv is a ValueError here instead of being dropped.
+        background (v_attr and map_attr only): None leaves the interpolated / sampled value on every pixel (uncovered pixels: 0, and the maps'
+        sample at uv = (-1, -1)); a number or a tensor that broadcasts to the buffer ([C], [H,W,C], [B,H,W,C]) fills the uncovered pixels.
+        enable_antialis is accepted and has no effect: there is no dr.antialias in this build, alpha is the coverage mask, as on the turntable.
+        Refused, never dropped (NotImplementedError when set): render_voxel_attr / render_voxel_network (the reference's branch cannot execute: it
+        permutes the 5-D voxel_attr.expand(batch_size, *shape[-4:]) with four indices, :203-204), render_all_point_cloud /
+        render_visible_point_cloud (draw_mask hands the float pixel coordinates of discretize to torch.scatter as the index, :151-154, :28-36)
+        and render_map_network (a callable of the caller's: apply it to 'uv').  Any other keyword is a TypeError.  render_v_attr without v_attr,
+        render_map_attr without map_attr, more than four maps, or a v_attr whose first dimension is not V raise ValueError."""
+        for k_, v_ in kwargs.items():
+            if k_ not in self._SCREEN_FLAGS_UNBUILT:
+                raise TypeError("simple_rendering() got an unexpected keyword argument %r" % k_)
+            if v_:
+                raise NotImplementedError("simple_rendering(%s=%r) is not built" % (k_, v_))
+        flags = dict(z_depth=render_z_depth, world_normal=render_world_normal, camera_normal=render_camera_normal, world_position=render_world_position,
+                     camera_position=render_camera_position, distance=render_distance, ray_direction=render_ray_direction,
+                     cos_ray_normal=render_cos_ray_normal, v_attr=render_v_attr, uv=render_uv, map_attr=render_map_attr)
+        want = [k for k in self._SCREEN_FLAGS if flags[k]]
+        m = self.pbr_mesh
+        assert m is not None, "update_from_file first"
+        if grid_interpolate_mode not in ops.SCREEN_FILTERS:
+            raise ValueError("simple_rendering(grid_interpolate_mode=%r): one of %s" % (grid_interpolate_mode, ", ".join(ops.SCREEN_FILTERS)))
+        if render_v_attr:
+            v_attr = self._vertex_attr(v_attr, "simple_rendering")
+        maps = ()
+        if render_map_attr:
+            if not render_uv:
+                raise ValueError("simple_rendering(render_map_attr=True) samples the maps at 'uv': set render_uv=True as well (the reference renders "
+                                 "map_attr under render_uv only)")
+            if map_attr is None:
+                raise ValueError("simple_rendering(render_map_attr=True) needs map_attr")
+            maps = tuple(map_attr) if isinstance(map_attr, (tuple, list)) else (map_attr,)
+            if not 1 <= len(maps) <= ops.SCREEN_MAX_MAPS:
+                raise ValueError("simple_rendering: map_attr holds %d maps, 1 to %d are built" % (len(maps), ops.SCREEN_MAX_MAPS))
+            maps = tuple(torch.as_tensor(t, dtype=torch.float32).to(self.device) for t in maps)
+            maps = tuple((t[0] if t.dim() == 4 and t.shape[0] == 1 else t).contiguous() for t in maps)
+            for t in maps:
+                if t.dim() != 3 or min(t.shape) < 1:
+                    raise ValueError("simple_rendering: a map is %s, expected [Ht, Wt, C] or [1, Ht, Wt, C]" % (tuple(t.shape),))
+        with self._stage("view_raster"):
+            mvp, c2ws_cpu, clip, _, rast = self._view_raster(c2ws, intrinsics, render_size, perspective)
+        with self._stage("screen_gbuffer"):
+            need_nrm = any(k in ("world_normal",) + ops.SCREEN_GBUFFERS_NRM_CAM for k in want)      # the normals are built lazily, on the host
+            out = ops.screen_gbuffer(rast, m.faces, m.vertices, v_nrm=m.vertex_normals if need_nrm else None, v_uv=m.uvs_2d if render_uv else None,
+                                     v_attr=v_attr if render_v_attr else None, maps=maps, c2ws=c2ws_cpu, want=["mask", "alpha"] + want,
+                                     background=background, filter=grid_interpolate_mode,
+                                     clip_w=clip[..., 3].contiguous() if render_z_depth else None)
+        out["mask"] = out["mask"].bool()[..., None]
         return out
 
     def compute_uv_mask(self, texture_size=2048):
