@@ -210,6 +210,14 @@ def test_ln_mod_and_sched():
     out = xd.float().cpu()
     assert torch.equal(out[64:], cond.float())
     assert (out[:64] - ref).abs().max().item() <= 2 ** -7 * ref.abs().max().item()
+    # one multiply, one add, one bf16 rounding: bit-equal to the float32 evaluation without contraction, which lies within half a bf16 ulp + 2^-23
+    # relative of the float64 value (tests/test_dit_glue_edges_gpu.py states the rule)
+    ds = torch.tensor(-0.0371, dtype=torch.float32)
+    exp = (lat[:64].float() + ds * v[:64].float()).to(BF).float()
+    assert torch.equal(out[:64], exp), "sched_step: %d elements differ from the float32 evaluation" % int((out[:64] != exp).sum())
+    e64 = lat[:64].double() + ds.double() * v[:64].double()
+    half_ulp = 2.0 ** (torch.floor(torch.log2(e64.abs().clamp_min(2.0 ** -126))) - 8)
+    assert bool(((exp.double() - e64).abs() <= half_ulp + 2.0 ** -23 * torch.maximum(e64.abs(), (ds.double() * v[:64].double()).abs())).all())
 
 
 def test_qkv_post():

@@ -361,7 +361,9 @@ __global__ __launch_bounds__(256) void ln_mod_kernel(LnModParams p) {
 
 extern "C" int utx_launch_ln_mod(const LnModParams* hp, hipStream_t stream) {
     LnModParams p = *hp;
+    if (!p.x || !p.shift || !p.scale) return -2;      // utx_plan_run comes here without utx_ln_mod's checks in front
     if (p.n_tok <= 0 || p.D <= 0 || (p.D & 7) || p.D > 4096 || (p.ldx & 7) || (p.ldy & 7)) return -2;
+    if (p.n_tok > 1 && (p.ldx < p.D || (!p.q && p.ldy < p.D) || (p.q && p.ldq < p.D))) return -2;      // rows that overlap
     if (p.q) {
         if (!p.qs || (p.D & 127) || (p.ldq & 7) || p.qs_row_blocks < (p.n_tok + 127) / 128 || ((uintptr_t)p.qs & 15) || ((uintptr_t)p.q & 7)) return -2;
         hipLaunchKernelGGL(ln_mod_kernel<true>, dim3((p.n_tok + 3) / 4), dim3(256), 0, stream, p);
@@ -423,7 +425,8 @@ __global__ __launch_bounds__(256) void sched_step_kernel(SchedParams p) {
 
 extern "C" int utx_launch_sched_step(const SchedParams* hp, hipStream_t stream) {
     SchedParams p = *hp;
-    if (p.n_total_elems <= 0 || (p.n_total_elems & 7) || (p.n_noise_elems & 7)) return -2;
+    if (!p.x || !p.v || p.n_total_elems <= 0 || (p.n_total_elems & 7) || (p.n_noise_elems & 7)) return -2;
+    if (p.n_noise_elems < 0 || p.n_noise_elems > p.n_total_elems) return -2;      // < 0: cond would be read at e + |n_noise| past its n_total elements
     long nchunk = p.n_total_elems >> 3;
     int blocks = (int)((nchunk + 255) / 256);
     if (blocks > 2048) blocks = 2048;

@@ -869,7 +869,9 @@ extern "C" int utx_launch_gemm_bf16(const GemmParams* hp, hipStream_t stream) {
 
 extern "C" int utx_launch_gemv_bf16(const GemvParams* hp, hipStream_t stream) {
     GemvParams p = *hp;
+    if (!p.x || !p.W || !p.y) return -2;      // utx_plan_run comes here without utx_gemv_bf16's checks in front
     if (p.M <= 0 || p.M > 8 || p.N <= 0 || p.K <= 0 || (p.K % 8) || (p.ldw & 7) || (p.ldx & 7)) return -2;
+    if ((p.M > 1 && (p.ldx < p.K || p.ldy < p.N)) || (p.N > 1 && p.ldw < p.K)) return -2;      // rows that overlap: row m's outputs would land in row m + 1's
     hipLaunchKernelGGL(gemv_bf16_kernel, dim3((p.N + 3) / 4), dim3(256), 0, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
