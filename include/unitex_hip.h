@@ -480,6 +480,22 @@ int utx_screen_gbuffer(utx_ctx* ctx, const float* rast, const int* faces, const 
                        int n_maps, const float* const* maps_host, const int* map_dims_host, int filter, int bg_kind, float bg_scalar,
                        const float* bg_v_attr, const float* bg_map_attr, unsigned want, void* const* outs_host, utx_stream stream);
 
+/* Atlas-space view projection: render_uv / render_map_attr of NVDiffRendererBase.simple_inverse_rendering (render/nvdiffrast/renderer_base.py:504-559)
+ * with alpha = coverage.  ONE launch for every texel of every view.  rast2d [H2D][W2D][4] is the atlas raster (16-byte aligned), faces [F][3],
+ * face_mask [B][F] uint8 (utx_visible_faces_*), v_ndc [B][V][2] the views' NDC xy per vertex (utx_transform_points).  Per (b, texel), tri = rast2d.w - 1:
+ *   vis = tri >= 0 && face_mask[b][tri];  uv [B][H2D][W2D][2] = vis ? interp(v_ndc[b]) (utx_interpolate's order) : (-1, -1);  uv_alpha [B][H2D][W2D][1] = vis.
+ * With map != null -- map [Bm][Hm][Wm][C] fp32, Bm = 1 (shared) or B (one image per view), C >= 1; rast_map [B][Hm][Wm][4], the views rasterised at the
+ * map's own size, of which only .w is read -- also map_attr [B][H2D][W2D][C]:
+ *   s = the map sampled at uv (filter: UTX_SGB_FILTER_*, the lookups of utx_screen_gbuffer; an invisible texel samples at (-1, -1));
+ *   cov = the nearest, zero-padded lookup of rast_map.w > 0 at uv;  uv_alpha = cov < 1 ? 0 : uv_alpha;
+ *   bg_kind NONE: map_attr = cov < 1 ? map[b or 0][0][0][:] : s;  SCALAR / VECTOR (bg [C]) / DENSE (bg [B][H2D][W2D][C]): map_attr = uv_alpha ? s : bg.
+ * uv is not gated by cov.  With map == null the map arguments are not read and map_attr is not written.  Stream-ordered, no workspace.
+ * Returns -2 for a null rast2d / faces / face_mask / v_ndc / uv / uv_alpha, a rast2d off a 16-byte boundary, F, V, B, H2D or W2D <= 0, and with a map:
+ * a null rast_map / map_attr, Bm not in {1, B}, Hm, Wm or C <= 0, an unknown filter or bg_kind, a VECTOR / DENSE background with a null bg. */
+int utx_uv_project(utx_ctx* ctx, const float* rast2d, const int* faces, int F, const unsigned char* face_mask, const float* v_ndc, int V, int B, int H2D,
+                   int W2D, const float* map, int Bm, int Hm, int Wm, int C, const float* rast_map, int filter, int bg_kind, float bg_scalar,
+                   const float* bg, float* uv, float* uv_alpha, float* map_attr, utx_stream stream);
+
 /* Image-based PBR shading of the turntable: PBRModel (texture/pbr/pbr.py:18-49, 91-130), NVDiffRendererPBR.render_base / render_pbr
  * (render/nvdiffrast/renderer_pbr.py:19-94) and the environment-light prefilters of the renderutils plugin (texture/pbr/renderutils/ops.py:398-465,
  * c_src/cubemap.cu:12-139, 174-298).  Cubemaps are [6][N][N][3] fp32; face s and its in-face coordinates (fx, fy) in [-1, 1] follow cube_to_dir:
@@ -589,6 +605,32 @@ int utx_bvh_trace(utx_ctx* ctx, utx_bvh* bvh, const float* rays_o, const float* 
 int utx_bvh_trace_count(utx_ctx* ctx, utx_bvh* bvh, const float* rays_o, const float* rays_d, long R, int* tid,
                         unsigned long long* visited, utx_stream stream);
 int utx_bvh_depth(utx_bvh* bvh);
+
+/* Face and vertex visibility of a camera batch: Mesh.get_visible_faces / get_visible_vertices (mesh/structure.py:801-857),
+ * NVDiffRendererBase.get_visible_faces / get_visible_vertices (render/nvdiffrast/renderer_base.py:65-99) and erode_face
+ * (geometry/triangle_topology/topology.py:12-25).  Masks are uint8 (0 / 1), [B][F] per face and [B][V] per vertex; B <= 65535.
+ * utx_visible_faces_rays: ONE launch for all B views behind a memset of mask.  One ray per (view, face) aimed at the face's centroid
+ *   ((v0 + v1) + v2) / 3: perspective != 0 from o = c2w[:3,3] along centroid - o, otherwise from centroid + 2 sqrt(3) c2w[:3,2] along -c2w[:3,2]
+ *   (c2ws [B][4][4], row-major).  The ray marks the face it hits FIRST -- the smallest t among the hits with t >= 0, ties to the smallest face id, no
+ *   backface culling: Embree's closest hit, not the last-hit-wins traversal of utx_bvh_trace -- which need not be the face it was aimed at; a face is
+ *   visible iff some ray of the view lands on it (the reference's scatter).  verts / faces are the arrays the tree was built from (F must equal the
+ *   tree's).  The packed (stackless) walk is used up to the depth rule of utx_bvh_trace, the stack walk beyond it or with UTX_VF_STACK_WALK; both
+ *   visit the nodes in one order and give equal masks.  Rays are issued in the tree's sorted leaf order (a wave's rays are neighbours in space);
+ *   UTX_VF_FACE_ORDER issues them in face order (same mask; for the node count).  visited (may be null): device counter the number of visited nodes is
+ *   ADDED to.
+ * utx_visible_faces_raster: the faces whose id + 1 appears in rast [B][H][W][4].w (ids outside [1, F] are ignored); memset + one launch.
+ * utx_erode_faces: in place, `depth` rounds of: a face stays set iff none of its vertices belongs to an unset face.  Two launches per round (a vertex
+ *   scatter, a face gather); vstamp [B][V] int32 is the caller's scratch (zeroed here).  depth <= 0 does nothing.
+ * utx_visible_vertices: out [B][V]: a vertex is set iff it belongs to a set face; memset + one launch.
+ * All stream-ordered.  Return -2 for a null operand, F <= 0, V <= 0, B <= 0 or > 65535, H or W <= 0, unknown flags, a tree of another F, and a tree deeper than 94
+ * levels on the stack walk (its stack holds 96 entries; an LBVH of 30 Morton bits and 32 index bits is at most 62 deep). */
+#define UTX_VF_STACK_WALK 1
+#define UTX_VF_FACE_ORDER 2
+int utx_visible_faces_rays(utx_ctx* ctx, utx_bvh* bvh, const float* verts, const int* faces, int F, const float* c2ws, int B, int perspective, int flags,
+                           unsigned char* mask, unsigned long long* visited, utx_stream stream);
+int utx_visible_faces_raster(utx_ctx* ctx, const float* rast, int B, int H, int W, int F, unsigned char* mask, utx_stream stream);
+int utx_erode_faces(utx_ctx* ctx, unsigned char* mask, const int* faces, int B, int F, int V, int depth, int* vstamp, utx_stream stream);
+int utx_visible_vertices(utx_ctx* ctx, const unsigned char* mask, const int* faces, int B, int F, int V, unsigned char* out, utx_stream stream);
 
 /* fused per-(view, texel) gather + visibility of uv_to_pcd (renderer_inverse.py:277-298,316-325) */
 typedef struct utx_backproject_desc {

@@ -211,6 +211,79 @@ __global__ __launch_bounds__(256) void bvh_trace_kernel(const int* info, const f
     tid[i] = bvh_trace_one(info, aabb, vert, faces, o, d);
 }
 
+// ---- face visibility by rays: Mesh.get_visible_faces of the reference (mesh/structure.py:801-844).  One ray per (view, face), aimed at the face's
+// centroid ((v0 + v1) + v2) / 3: perspective from the camera centre o = c2w[:3,3] along centroid - o, orthographic from centroid + 2 sqrt(3) c2w[:3,2]
+// along -c2w[:3,2].  The ray marks the face it hits FIRST (closest hit, bvh_device.h) -- not the face it was aimed at: that is the reference's scatter
+// of the primitive ids, so a face is visible iff some ray of the view lands on it.  mask [B][F] was zeroed by the launcher; the stores are plain byte
+// stores of the same value 1, so their order does not matter.
+// blockIdx.y is the view; thread i of a view takes the face order[i] -- the tree's sorted leaf order, so that the 64 rays of a wave aim at neighbours
+// in space and fetch the same nodes -- or face i when order is null.
+template <bool PACKED>
+__global__ __launch_bounds__(256) void visible_faces_rays_kernel(const float4* __restrict__ nodes, const float4* __restrict__ tris, const int* __restrict__ info,
+                                                                 const float* __restrict__ aabb, const float* __restrict__ vert, const int* __restrict__ faces,
+                                                                 const int* __restrict__ order, int F, const float* __restrict__ c2ws, int perspective,
+                                                                 unsigned char* mask, unsigned long long* visited) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int b = blockIdx.y;
+    unsigned nv = 0;
+    if (i < F) {
+        const int f = order ? order[i] : i;
+        const float* m = c2ws + 16 * (long)b;
+        const int* fv = faces + 3 * (long)f;
+        const float *v0 = vert + 3 * (long)fv[0], *v1 = vert + 3 * (long)fv[1], *v2 = vert + 3 * (long)fv[2];
+        float o[3], d[3];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const float c = ((v0[k] + v1[k]) + v2[k]) / 3.0f;
+            if (perspective) { o[k] = m[4 * k + 3]; d[k] = c - o[k]; }
+            else { o[k] = c + 3.4641016151377544f * m[4 * k + 2]; d[k] = -m[4 * k + 2]; }
+        }
+        const CloseRay r = close_ray(o, d);
+        const int hit = PACKED ? bvh_closest_packed(nodes, tris, r, nv) : bvh_closest_stack(info, aabb, vert, faces, r, nv);
+        if (hit >= 0) mask[(long)b * F + hit] = 1;
+    }
+    if (visited) {      // diagnostics (tools/bench_uv_project.py: nodes visited per ray): wave sum, one atomic per wave
+        for (int o = 32; o > 0; o >>= 1) nv += __shfl_xor(nv, o, 64);
+        if ((threadIdx.x & 63) == 0) atomicAdd(visited, (unsigned long long)nv);
+    }
+}
+
+// ---- face visibility by rasterisation: NVDiffRendererBase.get_visible_faces (render/nvdiffrast/renderer_base.py:77-81): the faces whose id appears in a
+// view's raster.  One thread per pixel of rast [B][H][W][4]; mask [B][F] zeroed by the launcher.
+__global__ __launch_bounds__(256) void visible_faces_raster_kernel(const float* __restrict__ rast, long npix, long total, int F, unsigned char* mask) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int id = (int)rast[4 * i + 3] - 1;
+    if (id >= 0 && id < F) mask[(i / npix) * F + id] = 1;
+}
+
+// ---- erode_face (geometry/triangle_topology/topology.py:12-25): a face stays set iff none of its vertices belongs to an unset face.  One round is two
+// launches: the unset faces stamp their vertices with the round's number, then every set face reads its three stamps.  The stamps grow from round to round, so
+// the scratch [B][V] (the caller's) is zeroed once, by the launcher.
+__global__ __launch_bounds__(256) void erode_scatter_kernel(const unsigned char* __restrict__ mask, const int* __restrict__ faces, int F, long V, int stamp, int* vstamp) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    const long b = blockIdx.y;
+    if (f >= F || mask[b * F + f]) return;
+    int* s = vstamp + b * V;
+    s[faces[3 * (long)f]] = stamp; s[faces[3 * (long)f + 1]] = stamp; s[faces[3 * (long)f + 2]] = stamp;
+}
+__global__ __launch_bounds__(256) void erode_gather_kernel(unsigned char* mask, const int* __restrict__ faces, int F, long V, int stamp, const int* __restrict__ vstamp) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    const long b = blockIdx.y;
+    if (f >= F || !mask[b * F + f]) return;
+    const int* s = vstamp + b * V;
+    if (s[faces[3 * (long)f]] == stamp || s[faces[3 * (long)f + 1]] == stamp || s[faces[3 * (long)f + 2]] == stamp) mask[b * F + f] = 0;
+}
+
+// ---- get_visible_vertices (renderer_base.py:87-99, structure.py:846-857): a vertex is set iff it belongs to a set face; out [B][V] zeroed by the launcher
+__global__ __launch_bounds__(256) void visible_vertices_kernel(const unsigned char* __restrict__ mask, const int* __restrict__ faces, int F, long V, unsigned char* out) {
+    const int f = blockIdx.x * blockDim.x + threadIdx.x;
+    const long b = blockIdx.y;
+    if (f >= F || !mask[b * F + f]) return;
+    unsigned char* o = out + b * V;
+    o[faces[3 * (long)f]] = 1; o[faces[3 * (long)f + 1]] = 1; o[faces[3 * (long)f + 2]] = 1;
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
@@ -366,5 +439,51 @@ extern "C" int utx_bvh_trace_impl(utx_bvh* b, const float* ro, const float* rd, 
     }
     if (visited) return -2;     // the node count is a diagnostic of the packed traversal
     hipLaunchKernelGGL(bvh_trace_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, stream, b->info, b->aabb, b->verts, b->faces, ro, rd, R, tid);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// flags: UTX_VF_STACK_WALK forces the stack walk (it is taken anyway when the tree is deeper than the packed walk's rule), UTX_VF_FACE_ORDER issues the
+// rays in face order instead of the tree's sorted leaf order (A/B of the node count; the mask is the same)
+extern "C" int utx_visible_faces_rays_impl(utx_bvh* b, const float* verts, const int* faces, int F, const float* c2ws, int B, int perspective, int flags,
+                                           unsigned char* mask, unsigned long long* visited, hipStream_t stream) {
+    if (!b || F <= 0 || F != b->F || B <= 0 || B > 65535) return -2;
+    const int depth = utx_bvh_depth_impl(b);
+    if (depth < 0) return -7;
+    const bool packed = depth <= UTX_BVH_PACKED_MAX_DEPTH && !(flags & 1);
+    if (!packed && depth + 2 > CLOSE_STACK) return -2;      // the stack walk holds at most depth + 1 entries: a deeper tree is refused, never walked with subtrees dropped
+    if (hipMemsetAsync(mask, 0, (size_t)B * F, stream) != hipSuccess) return -7;
+    const int* order = (flags & 2) ? nullptr : b->idx_sorted;
+    const dim3 g((unsigned)((F + 255) / 256), (unsigned)B), blk(256);
+    if (packed)
+        hipLaunchKernelGGL(visible_faces_rays_kernel<true>, g, blk, 0, stream, b->nodes, b->tris, b->info, b->aabb, verts, faces, order, F, c2ws, perspective, mask, visited);
+    else
+        hipLaunchKernelGGL(visible_faces_rays_kernel<false>, g, blk, 0, stream, b->nodes, b->tris, b->info, b->aabb, verts, faces, order, F, c2ws, perspective, mask, visited);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+extern "C" int utx_launch_visible_faces_raster(const float* rast, int B, int H, int W, int F, unsigned char* mask, hipStream_t stream) {
+    if (B <= 0 || H <= 0 || W <= 0 || F <= 0) return -2;
+    if (hipMemsetAsync(mask, 0, (size_t)B * F, stream) != hipSuccess) return -7;
+    const long npix = (long)H * W, total = npix * B;
+    hipLaunchKernelGGL(visible_faces_raster_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, rast, npix, total, F, mask);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+extern "C" int utx_launch_erode_faces(unsigned char* mask, const int* faces, int B, int F, int V, int depth, int* vstamp, hipStream_t stream) {
+    if (B <= 0 || B > 65535 || F <= 0 || V <= 0) return -2;
+    if (depth <= 0) return 0;
+    if (hipMemsetAsync(vstamp, 0, (size_t)B * V * sizeof(int), stream) != hipSuccess) return -7;
+    const dim3 g((unsigned)((F + 255) / 256), (unsigned)B), blk(256);
+    for (int round = 1; round <= depth; ++round) {
+        hipLaunchKernelGGL(erode_scatter_kernel, g, blk, 0, stream, (const unsigned char*)mask, faces, F, (long)V, round, vstamp);
+        hipLaunchKernelGGL(erode_gather_kernel, g, blk, 0, stream, mask, faces, F, (long)V, round, (const int*)vstamp);
+    }
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+extern "C" int utx_launch_visible_vertices(const unsigned char* mask, const int* faces, int B, int F, int V, unsigned char* out, hipStream_t stream) {
+    if (B <= 0 || B > 65535 || F <= 0 || V <= 0) return -2;
+    if (hipMemsetAsync(out, 0, (size_t)B * V, stream) != hipSuccess) return -7;
+    hipLaunchKernelGGL(visible_vertices_kernel, dim3((unsigned)((F + 255) / 256), (unsigned)B), dim3(256), 0, stream, mask, faces, F, (long)V, out);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }

@@ -188,6 +188,107 @@ __device__ __forceinline__ int bvh_trace_packet(const float4* __restrict__ nodes
     return hit_tid;
 }
 
+// ---- CLOSEST hit (utx_visible_faces_rays): what Mesh.get_visible_faces of the reference gets from Embree through open3d's RaycastingScene
+// (mesh/structure.py:801-844) -- the hit with the smallest t among those with t >= 0, no backface culling -- and none of the quirks above.  The direction
+// is NOT normalised (t is in units of |rd|, as Embree's): the order of the hits along a ray does not depend on the scale.  Ties in t go to the smallest
+// primitive id, so the result does not depend on the order in which the triangles are met.
+// The ray: origin, direction and the reciprocal direction of the slab test, formed once per ray; a zero component is replaced by 1e-30 (1 / 1e-30 is finite, so
+// (bb - ro) * inv is 0 or +-huge, never NaN).
+struct CloseRay { float o[3], d[3], inv[3]; };
+__device__ __forceinline__ CloseRay close_ray(const float* ro, const float* rd) {
+    CloseRay r;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { r.o[i] = ro[i]; r.d[i] = rd[i]; r.inv[i] = 1.0f / (rd[i] == 0.f ? 1e-30f : rd[i]); }
+    return r;
+}
+// slab test against [0, limit]; conservative: the far side is widened by 4e-7 (two ulp; Ize, "Robust BVH ray traversal", 2013), so that a box of no thickness
+// (an axis-aligned triangle) and a hit on a box face are not lost to the rounding of the three products
+__device__ __forceinline__ bool close_box(const CloseRay& r, float limit, const float* bb) {
+    float tmin = 0.f, tmax = limit;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const float t0 = (bb[i] - r.o[i]) * r.inv[i], t1 = (bb[3 + i] - r.o[i]) * r.inv[i];
+        tmin = fmaxf(tmin, fminf(t0, t1));
+        tmax = fminf(tmax, fmaxf(t0, t1) * 1.0000004f);
+    }
+    return tmin <= tmax;
+}
+// Moeller-Trumbore, both sides; t >= 0 only
+__device__ __forceinline__ bool close_tri(const CloseRay& r, const float* v0, const float* v1, const float* v2, float& t_out) {
+    const float E1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]};
+    const float E2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
+    float P[3]; cross3(r.d, E2, P);
+    const float det = dot3(E1, P);
+    if (det == 0.f) return false;
+    const float inv = 1.0f / det;
+    const float T[3] = {r.o[0] - v0[0], r.o[1] - v0[1], r.o[2] - v0[2]};
+    const float u = dot3(T, P) * inv;
+    if (!(u >= 0.f && u <= 1.f)) return false;
+    float Q[3]; cross3(T, E1, Q);
+    const float v = dot3(r.d, Q) * inv;
+    if (!(v >= 0.f && u + v <= 1.f)) return false;
+    const float t = dot3(E2, Q) * inv;
+    if (!(t >= 0.f)) return false;
+    t_out = t;
+    return true;
+}
+__device__ __forceinline__ void close_take(float t, int prim, float& closest, int& hit) {
+    if (t < closest || (t == closest && prim < hit)) { closest = t; hit = prim; }
+}
+// a subtree is skipped only if its box starts beyond the best hit by more than a part in a million: a triangle that TIES with the best hit is still tested
+#define CLOSE_LIMIT(closest) ((closest) * 1.000001f)
+
+// the packed walk (no stack: any depth would do; the launcher keeps the depth rule of the other traversals)
+__device__ __forceinline__ int bvh_closest_packed(const float4* __restrict__ nodes, const float4* __restrict__ tris, const CloseRay& r, unsigned& nv) {
+    float closest = __int_as_float(0x7f800000);
+    int hit = -1, nd = 0;
+    while (nd >= 0) {
+        const float4 a = nodes[2 * (long)nd], b = nodes[2 * (long)nd + 1];
+        const float bb[6] = {a.x, a.y, a.z, a.w, b.x, b.y};
+        const int link = __float_as_int(b.z), esc = __float_as_int(b.w);
+        ++nv;
+        if (!close_box(r, CLOSE_LIMIT(closest), bb)) { nd = esc; continue; }
+        if (link > 0) { nd = link; continue; }
+        const int prim = ~link;
+        const float4 t0 = tris[3 * (long)prim], t1 = tris[3 * (long)prim + 1], t2 = tris[3 * (long)prim + 2];
+        const float v0[3] = {t0.x, t0.y, t0.z}, v1[3] = {t1.x, t1.y, t1.z}, v2[3] = {t2.x, t2.y, t2.z};
+        float t;
+        if (close_tri(r, v0, v1, v2, t)) close_take(t, prim, closest, hit);
+        nd = esc;
+    }
+    return hit;
+}
+// the stack walk over the unpacked arrays, in the SAME order (first and second child pushed, the second popped first), with the same tests on the same
+// numbers: its result equals the packed walk's.  The walk holds at most depth + 1 entries; the launcher (utx_visible_faces_rays_impl) refuses a tree with
+// depth + 2 > CLOSE_STACK, so the guard in front of the push below never drops a subtree (a tree of 30 Morton bits + 32 index bits is at most 62 deep).
+#define CLOSE_STACK 96
+__device__ __forceinline__ int bvh_closest_stack(const int* __restrict__ info, const float* __restrict__ aabb, const float* __restrict__ vert,
+                                                 const int* __restrict__ faces, const CloseRay& r, unsigned& nv) {
+    int stack[CLOSE_STACK];
+    int count = 0;
+    stack[count++] = 0;
+    float closest = __int_as_float(0x7f800000);
+    int hit = -1;
+    while (count > 0) {
+        const int nd = stack[--count];
+        float bb[6];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) bb[k] = aabb[6 * (long)nd + k];
+        ++nv;
+        if (!close_box(r, CLOSE_LIMIT(closest), bb)) continue;
+        const int L = info[3 * (long)nd], R = info[3 * (long)nd + 1];
+        if (L != 0 || R != 0) {
+            if (count + 2 <= CLOSE_STACK) { stack[count++] = L; stack[count++] = R; }
+        } else {
+            const int prim = info[3 * (long)nd + 2];
+            const int* f = faces + 3 * (long)prim;
+            float t;
+            if (close_tri(r, vert + 3 * (long)f[0], vert + 3 * (long)f[1], vert + 3 * (long)f[2], t)) close_take(t, prim, closest, hit);
+        }
+    }
+    return hit;
+}
+
 #include <atomic>
 struct utx_bvh {
     int F;

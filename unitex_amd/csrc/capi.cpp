@@ -411,6 +411,20 @@ int utx_screen_gbuffer(utx_ctx* ctx, const float* rast, const int* faces, const 
                                                 (want & UTX_SGB_MAP_ATTR) ? n_maps : 0, maps_host, map_dims_host, filter, bg_kind, bg_scalar, bg_v_attr,
                                                 bg_map_attr, want, outs_host, (hipStream_t)stream));
 }
+int utx_uv_project(utx_ctx* ctx, const float* rast2d, const int* faces, int F, const unsigned char* face_mask, const float* v_ndc, int V, int B, int H2D,
+                   int W2D, const float* map, int Bm, int Hm, int Wm, int C, const float* rast_map, int filter, int bg_kind, float bg_scalar,
+                   const float* bg, float* uv, float* uv_alpha, float* map_attr, utx_stream stream) {
+    const char* const me = "utx_uv_project";
+    if (!rast2d || !faces || !face_mask || !v_ndc || !uv || !uv_alpha || ((uintptr_t)rast2d & 15)) return fail(ctx, -2, me);      // rast2d is read as float4
+    if (F <= 0 || V <= 0 || B <= 0 || H2D <= 0 || W2D <= 0) return fail(ctx, -2, me);
+    if (map) {
+        if (!rast_map || !map_attr || (Bm != 1 && Bm != B) || Hm <= 0 || Wm <= 0 || C <= 0) return fail(ctx, -2, me);
+        if (filter < UTX_SGB_FILTER_BILINEAR || filter > UTX_SGB_FILTER_NVDIFFRAST || bg_kind < UTX_SGB_BG_NONE || bg_kind > UTX_SGB_BG_DENSE) return fail(ctx, -2, me);
+        if ((bg_kind == UTX_SGB_BG_VECTOR || bg_kind == UTX_SGB_BG_DENSE) && !bg) return fail(ctx, -2, me);
+    }
+    UTX_CALL(ctx, me, utx_launch_uv_project(rast2d, faces, F, face_mask, v_ndc, V, B, H2D, W2D, map, Bm, Hm, Wm, C, rast_map, map ? filter : 0, bg_kind, bg_scalar, bg, uv,
+                                            uv_alpha, map ? map_attr : nullptr, (hipStream_t)stream));
+}
 int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws, int n_views, float* out, utx_stream stream) {
     if (!nrm || !c2ws || !out) return fail(ctx, -2, "utx_camera_normals");
     UTX_CALL(ctx, "utx_camera_normals", utx_launch_camera_normals(nrm, V, c2ws, n_views, out, (hipStream_t)stream));
@@ -504,6 +518,25 @@ int utx_bvh_trace_count(utx_ctx* ctx, utx_bvh* bvh, const float* ro, const float
     UTX_CALL(ctx, "utx_bvh_trace_count", utx_bvh_trace_impl(bvh, ro, rd, R, tid, visited, 0, (hipStream_t)stream));
 }
 int utx_bvh_depth(utx_bvh* bvh) { return bvh ? utx_bvh_depth_impl(bvh) : -2; }
+int utx_visible_faces_rays(utx_ctx* ctx, utx_bvh* bvh, const float* verts, const int* faces, int F, const float* c2ws, int B, int perspective, int flags,
+                           unsigned char* mask, unsigned long long* visited, utx_stream stream) {
+    const char* const me = "utx_visible_faces_rays";
+    if (!bvh || !verts || !faces || !c2ws || !mask) return fail(ctx, -2, me);
+    if (F <= 0 || B <= 0 || B > 65535 || (flags & ~(UTX_VF_STACK_WALK | UTX_VF_FACE_ORDER))) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_visible_faces_rays_impl(bvh, verts, faces, F, c2ws, B, perspective, flags, mask, visited, (hipStream_t)stream));
+}
+int utx_visible_faces_raster(utx_ctx* ctx, const float* rast, int B, int H, int W, int F, unsigned char* mask, utx_stream stream) {
+    if (!rast || !mask || B <= 0 || H <= 0 || W <= 0 || F <= 0) return fail(ctx, -2, "utx_visible_faces_raster");
+    UTX_CALL(ctx, "utx_visible_faces_raster", utx_launch_visible_faces_raster(rast, B, H, W, F, mask, (hipStream_t)stream));
+}
+int utx_erode_faces(utx_ctx* ctx, unsigned char* mask, const int* faces, int B, int F, int V, int depth, int* vstamp, utx_stream stream) {
+    if (!mask || !faces || B <= 0 || B > 65535 || F <= 0 || V <= 0 || (depth > 0 && !vstamp)) return fail(ctx, -2, "utx_erode_faces");
+    UTX_CALL(ctx, "utx_erode_faces", utx_launch_erode_faces(mask, faces, B, F, V, depth, vstamp, (hipStream_t)stream));
+}
+int utx_visible_vertices(utx_ctx* ctx, const unsigned char* mask, const int* faces, int B, int F, int V, unsigned char* out, utx_stream stream) {
+    if (!mask || !faces || !out || B <= 0 || B > 65535 || F <= 0 || V <= 0) return fail(ctx, -2, "utx_visible_vertices");
+    UTX_CALL(ctx, "utx_visible_vertices", utx_launch_visible_vertices(mask, faces, B, F, V, out, (hipStream_t)stream));
+}
 int utx_backproject(utx_ctx* ctx, const utx_backproject_desc* d, utx_bvh* bvh, utx_stream stream) {
     if (!d || !bvh || !d->rast2d || !d->verts || !d->faces || !d->fnormal || !d->vndc || !d->dirs || !d->images ||
         !d->color || !d->rayvis || !d->alphaok || d->view_begin < 0 || d->view_begin + d->view_count > d->n_views)

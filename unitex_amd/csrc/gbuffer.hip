@@ -1,5 +1,5 @@
 // Geometry buffers (gfx950): the screen-space ones of the orbit video (utx_gbuffer_shade, utx_gbuffer_range, utx_camera_normals) and the atlas-space
-// ones of simple_inverse_rendering (utx_uv_gbuffer), and the screen-space buffers of a camera batch of simple_rendering (utx_screen_gbuffer).  All interpolate with shade_device.h's sd_interp, utx_interpolate's (a0*u + a1*v) + a2*w, and
+// ones of simple_inverse_rendering (utx_uv_gbuffer, and utx_uv_project: its projection of the camera views into the atlas), and the screen-space buffers of a camera batch of simple_rendering (utx_screen_gbuffer).  All interpolate with shade_device.h's sd_interp, utx_interpolate's (a0*u + a1*v) + a2*w, and
 // normalise with its F.normalize, so a covered pixel's value is bit-identical to interpolate_kernel's wherever it is computed.
 //
 // HBM-bound.  Plain vector loads and stores, no LDS, no scratch, no inline assembly; atomics only in the range reduction.  Built with -ffp-contract=off
@@ -467,5 +467,83 @@ extern "C" int utx_launch_screen_gbuffer(const float* rast, const int* tri, cons
     if (filter == 0) hipLaunchKernelGGL(screen_gbuffer_kernel<0>, g, blk, 0, stream, a);
     else if (filter == 1) hipLaunchKernelGGL(screen_gbuffer_kernel<1>, g, blk, 0, stream, a);
     else hipLaunchKernelGGL(screen_gbuffer_kernel<2>, g, blk, 0, stream, a);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// ---- atlas-space view projection: render_uv / render_map_attr of NVDiffRendererBase.simple_inverse_rendering (render/nvdiffrast/renderer_base.py:504-559)
+// with alpha = coverage (no dr.antialias), every texel of every view in ONE launch.
+//
+// One thread per (view, texel) of the atlas raster rast2d [H2D][W2D][4], x fastest.  With tri = rast2d.w - 1:
+//   vis       tri >= 0 and face_mask[b][tri]                     (:513-520: the raster with the faces the view does not see taken out)
+//   uv        vis ? interp(v_ndc[b]) : (-1, -1)                  (:527-536; v_ndc = the view's NDC xy per vertex, utx_transform_points)
+//   uv_alpha  vis                                                (:524)
+// and with a map [Bm][Hm][Wm][C] (Bm = 1: shared, Bm = B: one image per view) and rast_map [B][Hm][Wm][4], the views rasterised at the map's size (:544):
+//   s         the map sampled at uv with FILTER (sgb_sample_map above: the lookups of utx_screen_gbuffer); for an invisible texel that is the
+//             sample at (-1, -1), as in the reference
+//   cov       grid_sample(nearest, zero padding) of the view's coverage rast_map.w > 0 at uv (:545-546): only .w is read, straight from the raster
+//   uv_alpha  cov < 1 ? 0 : uv_alpha                             (:547)
+//   map_attr  with a background: uv_alpha ? s : bg (:548-554, a lerp with a weight of 0 or 1);  without: cov < 1 ? map[b or 0][0][0][:] : s  (:556)
+// uv itself is not gated by cov.  The atlas record is read once per view; no [B][H][W][4] raster of the visible faces is ever written.
+struct UvProjectArgs {
+    const float4* rast2d; const int* tri; const unsigned char* face_mask; const float* v_ndc;
+    const float* map; const float* rast_map; const float* bg;
+    long F, V, npix, total;
+    int Bm, Hm, Wm, C, bg_kind;
+    float bg_scalar;
+    float *uv, *uv_alpha, *map_attr;
+};
+
+template <int FILTER>
+__global__ __launch_bounds__(256) void uv_project_kernel(UvProjectArgs a) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.total) return;
+    const long b = i / a.npix;
+    const float4 r = a.rast2d[i - b * a.npix];
+    const int id = (int)r.w - 1;
+    const bool vis = id >= 0 && id < a.F && a.face_mask[b * a.F + id] != 0;
+    float g[2] = {-1.0f, -1.0f};
+    if (vis) {
+        const float u = r.x, v = r.y, w = sd_bary_w(u, v);
+        const float* n = a.v_ndc + 2 * a.V * b;
+        sd_interp<2>(n + 2 * (long)a.tri[3 * id + 0], n + 2 * (long)a.tri[3 * id + 1], n + 2 * (long)a.tri[3 * id + 2], u, v, w, g);
+    }
+    a.uv[2 * i] = g[0]; a.uv[2 * i + 1] = g[1];
+    bool alpha = vis;
+    if (a.map_attr) {
+        const long msize = (long)a.Hm * a.Wm;
+        const float* m = a.map + (a.Bm > 1 ? b : 0) * msize * a.C;
+        const long o = grid_nearest(a.Hm, a.Wm, g[0], g[1]);
+        const bool cov = o >= 0 && a.rast_map[4 * (b * msize + o) + 3] > 0.0f;
+        alpha = alpha && cov;
+        float* out = a.map_attr + i * a.C;
+        if (a.bg_kind != SGB_BG_NONE && !alpha) {
+            for (int c = 0; c < a.C; ++c)
+                out[c] = a.bg_kind == SGB_BG_SCALAR ? a.bg_scalar : a.bg_kind == SGB_BG_VECTOR ? a.bg[c] : a.bg[i * a.C + c];
+        } else if (a.bg_kind == SGB_BG_NONE && !cov) {
+            for (int c = 0; c < a.C; ++c) out[c] = m[c];
+        } else {
+            sgb_sample_map<FILTER>(m, a.Hm, a.Wm, a.C, g[0], g[1], out);
+        }
+    }
+    a.uv_alpha[i] = alpha ? 1.0f : 0.0f;
+}
+
+// the arguments were checked by utx_uv_project (capi.cpp); map == nullptr: uv and uv_alpha only
+extern "C" int utx_launch_uv_project(const float* rast2d, const int* tri, int F, const unsigned char* face_mask, const float* v_ndc, int V, int B, int H2D, int W2D,
+                                     const float* map, int Bm, int Hm, int Wm, int C, const float* rast_map, int filter, int bg_kind, float bg_scalar,
+                                     const float* bg, float* uv, float* uv_alpha, float* map_attr, hipStream_t stream) {
+    if (B <= 0 || H2D <= 0 || W2D <= 0 || F <= 0 || V <= 0 || filter < 0 || filter > 2) return -2;
+    UvProjectArgs a = {};
+    a.rast2d = (const float4*)rast2d; a.tri = tri; a.face_mask = face_mask; a.v_ndc = v_ndc;
+    a.F = F; a.V = V; a.npix = (long)H2D * W2D; a.total = a.npix * B;
+    a.uv = uv; a.uv_alpha = uv_alpha;
+    if (map) {
+        a.map = map; a.rast_map = rast_map; a.bg = bg; a.Bm = Bm; a.Hm = Hm; a.Wm = Wm; a.C = C; a.bg_kind = bg_kind; a.bg_scalar = bg_scalar;
+        a.map_attr = map_attr;
+    }
+    const dim3 g((unsigned)((a.total + 255) / 256)), blk(256);
+    if (filter == 0) hipLaunchKernelGGL(uv_project_kernel<0>, g, blk, 0, stream, a);
+    else if (filter == 1) hipLaunchKernelGGL(uv_project_kernel<1>, g, blk, 0, stream, a);
+    else hipLaunchKernelGGL(uv_project_kernel<2>, g, blk, 0, stream, a);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }

@@ -149,6 +149,9 @@ int utx_launch_uv_gbuffer(const float* rast, const int* tri, const float* v_pos,
 int utx_launch_screen_gbuffer(const float* rast, const int* tri, const float* v_pos, const float* v_nrm, const float* v_uv, const float* v_attr, int Ca, const float* clip_w,
                               const float* v_pos_cam, const float* v_nrm_cam, int V, int B, int H, int W, int n_maps, const float* const* maps_host, const int* map_dims_host,
                               int filter, int bg_kind, float bg_scalar, const float* bg_v_attr, const float* bg_map_attr, unsigned want, void* const* outs_host, hipStream_t stream);
+int utx_launch_uv_project(const float* rast2d, const int* tri, int F, const unsigned char* face_mask, const float* v_ndc, int V, int B, int H2D, int W2D, const float* map,
+                          int Bm, int Hm, int Wm, int C, const float* rast_map, int filter, int bg_kind, float bg_scalar, const float* bg, float* uv, float* uv_alpha,
+                          float* map_attr, hipStream_t stream);
 // pbr.hip
 int utx_cubemap_table_impl(int N, float costheta_cutoff, float* texels_host, float* tiles_host);
 int utx_launch_latlong_to_cubemap(const float* lat, int Hi, int Wi, int N, float* out, hipStream_t stream);
@@ -174,6 +177,11 @@ void utx_bvh_free_impl(utx_bvh* b);
 int utx_bvh_arrays_impl(utx_bvh* b, int** info, float** aabb, unsigned** codes_sorted, int** idx_sorted);
 int utx_bvh_trace_impl(utx_bvh* b, const float* ro, const float* rd, long R, int* tid, unsigned long long* visited, int force_stack, hipStream_t stream);
 int utx_bvh_depth_impl(utx_bvh* b);
+int utx_visible_faces_rays_impl(utx_bvh* b, const float* verts, const int* faces, int F, const float* c2ws, int B, int perspective, int flags, unsigned char* mask,
+                                unsigned long long* visited, hipStream_t stream);
+int utx_launch_visible_faces_raster(const float* rast, int B, int H, int W, int F, unsigned char* mask, hipStream_t stream);
+int utx_launch_erode_faces(unsigned char* mask, const int* faces, int B, int F, int V, int depth, int* vstamp, hipStream_t stream);
+int utx_launch_visible_vertices(const unsigned char* mask, const int* faces, int B, int F, int V, unsigned char* out, hipStream_t stream);
 int utx_launch_backproject(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_backproject_vis(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_composite_winner(const void* vis, int n_views, const int* order, int n_order, long T, void* winner, hipStream_t stream);

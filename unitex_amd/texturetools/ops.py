@@ -312,6 +312,114 @@ def screen_gbuffer(rast, faces, v_pos, v_nrm=None, v_uv=None, v_attr=None, maps=
     return out
 
 
+def _u8(t):
+    assert t.is_cuda and t.dtype == U8 and t.is_contiguous(), "expected a contiguous CUDA uint8 tensor"
+    return t
+
+
+def visible_faces_rays(bvh, c2ws, perspective=True, force_stack=False, face_order=False, count=False):
+    """utx_visible_faces_rays: Mesh.get_visible_faces of the reference on the tree `bvh` (ops.BVH): c2ws [B,4,4] -> mask uint8 [B,F].  One ray per
+    (view, face) aimed at the face's centroid marks the face it hits first (closest hit, t >= 0, ties to the smallest id, no backface culling).
+    force_stack: the stack walk instead of the packed one (equal masks); face_order: rays in face order instead of the tree's sorted leaf order
+    (equal masks); count: also return the number of tree nodes the rays visited."""
+    c2ws = _f(c2ws)
+    if c2ws.dim() != 3 or tuple(c2ws.shape[1:]) != (4, 4) or c2ws.shape[0] < 1:
+        raise ValueError("visible_faces_rays: c2ws is %s, expected [B >= 1, 4, 4]" % (tuple(c2ws.shape),))
+    ctx = bvh.ctx
+    B, F = c2ws.shape[0], bvh.faces.shape[0]
+    mask = torch.empty(B, F, dtype=U8, device=c2ws.device)
+    visited = torch.zeros(1, dtype=torch.int64, device=c2ws.device) if count else None
+    ctx.check(ctx.lib.utx_visible_faces_rays(ctx.handle, bvh.handle, ptr(bvh.verts), ptr(bvh.faces), F, ptr(c2ws), B, int(bool(perspective)),
+                                             (1 if force_stack else 0) | (2 if face_order else 0), ptr(mask), ptr(visited) if count else None, ctx.stream()))
+    return (mask, int(visited.item())) if count else mask
+
+
+def visible_faces_raster(rast, F):
+    """utx_visible_faces_raster: rast [B,H,W,4] -> mask uint8 [B,F] of the faces whose id appears in a view's raster (renderer_base.py:77-81)"""
+    assert rast.dim() == 4 and rast.shape[3] == 4, "rast is [B, H, W, 4]"
+    ctx = get_ctx(rast.device.index)
+    B, H, W = rast.shape[:3]
+    mask = torch.empty(B, int(F), dtype=U8, device=rast.device)
+    ctx.check(ctx.lib.utx_visible_faces_raster(ctx.handle, ptr(_f(rast)), B, H, W, int(F), ptr(mask), ctx.stream()))
+    return mask
+
+
+def erode_faces(mask, faces, V, depth=1):
+    """utx_erode_faces: erode_face of the reference (topology.py:12-25) on every row of mask uint8 [B,F]: `depth` times, a face stays set iff none of
+    its vertices belongs to an unset face.  Returns a new mask."""
+    assert mask.dim() == 2 and mask.shape[1] == faces.shape[0], "mask is [B, F]"
+    out = _u8(mask).clone()
+    if depth <= 0:
+        return out
+    ctx = get_ctx(mask.device.index)
+    B, F = mask.shape
+    vstamp = torch.empty(B, int(V), dtype=I32, device=mask.device)
+    ctx.check(ctx.lib.utx_erode_faces(ctx.handle, ptr(out), ptr(_i(faces)), B, F, int(V), int(depth), ptr(vstamp), ctx.stream()))
+    return out
+
+
+def visible_vertices(mask, faces, V):
+    """utx_visible_vertices: mask uint8 [B,F] -> uint8 [B,V]: a vertex is set iff it belongs to a set face"""
+    assert mask.dim() == 2 and mask.shape[1] == faces.shape[0], "mask is [B, F]"
+    ctx = get_ctx(mask.device.index)
+    B, F = mask.shape
+    out = torch.empty(B, int(V), dtype=U8, device=mask.device)
+    ctx.check(ctx.lib.utx_visible_vertices(ctx.handle, ptr(_u8(mask)), ptr(_i(faces)), B, F, int(V), ptr(out), ctx.stream()))
+    return out
+
+
+def uv_project(rast2d, faces, face_mask, v_ndc, map_attr=None, rast_map=None, filter="bilinear", background=None):
+    """utx_uv_project, the atlas-space view projection in one launch: rast2d [H,W,4] (the atlas raster), faces [F,3] int32, face_mask uint8 [B,F]
+    (visible_faces_*), v_ndc [B,V,2] (transform_points) -> dict: 'uv' [B,H,W,2] (the view's NDC of the texel's surface point, -1 where the view does not
+    see it) and 'uv_alpha' [B,H,W,1]; with map_attr [Bm,Hm,Wm,C] (Bm = 1 or B) and rast_map [B,Hm,Wm,4] (the views rasterised at the map's size) also
+    'map_attr' [B,H,W,C], and uv_alpha additionally needs the view's coverage at uv.  filter: SCREEN_FILTERS; background: None (texels without coverage
+    take the map's texel [0, 0]), a number, or a tensor that broadcasts to [B,H,W,C] (it fills the texels with uv_alpha = 0)."""
+    if filter not in SCREEN_FILTERS:
+        raise ValueError("uv_project: filter %r (known: %s)" % (filter, ", ".join(SCREEN_FILTERS)))
+    assert rast2d.dim() == 3 and rast2d.shape[2] == 4 and faces.shape[1] == 3, "rast2d is [H, W, 4], faces [F, 3]"
+    H, W = rast2d.shape[:2]
+    F = faces.shape[0]
+    if face_mask.dim() != 2 or face_mask.shape[1] != F or face_mask.shape[0] < 1:
+        raise ValueError("uv_project: face_mask is %s, expected [B >= 1, F = %d]" % (tuple(face_mask.shape), F))
+    B = face_mask.shape[0]
+    if v_ndc.dim() != 3 or v_ndc.shape[0] != B or v_ndc.shape[2] != 2:
+        raise ValueError("uv_project: v_ndc is %s, expected [B = %d, V, 2]" % (tuple(v_ndc.shape), B))
+    V = v_ndc.shape[1]
+    dev = rast2d.device
+    Bm = Hm = Wm = Cm = kind = 0
+    scalar, bg = 0.0, None
+    if map_attr is not None:
+        if map_attr.dim() != 4 or min(map_attr.shape) < 1 or map_attr.shape[0] not in (1, B):
+            raise ValueError("uv_project: map_attr is %s, expected [1 or B = %d, Hm, Wm, C] with no empty side" % (tuple(map_attr.shape), B))
+        Bm, Hm, Wm, Cm = map_attr.shape
+        if rast_map is None or tuple(rast_map.shape) != (B, Hm, Wm, 4):
+            raise ValueError("uv_project: rast_map is %s, expected the views' rasters at the map's size %s" %
+                             (None if rast_map is None else tuple(rast_map.shape), (B, Hm, Wm, 4)))
+        if background is not None:
+            if isinstance(background, (int, float)):
+                kind, scalar = 1, float(background)
+            elif isinstance(background, torch.Tensor):
+                bgt = background.to(dev, F32)
+                kind = 2 if bgt.dim() <= 1 else 3
+                try:
+                    bg = bgt.expand(Cm).contiguous() if kind == 2 else bgt.expand(B, H, W, Cm).contiguous()
+                except RuntimeError:
+                    raise ValueError("uv_project: background %s does not broadcast to %s" % (tuple(bgt.shape), (B, H, W, Cm)))
+            else:
+                raise ValueError("uv_project: background is %r: expected None, a number or a tensor" % type(background))
+    ctx = get_ctx(dev.index)
+    out = {"uv_alpha": torch.empty(B, H, W, 1, dtype=F32, device=dev), "uv": torch.empty(B, H, W, 2, dtype=F32, device=dev)}
+    if map_attr is not None:
+        out["map_attr"] = torch.empty(B, H, W, Cm, dtype=F32, device=dev)
+    if H * W == 0:
+        return out
+    opt = lambda t: ptr(_f(t)) if t is not None else None
+    ctx.check(ctx.lib.utx_uv_project(ctx.handle, ptr(_f(rast2d)), ptr(_i(faces)), F, ptr(_u8(face_mask)), ptr(_f(v_ndc)), V, B, H, W, opt(map_attr), Bm, Hm, Wm, Cm,
+                                     opt(rast_map), SCREEN_FILTERS[filter], kind, scalar, opt(bg), ptr(out["uv"]), ptr(out["uv_alpha"]),
+                                     ptr(out["map_attr"]) if map_attr is not None else None, ctx.stream()))
+    return out
+
+
 def cubemap_tables(N, costheta_cutoff=None, device="cuda"):
     """utx_cubemap_table: (texels [6,N,N,4] = unit direction + pixel_area, tiles [6,nt,nt,4] or None) on `device`, built on the host in fp64.
     Runs without a GPU when device is 'cpu' (the tests' oracle reads the same table)."""

@@ -37,6 +37,9 @@ from . import camera, meshes, ops
 PRIORITY = [0, 3, 4, 1, 2, 5]  # frtbld -> f, b, l, r, t, d  (reference renderer_inverse.py:44)
 
 
+_UNSET = object()      # 'the keyword was not passed' (simple_inverse_rendering takes intrinsics only with render_uv)
+
+
 def _check_seam_sizes(k_boundary, k_boundary_blur):
     """the seam windows of bake_mv_to_uv_reproject_blur: 2 (k // 2) + 1 wide, so any k >= 0; radii above ops.SEAM_RADIUS_MAX are not built"""
     for name, k in (("reproject_kernel_size_boundary", k_boundary), ("reproject_kernel_size_boundary_blur", k_boundary_blur)):
@@ -296,12 +299,13 @@ class NVDiffRendererInverse:
 
     # flag of simple_inverse_rendering -> key of the returned dict, camera-independent first
     _UV_FLAGS = ("world_normal", "world_position", "camera_normal", "camera_position", "distance", "z_depth", "ray_direction", "cos_ray_normal")
-    _UV_FLAGS_UNBUILT = ("render_voxel_attr", "render_uv", "render_map_attr", "render_all_point_cloud", "render_visible_point_cloud")
+    _UV_FLAGS_UNBUILT = ("render_voxel_attr", "render_all_point_cloud", "render_visible_point_cloud")
 
     def simple_inverse_rendering(self, c2ws=None, texture_size=2048, render_world_normal=False, render_world_position=False,
                                  render_camera_normal=False, render_camera_position=False, render_distance=False, render_z_depth=False,
                                  render_ray_direction=False, render_cos_ray_normal=False, enable_antialis=True, render_v_attr=False, v_attr=None,
-                                 background=None, **kwargs):
+                                 background=None, intrinsics=_UNSET, perspective=True, map_attr=None, render_uv=False, render_map_attr=False,
+                                 grid_interpolate_mode="bilinear", visible_faces="rays", **kwargs):
         """NVDiffRendererBase.simple_inverse_rendering (render/nvdiffrast/renderer_base.py:352-489) on the mesh of update_from_file: the geometry
         buffers rendered into the UV atlas instead of onto a screen, all of them in one kernel launch (ops.uv_gbuffer).  Returns the reference's
         dict: 'mask' bool [1,H,W,1], 'alpha' float32 [1,H,W,1] and, per flag, 'world_normal' / 'world_position' [1,H,W,3] and, per camera of
@@ -313,15 +317,53 @@ class NVDiffRendererInverse:
         (ops.screen_gbuffer on the atlas raster as a batch of one), then the background rule of simple_rendering: None leaves the interpolated value
         (0 outside the charts), a number or a tensor that broadcasts to [1,H,W,Ca] fills the uncovered texels.
         A camera-dependent flag without c2ws raises ValueError, and so does a v_attr that is not [V,Ca]; render_v_attr with no v_attr at all is
-        refused like an unbuilt flag (NotImplementedError: the mesh has no attribute of its own to render); render_uv and render_map_attr
-        (they need Mesh.get_visible_faces and read a rebound batch_size, :446, :514; back-projection is this build's answer to them),
-        render_voxel_attr, render_all_point_cloud and render_visible_point_cloud are not built and raise NotImplementedError when set; any other
-        keyword is a TypeError."""
+        refused like an unbuilt flag (NotImplementedError: the mesh has no attribute of its own to render); render_voxel_attr,
+        render_all_point_cloud and render_visible_point_cloud are not built and raise NotImplementedError when set; any other keyword is a TypeError.
+        render_uv (:504-536) projects the cameras c2ws [B,4,4] / intrinsics [B,3,3] into the atlas: 'uv_alpha' [B,H,W,1], 1 on the texels whose
+        face the view sees, and 'uv' [B,H,W,2], the view's NDC of the texel's surface point (-1 elsewhere).  The faces a view sees come from
+        get_visible_faces: visible_faces='rays' (the reference's Mesh.get_visible_faces) or 'raster' (its commented-out twin, :512), which
+        rasterises at the size of map_attr and therefore needs one.  perspective replaces the reference's enable_perspective() /
+        enable_orthogonal() state, as in simple_rendering; intrinsics is taken only with render_uv -- nothing else projects -- and is a
+        TypeError without it.  render_map_attr (:538-559) adds 'map_attr' [B,H,W,C]: map_attr [Hm,Wm,C], [1,Hm,Wm,C] or [B,Hm,Wm,C] (one image
+        per view) sampled at 'uv' with grid_interpolate_mode ('bilinear' | 'nearest' | 'nvdiffrast', as simple_rendering); the views are
+        rasterised once more at the map's size and 'uv_alpha' drops to 0 where the view's coverage, looked up at uv, is missing; background
+        None puts the map's texel [0, 0] there, a number or a tensor that broadcasts to [B,H,W,C] fills every texel with uv_alpha = 0.  One
+        kernel launch (ops.uv_project) for all views.  render_uv together with the camera-dependent geometry flags equals the separate calls
+        (the reference cannot make that call: :446 rebinds batch_size to a torch.Size, which :514 then hands to Tensor.tile).
+        render_uv without cameras and render_map_attr without render_uv raise NotImplementedError; c2ws without intrinsics, render_map_attr
+        without map_attr, a map of the wrong rank or of a batch that is neither 1 nor B, an unknown visible_faces or grid_interpolate_mode
+        raise ValueError."""
         for k_, v_ in kwargs.items():
             if k_ not in self._UV_FLAGS_UNBUILT:
                 raise TypeError("simple_inverse_rendering() got an unexpected keyword argument %r" % k_)
             if v_:
                 raise NotImplementedError("simple_inverse_rendering(%s=%r) is not built" % (k_, v_))
+        if intrinsics is not _UNSET and not render_uv:
+            raise TypeError("simple_inverse_rendering() takes intrinsics only with render_uv=True: no other buffer projects")
+        if render_map_attr and not render_uv:
+            raise NotImplementedError("simple_inverse_rendering(render_map_attr=True) without render_uv is not built: the map is sampled at 'uv'")
+        if render_uv:
+            if c2ws is None:
+                raise NotImplementedError("simple_inverse_rendering(render_uv=True) without cameras is not built: pass c2ws and intrinsics")
+            if intrinsics is _UNSET or intrinsics is None:
+                raise ValueError("simple_inverse_rendering(render_uv=True) projects the cameras: intrinsics is required")
+            if grid_interpolate_mode not in ops.SCREEN_FILTERS:
+                raise ValueError("simple_inverse_rendering(grid_interpolate_mode=%r): one of %s" % (grid_interpolate_mode, ", ".join(ops.SCREEN_FILTERS)))
+            if visible_faces not in ("rays", "raster"):
+                raise ValueError("simple_inverse_rendering(visible_faces=%r): 'rays' or 'raster'" % (visible_faces,))
+            n_views = torch.as_tensor(c2ws).shape[0]
+            if render_map_attr:
+                if map_attr is None:
+                    raise ValueError("simple_inverse_rendering(render_map_attr=True) needs map_attr")
+                map_attr = torch.as_tensor(map_attr, dtype=torch.float32)
+                if map_attr.dim() == 3:
+                    map_attr = map_attr[None]
+                if map_attr.dim() != 4 or min(map_attr.shape) < 1:
+                    raise ValueError("simple_inverse_rendering: map_attr is %s, expected [Hm, Wm, C], [1, Hm, Wm, C] or [B, Hm, Wm, C]" % (tuple(map_attr.shape),))
+                if map_attr.shape[0] not in (1, n_views):
+                    raise ValueError("simple_inverse_rendering: map_attr holds %d images, the call has %d cameras: 1 or one per camera" % (map_attr.shape[0], n_views))
+            elif visible_faces == "raster":
+                raise ValueError("simple_inverse_rendering(visible_faces='raster') rasterises at the size of map_attr: set render_map_attr and pass one")
         if render_v_attr and v_attr is None:      # the mesh carries no per-vertex attribute of its own that could stand in
             raise NotImplementedError("simple_inverse_rendering(render_v_attr=True) without v_attr is not built: pass v_attr [V, Ca]")
         flags = dict(world_normal=render_world_normal, world_position=render_world_position, camera_normal=render_camera_normal,
@@ -342,9 +384,63 @@ class NVDiffRendererInverse:
             out = ops.uv_gbuffer(rast2d, m.faces, m.vertices, m.vertex_normals if need_nrm else None, c2ws=c2ws, want=["mask", "alpha"] + want)
             if render_v_attr:
                 out["v_attr"] = ops.screen_gbuffer(rast2d[None], m.faces, m.vertices, v_attr=v_attr, want=("v_attr",), background=background)["v_attr"]
+        if render_uv:
+            rast_map = None
+            if render_map_attr:
+                map_attr = map_attr.to(self.device).contiguous()
+                with self._stage("view_raster"):
+                    _, _, _, ndc, rast_map = self._view_raster(c2ws, intrinsics, tuple(map_attr.shape[1:3]), perspective)
+            else:
+                ndc = ops.transform_points(m.vertices, self._mvp(c2ws, intrinsics, perspective)[0])[1]
+            with self._stage("visible_faces"):
+                face_mask = self._visible_faces(c2ws, perspective, visible_faces, rast_map, 0)
+            with self._stage("uv_project"):
+                out.update(ops.uv_project(rast2d, m.faces, face_mask, ndc, map_attr if render_map_attr else None, rast_map,
+                                          filter=grid_interpolate_mode, background=background))
         out["mask"] = out["mask"].bool()[None, ..., None]
         out["alpha"] = out["alpha"][None]
         return out
+
+    def _visible_faces(self, c2ws, perspective, method, rast, erode_neighbor):
+        """face mask uint8 [B,F] on the device: method 'rays' on the mesh's cached tree, 'raster' from the views' rasters rast [B,H,W,4]"""
+        m = self.pbr_mesh
+        if method == "rays":
+            mask = ops.visible_faces_rays(m.optix, torch.as_tensor(c2ws, dtype=torch.float32).to(self.device).contiguous(), perspective=perspective)
+        else:
+            mask = ops.visible_faces_raster(rast, m.faces.shape[0])
+        if erode_neighbor > 0:
+            mask = ops.erode_faces(mask, m.faces, m.vertices.shape[0], erode_neighbor)
+        return mask
+
+    def _visible_faces_checked(self, who, c2ws, perspective, method, intrinsics, render_size, erode_neighbor):
+        if method not in ("rays", "raster"):
+            raise ValueError("%s(method=%r): 'rays' or 'raster'" % (who, method))
+        if method == "raster" and (intrinsics is None or render_size is None):
+            raise ValueError("%s(method='raster') rasterises the views: intrinsics and render_size are required" % who)
+        if int(erode_neighbor) < 0:
+            raise ValueError("%s(erode_neighbor=%r): a number of rounds >= 0" % (who, erode_neighbor))
+        c2ws = torch.as_tensor(c2ws, dtype=torch.float32)
+        if c2ws.dim() != 3 or tuple(c2ws.shape[1:]) != (4, 4) or c2ws.shape[0] < 1:
+            raise ValueError("%s: c2ws is %s, expected [B >= 1, 4, 4]" % (who, tuple(c2ws.shape)))
+        assert self.pbr_mesh is not None, "update_from_file first"
+        rast = self._view_raster(c2ws, intrinsics, render_size, perspective)[4] if method == "raster" else None
+        return self._visible_faces(c2ws, perspective, method, rast, int(erode_neighbor))
+
+    def get_visible_faces(self, c2ws, perspective=True, method="rays", intrinsics=None, render_size=None, erode_neighbor=0):
+        """The faces each camera of c2ws [B,4,4] sees, bool [B,F], on the mesh of update_from_file / update_from_arrays.
+        method='rays' is Mesh.get_visible_faces of the reference (mesh/structure.py:801-844): one ray per face, aimed at its centroid (perspective:
+        from the camera centre; orthographic: along the view direction), marks the face it hits FIRST -- closest hit on the mesh's cached tree,
+        no backface culling -- so a face is visible iff some ray of the view lands on it.  method='raster' is NVDiffRendererBase.get_visible_faces
+        (render/nvdiffrast/renderer_base.py:65-85): the faces whose id appears in the view rasterised at render_size with intrinsics [B,3,3]
+        (both required; ValueError without them).  erode_neighbor > 0 applies erode_face that many times (the reference's self.erode_neighbor,
+        which only its raster twin reads; here either method takes it)."""
+        return self._visible_faces_checked("get_visible_faces", c2ws, perspective, method, intrinsics, render_size, erode_neighbor).bool()
+
+    def get_visible_vertices(self, c2ws, perspective=True, method="rays", intrinsics=None, render_size=None, erode_neighbor=0):
+        """The vertices each camera sees, bool [B,V]: those of the faces of get_visible_faces (same arguments; structure.py:846-857,
+        renderer_base.py:87-99)."""
+        mask = self._visible_faces_checked("get_visible_vertices", c2ws, perspective, method, intrinsics, render_size, erode_neighbor)
+        return ops.visible_vertices(mask, self.pbr_mesh.faces, self.pbr_mesh.vertices.shape[0]).bool()
 
     def _vertex_attr(self, v_attr, who):
         """v_attr [V,Ca] of the caller -> contiguous float32 on the device, or ValueError"""
