@@ -94,6 +94,21 @@ static int fail(utx_ctx* ctx, int code, const char* what) {
 }
 #define UTX_CALL(ctx, name, expr) do { int rc_ = (expr); if (rc_ != 0) return fail(ctx, rc_, name); return 0; } while (0)
 
+// argument checks that utx_uv_gbuffer, utx_screen_gbuffer and utx_uv_project share
+static bool outs_present(unsigned want, void* const* outs_host, int count) {      // every requested bit has a buffer
+    for (int k = 0; k < count; ++k)
+        if (((want >> k) & 1u) && !outs_host[k]) return false;
+    return true;
+}
+static bool bg_needs_pointer(int bg_kind) { return bg_kind == UTX_SGB_BG_VECTOR || bg_kind == UTX_SGB_BG_DENSE; }
+static bool filter_and_bg_ok(int filter, int bg_kind) {
+    return filter >= UTX_SGB_FILTER_BILINEAR && filter <= UTX_SGB_FILTER_NVDIFFRAST && bg_kind >= UTX_SGB_BG_NONE && bg_kind <= UTX_SGB_BG_DENSE;
+}
+// need_*_cam: the entry point's bits that read v_nrm_cam / v_pos_cam (its own: the two enumerations differ, and z_depth is camera z on the atlas only)
+static bool cam_arrays_present(unsigned want, unsigned need_nrm_cam, unsigned need_pos_cam, const float* v_nrm_cam, const float* v_pos_cam) {
+    return !((want & need_nrm_cam) && !v_nrm_cam) && !((want & need_pos_cam) && !v_pos_cam);
+}
+
 extern "C" {
 
 int utx_version(void) { return UTX_VERSION; }
@@ -375,10 +390,9 @@ int utx_uv_gbuffer(utx_ctx* ctx, const float* rast2d, const int* faces, const fl
     const unsigned need_pos_cam = UTX_UVGB_CAMERA_POSITION | UTX_UVGB_DISTANCE | UTX_UVGB_Z_DEPTH | UTX_UVGB_RAY_DIRECTION | UTX_UVGB_COS_RAY_NORMAL;
     if (!rast2d || !faces || !outs_host || ((uintptr_t)rast2d & 15)) return fail(ctx, -2, "utx_uv_gbuffer");      // rast2d is read as float4
     if (H2D <= 0 || W2D <= 0 || V <= 0 || B < 0 || want == 0 || (want & ~(unsigned)UTX_UVGB_ALL)) return fail(ctx, -2, "utx_uv_gbuffer");
-    for (int k = 0; k < UTX_UVGB_COUNT; ++k)
-        if (((want >> k) & 1u) && !outs_host[k]) return fail(ctx, -2, "utx_uv_gbuffer");
+    if (!outs_present(want, outs_host, UTX_UVGB_COUNT)) return fail(ctx, -2, "utx_uv_gbuffer");
     if (((want & UTX_UVGB_WORLD_POSITION) && !v_pos) || ((want & UTX_UVGB_WORLD_NORMAL) && !v_nrm)) return fail(ctx, -2, "utx_uv_gbuffer");
-    if (B > 0 && (((want & need_nrm_cam) && !v_nrm_cam) || ((want & need_pos_cam) && !v_pos_cam))) return fail(ctx, -2, "utx_uv_gbuffer");
+    if (B > 0 && !cam_arrays_present(want, need_nrm_cam, need_pos_cam, v_nrm_cam, v_pos_cam)) return fail(ctx, -2, "utx_uv_gbuffer");
     UTX_CALL(ctx, "utx_uv_gbuffer", utx_launch_uv_gbuffer(rast2d, faces, v_pos, v_nrm, v_pos_cam, v_nrm_cam, V, B, H2D, W2D, want, outs_host,
                                                           (hipStream_t)stream));
 }
@@ -391,14 +405,12 @@ int utx_screen_gbuffer(utx_ctx* ctx, const float* rast, const int* faces, const 
     const unsigned need_pos_cam = UTX_SGB_CAMERA_POSITION | UTX_SGB_DISTANCE | UTX_SGB_RAY_DIRECTION | UTX_SGB_COS_RAY_NORMAL;
     if (!rast || !faces || !outs_host || ((uintptr_t)rast & 15)) return fail(ctx, -2, me);      // rast is read as float4
     if (H < 0 || W < 0 || V <= 0 || B < 0 || (want & ~(unsigned)UTX_SGB_ALL)) return fail(ctx, -2, me);
-    if (filter < UTX_SGB_FILTER_BILINEAR || filter > UTX_SGB_FILTER_NVDIFFRAST || bg_kind < UTX_SGB_BG_NONE || bg_kind > UTX_SGB_BG_DENSE) return fail(ctx, -2, me);
-    for (int k = 0; k < UTX_SGB_COUNT; ++k)
-        if (((want >> k) & 1u) && !outs_host[k]) return fail(ctx, -2, me);
+    if (!filter_and_bg_ok(filter, bg_kind) || !outs_present(want, outs_host, UTX_SGB_COUNT)) return fail(ctx, -2, me);
     if (B == 0 && (want & (need_nrm_cam | need_pos_cam | UTX_SGB_Z_DEPTH))) return fail(ctx, -2, me);      // a per-view array of no view has no address
     if (((want & UTX_SGB_WORLD_POSITION) && !v_pos) || ((want & UTX_SGB_WORLD_NORMAL) && !v_nrm)) return fail(ctx, -2, me);
-    if (((want & need_nrm_cam) && !v_nrm_cam) || ((want & need_pos_cam) && !v_pos_cam) || ((want & UTX_SGB_Z_DEPTH) && !clip_w)) return fail(ctx, -2, me);
+    if (!cam_arrays_present(want, need_nrm_cam, need_pos_cam, v_nrm_cam, v_pos_cam) || ((want & UTX_SGB_Z_DEPTH) && !clip_w)) return fail(ctx, -2, me);
     if ((want & (UTX_SGB_UV | UTX_SGB_MAP_ATTR)) && !v_uv) return fail(ctx, -2, me);
-    const bool bg_ptr = bg_kind == UTX_SGB_BG_VECTOR || bg_kind == UTX_SGB_BG_DENSE;
+    const bool bg_ptr = bg_needs_pointer(bg_kind);
     if (want & UTX_SGB_V_ATTR) {
         if (!v_attr || Ca <= 0 || (bg_ptr && !bg_v_attr)) return fail(ctx, -2, me);
     }
@@ -419,8 +431,7 @@ int utx_uv_project(utx_ctx* ctx, const float* rast2d, const int* faces, int F, c
     if (F <= 0 || V <= 0 || B <= 0 || H2D <= 0 || W2D <= 0) return fail(ctx, -2, me);
     if (map) {
         if (!rast_map || !map_attr || (Bm != 1 && Bm != B) || Hm <= 0 || Wm <= 0 || C <= 0) return fail(ctx, -2, me);
-        if (filter < UTX_SGB_FILTER_BILINEAR || filter > UTX_SGB_FILTER_NVDIFFRAST || bg_kind < UTX_SGB_BG_NONE || bg_kind > UTX_SGB_BG_DENSE) return fail(ctx, -2, me);
-        if ((bg_kind == UTX_SGB_BG_VECTOR || bg_kind == UTX_SGB_BG_DENSE) && !bg) return fail(ctx, -2, me);
+        if (!filter_and_bg_ok(filter, bg_kind) || (bg_needs_pointer(bg_kind) && !bg)) return fail(ctx, -2, me);
     }
     UTX_CALL(ctx, me, utx_launch_uv_project(rast2d, faces, F, face_mask, v_ndc, V, B, H2D, W2D, map, Bm, Hm, Wm, C, rast_map, map ? filter : 0, bg_kind, bg_scalar, bg, uv,
                                             uv_alpha, map ? map_attr : nullptr, (hipStream_t)stream));

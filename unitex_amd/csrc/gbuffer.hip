@@ -1,6 +1,10 @@
-// Geometry buffers (gfx950): the screen-space ones of the orbit video (utx_gbuffer_shade, utx_gbuffer_range, utx_camera_normals) and the atlas-space
-// ones of simple_inverse_rendering (utx_uv_gbuffer, and utx_uv_project: its projection of the camera views into the atlas), and the screen-space buffers of a camera batch of simple_rendering (utx_screen_gbuffer).  All interpolate with shade_device.h's sd_interp, utx_interpolate's (a0*u + a1*v) + a2*w, and
-// normalise with its F.normalize, so a covered pixel's value is bit-identical to interpolate_kernel's wherever it is computed.
+// Geometry buffers (gfx950).  Entry points:
+//   utx_gbuffer_shade, utx_gbuffer_range, utx_camera_normals   the screen-space buffers of the orbit video
+//   utx_uv_gbuffer                                             the atlas-space buffers of simple_inverse_rendering
+//   utx_screen_gbuffer                                         the screen-space buffers of a camera batch (simple_rendering)
+//   utx_uv_project                                             simple_inverse_rendering's projection of the camera views into the atlas
+// All interpolate with shade_device.h's sd_interp, utx_interpolate's (a0*u + a1*v) + a2*w, and normalise with its F.normalize, so a covered pixel's
+// value is bit-identical to interpolate_kernel's wherever it is computed.
 //
 // HBM-bound.  Plain vector loads and stores, no LDS, no scratch, no inline assembly; atomics only in the range reduction.  Built with -ffp-contract=off
 // (every operation one correctly rounded fp32 operation) and without packed fp32 (csrc/build.py NO_PK): the sums of products below are exactly what hipcc
@@ -166,136 +170,143 @@ extern "C" int utx_launch_camera_normals(const float* nrm, int V, const float* c
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-// ---- atlas-space geometry buffers: NVDiffRendererBase.simple_inverse_rendering of the reference
-// (TextureTools/texturetools/render/nvdiffrast/renderer_base.py:352-489) with alpha = coverage (no dr.antialias), every requested buffer of
-// every camera in ONE launch.
+// ---- the per-pixel geometry of the atlas (utx_uv_gbuffer: simple_inverse_rendering, render/nvdiffrast/renderer_base.py:352-489) and of the screen
+// (utx_screen_gbuffer: simple_rendering, :101-350), both with alpha = coverage (no dr.antialias).  A pixel is a texel of the UV raster or a pixel of
+// one view's raster; its record is (u, v, z/w, id + 1), w = (1 - u) - v is formed once.  torch.lerp(bg, x, alpha) with alpha in {0, 1} returns x or
+// bg exactly, so it is a select.
 //
-// One thread per texel of the UV raster, x fastest.  The thread reads its raster record (u, v, z/w, id + 1) and the triangle's three vertex
-// indices once, forms w = (1 - u) - v once, and then loops over the views itself: per view two gathers of three vertices (camera-space position and
-// normal), the interpolation and the table below.  torch.lerp(bg, x, alpha) with alpha in {0, 1} returns x or bg exactly, so it is a select.
-//
-//   buffer               covered texel                                         background
-//   world_normal         normalize(interp(v_nrm))                              -1     (:401-407)
-//   world_position       interp(v_pos)                                         -1     (:419-429)
-//   camera_normal[b]     normalize(interp(v_nrm_cam[b]))                       -1     (:409-417)
-//   camera_position[b]   interp(v_pos_cam[b])                                   0     (:445-455)
-//   distance[b]          sqrt((x*x + y*y) + z*z) of camera_position             0     (:456-461)
-//   z_depth[b]           camera_position.z                                      0     (:462-467)
-//   ray_direction[b]     normalize(camera_position)                            -1     (:468-473)
-//   cos_ray_normal[b]    (cn.x*rd.x + cn.y*rd.y) + cn.z*rd.z, both as above    -1     (:475-489)
+//   buffer               covered pixel                                         background   (atlas, screen)
+//   world_normal         normalize(interp(v_nrm))                              -1     (:401-407, :172-178)
+//   world_position       interp(v_pos)                                         -1     (:419-429, :190-200)
+//   camera_normal[b]     normalize(interp(v_nrm_cam[b]))                       -1     (:409-417, :180-188)
+//   camera_position[b]   interp(v_pos_cam[b])                                   0     (:445-455, :241-248)
+//   distance[b]          sqrt((x*x + y*y) + z*z) of camera_position             0     (:456-461, :249-254)
+//   ray_direction[b]     normalize(camera_position)                            -1     (:468-473, :255-260)
+//   cos_ray_normal[b]    (cn.x*rd.x + cn.y*rd.y) + cn.z*rd.z, both as above    -1     (:475-489, :262-274)
+//   z_depth[b]           atlas: camera_position.z; screen: interp(clip_w[b])    0     (:462-467, :165-170) -- each kernel's own, see there
 //   normalize(x) = x / max(|x|, 1e-12), |x| = sqrt((x*x + y*y) + z*z)
+// distance on the screen: with render_camera_position set the reference takes the norm of the ALREADY MASKED position (:245, :250), without it of
+// the raw one and masks afterwards (:251); with alpha = mask both give |p| on a covered pixel and 0 on the background, which is what is written.
 //
-// 16 B read and up to 29 + 48 B written per texel and view; the vertex gathers hit L2 (neighbouring texels share a triangle).
-struct UvGbufferOut {
+// The two kernels stay two launches: the atlas has ONE raster for all views, so its thread reads the record and the triangle once, writes the world
+// buffers once and loops over the views; the screen has a raster per view, one thread per (view, pixel).  A shared launch geometry would re-read the
+// atlas record B times.
+struct GeomOut {      // the buffers both kernels write; a null pointer = not requested
     unsigned char* mask;
     float *alpha, *world_normal, *world_position, *camera_normal, *camera_position, *distance, *z_depth, *ray_direction, *cos_ray_normal;
 };
+enum { GEOM_OUT_COUNT = 10 };
 
-__device__ __forceinline__ void uvgb_store3(float* base, long texel, const float v[3]) {
-    float* o = base + 3 * texel;
+struct GeomPixel { bool covered; long i0, i1, i2; float u, v, w; };      // a raster record: coverage, the triangle's vertices, the barycentrics
+
+__device__ __forceinline__ GeomPixel geom_pixel(const float4 r, const int* __restrict__ tri) {
+    const int id = (int)r.w - 1;
+    GeomPixel p = {id >= 0, 0, 0, 0, r.x, r.y, sd_bary_w(r.x, r.y)};
+    if (p.covered) { p.i0 = tri[3 * id + 0]; p.i1 = tri[3 * id + 1]; p.i2 = tri[3 * id + 2]; }
+    return p;
+}
+
+__device__ __forceinline__ void geom_store3(float* base, long pixel, const float v[3]) {
+    float* o = base + 3 * pixel;
     o[0] = v[0]; o[1] = v[1]; o[2] = v[2];
 }
 
-__global__ __launch_bounds__(256) void uv_gbuffer_kernel(const float4* __restrict__ rast, const int* __restrict__ tri, const float* __restrict__ v_pos,
-                                                         const float* __restrict__ v_nrm, const float* __restrict__ v_pos_cam,
-                                                         const float* __restrict__ v_nrm_cam, long V, int B, long npix, UvGbufferOut o) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= npix) return;
-    const float4 r = rast[i];
-    const int id = (int)r.w - 1;
-    const bool covered = id >= 0;
-    const float u = r.x, v = r.y, w = sd_bary_w(u, v);
-    long i0 = 0, i1 = 0, i2 = 0;
-    if (covered) { i0 = tri[3 * id + 0]; i1 = tri[3 * id + 1]; i2 = tri[3 * id + 2]; }
-    if (o.mask) o.mask[i] = covered ? 1 : 0;
-    if (o.alpha) o.alpha[i] = covered ? 1.0f : 0.0f;
+// mask, alpha and the world buffers of the pixel at index i
+__device__ __forceinline__ void geom_world(const GeomPixel& p, const float* __restrict__ v_pos, const float* __restrict__ v_nrm, const GeomOut& o, long i) {
+    if (o.mask) o.mask[i] = p.covered ? 1 : 0;
+    if (o.alpha) o.alpha[i] = p.covered ? 1.0f : 0.0f;
     if (o.world_normal) {
         float n[3] = {-1.0f, -1.0f, -1.0f};
-        if (covered) {
-            float p[3];
-            sd_interp<3>(v_nrm + 3 * i0, v_nrm + 3 * i1, v_nrm + 3 * i2, u, v, w, p);
-            sd_normalize3(p, sd_length3(p), n);
+        if (p.covered) {
+            float x[3];
+            sd_interp<3>(v_nrm + 3 * p.i0, v_nrm + 3 * p.i1, v_nrm + 3 * p.i2, p.u, p.v, p.w, x);
+            sd_normalize3(x, sd_length3(x), n);
         }
-        uvgb_store3(o.world_normal, i, n);
+        geom_store3(o.world_normal, i, n);
     }
     if (o.world_position) {
-        float p[3] = {-1.0f, -1.0f, -1.0f};
-        if (covered) sd_interp<3>(v_pos + 3 * i0, v_pos + 3 * i1, v_pos + 3 * i2, u, v, w, p);
-        uvgb_store3(o.world_position, i, p);
-    }
-    const bool want_cn = o.camera_normal || o.cos_ray_normal;
-    const bool want_cp = o.camera_position || o.distance || o.z_depth || o.ray_direction || o.cos_ray_normal;
-    for (int b = 0; b < B; ++b) {
-        const long t = (long)b * npix + i;
-        float cn[3] = {-1.0f, -1.0f, -1.0f}, cp[3] = {0.0f, 0.0f, 0.0f}, rd[3] = {-1.0f, -1.0f, -1.0f};
-        float dist = 0.0f, cosv = -1.0f;
-        if (covered) {
-            if (want_cn) {
-                float p[3];
-                const float* a = v_nrm_cam + 3 * V * b;
-                sd_interp<3>(a + 3 * i0, a + 3 * i1, a + 3 * i2, u, v, w, p);
-                sd_normalize3(p, sd_length3(p), cn);
-            }
-            if (want_cp) {
-                const float* a = v_pos_cam + 3 * V * b;
-                sd_interp<3>(a + 3 * i0, a + 3 * i1, a + 3 * i2, u, v, w, cp);
-                dist = sd_length3(cp);
-                sd_normalize3(cp, dist, rd);
-            }
-            if (o.cos_ray_normal) cosv = sd_dot3(cn, rd);
-        }
-        if (o.camera_normal) uvgb_store3(o.camera_normal, t, cn);
-        if (o.camera_position) uvgb_store3(o.camera_position, t, cp);
-        if (o.distance) o.distance[t] = dist;
-        if (o.z_depth) o.z_depth[t] = cp[2];
-        if (o.ray_direction) uvgb_store3(o.ray_direction, t, rd);
-        if (o.cos_ray_normal) o.cos_ray_normal[t] = cosv;
+        float x[3] = {-1.0f, -1.0f, -1.0f};
+        if (p.covered) sd_interp<3>(v_pos + 3 * p.i0, v_pos + 3 * p.i1, v_pos + 3 * p.i2, p.u, p.v, p.w, x);
+        geom_store3(o.world_position, i, x);
     }
 }
 
-// outs_host[k] is the buffer of bit k of `want` (unitex_hip.h UTX_UVGB_*); pointers of buffers that were not requested are never read
+// the camera buffers of ONE view (v_pos_cam / v_nrm_cam: that view's [V][3]) at index t, all but z_depth.  cp returns the interpolated camera
+// position (0 on the background); cp_for_caller: the caller reads it even if no buffer here does.
+__device__ __forceinline__ void geom_view(const GeomPixel& p, const float* __restrict__ v_pos_cam, const float* __restrict__ v_nrm_cam, const GeomOut& o,
+                                          long t, bool cp_for_caller, float cp[3]) {
+    const bool want_cn = o.camera_normal || o.cos_ray_normal;
+    const bool want_cp = o.camera_position || o.distance || o.ray_direction || o.cos_ray_normal || cp_for_caller;
+    float cn[3] = {-1.0f, -1.0f, -1.0f}, rd[3] = {-1.0f, -1.0f, -1.0f};
+    float dist = 0.0f, cosv = -1.0f;
+    cp[0] = cp[1] = cp[2] = 0.0f;
+    if (p.covered) {
+        if (want_cn) {
+            float x[3];
+            sd_interp<3>(v_nrm_cam + 3 * p.i0, v_nrm_cam + 3 * p.i1, v_nrm_cam + 3 * p.i2, p.u, p.v, p.w, x);
+            sd_normalize3(x, sd_length3(x), cn);
+        }
+        if (want_cp) {
+            sd_interp<3>(v_pos_cam + 3 * p.i0, v_pos_cam + 3 * p.i1, v_pos_cam + 3 * p.i2, p.u, p.v, p.w, cp);
+            dist = sd_length3(cp);
+            sd_normalize3(cp, dist, rd);
+        }
+        if (o.cos_ray_normal) cosv = sd_dot3(cn, rd);
+    }
+    if (o.camera_normal) geom_store3(o.camera_normal, t, cn);
+    if (o.camera_position) geom_store3(o.camera_position, t, cp);
+    if (o.distance) o.distance[t] = dist;
+    if (o.ray_direction) geom_store3(o.ray_direction, t, rd);
+    if (o.cos_ray_normal) o.cos_ray_normal[t] = cosv;
+}
+
+// the buffer of the bit `mask` of `want`, or null: outs_host[k] belongs to bit k, and the entry of a buffer that was not requested is never read
+static void* wanted(unsigned want, void* const* outs_host, unsigned mask) { return (want & mask) ? outs_host[__builtin_ctz(mask)] : nullptr; }
+
+// bits[k]: the ABI's bit (UTX_UVGB_* / UTX_SGB_*, which order theirs differently) of the k-th member of GeomOut
+static GeomOut geom_out(unsigned want, void* const* outs_host, const unsigned (&bits)[GEOM_OUT_COUNT]) {
+    void* p[GEOM_OUT_COUNT];
+    for (int k = 0; k < GEOM_OUT_COUNT; ++k) p[k] = wanted(want, outs_host, bits[k]);
+    return {(unsigned char*)p[0], (float*)p[1], (float*)p[2], (float*)p[3], (float*)p[4], (float*)p[5], (float*)p[6], (float*)p[7], (float*)p[8], (float*)p[9]};
+}
+
+// ---- atlas-space geometry buffers, every requested buffer of every camera in ONE launch.  One thread per texel of the UV raster, x fastest; per view
+// two gathers of three vertices (camera-space position and normal) and the table above.  z_depth is the camera z of the interpolated position.
+// 16 B read and up to 29 + 48 B written per texel and view; the vertex gathers hit L2 (neighbouring texels share a triangle).
+__global__ __launch_bounds__(256) void uv_gbuffer_kernel(const float4* __restrict__ rast, const int* __restrict__ tri, const float* __restrict__ v_pos,
+                                                         const float* __restrict__ v_nrm, const float* __restrict__ v_pos_cam,
+                                                         const float* __restrict__ v_nrm_cam, long V, int B, long npix, GeomOut o) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= npix) return;
+    const GeomPixel p = geom_pixel(rast[i], tri);
+    geom_world(p, v_pos, v_nrm, o, i);
+    for (int b = 0; b < B; ++b) {
+        const long t = (long)b * npix + i;
+        float cp[3];
+        geom_view(p, v_pos_cam + 3 * V * b, v_nrm_cam + 3 * V * b, o, t, o.z_depth != nullptr, cp);
+        if (o.z_depth) o.z_depth[t] = cp[2];
+    }
+}
+
 extern "C" int utx_launch_uv_gbuffer(const float* rast, const int* tri, const float* v_pos, const float* v_nrm, const float* v_pos_cam,
                                      const float* v_nrm_cam, int V, int B, int H2D, int W2D, unsigned want, void* const* outs_host,
                                      hipStream_t stream) {
     if (H2D <= 0 || W2D <= 0 || B < 0 || V <= 0 || !outs_host) return -2;
     const long npix = (long)H2D * W2D;
-    auto out = [&](int bit) -> void* { return (want >> bit) & 1u ? outs_host[bit] : nullptr; };
-    UvGbufferOut o;
-    o.mask = (unsigned char*)out(0);
-    o.alpha = (float*)out(1);
-    o.world_normal = (float*)out(2);
-    o.world_position = (float*)out(3);
-    o.camera_normal = (float*)out(4);
-    o.camera_position = (float*)out(5);
-    o.distance = (float*)out(6);
-    o.z_depth = (float*)out(7);
-    o.ray_direction = (float*)out(8);
-    o.cos_ray_normal = (float*)out(9);
+    const GeomOut o = geom_out(want, outs_host, {UTX_UVGB_MASK, UTX_UVGB_ALPHA, UTX_UVGB_WORLD_NORMAL, UTX_UVGB_WORLD_POSITION, UTX_UVGB_CAMERA_NORMAL,
+                                                 UTX_UVGB_CAMERA_POSITION, UTX_UVGB_DISTANCE, UTX_UVGB_Z_DEPTH, UTX_UVGB_RAY_DIRECTION, UTX_UVGB_COS_RAY_NORMAL});
     hipLaunchKernelGGL(uv_gbuffer_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, (const float4*)rast, tri, v_pos, v_nrm,
                        v_pos_cam, v_nrm_cam, (long)V, B, npix, o);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-// ---- screen-space buffers of a camera batch: NVDiffRendererBase.simple_rendering of the reference (render/nvdiffrast/renderer_base.py:101-350) with
-// alpha = coverage (no dr.antialias), every requested buffer of every camera in ONE launch.
-//
-// One thread per pixel of rast [B][H][W][4], x fastest.  The thread reads its raster record and the triangle's three vertex indices once, forms
-// w = (1 - u) - v once and writes every requested buffer.  torch.lerp(bg, x, alpha) with alpha in {0, 1} returns x or bg exactly, so it is a select.
+// ---- screen-space buffers of a camera batch, every requested buffer of every camera in ONE launch.  One thread per pixel of rast [B][H][W][4], x
+// fastest: 16 B read and up to 77 B + the three buffers below written.  z_depth is the interpolated clip w, NOT camera z as on the atlas.
 //
 //   buffer            covered pixel                                          background
-//   world_normal      normalize(interp(v_nrm))                               -1     (:172-178)
-//   camera_normal     normalize(interp(v_nrm_cam[b]))                        -1     (:180-188)
-//   world_position    interp(v_pos)                                          -1     (:190-200)
-//   camera_position   interp(v_pos_cam[b])                                    0     (:241-248)
-//   distance          sqrt((x*x + y*y) + z*z) of the interpolated position    0     (:249-254)
-//   ray_direction     normalize(interp(v_pos_cam[b]))                        -1     (:255-260)
-//   z_depth           interp(clip_w[b]): clip w, NOT camera z as on the atlas 0     (:165-170)
-//   cos_ray_normal    dot(camera_normal, ray_direction), both as above       -1     (:262-274)
 //   v_attr            interp(v_attr), Ca channels                            rule   (:276-287)
 //   uv                interp(v_uv), in [-1, 1]                               -1     (:289-303)
 //   map_attr          the maps sampled at uv, concatenated along channels    rule   (:305-336)
-// distance: with render_camera_position set the reference takes the norm of the ALREADY MASKED position (:245, :250), without it of the raw one and
-// masks afterwards (:251); with alpha = mask both give |p| on a covered pixel and 0 on the background, which is what is written here.
 // rule (:278-284, :327-333): without a background the value stays as computed on EVERY pixel -- dr.interpolate's 0 for v_attr, the maps' sample at the
 // background's uv = (-1, -1) for map_attr; with one (a scalar, a [C] vector or a dense [B][H][W][C] image) covered pixels keep the value and the rest
 // take the background.
@@ -313,13 +324,13 @@ struct ScreenGbufferArgs {
     float bg_scalar;
     const float *bg_v_attr, *bg_map_attr;
     long V, npix, total;      // vertices, pixels of one view, pixels of all views
-    unsigned char* mask;
-    float *alpha, *world_normal, *camera_normal, *world_position, *camera_position, *distance, *ray_direction, *z_depth, *cos_ray_normal, *o_v_attr, *uv,
-        *map_attr;
+    GeomOut o;
+    float *o_v_attr, *uv, *map_attr;
 };
 
-__device__ __forceinline__ float sgb_background(const ScreenGbufferArgs& a, const float* bg, long pixel, int C, int c) {
-    return a.bg_kind == SGB_BG_SCALAR ? a.bg_scalar : a.bg_kind == SGB_BG_VECTOR ? bg[c] : bg[pixel * C + c];
+// channel c of the background of a pixel, kind != SGB_BG_NONE: the scalar, the [C] vector's or the dense [pixels][C] image's
+__device__ __forceinline__ float sgb_background(int kind, float scalar, const float* bg, long pixel, int C, int c) {
+    return kind == SGB_BG_SCALAR ? scalar : kind == SGB_BG_VECTOR ? bg[c] : bg[pixel * C + c];
 }
 
 // C channels of one map [Ht][Wt][C] at the NDC (gx, gy)
@@ -346,74 +357,32 @@ __global__ __launch_bounds__(256) void screen_gbuffer_kernel(ScreenGbufferArgs a
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.total) return;
     const long b = i / a.npix;
-    const float4 r = a.rast[i];
-    const int id = (int)r.w - 1;
-    const bool covered = id >= 0;
-    const float u = r.x, v = r.y, w = sd_bary_w(u, v);
-    long i0 = 0, i1 = 0, i2 = 0;
-    if (covered) { i0 = a.tri[3 * id + 0]; i1 = a.tri[3 * id + 1]; i2 = a.tri[3 * id + 2]; }
-    if (a.mask) a.mask[i] = covered ? 1 : 0;
-    if (a.alpha) a.alpha[i] = covered ? 1.0f : 0.0f;
-    if (a.world_normal) {
-        float n[3] = {-1.0f, -1.0f, -1.0f};
-        if (covered) {
-            float p[3];
-            sd_interp<3>(a.v_nrm + 3 * i0, a.v_nrm + 3 * i1, a.v_nrm + 3 * i2, u, v, w, p);
-            sd_normalize3(p, sd_length3(p), n);
-        }
-        uvgb_store3(a.world_normal, i, n);
-    }
-    if (a.world_position) {
-        float p[3] = {-1.0f, -1.0f, -1.0f};
-        if (covered) sd_interp<3>(a.v_pos + 3 * i0, a.v_pos + 3 * i1, a.v_pos + 3 * i2, u, v, w, p);
-        uvgb_store3(a.world_position, i, p);
-    }
-    if (a.z_depth) {
+    const GeomPixel p = geom_pixel(a.rast[i], a.tri);
+    const bool covered = p.covered;
+    const float u = p.u, v = p.v, w = p.w;
+    geom_world(p, a.v_pos, a.v_nrm, a.o, i);
+    if (a.o.z_depth) {
         const float* cw = a.clip_w + a.V * b;
-        a.z_depth[i] = covered ? sd_interp1(cw[i0], cw[i1], cw[i2], u, v, w) : 0.0f;
+        a.o.z_depth[i] = covered ? sd_interp1(cw[p.i0], cw[p.i1], cw[p.i2], u, v, w) : 0.0f;
     }
-    const bool want_cn = a.camera_normal || a.cos_ray_normal;
-    const bool want_cp = a.camera_position || a.distance || a.ray_direction || a.cos_ray_normal;
-    if (want_cn || want_cp) {
-        float cn[3] = {-1.0f, -1.0f, -1.0f}, cp[3] = {0.0f, 0.0f, 0.0f}, rd[3] = {-1.0f, -1.0f, -1.0f};
-        float dist = 0.0f, cosv = -1.0f;
-        if (covered) {
-            if (want_cn) {
-                float p[3];
-                const float* n = a.v_nrm_cam + 3 * a.V * b;
-                sd_interp<3>(n + 3 * i0, n + 3 * i1, n + 3 * i2, u, v, w, p);
-                sd_normalize3(p, sd_length3(p), cn);
-            }
-            if (want_cp) {
-                const float* p = a.v_pos_cam + 3 * a.V * b;
-                sd_interp<3>(p + 3 * i0, p + 3 * i1, p + 3 * i2, u, v, w, cp);
-                dist = sd_length3(cp);
-                sd_normalize3(cp, dist, rd);
-            }
-            if (a.cos_ray_normal) cosv = sd_dot3(cn, rd);
-        }
-        if (a.camera_normal) uvgb_store3(a.camera_normal, i, cn);
-        if (a.camera_position) uvgb_store3(a.camera_position, i, cp);
-        if (a.distance) a.distance[i] = dist;
-        if (a.ray_direction) uvgb_store3(a.ray_direction, i, rd);
-        if (a.cos_ray_normal) a.cos_ray_normal[i] = cosv;
-    }
+    float cp[3];
+    geom_view(p, a.v_pos_cam + 3 * a.V * b, a.v_nrm_cam + 3 * a.V * b, a.o, i, false, cp);
     if (a.o_v_attr) {
         float* o = a.o_v_attr + i * a.Ca;
-        const float *p0 = a.v_attr + i0 * a.Ca, *p1 = a.v_attr + i1 * a.Ca, *p2 = a.v_attr + i2 * a.Ca;
+        const float *p0 = a.v_attr + p.i0 * a.Ca, *p1 = a.v_attr + p.i1 * a.Ca, *p2 = a.v_attr + p.i2 * a.Ca;
         for (int c = 0; c < a.Ca; ++c) {
             if (covered) o[c] = sd_interp1(p0[c], p1[c], p2[c], u, v, w);
-            else o[c] = a.bg_kind == SGB_BG_NONE ? 0.0f : sgb_background(a, a.bg_v_attr, i, a.Ca, c);
+            else o[c] = a.bg_kind == SGB_BG_NONE ? 0.0f : sgb_background(a.bg_kind, a.bg_scalar, a.bg_v_attr, i, a.Ca, c);
         }
     }
     if (a.uv || a.map_attr) {
         float g[2] = {-1.0f, -1.0f};
-        if (covered) sd_interp<2>(a.v_uv + 2 * i0, a.v_uv + 2 * i1, a.v_uv + 2 * i2, u, v, w, g);
+        if (covered) sd_interp<2>(a.v_uv + 2 * p.i0, a.v_uv + 2 * p.i1, a.v_uv + 2 * p.i2, u, v, w, g);
         if (a.uv) { a.uv[2 * i] = g[0]; a.uv[2 * i + 1] = g[1]; }
         if (a.map_attr) {
             float* o = a.map_attr + i * a.Cm;
             if (!covered && a.bg_kind != SGB_BG_NONE) {
-                for (int c = 0; c < a.Cm; ++c) o[c] = sgb_background(a, a.bg_map_attr, i, a.Cm, c);
+                for (int c = 0; c < a.Cm; ++c) o[c] = sgb_background(a.bg_kind, a.bg_scalar, a.bg_map_attr, i, a.Cm, c);
             } else {
 #pragma unroll
                 for (int m = 0; m < UTX_SGB_MAX_MAPS; ++m) {
@@ -427,8 +396,15 @@ __global__ __launch_bounds__(256) void screen_gbuffer_kernel(ScreenGbufferArgs a
     }
 }
 
-// outs_host[k] is the buffer of bit k of `want` (unitex_hip.h UTX_SGB_*); pointers of buffers that were not requested are never read.  The arguments
-// were checked by utx_screen_gbuffer (capi.cpp); B * H * W == 0 or want == 0 launches nothing.
+// FILTER is a template argument of the kernels that sample a map: `filter` (0, 1 or 2, checked by the caller) -> the instance, one thread per pixel
+#define LAUNCH_BY_FILTER(KERNEL, filter, args, stream) do { \
+        const dim3 g_((unsigned)(((args).total + 255) / 256)), b_(256); \
+        if ((filter) == 0) hipLaunchKernelGGL(KERNEL<0>, g_, b_, 0, stream, args); \
+        else if ((filter) == 1) hipLaunchKernelGGL(KERNEL<1>, g_, b_, 0, stream, args); \
+        else hipLaunchKernelGGL(KERNEL<2>, g_, b_, 0, stream, args); \
+    } while (0)
+
+// the arguments were checked by utx_screen_gbuffer (capi.cpp); B * H * W == 0 or want == 0 launches nothing
 extern "C" int utx_launch_screen_gbuffer(const float* rast, const int* tri, const float* v_pos, const float* v_nrm, const float* v_uv, const float* v_attr,
                                          int Ca, const float* clip_w, const float* v_pos_cam, const float* v_nrm_cam, int V, int B, int H, int W,
                                          int n_maps, const float* const* maps_host, const int* map_dims_host, int filter, int bg_kind, float bg_scalar,
@@ -438,23 +414,14 @@ extern "C" int utx_launch_screen_gbuffer(const float* rast, const int* tri, cons
     a.npix = (long)H * W;
     a.total = a.npix * B;
     if (a.total == 0 || want == 0) return 0;
-    auto out = [&](int bit) -> void* { return (want >> bit) & 1u ? outs_host[bit] : nullptr; };
     a.rast = (const float4*)rast; a.tri = tri;
     a.v_pos = v_pos; a.v_nrm = v_nrm; a.v_uv = v_uv; a.v_attr = v_attr; a.clip_w = clip_w; a.v_pos_cam = v_pos_cam; a.v_nrm_cam = v_nrm_cam;
     a.V = V; a.Ca = Ca; a.bg_kind = bg_kind; a.bg_scalar = bg_scalar; a.bg_v_attr = bg_v_attr; a.bg_map_attr = bg_map_attr;
-    a.mask = (unsigned char*)out(0);
-    a.alpha = (float*)out(1);
-    a.world_normal = (float*)out(2);
-    a.camera_normal = (float*)out(3);
-    a.world_position = (float*)out(4);
-    a.camera_position = (float*)out(5);
-    a.distance = (float*)out(6);
-    a.ray_direction = (float*)out(7);
-    a.z_depth = (float*)out(8);
-    a.cos_ray_normal = (float*)out(9);
-    a.o_v_attr = (float*)out(10);
-    a.uv = (float*)out(11);
-    a.map_attr = (float*)out(12);
+    a.o = geom_out(want, outs_host, {UTX_SGB_MASK, UTX_SGB_ALPHA, UTX_SGB_WORLD_NORMAL, UTX_SGB_WORLD_POSITION, UTX_SGB_CAMERA_NORMAL, UTX_SGB_CAMERA_POSITION,
+                                     UTX_SGB_DISTANCE, UTX_SGB_Z_DEPTH, UTX_SGB_RAY_DIRECTION, UTX_SGB_COS_RAY_NORMAL});
+    a.o_v_attr = (float*)wanted(want, outs_host, UTX_SGB_V_ATTR);
+    a.uv = (float*)wanted(want, outs_host, UTX_SGB_UV);
+    a.map_attr = (float*)wanted(want, outs_host, UTX_SGB_MAP_ATTR);
     if (a.map_attr) {
         a.n_maps = n_maps;
         for (int m = 0; m < n_maps; ++m) {
@@ -463,10 +430,7 @@ extern "C" int utx_launch_screen_gbuffer(const float* rast, const int* tri, cons
             a.Cm += a.map_c[m];
         }
     }
-    const dim3 g((unsigned)((a.total + 255) / 256)), blk(256);
-    if (filter == 0) hipLaunchKernelGGL(screen_gbuffer_kernel<0>, g, blk, 0, stream, a);
-    else if (filter == 1) hipLaunchKernelGGL(screen_gbuffer_kernel<1>, g, blk, 0, stream, a);
-    else hipLaunchKernelGGL(screen_gbuffer_kernel<2>, g, blk, 0, stream, a);
+    LAUNCH_BY_FILTER(screen_gbuffer_kernel, filter, a, stream);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
@@ -517,8 +481,7 @@ __global__ __launch_bounds__(256) void uv_project_kernel(UvProjectArgs a) {
         alpha = alpha && cov;
         float* out = a.map_attr + i * a.C;
         if (a.bg_kind != SGB_BG_NONE && !alpha) {
-            for (int c = 0; c < a.C; ++c)
-                out[c] = a.bg_kind == SGB_BG_SCALAR ? a.bg_scalar : a.bg_kind == SGB_BG_VECTOR ? a.bg[c] : a.bg[i * a.C + c];
+            for (int c = 0; c < a.C; ++c) out[c] = sgb_background(a.bg_kind, a.bg_scalar, a.bg, i, a.C, c);
         } else if (a.bg_kind == SGB_BG_NONE && !cov) {
             for (int c = 0; c < a.C; ++c) out[c] = m[c];
         } else {
@@ -541,9 +504,7 @@ extern "C" int utx_launch_uv_project(const float* rast2d, const int* tri, int F,
         a.map = map; a.rast_map = rast_map; a.bg = bg; a.Bm = Bm; a.Hm = Hm; a.Wm = Wm; a.C = C; a.bg_kind = bg_kind; a.bg_scalar = bg_scalar;
         a.map_attr = map_attr;
     }
-    const dim3 g((unsigned)((a.total + 255) / 256)), blk(256);
-    if (filter == 0) hipLaunchKernelGGL(uv_project_kernel<0>, g, blk, 0, stream, a);
-    else if (filter == 1) hipLaunchKernelGGL(uv_project_kernel<1>, g, blk, 0, stream, a);
-    else hipLaunchKernelGGL(uv_project_kernel<2>, g, blk, 0, stream, a);
+    LAUNCH_BY_FILTER(uv_project_kernel, filter, a, stream);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
+#undef LAUNCH_BY_FILTER

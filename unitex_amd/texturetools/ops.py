@@ -22,6 +22,11 @@ def _i(t):
     return t
 
 
+def _opt(t):
+    """the pointer of an optional float32 tensor"""
+    return ptr(_f(t)) if t is not None else None
+
+
 def transform_points(verts, mvp, want_ndc=True):
     """verts [V,3], mvp [n,4,4] -> clip [n,V,4], ndc [n,V,2]"""
     ctx = get_ctx(verts.device.index)
@@ -142,6 +147,37 @@ def camera_normals(nrm, c2ws):
     return out
 
 
+def _camera_arrays(v_pos, v_nrm, c2ws, B, need_pos, need_nrm, v_pos_cam, v_nrm_cam):
+    """(v_pos_cam, v_nrm_cam) [B,V,3] of uv_gbuffer / screen_gbuffer: each is built from c2ws [B,4,4] with the existing kernels (transform_points
+    with M = w2c, camera_normals) only when a requested buffer reads it, the caller did not pass it, and there is a view (B > 0)"""
+    if B > 0 and need_pos and v_pos_cam is None:
+        from . import camera
+        w2c = camera.c2w_to_w2c(torch.as_tensor(c2ws, dtype=F32).cpu()).to(v_pos.device, F32).contiguous()
+        v_pos_cam = transform_points(v_pos, w2c, want_ndc=False)[0][..., :3].contiguous()
+    if B > 0 and need_nrm and v_nrm_cam is None:
+        assert v_nrm is not None, "v_nrm [V, 3] is required by the normal buffers"
+        v_nrm_cam = camera_normals(v_nrm, torch.as_tensor(c2ws, dtype=F32).to(v_pos.device).contiguous())
+    return v_pos_cam, v_nrm_cam
+
+
+def _background(who, background, dev):
+    """`background` of screen_gbuffer / uv_project -> (bg_kind of the ABI, the scalar, expand): None, a number, a [C] vector or a dense image.
+    expand(shape, of="") is what the kernel reads for a buffer of shape (B, H, W, C): the vector or the image made contiguous, None for the other kinds."""
+    if background is None or isinstance(background, (int, float)):
+        return (0 if background is None else 1), float(background or 0.0), lambda shape, of="": None
+    if not isinstance(background, torch.Tensor):
+        raise ValueError("%s: background is %r: expected None, a number or a tensor" % (who, type(background)))
+    bgt = background.to(dev, F32)
+    kind = 2 if bgt.dim() <= 1 else 3
+
+    def expand(shape, of=""):
+        try:
+            return bgt.expand(shape[-1] if kind == 2 else shape).contiguous()
+        except RuntimeError:
+            raise ValueError("%s: background %s does not broadcast to %s%s" % (who, tuple(bgt.shape), tuple(shape), of))
+    return kind, 0.0, expand
+
+
 # name -> (bit of utx_uv_gbuffer's `want`, channels, one layer per camera); the order is the header's UTX_UVGB_* bits
 UV_GBUFFERS = {"mask": (0, 1, False), "alpha": (1, 1, False), "world_normal": (2, 3, False), "world_position": (3, 3, False),
                "camera_normal": (4, 3, True), "camera_position": (5, 3, True), "distance": (6, 1, True), "z_depth": (7, 1, True),
@@ -169,17 +205,10 @@ def uv_gbuffer(rast2d, faces, v_pos, v_nrm, c2ws=None, want=("mask", "alpha", "w
     dev = rast2d.device
     H, W = rast2d.shape[:2]
     V = v_pos.shape[0]
-    if c2ws is not None:
-        c2ws = torch.as_tensor(c2ws, dtype=F32)
-    if c2ws is not None and c2ws.shape[0] > 0:
-        if need_pos and v_pos_cam is None:
-            from . import camera
-            w2c = camera.c2w_to_w2c(c2ws.cpu()).to(dev, F32).contiguous()
-            v_pos_cam = transform_points(v_pos, w2c, want_ndc=False)[0][..., :3].contiguous()
-        if need_nrm and v_nrm_cam is None:
-            v_nrm_cam = camera_normals(v_nrm, c2ws.to(dev).contiguous())
+    n_cams = torch.as_tensor(c2ws).shape[0] if c2ws is not None else 0
+    v_pos_cam, v_nrm_cam = _camera_arrays(v_pos, v_nrm, c2ws, n_cams, need_pos, need_nrm, v_pos_cam, v_nrm_cam)
     per_view = [a for a in (v_pos_cam, v_nrm_cam) if a is not None]
-    B = per_view[0].shape[0] if per_view else (c2ws.shape[0] if c2ws is not None else 0)
+    B = per_view[0].shape[0] if per_view else n_cams
     for a in per_view:
         assert tuple(a.shape) == (B, V, 3), "per-view vertex arrays are [B, V, 3]"
     assert faces.shape[1] == 3 and rast2d.shape[2] == 4 and tuple(v_pos.shape) == (V, 3)
@@ -201,9 +230,8 @@ def uv_gbuffer(rast2d, faces, v_pos, v_nrm, c2ws=None, want=("mask", "alpha", "w
         bits &= ~sum(1 << UV_GBUFFERS[k][0] for k in want if UV_GBUFFERS[k][2])
         if bits == 0:
             return out
-    ctx.check(ctx.lib.utx_uv_gbuffer(ctx.handle, ptr(_f(rast2d)), ptr(_i(faces)), ptr(_f(v_pos)), ptr(_f(v_nrm) if v_nrm is not None else None),
-                                     ptr(_f(v_pos_cam) if v_pos_cam is not None and B else None), ptr(_f(v_nrm_cam) if v_nrm_cam is not None and B else None),
-                                     V, B, H, W, bits, ptrs, ctx.stream()))
+    ctx.check(ctx.lib.utx_uv_gbuffer(ctx.handle, ptr(_f(rast2d)), ptr(_i(faces)), ptr(_f(v_pos)), _opt(v_nrm), _opt(v_pos_cam if B else None),
+                                     _opt(v_nrm_cam if B else None), V, B, H, W, bits, ptrs, ctx.stream()))
     return out
 
 
@@ -250,13 +278,7 @@ def screen_gbuffer(rast, faces, v_pos, v_nrm=None, v_uv=None, v_attr=None, maps=
     if B > 0:
         if need_w and clip_w is None:
             clip_w = transform_points(v_pos, torch.as_tensor(mvp, dtype=F32).to(dev).contiguous(), want_ndc=False)[0][..., 3].contiguous()
-        if need_pos and v_pos_cam is None:
-            from . import camera
-            w2c = camera.c2w_to_w2c(torch.as_tensor(c2ws, dtype=F32).cpu()).to(dev, F32).contiguous()
-            v_pos_cam = transform_points(v_pos, w2c, want_ndc=False)[0][..., :3].contiguous()
-        if need_nrm and v_nrm_cam is None:
-            assert v_nrm is not None, "v_nrm [V, 3] is required by the normal buffers"
-            v_nrm_cam = camera_normals(v_nrm, torch.as_tensor(c2ws, dtype=F32).to(dev).contiguous())
+        v_pos_cam, v_nrm_cam = _camera_arrays(v_pos, v_nrm, c2ws, B, need_pos, need_nrm, v_pos_cam, v_nrm_cam)
         for a, shp in ((clip_w, (B, V)), (v_pos_cam, (B, V, 3)), (v_nrm_cam, (B, V, 3))):
             if a is not None and tuple(a.shape) != shp:
                 raise ValueError("screen_gbuffer: a per-view vertex array is %s, expected %s" % (tuple(a.shape), shp))
@@ -278,21 +300,8 @@ def screen_gbuffer(rast, faces, v_pos, v_nrm=None, v_uv=None, v_attr=None, maps=
                 raise ValueError("screen_gbuffer: a map is %s, expected [Ht, Wt, C] with no empty side" % (tuple(m.shape),))
         Cm = sum(m.shape[2] for m in maps)
     # the background: None, a number, a [C] vector or a dense image, per buffer (the two channel counts may differ)
-    kind, scalar, bgs = 0, 0.0, {"v_attr": None, "map_attr": None}
-    if background is not None and ("v_attr" in want or "map_attr" in want):
-        if isinstance(background, (int, float)):
-            kind, scalar = 1, float(background)
-        elif isinstance(background, torch.Tensor):
-            bgt = background.to(dev, F32)
-            kind = 2 if bgt.dim() <= 1 else 3
-            for k, ch in (("v_attr", Ca), ("map_attr", Cm)):
-                if k in want:
-                    try:
-                        bgs[k] = bgt.expand(ch).contiguous() if kind == 2 else bgt.expand(B, H, W, ch).contiguous()
-                    except RuntimeError:
-                        raise ValueError("screen_gbuffer: background %s does not broadcast to %s of %s" % (tuple(bgt.shape), (B, H, W, ch), k))
-        else:
-            raise ValueError("screen_gbuffer: background is %r: expected None, a number or a tensor" % type(background))
+    kind, scalar, expand = _background("screen_gbuffer", background if "v_attr" in want or "map_attr" in want else None, dev)
+    bgs = {k: expand((B, H, W, ch), " of " + k) if k in want else None for k, ch in (("v_attr", Ca), ("map_attr", Cm))}
     out, bits = {}, 0
     ptrs = (C.c_void_p * len(SCREEN_GBUFFERS))()
     for k in want:
@@ -305,10 +314,9 @@ def screen_gbuffer(rast, faces, v_pos, v_nrm=None, v_uv=None, v_attr=None, maps=
         return out
     mptr = (C.c_void_p * SCREEN_MAX_MAPS)(*[_f(m).data_ptr() for m in maps])
     mdim = (C.c_int * (3 * SCREEN_MAX_MAPS))(*[int(d) for m in maps for d in m.shape])
-    opt = lambda t: ptr(_f(t)) if t is not None else None
-    ctx.check(ctx.lib.utx_screen_gbuffer(ctx.handle, ptr(_f(rast)), ptr(_i(faces)), ptr(_f(v_pos)), opt(v_nrm), opt(v_uv), opt(v_attr if Ca else None), Ca,
-                                         opt(clip_w), opt(v_pos_cam), opt(v_nrm_cam), V, B, H, W, len(maps), mptr, mdim, SCREEN_FILTERS[filter], kind, scalar,
-                                         opt(bgs["v_attr"]), opt(bgs["map_attr"]), bits, ptrs, ctx.stream()))
+    ctx.check(ctx.lib.utx_screen_gbuffer(ctx.handle, ptr(_f(rast)), ptr(_i(faces)), ptr(_f(v_pos)), _opt(v_nrm), _opt(v_uv), _opt(v_attr if Ca else None), Ca,
+                                         _opt(clip_w), _opt(v_pos_cam), _opt(v_nrm_cam), V, B, H, W, len(maps), mptr, mdim, SCREEN_FILTERS[filter], kind, scalar,
+                                         _opt(bgs["v_attr"]), _opt(bgs["map_attr"]), bits, ptrs, ctx.stream()))
     return out
 
 
@@ -395,27 +403,16 @@ def uv_project(rast2d, faces, face_mask, v_ndc, map_attr=None, rast_map=None, fi
         if rast_map is None or tuple(rast_map.shape) != (B, Hm, Wm, 4):
             raise ValueError("uv_project: rast_map is %s, expected the views' rasters at the map's size %s" %
                              (None if rast_map is None else tuple(rast_map.shape), (B, Hm, Wm, 4)))
-        if background is not None:
-            if isinstance(background, (int, float)):
-                kind, scalar = 1, float(background)
-            elif isinstance(background, torch.Tensor):
-                bgt = background.to(dev, F32)
-                kind = 2 if bgt.dim() <= 1 else 3
-                try:
-                    bg = bgt.expand(Cm).contiguous() if kind == 2 else bgt.expand(B, H, W, Cm).contiguous()
-                except RuntimeError:
-                    raise ValueError("uv_project: background %s does not broadcast to %s" % (tuple(bgt.shape), (B, H, W, Cm)))
-            else:
-                raise ValueError("uv_project: background is %r: expected None, a number or a tensor" % type(background))
+        kind, scalar, expand = _background("uv_project", background, dev)
+        bg = expand((B, H, W, Cm))
     ctx = get_ctx(dev.index)
     out = {"uv_alpha": torch.empty(B, H, W, 1, dtype=F32, device=dev), "uv": torch.empty(B, H, W, 2, dtype=F32, device=dev)}
     if map_attr is not None:
         out["map_attr"] = torch.empty(B, H, W, Cm, dtype=F32, device=dev)
     if H * W == 0:
         return out
-    opt = lambda t: ptr(_f(t)) if t is not None else None
-    ctx.check(ctx.lib.utx_uv_project(ctx.handle, ptr(_f(rast2d)), ptr(_i(faces)), F, ptr(_u8(face_mask)), ptr(_f(v_ndc)), V, B, H, W, opt(map_attr), Bm, Hm, Wm, Cm,
-                                     opt(rast_map), SCREEN_FILTERS[filter], kind, scalar, opt(bg), ptr(out["uv"]), ptr(out["uv_alpha"]),
+    ctx.check(ctx.lib.utx_uv_project(ctx.handle, ptr(_f(rast2d)), ptr(_i(faces)), F, ptr(_u8(face_mask)), ptr(_f(v_ndc)), V, B, H, W, _opt(map_attr), Bm, Hm, Wm, Cm,
+                                     _opt(rast_map), SCREEN_FILTERS[filter], kind, scalar, _opt(bg), ptr(out["uv"]), ptr(out["uv_alpha"]),
                                      ptr(out["map_attr"]) if map_attr is not None else None, ctx.stream()))
     return out
 

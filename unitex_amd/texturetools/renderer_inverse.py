@@ -58,6 +58,26 @@ def _check_gaussian_ksize(k):
         raise NotImplementedError("reproject_kernel_size_blur=%r: the Gaussian seam blur is built up to a kernel size of %d" % (k, ops.GAUSS_KSIZE_MAX))
 
 
+def _refuse_unbuilt(who, kwargs, known):
+    """the reference's flags that simple_inverse_rendering / simple_rendering do not build: one of `known` is refused when set, any other keyword is
+    a TypeError"""
+    for k_, v_ in kwargs.items():
+        if k_ not in known:
+            raise TypeError("%s() got an unexpected keyword argument %r" % (who, k_))
+        if v_:
+            raise NotImplementedError("%s(%s=%r) is not built" % (who, k_, v_))
+
+
+def _check_grid_interpolate_mode(who, mode):
+    if mode not in ops.SCREEN_FILTERS:
+        raise ValueError("%s(grid_interpolate_mode=%r): one of %s" % (who, mode, ", ".join(ops.SCREEN_FILTERS)))
+
+
+def _reads_vertex_normals(want):
+    """does a buffer of `want` read the vertex normals?  (they are built lazily, on the host; the atlas and the screen name these buffers alike)"""
+    return any(k in ("world_normal",) + ops.SCREEN_GBUFFERS_NRM_CAM for k in want)
+
+
 class DeviceMesh:
     """PBRMesh of the reference (mesh/structure_v2.py:25-77) reduced to what the inverse renderer reads:
     vertices, faces, per-face normals, UVs mapped to [-1, 1], and the lazily built LBVH ('optix')."""
@@ -333,11 +353,7 @@ class NVDiffRendererInverse:
         render_uv without cameras and render_map_attr without render_uv raise NotImplementedError; c2ws without intrinsics, render_map_attr
         without map_attr, a map of the wrong rank or of a batch that is neither 1 nor B, an unknown visible_faces or grid_interpolate_mode
         raise ValueError."""
-        for k_, v_ in kwargs.items():
-            if k_ not in self._UV_FLAGS_UNBUILT:
-                raise TypeError("simple_inverse_rendering() got an unexpected keyword argument %r" % k_)
-            if v_:
-                raise NotImplementedError("simple_inverse_rendering(%s=%r) is not built" % (k_, v_))
+        _refuse_unbuilt("simple_inverse_rendering", kwargs, self._UV_FLAGS_UNBUILT)
         if intrinsics is not _UNSET and not render_uv:
             raise TypeError("simple_inverse_rendering() takes intrinsics only with render_uv=True: no other buffer projects")
         if render_map_attr and not render_uv:
@@ -347,8 +363,7 @@ class NVDiffRendererInverse:
                 raise NotImplementedError("simple_inverse_rendering(render_uv=True) without cameras is not built: pass c2ws and intrinsics")
             if intrinsics is _UNSET or intrinsics is None:
                 raise ValueError("simple_inverse_rendering(render_uv=True) projects the cameras: intrinsics is required")
-            if grid_interpolate_mode not in ops.SCREEN_FILTERS:
-                raise ValueError("simple_inverse_rendering(grid_interpolate_mode=%r): one of %s" % (grid_interpolate_mode, ", ".join(ops.SCREEN_FILTERS)))
+            _check_grid_interpolate_mode("simple_inverse_rendering", grid_interpolate_mode)
             if visible_faces not in ("rays", "raster"):
                 raise ValueError("simple_inverse_rendering(visible_faces=%r): 'rays' or 'raster'" % (visible_faces,))
             n_views = torch.as_tensor(c2ws).shape[0]
@@ -380,8 +395,8 @@ class NVDiffRendererInverse:
             v_attr = self._vertex_attr(v_attr, "simple_inverse_rendering")
         rast2d = self._uv_raster(int(H2D), int(W2D))
         with self._stage("uv_gbuffer"):
-            need_nrm = any(k in ("world_normal",) + ops.UV_GBUFFERS_NRM_CAM for k in want)      # the normals are built lazily, on the host
-            out = ops.uv_gbuffer(rast2d, m.faces, m.vertices, m.vertex_normals if need_nrm else None, c2ws=c2ws, want=["mask", "alpha"] + want)
+            out = ops.uv_gbuffer(rast2d, m.faces, m.vertices, m.vertex_normals if _reads_vertex_normals(want) else None, c2ws=c2ws,
+                                 want=["mask", "alpha"] + want)
             if render_v_attr:
                 out["v_attr"] = ops.screen_gbuffer(rast2d[None], m.faces, m.vertices, v_attr=v_attr, want=("v_attr",), background=background)["v_attr"]
         if render_uv:
@@ -482,19 +497,14 @@ class NVDiffRendererInverse:
         render_visible_point_cloud (draw_mask hands the float pixel coordinates of discretize to torch.scatter as the index, :151-154, :28-36)
         and render_map_network (a callable of the caller's: apply it to 'uv').  Any other keyword is a TypeError.  render_v_attr without v_attr,
         render_map_attr without map_attr, more than four maps, or a v_attr whose first dimension is not V raise ValueError."""
-        for k_, v_ in kwargs.items():
-            if k_ not in self._SCREEN_FLAGS_UNBUILT:
-                raise TypeError("simple_rendering() got an unexpected keyword argument %r" % k_)
-            if v_:
-                raise NotImplementedError("simple_rendering(%s=%r) is not built" % (k_, v_))
+        _refuse_unbuilt("simple_rendering", kwargs, self._SCREEN_FLAGS_UNBUILT)
         flags = dict(z_depth=render_z_depth, world_normal=render_world_normal, camera_normal=render_camera_normal, world_position=render_world_position,
                      camera_position=render_camera_position, distance=render_distance, ray_direction=render_ray_direction,
                      cos_ray_normal=render_cos_ray_normal, v_attr=render_v_attr, uv=render_uv, map_attr=render_map_attr)
         want = [k for k in self._SCREEN_FLAGS if flags[k]]
         m = self.pbr_mesh
         assert m is not None, "update_from_file first"
-        if grid_interpolate_mode not in ops.SCREEN_FILTERS:
-            raise ValueError("simple_rendering(grid_interpolate_mode=%r): one of %s" % (grid_interpolate_mode, ", ".join(ops.SCREEN_FILTERS)))
+        _check_grid_interpolate_mode("simple_rendering", grid_interpolate_mode)
         if render_v_attr:
             v_attr = self._vertex_attr(v_attr, "simple_rendering")
         maps = ()
@@ -515,8 +525,7 @@ class NVDiffRendererInverse:
         with self._stage("view_raster"):
             mvp, c2ws_cpu, clip, _, rast = self._view_raster(c2ws, intrinsics, render_size, perspective)
         with self._stage("screen_gbuffer"):
-            need_nrm = any(k in ("world_normal",) + ops.SCREEN_GBUFFERS_NRM_CAM for k in want)      # the normals are built lazily, on the host
-            out = ops.screen_gbuffer(rast, m.faces, m.vertices, v_nrm=m.vertex_normals if need_nrm else None, v_uv=m.uvs_2d if render_uv else None,
+            out = ops.screen_gbuffer(rast, m.faces, m.vertices, v_nrm=m.vertex_normals if _reads_vertex_normals(want) else None, v_uv=m.uvs_2d if render_uv else None,
                                      v_attr=v_attr if render_v_attr else None, maps=maps, c2ws=c2ws_cpu, want=["mask", "alpha"] + want,
                                      background=background, filter=grid_interpolate_mode,
                                      clip_w=clip[..., 3].contiguous() if render_z_depth else None)
