@@ -40,12 +40,12 @@ int utx_init(int device, utx_ctx** ctx);
 void utx_free(utx_ctx* ctx);
 const char* utx_last_error(utx_ctx* ctx);
 
-/* Launch options (kernel selection / scheduling A/B).  Every one is RESULT-PRESERVING: identical bits, except that the three
- * tail-split switches (UTX_ATTN_TAILSPLIT, UTX_GEMM_TAILSPLIT, UTX_GEMM_STREAMK) change the fp32 summation order inside the tiles
+/* Launch options (kernel selection / scheduling A/B).  Every one is RESULT-PRESERVING: identical bits, except that the two
+ * tail-split switches (UTX_ATTN_TAILSPLIT, UTX_GEMM_STREAMK) change the fp32 summation order inside the tiles
  * they split -- the same result up to rounding, deterministic from launch to launch.  The first utx_init reads the environment
  * variables of the same names once; later changes go through utx_set_option only (no getenv on the launch path).  Names:
- * UTX_ATTN_Q64, UTX_ATTN_TAILSPLIT, UTX_GEMM_GROUP_M, UTX_GEMM_TILE, UTX_GEMM_TAILSPLIT,
- * UTX_GEMM_STREAMK, UTX_GEMM_PERS_GRID, UTX_GEMM_PERS_SCHED, UTX_BVH_STACK_WALK, UTX_BVH_PACKET, UTX_ATTN_PEEL, UTX_ATTN8_PEEL, UTX_NN_GRID.  UTX_ATTN_Q64 (default 1: the
+ * UTX_ATTN_Q64, UTX_ATTN_TAILSPLIT, UTX_GEMM_GROUP_M, UTX_GEMM_TILE (0, 128 or 2564: with any other value utx_gemm_bf16 and utx_gemm_plan return -2),
+ * UTX_GEMM_STREAMK, UTX_GEMM_FASTK, UTX_GEMM_PERS_GRID, UTX_BVH_STACK_WALK, UTX_BVH_PACKET, UTX_ATTN_PEEL, UTX_ATTN8_PEEL, UTX_NN_GRID.  UTX_ATTN_Q64 (default 1: the
  * 4 x 64 attention kernel for the launches it takes) keeps the bits wherever the 8 x 32 kernel does not re-centre its running maximum behind the first 32 keys; where it does, the two
  * kernels return two roundings of the same softmax.  The timing-ablation switches that compute wrong
  * results (UTX_ATTN_VAR, UTX_ATTN_DEBUG, UTX_GEMM_DEBUG) exist only in the separately built libunitex_hip_ablate.so (tools/ only): in
@@ -202,8 +202,9 @@ int utx_gemm_bf16(utx_ctx* ctx, const utx_gemm_desc* d, utx_stream stream);
 size_t utx_gemm_streamk_workspace_bytes(utx_ctx* ctx);   /* size of utx_gemm_desc.sk_work for this device (2 partial tiles per CU) */
 /* What utx_gemm_bf16 would do with this descriptor on a device of n_cus compute units under the current launch options -- the library's own dispatch
  * arithmetic, no device needed (the host uses it to decide which projections can take the fused q / k epilogue, and bench.py to report the launch census):
- * out[0] = kernel (0 128x128 tiles, 1 one wave per SIMD, 2 persistent 8-wave, 3 per-tile 8-phase, 4 two-barrier 256^2), out[1] = output tiles of that kernel (128^2 for kernel 0, else 256^2), out[2] = tiles
- * of the last round that are cut along K (0: unsplit; needs d->sk_work != NULL), out[3] = K ranges per such tile. */
+ * out[0] = kernel (0 128x128 tiles, 1 one wave per SIMD; 2, 3 and 4 named retired kernels and are never returned), out[1] = output tiles of that kernel (128^2 for kernel 0, else 256^2), out[2] = tiles
+ * of the last round that are cut along K (0: unsplit; needs d->sk_work != NULL), out[3] = K ranges per such tile.  Returns -2 for a bad argument and for a UTX_GEMM_TILE
+ * value that names no kernel, as utx_gemm_bf16 does. */
 int utx_gemm_plan(const utx_gemm_desc* d, int n_cus, int out[4]);
 
 /* OCP MX fp8 quantisation of a bf16 matrix along its rows (the activation operand of an mx8 GEMM):

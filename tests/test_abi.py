@@ -52,10 +52,10 @@ def test_product_library_has_no_wrong_result_switches():
     # sees exactly the options it can read -- a name missing here would be a switch tests could leak unnoticed
     import re
     table = re.findall(r'\{"(UTX_[A-Z0-9_]+)",\s*&UtxOptions::\w+,\s*(true|false)\}', open(os.path.join(ROOT, "unitex_amd", "csrc", "capi.cpp")).read())
-    assert len(_lib.OPTION_NAMES) == 14 and len(set(_lib.OPTION_NAMES)) == 14
+    assert len(_lib.OPTION_NAMES) == 12 and len(set(_lib.OPTION_NAMES)) == 12
     assert len(table) == len(_lib.OPTION_NAMES) + 3 and {n for n, abl in table if abl == "false"} == set(_lib.OPTION_NAMES), sorted({n for n, abl in table if abl == "false"} ^ set(_lib.OPTION_NAMES))
-    # retired with the register-staged kernel and the two-tile ring: unknown names now
-    for n in ("UTX_ATTN_GLDS", "UTX_ATTN_FAST", "UTX_ATTN_TPB"):
+    # retired with the register-staged kernel and the two-tile ring, and with the 8-phase and 8-wave 256 x 256 GEMM kernels: unknown names now
+    for n in ("UTX_ATTN_GLDS", "UTX_ATTN_FAST", "UTX_ATTN_TPB", "UTX_GEMM_TAILSPLIT", "UTX_GEMM_PERS_SCHED"):
         v = C.c_int()
         assert lib.utx_set_option(n.encode(), 1) == -2
         assert lib.utx_get_option(n.encode(), C.byref(v)) == -2
@@ -93,7 +93,7 @@ def test_bit_exact_kernels_are_built_without_fp_contraction():
     must = ["dit_elementwise.hip", "raster.hip", "bvh.hip", "backproject.hip", "texture_post.hip", "knn.hip"]
     for name in must:
         assert "-ffp-contract=off" in flags[name], "%s must be compiled with -ffp-contract=off (bit-exact tests depend on it)" % name
-    for name in ("gemm.hip", "gemm_w4.hip", "gemm_pers.hip", "attention.hip", "attention_glds.hip", "attention_q64.hip", "vae.hip", "unwrap.hip"):
+    for name in ("gemm.hip", "gemm_w4.hip", "attention.hip", "attention_glds.hip", "attention_q64.hip", "vae.hip", "unwrap.hip"):
         assert "-ffp-contract=off" not in flags[name]
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     src = open(os.path.join(here, "unitex_amd", "csrc", "unwrap.hip")).read()

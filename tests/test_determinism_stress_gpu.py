@@ -129,9 +129,10 @@ def test_fused_qk_epilogue_on_ragged_tiles_with_cold_tables():
         _lib.set_option("UTX_GEMM_STREAMK", 1)
 
 
-def test_gated_residual_gemm_100_launches_against_the_8_wave_kernel():
+def test_gated_residual_gemm_100_launches_against_the_128x128_kernel():
     """the default out-projection / MLP-down epilogue (gated residual, counted vmcnt waits behind residual loads and C stores) of the one-wave-per-SIMD
-    kernel against the 8-wave persistent kernel: same bits on every launch, full and ragged M, in place, under perturbation"""
+    kernel against the 128 x 128 kernel (gemm.hip: another tile shape, hipcc's own waits -- the independent witness since the 8-wave kernel was retired):
+    same bits on every launch, full and ragged M, in place, under perturbation"""
     from unitex_amd import _lib
     from unitex_amd.flux import ops
     noise = _Perturb()
@@ -144,14 +145,14 @@ def test_gated_residual_gemm_100_launches_against_the_8_wave_kernel():
         gate = (torch.rand(N, device="cuda", generator=g) * 2 - 1).to(BF)
         res = torch.randn(M, N, device="cuda", generator=g).to(BF)
         try:
-            _lib.set_option("UTX_GEMM_TILE", 2560)
+            _lib.set_option("UTX_GEMM_TILE", 128)
             h8 = res.clone()
             ops.gemm(A, B, bias=bias, gate=gate, res=h8, out=h8)
         finally:
             _lib.set_option("UTX_GEMM_TILE", 0)
         assert ops.gemm_plan(M, N, K)["kernel"] == "w4"
         try:
-            _lib.set_option("UTX_GEMM_STREAMK", 0)      # whole tiles only: the same K order as the 8-wave kernel
+            _lib.set_option("UTX_GEMM_STREAMK", 0)      # whole tiles only: the same K order as the 128 x 128 kernel
             for i in range(20):
                 noise(i)
                 h = res.clone()

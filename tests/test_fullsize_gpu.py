@@ -4,7 +4,7 @@ The oracle cannot run whole tensors of this size in seconds, so each test uses w
   * attention: sampled query rows against the oracle over ALL keys (exact same arithmetic contract as the small
     tests), plus two size-independent properties -- constant-V rows (softmax weights sum to 1) and invariance of the
     result under a permutation of the key/value order (online softmax must not depend on tile order);
-  * GEMM: the three kernels (8-phase 256^2, 2-barrier 256^2, 128^2) accumulate every output in the same K order
+  * GEMM: the two kernels (one-wave-per-SIMD 256^2, 128^2) accumulate every output in the same K order
     with the same MFMA, so they must agree BIT FOR BIT on every epilogue; sampled rows against the oracle.
 """
 import math
@@ -88,7 +88,7 @@ def _gemm_variants(fn):
     outs = {}
     _lib.set_option("UTX_GEMM_STREAMK", 0)
     try:
-        for tile in ("128", "2562", "256", "2560", "2564"):     # 2564 = the persistent one-wave-per-SIMD kernel (gemm_w4.hip), the default for the large shapes; 2560 = the persistent 8-wave kernel (gemm_pers.hip)
+        for tile in ("128", "2564"):     # 128 = the 128 x 128 kernel (gemm.hip); 2564 = the persistent one-wave-per-SIMD kernel (gemm_w4.hip), the default for the large shapes
             _set_tile(tile)
             outs[tile] = fn()
             torch.cuda.synchronize()
@@ -258,7 +258,7 @@ def test_gemm_full_size_kernels_agree_bitwise_and_match_oracle_rows(M):
         ops.gemm(x, W, bias=bias, out=c0, A2=T, B2=Bl, lora_n_limit=3 * D, lora_seg_n=D, gelu_from=3 * D, n_split=3 * D, C1=c1)
         return torch.cat([c0, c1], 1)
     o = _gemm_variants(fused)
-    assert all(_same_bits(o[k], o["128"]) for k in ("2562", "256", "2560", "2564")), "fused qkv|mlp: kernels disagree"
+    assert all(_same_bits(o[k], o["128"]) for k in ("2564",)), "fused qkv|mlp: kernels disagree"
     rows = torch.tensor([0, 255, 256, 1000, M // 2 + 17, M - 1])
     # oracle arithmetic (fp32 on the CPU, bf16 rounding at the same tensor boundaries) on the sampled rows
     y = x[rows].float().cpu() @ W.float().cpu().t()
@@ -266,7 +266,7 @@ def test_gemm_full_size_kernels_agree_bitwise_and_match_oracle_rows(M):
         y[:, si * D:(si + 1) * D] += T[rows].float().cpu()[:, si * R:(si + 1) * R] @ Bl.float().cpu()[si * D:(si + 1) * D].t()
     y = (y + bias.float().cpu()).to(BF).float()
     y[:, 3 * D:] = dit_ref.gelu_tanh(y[:, 3 * D:]).to(BF).float()
-    rel = ((o["256"][rows].float().cpu() - y).abs() / y.abs().clamp_min(1.0)).max().item()
+    rel = ((o["2564"][rows].float().cpu() - y).abs() / y.abs().clamp_min(1.0)).max().item()
     assert rel < 1.6e-2, "fused qkv|mlp vs oracle rows: %g" % rel
     del o
     # (2) out-projection with the K = 15360 concat input and the gated residual epilogue
@@ -281,22 +281,22 @@ def test_gemm_full_size_kernels_agree_bitwise_and_match_oracle_rows(M):
         ops.gemm(cat, Wo, bias=bo, out=r, gate=gate, res=r)
         return r
     o = _gemm_variants(gated)
-    assert all(_same_bits(o[k], o["128"]) for k in ("2562", "256", "2560", "2564")), "gated residual: kernels disagree"
+    assert all(_same_bits(o[k], o["128"]) for k in ("2564",)), "gated residual: kernels disagree"
     yy = ((cat[rows].float().cpu() @ Wo.float().cpu().t()) + bo.float().cpu()).to(BF).float()
     yy = (res[rows].float().cpu() + (gate.float().cpu() * yy).to(BF).float()).to(BF).float()
-    rel = ((o["256"][rows].float().cpu() - yy).abs() / yy.abs().clamp_min(1.0)).max().item()
+    rel = ((o["2564"][rows].float().cpu() - yy).abs() / yy.abs().clamp_min(1.0)).max().item()
     assert rel < 1.6e-2, "gated residual vs oracle rows: %g" % rel
 
 
 @pytest.mark.parametrize("M,N,K,K2", [(3500, 3584, 192, 64), (3584, 3584, 64, 0), (7000, 2048, 320, 128), (4096, 12544, 128, 64)])
 def test_gemm_persistent_kernel_edge_shapes_bit_identical_to_tiled_kernels(M, N, K, K2):
-    """the persistent continuous-stream kernels (gemm_w4.hip: default for >= 192 tiles of 256 x 256; gemm_pers.hip) at the shapes that stress their tile
+    """the persistent continuous-stream kernel (gemm_w4.hip: default for >= 192 tiles of 256 x 256) at the shapes that stress its tile
     boundary logic: ragged M (rows >= M in the last tile row, including waves with no valid row), an ODD number of K-tiles per
     tile (K = 192, and 48 + 1 style LoRA segments: the stream re-enters at odd LDS parity), a single K-tile per tile (K = 64:
     every K-tile is first and last), tiles with and without the LoRA segment in one launch, GELU / column split on a tile
-    boundary, and the gated residual updated IN PLACE (res aliases C).  All five kernels (incl. the one-wave-per-SIMD kernel of
-    gemm_w4.hip, whose stream unit is a 64-k K-tile: K = 64 is ONE K-tile per tile -- every K-tile first and last --, and its ragged-M gated slow
-    path) must agree bit for bit."""
+    boundary, and the gated residual updated IN PLACE (res aliases C).  Both kernels (the 128 x 128 kernel of gemm.hip and the one-wave-per-SIMD
+    kernel of gemm_w4.hip, whose stream unit is a 64-k K-tile: K = 64 is ONE K-tile per tile -- every K-tile first and last --, and its ragged-M gated
+    slow path) must agree bit for bit."""
     ops = _ops()
     g = torch.Generator(device="cuda").manual_seed(M + N + K)
     A = (torch.randn(M, K, device="cuda", generator=g) / 2).to(BF)
@@ -317,10 +317,10 @@ def test_gemm_persistent_kernel_edge_shapes_bit_identical_to_tiled_kernels(M, N,
         ops.gemm(A, W, bias=bias, out=c0, gelu_from=split, n_split=split, C1=c1, alpha=0.75, **kw)
         return torch.cat([c0, c1], 1)
     o = _gemm_variants(plain)
-    assert all(_same_bits(o[k], o["128"]) for k in ("2562", "256", "2560", "2564")), "plain / GELU / split epilogue: kernels disagree"
+    assert all(_same_bits(o[k], o["128"]) for k in ("2564",)), "plain / GELU / split epilogue: kernels disagree"
     ref = (0.75 * (A.float() @ W.float().t() + ((kw["A2"].float() @ kw["B2"].float().t()) if K2 else 0.0)) + bias.float()).to(BF).float()
     ref[:, split:] = dit_ref.gelu_tanh(ref[:, split:].cpu()).to(BF).float().cuda()
-    rel = ((o["2560"].float() - ref).abs() / ref.abs().clamp_min(1.0)).max().item()
+    rel = ((o["2564"].float() - ref).abs() / ref.abs().clamp_min(1.0)).max().item()
     assert rel < 1.6e-2, "persistent kernel vs fp32 reference: %g" % rel
     gate = torch.randn(N, device="cuda", generator=g).to(BF)
     res = torch.randn(M, N, device="cuda", generator=g).to(BF)
@@ -330,26 +330,16 @@ def test_gemm_persistent_kernel_edge_shapes_bit_identical_to_tiled_kernels(M, N,
         ops.gemm(A, W, bias=bias, out=r, gate=gate, res=r, **kw)
         return r
     o = _gemm_variants(gated)
-    assert all(_same_bits(o[k], o["128"]) for k in ("2562", "256", "2560", "2564")), "gated residual (in place): kernels disagree"
+    assert all(_same_bits(o[k], o["128"]) for k in ("2564",)), "gated residual (in place): kernels disagree"
     # repeated launches: the stream has no state that survives a launch
     again = gated()
-    assert _same_bits(again, o["2560"])
-    # the alternative DMA placement of the persistent kernel (UTX_GEMM_PERS_SCHED) computes the same bits
-    from unitex_amd import _lib
-    try:
-        _set_tile("2560")
-        for forced in (1, 2):       # both DMA placements of the persistent kernel, whatever the shape heuristic picked above
-            _lib.set_option("UTX_GEMM_PERS_SCHED", forced)
-            assert _same_bits(gated(), o["2560"])
-    finally:
-        _lib.set_option("UTX_GEMM_PERS_SCHED", 0)
-        _set_tile(None)
+    assert _same_bits(again, o["2564"])
 
 
 def test_full_width_dit_blocks_at_config1_shape_match_oracle():
     """BASELINE.json configs[0] shape (512^2 x 4 views: 4096 noise + 4096 control + 1024 dual + 512 text = 9728 tokens) at
     the real FLUX width (D = 3072, 24 heads, joint_dim 4096, rank-64 LoRA), depth cut to 1 double + 1 single block so
-    the fp32 CPU oracle finishes in seconds.  This is the shape at which every large-M kernel choice (8-phase GEMM,
+    the fp32 CPU oracle finishes in seconds.  This is the shape at which every large-M kernel choice (one-wave-per-SIMD GEMM,
     fused LoRA K-segment, split / GELU / gated epilogues, 24-head attention) is the production one."""
     from unitex_amd.flux.transformer import FluxDiT, FluxShape
     cfg = dit_ref.FluxConfig(num_double=1, num_single=1)

@@ -52,10 +52,17 @@ def test_plan_of_the_flux_linears():
     _lib.set_option("UTX_GEMM_STREAMK", 1)
     assert ops.gemm_plan(13376, 21504, K=3072, K2=64, lora_n_limit=9216, lora_seg_n=3072, n_split=9216, gelu_from=9216)["tail_tiles"] == 0
     # kernel selection switches
-    for tile, name in ((128, "128x128"), (2560, "pers8"), (256, "8phase"), (2562, "2barrier"), (2564, "w4")):
+    before = ops.gemm_plan(13376, 3072, K=3072)
+    for tile, name in ((128, "128x128"), (2564, "w4")):
         _lib.set_option("UTX_GEMM_TILE", tile)
         assert ops.gemm_plan(13376, 3072, K=3072)["kernel"] == name
+    # the selectors of the retired 256 x 256 kernels (8-phase, 8-wave persistent, 2-barrier) and a value that never meant anything: refused, not dropped
+    for tile in (256, 2560, 2562, 1):
+        _lib.set_option("UTX_GEMM_TILE", tile)
+        with pytest.raises(ValueError):
+            ops.gemm_plan(13376, 3072, K=3072)
     _lib.set_option("UTX_GEMM_TILE", 0)
+    assert ops.gemm_plan(13376, 3072, K=3072) == before
     assert ops.gemm_takes_w4(50240, 21504, n_split=9216, gelu_from=9216, K2=64, lora_seg_n=3072, lora_n_limit=9216)
     assert not ops.gemm_takes_w4(50240, 21504 + 128)          # a column boundary off the 256 grid
 

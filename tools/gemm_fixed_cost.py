@@ -1,5 +1,6 @@
 #!/usr/bin/env python
-"""Per-tile fixed cost of the 8-phase GEMM (prologue + epilogue): time vs K at fixed M, N; intercept of the linear fit."""
+"""Per-tile fixed cost of a GEMM kernel (prologue + epilogue): time vs K at fixed M, N; intercept of the linear fit.
+   python tools/gemm_fixed_cost.py [UTX_GEMM_TILE]      (the figures in DESIGN 6 are the retired 8-phase kernel's)"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from unitex_amd.flux import ops
@@ -12,7 +13,7 @@ def timeit(fn, n=20):
         a.record(); fn(); b.record(); torch.cuda.synchronize(); ts.append(a.elapsed_time(b))
     ts.sort(); return ts[len(ts) // 2]
 from unitex_amd import _lib
-_lib.set_option("UTX_GEMM_TILE", int(sys.argv[1]) if len(sys.argv) > 1 else 0)   # 0 = persistent kernel (default), 256 = per-tile 8-phase kernel
+_lib.set_option("UTX_GEMM_TILE", int(sys.argv[1]) if len(sys.argv) > 1 else 0)   # 0 = one-wave-per-SIMD persistent kernel (default), 128 = the 128 x 128 kernel
 print("UTX_GEMM_TILE =", _lib.get_options()["UTX_GEMM_TILE"])
 M, N = 50688, 3072     # 2376 tiles = 9.28 rounds of 256 CUs -> 10 rounds
 rounds = 10

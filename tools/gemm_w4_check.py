@@ -1,6 +1,6 @@
 #!/usr/bin/env python
-"""gemm256_w4_kernel (UTX_GEMM_TILE=2564) against the persistent 8-wave kernel (2560): bit-identity + interleaved timing (+ the vendor
-library through torch for scale)."""
+"""gemm256_w4_kernel (UTX_GEMM_TILE=2564) against the 128 x 128 kernel (128): bit-identity + interleaved timing (+ the vendor
+library through torch for scale).  The logs under profiles/ (r02_gemm_w4_check_*.log) compared against the persistent 8-wave kernel, retired since."""
 import math, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from unitex_amd import _lib
@@ -31,14 +31,14 @@ for M, N, K, kind in shapes:
             ops.gemm(A, B, out=C, res=R, **kw)
         else:
             ops.gemm(A, B, out=C, **kw)
-    for tile in (2560, 2564):
+    for tile in (128, 2564):
         C = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=dev)
         run(tile, C); torch.cuda.synchronize()
         outs[tile] = C
-    same = torch.equal(outs[2560].view(torch.int16), outs[2564].view(torch.int16))
-    nbad = int((outs[2560].view(torch.int16) != outs[2564].view(torch.int16)).sum())
+    same = torch.equal(outs[128].view(torch.int16), outs[2564].view(torch.int16))
+    nbad = int((outs[128].view(torch.int16) != outs[2564].view(torch.int16)).sum())
     Ct = torch.empty(M, N, dtype=torch.bfloat16, device=dev)
-    fns = {"pers": lambda: run(2560, Ct), "w4": lambda: run(2564, Ct), "lib": lambda: torch.nn.functional.linear(A, B, bias)}
+    fns = {"t128": lambda: run(128, Ct), "w4": lambda: run(2564, Ct), "lib": lambda: torch.nn.functional.linear(A, B, bias)}
     ts = {k: [] for k in fns}
     for k, f in fns.items():
         f(); f()
@@ -47,7 +47,7 @@ for M, N, K, kind in shapes:
             ts[k].append(t1(f))
     fl = 2.0 * M * N * K
     med = {k: sorted(v)[len(v) // 2] for k, v in ts.items()}
-    print("M=%6d N=%6d K=%6d %-4s | identical %s (%d differ) | pers %7.3f ms %6.0f TF | w4 %7.3f ms %6.0f TF | lib %7.3f ms %6.0f TF | w4/pers %.3f w4/lib %.3f" % (
-        M, N, K, kind, same, nbad, med["pers"], fl / med["pers"] / 1e9, med["w4"], fl / med["w4"] / 1e9, med["lib"], fl / med["lib"] / 1e9,
-        med["pers"] / med["w4"], med["lib"] / med["w4"]), flush=True)
+    print("M=%6d N=%6d K=%6d %-4s | identical %s (%d differ) | 128^2 %7.3f ms %6.0f TF | w4 %7.3f ms %6.0f TF | lib %7.3f ms %6.0f TF | w4/128^2 %.3f w4/lib %.3f" % (
+        M, N, K, kind, same, nbad, med["t128"], fl / med["t128"] / 1e9, med["w4"], fl / med["w4"] / 1e9, med["lib"], fl / med["lib"] / 1e9,
+        med["t128"] / med["w4"], med["lib"] / med["w4"]), flush=True)
 _lib.set_option("UTX_GEMM_TILE", 0)

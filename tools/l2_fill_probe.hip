@@ -3,7 +3,7 @@
 //   hipcc --offload-arch=gfx950 -O3 tools/l2_fill_probe.hip -o /tmp/l2_fill_probe && /tmp/l2_fill_probe
 // Patterns (each wave-instruction moves 64 lanes x 16 B = 1 KB into a lane-linear LDS image):
 //   0  contiguous 1 KB                                     (pre-tiled operand)
-//   1  8 rows x 128 B, row stride 6144 B                   (gemm_pers.hip: K = 3072 bf16 rows, 64-k K-tile)
+//   1  8 rows x 128 B, row stride 6144 B                   (gemm.hip, gemm_w4.hip today: K = 3072 bf16 rows, 64-k K-tile)
 //   2  16 rows x 64 B, row stride 6144 B                   (gemm_w4.hip: 32-k sub-stage)
 //   3  8 rows x 128 B, row stride 8192 B                   (K = 4096)
 //   4  4 rows x 256 B, row stride 6144 B

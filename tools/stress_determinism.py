@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Race / determinism stress: the pipelined kernels (8-phase GEMM with DMA in flight across barriers, LDS-DMA attention)
+"""Race / determinism stress: the pipelined kernels (persistent GEMM with DMA in flight across barriers, LDS-DMA attention)
 must return bit-identical results run after run on the same inputs, also while another stream keeps the chip busy.
 usage: python tools/stress_determinism.py [reps]"""
 import os, sys, torch

@@ -283,7 +283,7 @@ def load_library():
 
 
 OPTION_NAMES = ["UTX_ATTN_Q64", "UTX_ATTN_TAILSPLIT",
-                "UTX_GEMM_GROUP_M", "UTX_GEMM_TILE", "UTX_GEMM_TAILSPLIT", "UTX_GEMM_PERS_GRID", "UTX_GEMM_PERS_SCHED",
+                "UTX_GEMM_GROUP_M", "UTX_GEMM_TILE", "UTX_GEMM_PERS_GRID",
                 "UTX_GEMM_STREAMK", "UTX_BVH_STACK_WALK", "UTX_BVH_PACKET", "UTX_ATTN_PEEL", "UTX_ATTN8_PEEL", "UTX_NN_GRID", "UTX_GEMM_FASTK"]
 
 

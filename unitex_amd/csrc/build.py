@@ -30,7 +30,6 @@ SOURCES = [
     ("attention_q64.hip", []),
     ("attention_fp8.hip", NO_PK),      # round 6: the key-split epilogue made hipcc form the cross-half packed pair (tests/test_asm_hazards_cpu.py): no packed fp32 in this TU either
     ("gemm.hip", []),
-    ("gemm_pers.hip", []),
     ("gemm_w4.hip", []),
     ("dit_elementwise.hip", ["-ffp-contract=off"] + NO_PK),
     ("vae.hip", NO_PK),

@@ -19,8 +19,7 @@ struct OptName { const char* name; int UtxOptions::*field; bool ablation; };
 static const OptName kOptions[] = {
     {"UTX_ATTN_Q64", &UtxOptions::attn_q64, false},         {"UTX_ATTN_TAILSPLIT", &UtxOptions::attn_tailsplit, false},
     {"UTX_GEMM_GROUP_M", &UtxOptions::gemm_group_m, false}, {"UTX_GEMM_TILE", &UtxOptions::gemm_tile, false},
-    {"UTX_GEMM_TAILSPLIT", &UtxOptions::gemm_tailsplit, false}, {"UTX_GEMM_PERS_GRID", &UtxOptions::gemm_pers_grid, false},
-    {"UTX_GEMM_PERS_SCHED", &UtxOptions::gemm_pers_sched, false}, {"UTX_GEMM_STREAMK", &UtxOptions::gemm_streamk, false},
+    {"UTX_GEMM_PERS_GRID", &UtxOptions::gemm_pers_grid, false}, {"UTX_GEMM_STREAMK", &UtxOptions::gemm_streamk, false},
     {"UTX_BVH_STACK_WALK", &UtxOptions::bvh_stack_walk, false}, {"UTX_BVH_PACKET", &UtxOptions::bvh_packet, false},
     {"UTX_ATTN_PEEL", &UtxOptions::attn_peel, false},             {"UTX_ATTN8_PEEL", &UtxOptions::attn8_peel, false},
     {"UTX_NN_GRID", &UtxOptions::nn_grid, false},                 {"UTX_GEMM_FASTK", &UtxOptions::gemm_fastk, false},
@@ -263,8 +262,7 @@ size_t utx_gemm_streamk_workspace_bytes(utx_ctx*) { return utx_gemm_streamk_work
 int utx_gemm_plan(const utx_gemm_desc* d, int n_cus, int out[4]) {
     if (!d || !out || n_cus <= 0 || d->M <= 0 || d->N <= 0 || d->K <= 0) return -2;
     options_from_env_once();
-    utx_gemm_plan_impl(d, n_cus, d->sk_work != nullptr, out);
-    return 0;
+    return utx_gemm_plan_impl(d, n_cus, d->sk_work != nullptr, out);
 }
 int utx_gemm_bf16(utx_ctx* ctx, const utx_gemm_desc* d, utx_stream stream) {
     if (!d || !d->A || !d->B || !d->C) return fail(ctx, -2, "utx_gemm_bf16");

@@ -6,7 +6,7 @@
 //   C[M,N] = epi( alpha * ( A[M,K] . B[N,K]^T  +  A2[M,K2] . B2[N,K2]^T ) + bias[N] )      (same contract as gemm.hip; bit-identical outputs)
 //
 // Why this structure (profiles/r02_gemm_clock_probe.log): on M = 50688, N = 21504, K = 3072 the vendor library's hand-scheduled 4-wave kernel
-// keeps the matrix pipe 81 % busy against 70 % for the 8-wave kernel of gemm_pers.hip at identical MFMA work -- there a compute wave and a load
+// keeps the matrix pipe 81 % busy against 70 % for the 8-wave persistent kernel (retired) at identical MFMA work -- there a compute wave and a load
 // wave alternate per SIMD behind two barriers per phase and the load phase (~350 cycles) outlasts the 256-cycle MFMA phase it should hide
 // behind.  With one wave per SIMD there is no phase to balance: a wave owns 128x128 (a third fewer fragment bytes per FLOP: 32 ds_read_b128 per
 // 64 MFMAs instead of 24 per 32), reads the fragments of K-step k+1 under the MFMAs of K-step k and meets the other three waves at ONE barrier
@@ -15,7 +15,7 @@
 //     matrix pipe's 2048 cycles at 2.1 GHz;
 //   * with real operand traffic the kernel is bound by how the L2 -> LDS path is fed.  A first version staged 32-k sub-stages (64-byte row
 //     segments, ring of four): tools/l2_fill_probe.hip shows that path delivers 34-44 GB/s per CU for 64-byte segments and 87-100 for 128-byte
-//     ones with every CU streaming; that version ran at exactly 35 GB/s per CU (1.48 us per K-tile, 0.94-0.99 x the 8-wave kernel).  This
+//     ones with every CU streaming; that version ran at exactly 35 GB/s per CU (1.48 us per K-tile, 0.94-0.99 x the 8-wave kernel (retired)).  This
 //     version stages 64-k K-tiles on 128-byte rows (two 64 KB stages) -- 1.33 us per K-tile;
 //   * a burst of DMAs backs the vector-memory path up into the issuing wave, which has no partner wave to hide behind: eight in a row cost
 //     ~30 cycles each beyond their MFMA shadow; one per three MFMAs (below) is worth +3-4 % over one per MFMA;
@@ -26,7 +26,7 @@
 //   * whole rounds of 256 tiles are the unit of time of a persistent kernel: 636 tiles (the reference strip's N = 3072 linears) are 2.48 rounds and
 //     cost 3.  The last, partly filled round is cut along K instead ("split tail" below, gemm_w4_fixup_kernel): -13 / -14 % on the K = 12288 /
 //     15360 linears of the reference strip, -7 % on BASELINE's strip, -35 % on the pruned last block (profiles/r02_gemm_streamk_check_v4.log).
-// Result: +8-11 % over gemm256_pers_kernel on the FLUX shapes, 2-13 % behind the vendor kernel (profiles/r02_gemm_w4_check_v8.log); bench A/B
+// Result: +8-11 % over the 8-wave persistent kernel (retired) on the FLUX shapes, 2-13 % behind the vendor kernel (profiles/r02_gemm_w4_check_v8.log); bench A/B
 // profiles/r02_bench_gemm_w4_ab.log.  Replacing every 32x32x16 MFMA by two 16x16x32 (the vendor kernel's shape; ablation) is worth 1-4 % more.
 //
 // Stream: K-tile = 64 k of the 256x256 tile = A[256][64] + B[256][64] bf16 = 64 KB, two stages in LDS (128 KB) + 8 KB of C staging per wave

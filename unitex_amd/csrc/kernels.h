@@ -65,13 +65,11 @@ struct UtxOptions {
                               // + its repair pass; 0: the 8 x 32 kernel everywhere (A/B; bit-identical wherever the 8 x 32 kernel does not re-centre behind the first block)
     int attn_tailsplit = 1;   // 1 (default): key-split tail round
     int gemm_group_m = 0;     // 0 = built-in GROUP_M
-    int gemm_tile = 0;        // 0 auto, 128, 256 (per-tile 8-phase), 2560 (persistent), 2562 (2-barrier 256^2), 2564 (one wave per SIMD)
-    int gemm_tailsplit = 0;   // 1: K-split tail round of the 8-phase GEMM (off by default)
-    int gemm_pers_grid = 0;   // persistent GEMM: number of workgroups (0 = one per CU)
-    int gemm_pers_sched = 0;  // persistent GEMM: DMA placement over the phases of a K-tile: 0 = by shape, 1 = force SCHED 0, 2 = force SCHED 1
+    int gemm_tile = 0;        // 0 auto, 128, 2564 (one wave per SIMD); any other value is refused with -2 (gemm.hip gemm_tile_known)
+    int gemm_pers_grid = 0;   // one-wave-per-SIMD GEMM: number of workgroups of its persistent grid (0 = one per CU)
     int gemm_streamk = 1;     // 1 (default): one-wave-per-SIMD GEMM balances the K loops of its last, partly filled round over all CUs (needs utx_gemm_desc.sk_work)
     int bvh_stack_walk = 0;   // 1: the reference's stack walk over the unpacked tree instead of the stackless packed walk (A/B; same results)
-    int attn_var_abl = 0, attn_debug_abl = 0, gemm_debug_abl = 0;
+    int attn_var_abl = 0, attn_debug_abl = 0, gemm_debug_abl = 0;      // gemm_debug_abl (UTX_GEMM_DEBUG): no remaining kernel reads it (its readers were the retired 256^2 kernels)
     int bvh_packet = 1;       // 1 (default): back-projection rays walk the tree as wave-wide packets over 8 x 8 texel tiles (bvh_trace_packet); 0: one thread per ray (A/B; same results)
     int attn_peel = 1;        // 1 (default since round 5): the pre-scaled 8 x 32 attention launch runs its fast loop (attention_glds.hip, FAST: first / ragged tile outside the loop, the tile's
                               // barrier between S2 and S3, next tile's first K fragments read under S3); 0: the general loop (the default until round 4).  Same bits either way.
@@ -108,10 +106,9 @@ int utx_launch_attn_fwd_blk(const void* q, const void* k, const void* vt, void* 
 int utx_launch_attn_fwd_q64(const AttnParams* p, int presc, hipStream_t stream);
 int utx_launch_gemm_bf16(const GemmParams* p, hipStream_t stream);
 size_t utx_gemm_streamk_workspace_bytes_impl(void);
-void utx_gemm_plan_impl(const GemmParams* p, int ncu, int sk_has_work, int out[4]);          // gemm.hip: kernel choice + split of the last round (pure)
+int utx_gemm_plan_impl(const GemmParams* p, int ncu, int sk_has_work, int out[4]);           // gemm.hip: kernel choice + split of the last round (pure); -2: unknown UTX_GEMM_TILE
 void utx_gemm_w4_split_plan(const GemmParams* p, int tiles, int grid, int has_work, int* T, int* S);   // gemm_w4.hip (pure)
 int utx_launch_gemm_w4(GemmParams p, hipStream_t stream);     // gemm_w4.hip: persistent 256x256 kernel, one wave per SIMD
-int utx_launch_gemm_pers(GemmParams p, hipStream_t stream);   // gemm_pers.hip: persistent 256x256 kernel (large-M linears)
 int utx_launch_gemv_bf16(const GemvParams* p, hipStream_t stream);
 int utx_launch_quant_mx8(const void* x, long ldx, void* q, long ldq, void* s, long lds, int M, int K, hipStream_t stream);
 int utx_launch_quant_mx8_packed(const void* x, long ldx, void* q, long ldq, void* s, long row_blocks, int M, int K, hipStream_t stream);
