@@ -633,6 +633,43 @@ int utx_visible_faces_raster(utx_ctx* ctx, const float* rast, int B, int H, int 
 int utx_erode_faces(utx_ctx* ctx, unsigned char* mask, const int* faces, int B, int F, int V, int depth, int* vstamp, utx_stream stream);
 int utx_visible_vertices(utx_ctx* ctx, const unsigned char* mask, const int* faces, int B, int F, int V, unsigned char* out, utx_stream stream);
 
+/* Vertex-colour bake from views: project_vertex_color / remapping_vertex_color / inpainting_vertex_color of the reference
+ * (texture/reprojection/mesh_remapping.py:508-627, :273-350).  All fp32, stream-ordered, row-major.
+ * utx_view_weight_maps: cos_ray_normal [B][H][W] (utx_screen_gbuffer) -> out [B][H][W][2] = (cos term, edge alpha).  cos term: clamp(cos, -1, 0), or with
+ *   camera_normal [B][H][W][3] given (orthographic cameras; else null) clamp(camera_normal.z, 0, 1).  Edge alpha: a = ((acos(clamp(cos, -1, 0)) - pi/2) /
+ *   (pi/2)).clamp(0, 1); torch.gradient's stencil along y and x (central difference over 2 inside, one-sided at the borders, hence H, W >= 2);
+ *   sqrt(dy^2 + dx^2) > float32(radians(10) / (pi/2)), strictly; then the (2 r + 1)^2 maximum with zeros outside the image.  One launch for r = 0; for r > 0
+ *   a second launch dilates out of tmp (B * H * W bytes, the caller's; may be null for r = 0).  arccos_out (may be null): `a` [B][H][W].
+ * utx_vertex_project: one thread per vertex, the views b = 0 .. B-1 in index order.  For a view with visible [b][v] != 0 (uint8 [B][V]): h = xform[b] (x, y, z, 1),
+ *   clip = proj[b] h (both [B][4][4], products summed in index order), ndc = clip.xy / clip.w.  Only with both ndc strictly inside (-1, 1): rgba = images
+ *   [B][4][Hi][Wi] sampled as grid_sample(bilinear, padding_mode='reflection', align_corners=False) -- unnormalise, reflect about [-0.5, size - 0.5], then clip
+ *   to [0, size - 1] --, (cos, alpha) = wmap [B][H][W][2] sampled as grid_sample(bilinear, zeros, align_corners=False), a = use_alpha ? rgba.a : 1,
+ *   c = rgb a + v_rgb (1 - a), w = weights[b] (cos^2)^2 (1 - alpha); otherwise c = v_rgb, w = 0.  v_rgb_acc += w c, v_weight_acc += w.
+ *   Outputs v_rgb_acc [V][3], v_weight_acc [V].
+ * utx_vertex_project_blend: the same launch followed, per vertex, by remapping_vertex_color's epilogue into blended [V][3]: acc / w where w > overlay_confidence;
+ *   blending UTX_VB_BLEND_SOFT: (v_rgb (blending_confidence - w) + acc) / blending_confidence where w <= blending_confidence, UTX_VB_BLEND_HARD: v_rgb there,
+ *   UTX_VB_BLEND_NONE: nothing; inpaint_mask [V] uint8 = (w <= inpainting_confidence).  v_rgb_acc may be null here.
+ * utx_vertex_inpaint_step: one Jacobi step on the CSR adjacency rowptr [V + 1] / col (neighbours ascending): for each of the n vertices i of idx, with
+ *   deg = rowptr[i + 1] - rowptr[i], S = sum over the neighbours j with mask_in[j] of rgb_in[j] (CSR order) and M their number: if deg M > 0,
+ *   rgb_out[i] = (deg S) / (deg M) and mask_out[i] = 1, else rgb_out[i] = rgb_in[i] and mask_out[i] = 0.  Rows outside idx are not written: the two buffer pairs
+ *   must agree on them.  *counter (device int32, zeroed here) receives the number of vertices of idx with mask_out = 1.  One launch; no block waits for another.
+ * A zero-size problem (B H W = 0, V = 0, n = 0) returns 0 without a launch.  -2: a negative size, H or W of 1, r < 0, a null or misaligned operand (wmap / out:
+ * 8 bytes, every other array: its element), an unknown blending, rgb_in == rgb_out or mask_in == mask_out; outputs untouched. */
+#define UTX_VB_BLEND_NONE 0
+#define UTX_VB_BLEND_SOFT 1
+#define UTX_VB_BLEND_HARD 2
+int utx_view_weight_maps(utx_ctx* ctx, const float* cos_ray_normal, const float* camera_normal, int B, int H, int W, int r, void* tmp, float* out,
+                         float* arccos_out, utx_stream stream);
+int utx_vertex_project(utx_ctx* ctx, const float* v_pos, int V, const unsigned char* visible, int B, const float* xform, const float* proj, const float* images,
+                       int Hi, int Wi, const float* wmap, int H, int W, const float* v_rgb, const float* weights, int use_alpha, float* v_rgb_acc,
+                       float* v_weight_acc, utx_stream stream);
+int utx_vertex_project_blend(utx_ctx* ctx, const float* v_pos, int V, const unsigned char* visible, int B, const float* xform, const float* proj,
+                             const float* images, int Hi, int Wi, const float* wmap, int H, int W, const float* v_rgb, const float* weights, int use_alpha,
+                             float* v_rgb_acc, float* v_weight_acc, float overlay_confidence, int blending, float blending_confidence,
+                             float inpainting_confidence, float* blended, unsigned char* inpaint_mask, utx_stream stream);
+int utx_vertex_inpaint_step(utx_ctx* ctx, const int* rowptr, const int* col, const int* idx, int n, const float* rgb_in, const unsigned char* mask_in,
+                            float* rgb_out, unsigned char* mask_out, int* counter, utx_stream stream);
+
 /* fused per-(view, texel) gather + visibility of uv_to_pcd (renderer_inverse.py:277-298,316-325) */
 typedef struct utx_backproject_desc {
     const void* rast2d;                 /* [T][4] f32 UV-space raster */

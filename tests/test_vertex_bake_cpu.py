@@ -1,0 +1,383 @@
+"""Vertex-colour bake (unitex_amd/texturetools/remapping.py, utx_view_weight_maps / utx_vertex_project / utx_vertex_inpaint_step), CPU side: the numpy
+restatement (tests/vertex_bake_ref.py) against torch's own CPU operators -- torch.gradient, max_pool2d, grid_sample with reflection and zero padding,
+a sparse Laplacian product -- composed here the way mesh_remapping.py composes them; the CSR builder against a dense adjacency; the dilation radius,
+the weight tables, every refusal, the C ABI's argument checks (they return before any device call) and the .ply round trip.
+
+Bounds (vertex_bake_ref): the arccos term ARCCOS_BOUND; alpha exact outside the pixels whose float64 gradient lies within GRAD_EDGE of the threshold;
+the accumulators twice project_bound (two float32 evaluations with summation orders of their own); the inpainting inpaint_bound(steps, d_max)."""
+import ctypes as C
+import math
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tests import vertex_bake_ref as R
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _cos_image(B, H, W, seed):
+    """a cos_ray_normal-like image: smooth facing term with a few creases and a background of 0, so that both alpha classes occur"""
+    rng = np.random.default_rng(seed)
+    y, x = np.meshgrid(np.linspace(-1, 1, H), np.linspace(-1, 1, W), indexing="ij")
+    out = np.zeros((B, H, W), np.float32)
+    for b in range(B):
+        r2 = (x - rng.uniform(-0.2, 0.2)) ** 2 + (y - rng.uniform(-0.2, 0.2)) ** 2
+        c = -np.sqrt(np.clip(1 - r2 / 0.8, 0, 1))
+        c = np.where(x * rng.uniform(-1, 1) + y > 0.3, c * 0.5, c)
+        out[b] = c.astype(np.float32)
+    return out
+
+
+def _torch_weight_maps(cosn, cam_nz, r):
+    """mesh_remapping.py:544-555 with torch's CPU operators"""
+    c = torch.from_numpy(cosn)[..., None]
+    images_cos = c.clamp(-1.0, 0.0)
+    arccos = ((torch.arccos(images_cos) - torch.pi / 2) / (torch.pi / 2)).clamp(0.0, 1.0)
+    dy, dx = torch.gradient(arccos, dim=[1, 2])
+    grad = torch.sqrt(dy.square() + dx.square())
+    alpha = (grad > math.radians(10) / (math.pi / 2)).float()
+    k = 2 * r + 1
+    if k > 1:
+        alpha = torch.nn.functional.max_pool2d(alpha.permute(0, 3, 1, 2), k, 1, k // 2).permute(0, 2, 3, 1)
+    if cam_nz is not None:
+        images_cos = torch.from_numpy(cam_nz)[..., None].clamp(0.0, 1.0)
+    return torch.cat([images_cos, alpha], -1).numpy(), arccos[..., 0].numpy()
+
+
+@pytest.mark.parametrize("r,ortho", [(0, False), (1, False), (2, True)])
+def test_weight_maps_restatement_against_torch(r, ortho):
+    B, H, W = 2, 33, 41
+    cosn = _cos_image(B, H, W, 3)
+    cam_nz = np.random.default_rng(4).uniform(-0.2, 1.2, (B, H, W)).astype(np.float32) if ortho else None
+    want, want_arccos = _torch_weight_maps(cosn, cam_nz, r)
+    got = R.weight_maps(cosn, cam_nz, r)
+    g64 = R.weight_maps(cosn, cam_nz, 0, np.float64)["grad"]
+    edge = R.dilate((np.abs(g64 - float(R.GRAD_THR32)) <= R.GRAD_EDGE).astype(np.float32), r) > 0
+    assert np.array_equal(got["out"][..., 0], want[..., 0])
+    assert np.abs(got["arccos"].astype(np.float64) - want_arccos).max() <= R.ARCCOS_BOUND
+    assert edge.mean() <= 0.01 and np.array_equal(got["out"][..., 1][~edge], want[..., 1][~edge])
+    assert 0 < want[..., 1].mean() < 1, "both alpha classes"
+
+
+def test_gradient_threshold_and_half_pi_are_the_float32_values_torch_uses():
+    assert np.float32(math.radians(10) / (math.pi / 2)) == np.float32(1.0) / np.float32(9.0) == R.GRAD_THR32
+    assert float(R.HALF_PI32) == 1.57079637050628662109375
+
+
+def test_dilation_against_max_pool2d():
+    a = (np.random.default_rng(5).uniform(0, 1, (2, 33, 65)) < 0.05).astype(np.float32)
+    for r in (1, 2):
+        want = torch.nn.functional.max_pool2d(torch.from_numpy(a)[:, None], 2 * r + 1, 1, r)[:, 0].numpy()
+        assert np.array_equal(R.dilate(a, r), want)
+
+
+def _hand_points(Hi, Wi):
+    """NDC points: exact pixel centres, exact halves between them, +-(1 - 2^-20), the outer half-pixel rim on all four sides"""
+    e = 1 - 2.0 ** -20
+    xs = [(2 * i + 1) / Wi - 1 for i in range(Wi)] + [2 * i / Wi - 1 for i in range(1, Wi)] + [-e, e, -1 + 0.5 / Wi, 1 - 0.5 / Wi, -1 + 0.25 / Wi, 1 - 0.75 / Wi, 0.0]
+    ys = [(2 * i + 1) / Hi - 1 for i in range(Hi)] + [2 * i / Hi - 1 for i in range(1, Hi)] + [-e, e, -1 + 0.5 / Hi, 1 - 0.5 / Hi, -1 + 0.25 / Hi, 1 - 0.75 / Hi, 0.0]
+    gx, gy = np.meshgrid(np.array(xs, np.float32), np.array(ys, np.float32))
+    return gx.reshape(-1), gy.reshape(-1)
+
+
+@pytest.mark.parametrize("Hi,Wi", [(5, 7), (1, 1), (1, 7), (4, 2)])
+def test_reflection_sampling_restatement_against_grid_sample(Hi, Wi):
+    img = np.random.default_rng(Hi * 10 + Wi).uniform(0, 1, (4, Hi, Wi)).astype(np.float32)
+    gx, gy = _hand_points(Hi, Wi)
+    grid = torch.from_numpy(np.stack([gx, gy], -1))[None, :, None]
+    for mode, fn in (("reflection", R.sample_reflect), ("zeros", R.sample_zeros)):
+        want = torch.nn.functional.grid_sample(torch.from_numpy(img)[None], grid, mode="bilinear", padding_mode=mode, align_corners=False)[0, :, :, 0].numpy()
+        got = fn(img, gx, gy)
+        assert np.abs(got.astype(np.float64) - want).max() <= 4 * R.U * img.max(), mode
+
+
+def _torch_project(case, use_alpha):
+    """mesh_remapping.py:557-594 with torch's CPU operators on the arrays of a synthetic case (matrices given instead of cameras)"""
+    t = {k: torch.from_numpy(v) for k, v in case.items()}
+    v_rgb, vis = t["v_rgb"], t["visible"].bool()
+    acc, wacc = torch.zeros_like(v_rgb), torch.zeros_like(v_rgb[..., [0]])
+    for b in range(vis.shape[0]):
+        v = t["v_pos"][vis[b]]
+        rgb_vis = v_rgb[vis[b]].clone()
+        w_vis = torch.zeros_like(rgb_vis[..., [0]])
+        homo = torch.cat([v, torch.ones_like(v[..., [0]])], -1) @ t["xform"][b].T
+        clip = homo @ t["proj"][b].T
+        ndc = clip[..., :2] / clip[..., [3]]
+        ok = torch.logical_and(ndc > -1, ndc < 1).prod(-1).bool()
+        g = ndc[ok][None, :, None]
+        rgba = torch.nn.functional.grid_sample(t["images"][b][None], g, padding_mode="reflection", mode="bilinear", align_corners=False)[0, :, :, 0].T
+        cw = torch.nn.functional.grid_sample(t["wmap"][b][None].permute(0, 3, 1, 2), g, padding_mode="zeros", mode="bilinear", align_corners=False)[0, :, :, 0].T
+        rgb, a = rgba[:, :3], rgba[:, 3:]
+        if not use_alpha:
+            a = torch.ones_like(a)
+        rgb_vis[ok] = rgb * a + rgb_vis[ok] * (1 - a)
+        w_vis[ok] = t["weights"][b] * cw[:, :1].square().square() * (1 - cw[:, 1:])
+        acc[vis[b]] = acc[vis[b]] + w_vis * rgb_vis
+        wacc[vis[b]] = wacc[vis[b]] + w_vis
+    return acc.numpy(), wacc.numpy()
+
+
+@pytest.mark.parametrize("use_alpha", [True, False])
+def test_projection_restatement_against_torch(use_alpha):
+    case = R.synthetic_case(257, 4, 11, dead_vertex=5, dead_view=2)
+    want_acc, want_w = _torch_project(case, use_alpha)
+    detail = []
+    acc, w = R.vertex_project(use_alpha=use_alpha, detail=detail, **case)
+    acc64, w64 = R.vertex_project(use_alpha=use_alpha, dtype=np.float64, **case)
+    e_acc, e_w = R.project_bound(**case)
+    for got_a, got_w in ((want_acc, want_w), (acc64, w64)):
+        assert (np.abs(acc.astype(np.float64) - got_a).max(1) <= 2 * e_acc).all()
+        assert (np.abs(w.astype(np.float64) - got_w)[:, 0] <= 2 * e_w).all()
+    assert e_acc.max() < 1e-3 * w.max() and (w[5] == 0).all() and (acc[5] == 0).all()      # the bound stays three orders below the accumulated weights
+    inside = np.stack([d[0] for d in detail])
+    assert inside.any() and (case["visible"].astype(bool) & ~inside).any(), "some visible vertex fails the strict NDC test"
+
+
+def test_epilogue_restatement_has_vertices_on_both_sides_of_every_branch():
+    case = R.synthetic_case(257, 4, 11)
+    acc, w = R.vertex_project(**case)
+    for blending in (None, "soft", "hard"):
+        over, out, mask = R.epilogue(acc, w, case["v_rgb"], 0.05, blending, 0.2, 0.5)
+        t_acc, t_w, t_rgb = torch.from_numpy(acc), torch.from_numpy(w), torch.from_numpy(case["v_rgb"])
+        t_over = torch.where(t_w > 0.05, torch.div(t_acc, t_w), t_acc)
+        t_out = t_over
+        if blending == "soft":
+            t_out = torch.where(t_w <= 0.2, (t_rgb * (0.2 - t_w) + t_over) / 0.2, t_over)
+        elif blending == "hard":
+            t_out = torch.where(t_w <= 0.2, t_rgb, t_over)
+        assert np.array_equal(over, t_over.numpy()) and np.array_equal(out, t_out.numpy())
+        assert np.array_equal(mask.astype(bool), (t_w[:, 0] <= 0.5).numpy())
+        for thr in (0.05, 0.2, 0.5):
+            assert 0 < (w > thr).mean() < 1
+
+
+def _grid_mesh(n):
+    idx = np.arange(n * n).reshape(n, n)
+    a, b, c, d = idx[:-1, :-1].ravel(), idx[:-1, 1:].ravel(), idx[1:, :-1].ravel(), idx[1:, 1:].ravel()
+    return np.concatenate([np.stack([a, b, c], -1), np.stack([b, d, c], -1)]).astype(np.int32)
+
+
+def test_csr_builder_against_a_dense_adjacency():
+    from unitex_amd.texturetools import ops
+    faces = np.concatenate([_grid_mesh(6), np.array([[40, 41, 42], [42, 41, 40], [43, 43, 44]], np.int32)])      # a doubled face, a degenerate one
+    V = 47                                                                                                     # 45 and 46 are isolated
+    rowptr, col = ops.vertex_adjacency(torch.from_numpy(faces), V)
+    want_rowptr, want_col = R.csr_from_dense(R.adjacency_dense(faces, V))
+    assert rowptr.dtype == torch.int32 and col.dtype == torch.int32
+    assert np.array_equal(rowptr.numpy(), want_rowptr) and np.array_equal(col.numpy(), want_col)
+    assert rowptr[46] == rowptr[47] == len(col)
+
+
+def test_inpainting_restatement_against_the_sparse_product():
+    """inpainting_vertex_color (:605-627) with torch's sparse product on L[i, j] = deg[i] (mesh/structure.py:743-763)"""
+    faces = _grid_mesh(7)
+    V = 49
+    A = R.adjacency_dense(faces, V)
+    rowptr, col = R.csr_from_dense(A)
+    rng = np.random.default_rng(2)
+    rgb = rng.uniform(0, 1, (V, 3)).astype(np.float32)
+    idx = np.array([v for v in range(V) if v % 7 > 1], np.int64)
+    got, steps, masks = R.inpaint(rowptr, col, rgb, idx)
+    deg = A.sum(1).astype(np.float32)
+    L = torch.from_numpy(A.astype(np.float32) * deg[:, None]).to_sparse()
+    v_rgb, v_mask = torch.from_numpy(rgb.copy()), torch.ones(V, 1)
+    tidx = torch.from_numpy(idx)
+    v_mask[tidx] = 0
+    cnt, t_steps = v_mask.sum(), 0
+    L_inv = torch.index_select(L, 0, tidx)
+    for _ in range(1000):
+        m_rgb, m_mask = torch.matmul(L_inv, v_rgb * v_mask), torch.matmul(L_inv, v_mask)
+        v_rgb[tidx] = torch.where(m_mask > 0, m_rgb / m_mask, v_rgb[tidx])
+        v_mask[tidx] = (m_mask > 0).float()
+        t_steps += 1
+        if v_mask.sum() > cnt:
+            cnt = v_mask.sum()
+        else:
+            break
+    dist = R.bfs_depth(rowptr, col, ~np.isin(np.arange(V), idx))
+    assert steps == t_steps == dist.max() + 1 and steps >= 3
+    for k, m in enumerate(masks):
+        assert np.array_equal(m, (dist >= 0) & (dist <= k + 1))
+    assert np.abs(got.astype(np.float64) - v_rgb.numpy()).max() <= R.inpaint_bound(steps, int(A.sum(1).max()))
+
+
+def test_dilation_radius_formula():
+    from unitex_amd.texturetools import ops
+    assert [ops.weight_map_radius(s) for s in (48, 511, 512, 1023, 1024)] == [0, 0, 1, 1, 2]
+    for s in (48, 512, 768, 1024, 2048):
+        assert 2 * ops.weight_map_radius(s) + 1 == 2 * (s // 512) + 1
+
+
+def test_weight_tables():
+    from unitex_amd.texturetools import remapping
+    assert remapping.default_weights(8) == [2.0, 0.05, 0.2, 0.02, 1.0, 0.02, 0.2, 0.05]
+    assert remapping.default_weights(6) == [2.0, 0.05, 0.2, 1.0, 0.2, 0.05]
+    assert remapping.default_weights(4) == [2.0, 0.2, 1.0, 0.2]
+    assert remapping.default_weights(2) == [1.0, 1.0]
+    assert remapping.default_weights(3) == [1.0] * 3 and remapping.default_weights(9) == [1.0] * 9
+
+
+def test_every_refusal():
+    from unitex_amd.texturetools import remapping as M
+    c2ws = torch.eye(4)[None].repeat(3, 1, 1)
+    intr, img = torch.eye(3), torch.zeros(3, 4, 4, 4)
+    with pytest.raises(NotImplementedError, match="visualize"):
+        M.project_vertex_color(None, c2ws, intr, img, torch.zeros(4, 3), torch.ones(3), visualize=True)
+    with pytest.raises(NotImplementedError, match="visualize"):
+        M.remapping_vertex_color(None, c2ws, intr, img, visualize=True)
+    with pytest.raises(NotImplementedError, match="visualize"):
+        M.initial_map_Kd_with_v_rgb(None, torch.zeros(4, 3), visualize=True)
+    with pytest.raises(NotImplementedError, match="use_pymeshlab"):
+        M.initial_map_Kd_with_v_rgb(None, torch.zeros(4, 3), use_pymeshlab=True)
+    with pytest.raises(NotImplementedError, match="use_cv_outpainting"):
+        M.initial_map_Kd_with_v_rgb(None, torch.zeros(4, 3), use_cv_outpainting=True)
+    with pytest.raises(ValueError, match="size mismatch: length of weights should be 3 but 2"):
+        M.remapping_vertex_color(None, c2ws, intr, img, weights=[1.0, 1.0])
+    with pytest.raises(ValueError, match="value error: medium is not supported"):
+        M.remapping_vertex_color(None, c2ws, intr, img, blending_type="medium")
+    with pytest.raises(TypeError, match="DeviceMesh"):
+        M.project_vertex_color(object(), c2ws, intr, img, torch.zeros(4, 3), torch.ones(3))
+    assert not hasattr(M, "remapping_uv_texture")
+    import inspect
+    sig = inspect.signature(M.remapping_vertex_color).parameters
+    assert list(sig)[:15] == ["mesh", "c2ws", "intrinsics", "images", "v_rgb", "weights", "use_alpha", "overlay_confidence", "use_blending", "blending_type",
+                              "blending_confidence", "use_inpainting", "inpainting_confidence", "render_size", "visualize"]
+    assert [sig[k].default for k in ("overlay_confidence", "blending_type", "blending_confidence", "inpainting_confidence", "render_size", "perspective",
+                                     "reference_transform")] == [0.2, "soft", 0.2, 0.2, 512, True, False]
+    assert inspect.signature(M.inpainting_vertex_color).parameters["max_iters"].default == 1000
+    assert inspect.signature(M.initial_map_Kd_with_v_rgb).parameters["texture_size"].default == 1024
+
+
+def test_c_abi_refuses_bad_arguments_before_any_device_call():
+    from unitex_amd import _lib
+    lib = _lib.load_library()
+    hdr = open(os.path.join(ROOT, "include", "unitex_hip.h")).read()
+    for name, nargs in (("utx_view_weight_maps", 11), ("utx_vertex_project", 19), ("utx_vertex_project_blend", 25), ("utx_vertex_inpaint_step", 11)):
+        assert "int %s(" % name in hdr and len(_lib.SYMBOLS[name][1]) == nargs
+    buf = (C.c_char * 4096)()
+    p = C.c_void_p((C.addressof(buf) + 63) & ~63)
+    odd = C.c_void_p(p.value + 2)
+    w = lib.utx_view_weight_maps
+    assert w(None, None, None, 1, 8, 8, 0, None, p, None, None) == -2 and w(None, p, None, 1, 8, 8, 0, None, None, None, None) == -2      # null
+    assert w(None, p, None, -1, 8, 8, 0, None, p, None, None) == -2 and w(None, p, None, 1, 8, 8, -1, None, p, None, None) == -2          # negative
+    assert w(None, p, None, 1, 1, 8, 0, None, p, None, None) == -2 and w(None, p, None, 1, 8, 8, 1, None, p, None, None) == -2            # one row; r > 0 without scratch
+    assert w(None, odd, None, 1, 8, 8, 0, None, p, None, None) == -2 and w(None, p, None, 1, 8, 8, 0, None, C.c_void_p(p.value + 4), None, None) == -2
+    assert w(None, None, None, 0, 8, 8, 0, None, None, None, None) == 0 and w(None, None, None, 2, 0, 8, 0, None, None, None, None) == 0  # zero size
+    vp = lib.utx_vertex_project
+    ok = [None, p, 4, p, 2, p, p, p, 4, 4, p, 4, 4, p, p, 1, p, p, None]
+    assert vp(None, None, 0, None, 2, None, None, None, 4, 4, None, 4, 4, None, None, 1, None, None, None) == 0                          # V = 0
+    for k in (1, 3, 5, 6, 7, 10, 13, 14, 16, 17):
+        bad = list(ok); bad[k] = None
+        assert vp(*bad) == -2, k
+    for k in (1, 5, 6, 7, 13, 14, 16, 17):
+        bad = list(ok); bad[k] = odd
+        assert vp(*bad) == -2, k
+    bad = list(ok); bad[10] = C.c_void_p(p.value + 4)
+    assert vp(*bad) == -2                                                                                                                 # wmap is read as float2
+    for k, v in ((2, -1), (4, -1), (8, -1), (8, 0), (12, 0)):
+        bad = list(ok); bad[k] = v
+        assert vp(*bad) == -2, k
+    vb = lib.utx_vertex_project_blend
+    okb = ok[:18] + [0.2, 1, 0.2, 0.2, p, p, None]
+    for k, v in ((19, 3), (19, -1), (22, None), (23, None), (22, odd), (17, None)):
+        bad = list(okb); bad[k] = v
+        assert vb(*bad) == -2, k
+    st = lib.utx_vertex_inpaint_step
+    q = C.c_void_p(p.value + 1024)
+    oks = [None, p, p, p, 3, p, p, q, q, p, None]
+    assert st(None, None, None, None, 0, None, None, None, None, None, None) == 0                                                        # nothing to fill
+    for k in range(1, 10):
+        if k != 4:
+            bad = list(oks); bad[k] = None
+            assert st(*bad) == -2, k
+    for k, v in ((4, -1), (7, p), (8, p), (1, odd), (9, odd)):
+        bad = list(oks); bad[k] = v
+        assert st(*bad) == -2, k
+
+
+def test_ply_round_trip_with_vertex_colours(tmp_path):
+    from unitex_amd.texturetools import meshes
+    rng = np.random.default_rng(0)
+    v, f = rng.uniform(-1, 1, (9, 3)).astype(np.float32), _grid_mesh(3)
+    c = np.concatenate([rng.uniform(-0.2, 1.2, (6, 3)), [[0.0, 0.5, 1.0], [1.0 - 2.0 ** -24, 254.9999 / 255, 1 / 255], [0.999, 0.004, 0.25]]]).astype(np.float32)
+    path = str(tmp_path / "m.ply")
+    meshes.save_ply_mesh(path, v, f, c)
+    rv, rf, ruv, rtex, rc = meshes.load_mesh(path, vertex_colors=True)
+    assert np.array_equal(rv, v) and np.array_equal(rf, f) and ruv is None and rtex is None
+    assert rc.dtype == np.uint8 and np.array_equal(rc, (np.clip(c, 0, 1) * np.float32(255)).astype(np.uint8))
+    assert rc[6].tolist() == [0, 127, 255] and rc[7].tolist() == [254, 254, 1]
+    assert len(meshes.load_mesh(path)) == 4 and len(meshes.load_ply(path)) == 3                       # the old forms are unchanged
+    meshes.save_ply_mesh(path, v, f)
+    assert meshes.load_mesh(path, vertex_colors=True)[4] is None
+    meshes.save_ply(path, v, rc)
+    assert np.array_equal(meshes.load_ply(path, faces_required=False, vertex_colors=True)[3], rc)
+
+
+# ---- the reference's own arrays (tests/golden/g20_vertex_bake.npz, made by tests/golden/make_golden_vertex_bake.py)
+
+G20_TAGS = (("p", True), ("o", False))
+
+
+def g20():
+    return np.load(os.path.join(ROOT, "tests", "golden", "g20_vertex_bake.npz"))
+
+
+def g20_case(f, tag, perspective, mode):
+    """the fixture's arrays as a projection problem; the matrices come from the PRODUCT's camera functions (texturetools/camera.py)"""
+    from unitex_amd.texturetools import camera
+    c2ws = torch.from_numpy(f["c2ws_" + tag])
+    intr = torch.from_numpy(f["intr_" + tag]).expand(3, -1, -1)
+    xform = (c2ws if mode == "ref" else camera.c2w_to_w2c(c2ws)).numpy()
+    return dict(v_pos=f["verts"], visible=f["vis_" + tag], xform=xform, proj=camera.intr_to_proj(intr, perspective=perspective).numpy(), images=f["images"][:3],
+                wmap=f["wmap_" + tag], v_rgb=f["v_rgb"], weights=f["weights3"])
+
+
+def g20_edge(f, tag):
+    g64 = R.weight_maps(f["cos_ray_normal_" + tag], None, 0, np.float64)["grad"]
+    return np.abs(g64 - float(R.GRAD_THR32)) <= R.GRAD_EDGE
+
+
+@pytest.mark.parametrize("tag,perspective", G20_TAGS)
+def test_restatement_weight_maps_against_g20(tag, perspective):
+    f = g20()
+    got = R.weight_maps(f["cos_ray_normal_" + tag], None, 0)
+    edge, cov = g20_edge(f, tag), f["wmap_" + tag][..., 0] != 0
+    assert edge[cov].sum() <= 0.005 * cov.sum()
+    assert np.array_equal(got["out"][..., 1][~edge], f["wmap_" + tag][..., 1][~edge])
+    # the gradient is a difference of two arccos terms (halved inside), the magnitude one more rounding of a value below 2
+    assert np.abs(got["grad"].astype(np.float64) - f["grad_" + tag]).max() <= 2 * R.ARCCOS_BOUND * math.sqrt(2) + 4 * R.U
+    if perspective:
+        assert np.array_equal(got["out"][..., 0], f["wmap_" + tag][..., 0])
+    else:
+        assert f["wmap_" + tag][..., 0].min() >= 0 and f["wmap_" + tag][..., 0].max() <= 1      # camera_normal.z clamped to [0, 1]
+
+
+@pytest.mark.parametrize("mode", ["w2c", "ref"])
+@pytest.mark.parametrize("tag,perspective", G20_TAGS)
+def test_restatement_every_stage_against_g20(tag, perspective, mode):
+    f = g20()
+    case = g20_case(f, tag, perspective, mode)
+    keep = ~f["near_" + tag].astype(bool)
+    assert (~keep).sum() <= 0.02 * f["vis_" + tag].any(0).sum()
+    e_acc, e_w = R.project_bound(**case)
+    for ua in (1, 0):
+        acc, w = R.vertex_project(use_alpha=bool(ua), **case)
+        key = "%s_%s_a%d" % (tag, mode, ua)
+        assert (np.abs(acc.astype(np.float64) - f["acc_" + key]).max(1) <= 2 * e_acc)[keep].all()
+        assert (np.abs(w.astype(np.float64) - f["wacc_" + key])[:, 0] <= 2 * e_w)[keep].all()
+    oc, bc, ic = (float(x) for x in f["conf"])
+    acc, w = f["acc_%s_%s_a1" % (tag, mode)], f["wacc_%s_%s_a1" % (tag, mode)]
+    over, soft, mask = R.epilogue(acc, w, f["v_rgb"], oc, "soft", bc, ic)
+    hard = R.epilogue(acc, w, f["v_rgb"], oc, "hard", bc, ic)[1]
+    assert np.array_equal(over, f["overlay_%s_%s" % (tag, mode)]) and np.array_equal(soft, f["soft_%s_%s" % (tag, mode)])
+    assert np.array_equal(hard, f["hard_%s_%s" % (tag, mode)])
+    acc0, w0 = R.vertex_project(**{**case, "v_rgb": np.zeros_like(f["v_rgb"])})
+    assert (np.abs(R.epilogue(acc0, w0, np.zeros_like(acc0), oc, None, bc, ic)[0].astype(np.float64) - f["nocolour_%s_%s" % (tag, mode)]).max(1)
+            <= 2 * e_acc / np.minimum(np.maximum(w0[:, 0], oc), 1.0))[keep].all()      # v_rgb = None: zeros, no blending; the overlay divides by a weight above oc
+    rowptr, col = R.csr_from_dense(R.adjacency_dense(f["faces"], acc.shape[0]))
+    got, steps, _ = R.inpaint(rowptr, col, soft, np.nonzero(mask)[0])
+    assert steps == int(f["steps_%s_%s" % (tag, mode)]) and (mode == "ref" or steps >= 3)
+    assert np.abs(got.astype(np.float64) - f["final_%s_%s" % (tag, mode)]).max() <= R.inpaint_bound(steps, int(np.diff(rowptr).max()))

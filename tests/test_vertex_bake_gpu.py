@@ -1,0 +1,452 @@
+"""Vertex-colour bake on the GPU: utx_view_weight_maps, utx_vertex_project / _blend, utx_vertex_inpaint_step through the C ABI and the wrappers of
+texturetools/ops.py, and texturetools/remapping.py end to end, against the numpy restatement (tests/vertex_bake_ref.py) and torch's own CPU operators
+(the compositions of tests/test_vertex_bake_cpu.py).
+
+Bounds, counted (vertex_bake_ref), never fitted:
+  cos channel        exact (a clamp)
+  arccos term        ARCCOS_BOUND = (ACOS_ULPS + 1) 2^-22 / (pi/2) + 2 * 2^-24: the device acosf's measured ulps (re-measured below over 10^6 inputs)
+                     plus one for the reference's, then one division on each side
+  edge alpha         exact outside the pixels whose float64 gradient magnitude lies within 1e-5 of the threshold (and their dilation)
+  dilation           exact
+  reflection lookup  4 * 2^-24 of the image maximum against torch's CPU grid_sample, on the colour recovered as acc / weight in float64 (the kernel's one
+                     product with the weight is inside the 4)
+  accumulators       twice project_bound per vertex (this evaluation and the other one, each with its own order in the two 4-term dot products)
+  epilogue           exact on the GPU's own accumulators (the same IEEE operations in the same order, no contraction)
+  inpainting         masks and step counts exact; colours inpaint_bound(steps, d_max) = steps (d_max + 3) 2^-24"""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from tests import test_vertex_bake_cpu as VC
+from tests import vertex_bake_ref as R
+
+pytestmark = pytest.mark.gpu
+SENTINEL = 0x5A
+
+
+def _cu(a, dtype=None):
+    t = torch.from_numpy(np.ascontiguousarray(a))
+    if dtype is not None:
+        t = t.to(dtype)
+    return t.cuda().contiguous()
+
+
+def _ops():
+    from unitex_amd.texturetools import ops
+    return ops
+
+
+def _gpu_project(case, use_alpha=True, epilogue=None):
+    out = _ops().vertex_project(*[_cu(case[k]) for k in ("v_pos", "visible", "xform", "proj", "images", "wmap", "v_rgb", "weights")], use_alpha=use_alpha,
+                                epilogue=epilogue)
+    return [o.cpu().numpy() for o in out]
+
+
+def test_device_acosf_stays_within_the_recorded_ulps():
+    """10^6 evenly spaced inputs of [-1, 0]: the arccos term a = (acosf(c) - h) / h back to acos = a h + h in float64, against float64 acos, in ulps of the
+    result (2^-22 on [2, pi], 2^-23 below); the division's own rounding (at most 0.2 ulp) is inside the figure"""
+    c = np.linspace(-1.0, 0.0, 10 ** 6).astype(np.float32).reshape(1, 1000, 1000)
+    _, a = _ops().view_weight_maps(_cu(c)[..., None], want_arccos=True)
+    h = float(R.HALF_PI32)
+    got = a.cpu().numpy().astype(np.float64) * h + h
+    want = np.arccos(c.astype(np.float64))
+    ulp = np.where(want >= 2.0, 2.0 ** -22, 2.0 ** -23)
+    err = np.abs(got - want) / ulp
+    print("device acosf on [-1, 0]: max %.3f ulp, mean %.3f ulp" % (err.max(), err.mean()))
+    assert err.max() <= R.ACOS_ULPS
+
+
+@pytest.mark.parametrize("r,ortho", [(0, False), (1, False), (2, True)])
+def test_weight_maps_against_torch_and_the_restatement(r, ortho):
+    B, H, W = 2, 33, 41
+    cosn = VC._cos_image(B, H, W, 3)
+    cam = np.random.default_rng(4).uniform(-0.2, 1.2, (B, H, W, 3)).astype(np.float32) if ortho else None
+    want, want_arccos = VC._torch_weight_maps(cosn, cam[..., 2] if ortho else None, r)
+    out, arccos = _ops().view_weight_maps(_cu(cosn)[..., None], _cu(cam) if ortho else None, r=r, want_arccos=True)
+    out, arccos = out.cpu().numpy(), arccos.cpu().numpy()
+    g64 = R.weight_maps(cosn, None, 0, np.float64)["grad"]
+    edge = R.dilate((np.abs(g64 - float(R.GRAD_THR32)) <= R.GRAD_EDGE).astype(np.float32), r) > 0
+    assert np.array_equal(out[..., 0], want[..., 0])
+    print("arccos term: max |gpu - torch| %.3g (bound %.3g)" % (np.abs(arccos.astype(np.float64) - want_arccos).max(), R.ARCCOS_BOUND))
+    assert np.abs(arccos.astype(np.float64) - want_arccos).max() <= R.ARCCOS_BOUND
+    assert edge.mean() <= 0.01 and np.array_equal(out[..., 1][~edge], want[..., 1][~edge])
+    assert np.array_equal(out[..., 1][~edge], R.weight_maps(cosn, None, r)["out"][..., 1][~edge])
+
+
+def test_dilation_exact_against_max_pool2d():
+    rng = np.random.default_rng(7)
+    cosn = np.where(rng.uniform(0, 1, (2, 33, 65)) < 0.03, -0.9, -1.0).astype(np.float32)
+    a0 = _ops().view_weight_maps(_cu(cosn)[..., None], r=0)[..., 1].cpu()
+    assert 0.02 < float(a0.mean()) < 0.5 and set(np.unique(a0.numpy())) == {0.0, 1.0}
+    for r in (1, 2):
+        got = _ops().view_weight_maps(_cu(cosn)[..., None], r=r)[..., 1].cpu()
+        assert torch.equal(got, torch.nn.functional.max_pool2d(a0[:, None], 2 * r + 1, 1, r)[:, 0])
+
+
+@pytest.mark.parametrize("Hi,Wi", [(5, 7), (1, 1), (1, 7), (4, 2)])
+def test_reflection_sampling_on_hand_made_points(Hi, Wi):
+    img = np.random.default_rng(Hi * 10 + Wi).uniform(0, 1, (1, 4, Hi, Wi)).astype(np.float32)
+    gx, gy = VC._hand_points(Hi, Wi)
+    V = gx.shape[0]
+    eye = np.eye(4, dtype=np.float32)[None]
+    case = dict(v_pos=np.stack([gx, gy, np.zeros_like(gx)], -1), visible=np.ones((1, V), np.uint8), xform=eye, proj=eye, images=img,
+                wmap=np.tile(np.array([-1.0, 0.0], np.float32), (1, 64, 64, 1)), v_rgb=np.zeros((V, 3), np.float32), weights=np.ones(1, np.float32))
+    acc, w = _gpu_project(case, use_alpha=False)
+    grid = torch.from_numpy(np.stack([gx, gy], -1))[None, :, None]
+    want = torch.nn.functional.grid_sample(torch.from_numpy(img), grid, mode="bilinear", padding_mode="reflection", align_corners=False)[0, :3, :, 0].numpy().T
+    assert (w > 0).all()      # the zero-padded weight map thins out towards the rim; any positive weight recovers the colour
+    err = np.abs(acc.astype(np.float64) / w.astype(np.float64) - want).max()
+    print("reflection lookup %dx%d: max |gpu - torch| %.3g (bound %.3g)" % (Hi, Wi, err, 4 * R.U * img.max()))
+    assert err <= 4 * R.U * img.max()
+
+
+@pytest.mark.parametrize("B", [1, 8])
+@pytest.mark.parametrize("V", [1, 63, 64, 65, 257])
+def test_launch_edges_between_sentinels(V, B):
+    from unitex_amd._lib import ptr
+    from unitex_amd.flux.ops import get_ctx
+    ctx = get_ctx(0)
+    case = R.synthetic_case(V, B, 100 * V + B, dead_vertex=V // 2, dead_view=B - 1 if B > 1 else None)
+    t = {k: _cu(v) for k, v in case.items()}
+    acc = torch.full((V + 2, 3), float("nan"), device="cuda")
+    wacc = torch.full((V + 2,), float("nan"), device="cuda")
+    bl = torch.full((V + 2, 3), float("nan"), device="cuda")
+    mk = torch.full((V + 2,), SENTINEL, dtype=torch.uint8, device="cuda")
+    off = lambda x, n: C.c_void_p(x.data_ptr() + n)
+    ctx.check(ctx.lib.utx_vertex_project_blend(ctx.handle, ptr(t["v_pos"]), V, ptr(t["visible"]), B, ptr(t["xform"]), ptr(t["proj"]), ptr(t["images"]), 5, 7,
+                                               ptr(t["wmap"]), 6, 9, ptr(t["v_rgb"]), ptr(t["weights"]), 1, off(acc, 12), off(wacc, 4), 0.05, 1, 0.2, 0.5,
+                                               off(bl, 12), off(mk, 1), ctx.stream()))
+    acc, wacc, bl, mk = acc.cpu().numpy(), wacc.cpu().numpy(), bl.cpu().numpy(), mk.cpu().numpy()
+    for a in (acc, wacc, bl):
+        assert np.isnan(a[0]).all() and np.isnan(a[-1]).all() and np.isfinite(a[1:-1]).all()
+    assert mk[0] == SENTINEL and mk[-1] == SENTINEL
+    want_acc, want_w = R.vertex_project(**case)
+    t_acc, t_w = VC._torch_project(case, True)
+    e_acc, e_w = R.project_bound(**case)
+    for wa, ww in ((want_acc, want_w), (t_acc, t_w)):
+        assert (np.abs(acc[1:-1].astype(np.float64) - wa).max(1) <= 2 * e_acc).all() and (np.abs(wacc[1:-1].astype(np.float64) - ww[:, 0]) <= 2 * e_w).all()
+    assert wacc[1 + V // 2] == 0 and (acc[1 + V // 2] == 0).all()
+    _, blended, mask = R.epilogue(acc[1:-1], wacc[1:-1, None], case["v_rgb"], 0.05, "soft", 0.2, 0.5)
+    assert np.array_equal(bl[1:-1], blended) and np.array_equal(mk[1:-1], mask)
+    plain = _gpu_project(case)
+    assert np.array_equal(plain[0], acc[1:-1]) and np.array_equal(plain[1][:, 0], wacc[1:-1])      # the two entry points accumulate alike
+
+
+@pytest.mark.parametrize("use_alpha", [True, False])
+def test_projection_and_every_epilogue_against_the_restatement(use_alpha):
+    case = R.synthetic_case(1000, 6, 21)
+    e_acc, e_w = R.project_bound(**case)
+    t_acc, t_w = VC._torch_project(case, use_alpha)
+    r_acc, r_w = R.vertex_project(use_alpha=use_alpha, **case)
+    first = None
+    for blending in (None, "soft", "hard"):
+        acc, w, bl, mk = _gpu_project(case, use_alpha, dict(overlay_confidence=0.05, blending=blending, blending_confidence=0.2, inpainting_confidence=0.5))
+        if first is None:
+            first = (acc, w)
+            for wa, ww in ((t_acc, t_w), (r_acc, r_w)):
+                d_acc, d_w = np.abs(acc.astype(np.float64) - wa).max(1), np.abs(w.astype(np.float64) - ww)[:, 0]
+                print("accumulators: max |gpu - other| %.3g / %.3g, largest share of the bound %.3g / %.3g" % (
+                    d_acc.max(), d_w.max(), (d_acc / np.maximum(2 * e_acc, 1e-300)).max(), (d_w / np.maximum(2 * e_w, 1e-300)).max()))
+                assert (d_acc <= 2 * e_acc).all() and (d_w <= 2 * e_w).all()
+        assert np.array_equal(acc, first[0]) and np.array_equal(w, first[1])
+        _, blended, mask = R.epilogue(acc, w, case["v_rgb"], 0.05, blending, 0.2, 0.5)
+        assert np.array_equal(bl, blended) and np.array_equal(mk, mask)
+        for thr in (0.05, 0.2, 0.5):
+            assert 0 < (w > thr).mean() < 1
+
+
+def _edges_csr(V, edges):
+    A = np.zeros((V, V), bool)
+    for a, b in edges:
+        A[a, b] = A[b, a] = True
+    return A, R.csr_from_dense(A)
+
+
+def _gpu_inpaint(rowptr, col, rgb, idx, max_iters=1000):
+    trace = []
+    out, steps = _ops().vertex_inpaint(_cu(rowptr), _cu(col), _cu(rgb), _cu(np.asarray(idx, np.int32)), max_iters=max_iters, trace=trace)
+    return out.cpu().numpy(), steps, [m.cpu().numpy().astype(bool) for m in trace]
+
+
+def test_inpainting_masks_steps_and_colours_on_a_mesh():
+    faces = VC._grid_mesh(9)
+    V = 81
+    A = R.adjacency_dense(faces, V)
+    rowptr, col = _ops().vertex_adjacency(torch.from_numpy(faces).cuda(), V)
+    assert np.array_equal(rowptr.cpu().numpy(), R.csr_from_dense(A)[0]) and np.array_equal(col.cpu().numpy(), R.csr_from_dense(A)[1])
+    rowptr, col = rowptr.cpu().numpy(), col.cpu().numpy()
+    rgb = np.random.default_rng(3).uniform(0, 1, (V, 3)).astype(np.float32)
+    idx = np.array([v for v in range(V) if v % 9 > 1 or v // 9 > 6], np.int32)
+    got, steps, masks = _gpu_inpaint(rowptr, col, rgb, idx)
+    want32, steps32, masks32 = R.inpaint(rowptr, col, rgb, idx)
+    want64, _, _ = R.inpaint(rowptr, col, rgb, idx, dtype=np.float64)
+    dist = R.bfs_depth(rowptr, col, ~np.isin(np.arange(V), idx))
+    assert steps == steps32 == dist.max() + 1 and steps >= 3
+    for k, m in enumerate(masks):
+        assert np.array_equal(m, (dist >= 0) & (dist <= k + 1)) and np.array_equal(m, masks32[k])      # ring by ring
+    bound = R.inpaint_bound(steps, int(A.sum(1).max()))
+    print("inpainting, %d steps: max |gpu - float64| %.3g (bound %.3g)" % (steps, np.abs(got - want64).max(), bound))
+    assert np.abs(got.astype(np.float64) - want64).max() <= bound and np.abs(got.astype(np.float64) - want32).max() <= bound
+    keep = ~np.isin(np.arange(V), idx)
+    assert np.array_equal(got[keep], rgb[keep])
+    again = _gpu_inpaint(rowptr, col, rgb, idx)
+    assert np.array_equal(again[0], got) and again[1] == steps      # determinism
+
+
+def test_inpainting_on_hand_made_graphs():
+    rng = np.random.default_rng(4)
+    # a 70-vertex chain with one seed: the fill walks one vertex per step, and the reference's last step adds nothing
+    A, (rowptr, col) = _edges_csr(70, [(i, i + 1) for i in range(69)])
+    rgb = rng.uniform(0, 1, (70, 3)).astype(np.float32)
+    got, steps, masks = _gpu_inpaint(rowptr, col, rgb, np.arange(1, 70))
+    assert steps == 70 and all(m.sum() == min(k + 2, 70) for k, m in enumerate(masks))
+    assert np.abs(got - rgb[0]).max() <= R.inpaint_bound(70, 2)
+    got5, steps5, masks5 = _gpu_inpaint(rowptr, col, rgb, np.arange(1, 70), max_iters=5)
+    assert steps5 == 5 and masks5[-1].sum() == 6 and np.array_equal(got5[6:], rgb[6:])
+    # two components, one without a seed, and an isolated vertex to fill
+    A, (rowptr, col) = _edges_csr(12, [(0, 1), (1, 2), (2, 3), (3, 0), (5, 6), (6, 7), (7, 8), (8, 5)])
+    rgb = rng.uniform(0, 1, (12, 3)).astype(np.float32)
+    idx = np.array([1, 2, 3, 5, 6, 7, 8, 10])
+    got, steps, masks = _gpu_inpaint(rowptr, col, rgb, idx)
+    want, steps_r, masks_r = R.inpaint(rowptr, col, rgb, idx)
+    assert steps == steps_r == 3 and all(np.array_equal(a, b) for a, b in zip(masks, masks_r))
+    assert not masks[-1][[5, 6, 7, 8, 10]].any() and masks[-1][[0, 1, 2, 3, 4, 9, 11]].all()
+    assert np.array_equal(got[[5, 6, 7, 8, 10]], rgb[[5, 6, 7, 8, 10]]) and np.abs(got - want).max() <= R.inpaint_bound(3, 2)
+    # every vertex invalid: one step, nothing changes; no vertex invalid: no launch
+    got, steps, masks = _gpu_inpaint(rowptr, col, rgb, np.arange(12))
+    assert steps == 1 and not masks[0].any() and np.array_equal(got, rgb)
+    got, steps, masks = _gpu_inpaint(rowptr, col, rgb, np.zeros(0, np.int32))
+    assert steps == 0 and masks == [] and np.array_equal(got, rgb)
+
+
+def test_c_abi_refusals_leave_the_outputs_untouched():
+    from unitex_amd._lib import ptr
+    from unitex_amd.flux.ops import get_ctx
+    ctx = get_ctx(0)
+    case = R.synthetic_case(65, 2, 5)
+    t = {k: _cu(v) for k, v in case.items()}
+    acc, wacc, bl = (torch.full(s, float("nan"), device="cuda") for s in ((65, 3), (65,), (65, 3)))
+    mk = torch.full((65,), SENTINEL, dtype=torch.uint8, device="cuda")
+    def call(**kw):
+        a = dict(V=65, B=2, wmap=ptr(t["wmap"]), blending=1, images=ptr(t["images"]))
+        a.update(kw)
+        return ctx.lib.utx_vertex_project_blend(ctx.handle, ptr(t["v_pos"]), a["V"], ptr(t["visible"]), a["B"], ptr(t["xform"]), ptr(t["proj"]), a["images"], 5, 7,
+                                                a["wmap"], 6, 9, ptr(t["v_rgb"]), ptr(t["weights"]), 1, ptr(acc), ptr(wacc), 0.05, a["blending"], 0.2, 0.5, ptr(bl),
+                                                ptr(mk), ctx.stream())
+    for kw in (dict(V=-1), dict(B=-1), dict(blending=3), dict(images=None), dict(wmap=C.c_void_p(t["wmap"].data_ptr() + 4))):
+        assert call(**kw) == -2, kw
+        assert b"utx_vertex_project_blend" in ctx.lib.utx_last_error(ctx.handle)
+    out = torch.full((2, 8, 8, 2), float("nan"), device="cuda")
+    cosn = torch.zeros(2, 8, 8, device="cuda")
+    assert ctx.lib.utx_view_weight_maps(ctx.handle, ptr(cosn), None, 2, 8, 8, 1, None, ptr(out), None, ctx.stream()) == -2
+    assert ctx.lib.utx_view_weight_maps(ctx.handle, ptr(cosn), None, 2, 1, 64, 0, None, ptr(out), None, ctx.stream()) == -2
+    rgb = torch.full((4, 3), float("nan"), device="cuda")
+    m8 = torch.full((4,), SENTINEL, dtype=torch.uint8, device="cuda")
+    i32 = torch.zeros(8, dtype=torch.int32, device="cuda")
+    cnt = torch.full((1,), 77, dtype=torch.int32, device="cuda")
+    assert ctx.lib.utx_vertex_inpaint_step(ctx.handle, ptr(i32), ptr(i32), ptr(i32), 2, ptr(rgb), ptr(m8), ptr(rgb), ptr(m8), ptr(cnt), ctx.stream()) == -2
+    assert ctx.lib.utx_vertex_inpaint_step(ctx.handle, ptr(i32), ptr(i32), ptr(i32), -2, ptr(rgb), ptr(m8), ptr(rgb), ptr(m8), ptr(cnt), ctx.stream()) == -2
+    torch.cuda.synchronize()
+    assert all(bool(torch.isnan(x).all()) for x in (acc, wacc, bl, out, rgb)) and bool((mk == SENTINEL).all()) and bool((m8 == SENTINEL).all()) and int(cnt) == 77
+    assert call(V=0) == 0 and bool(torch.isnan(wacc).all())      # a zero-size problem: 0 and no launch
+
+
+def _scene(perspective):
+    from unitex_amd.texturetools import camera, meshes
+    from unitex_amd.texturetools.renderer_inverse import DeviceMesh
+    verts, faces, uvs = meshes.make_bumpy_sphere(20, 10)
+    mesh = DeviceMesh(verts, faces, uvs, "cuda:0")
+    c2ws = camera.generate_orbit_views_c2ws(6, radius=2.8, height=0.5)
+    intr = camera.generate_intrinsics(40.0, 40.0, fov=True, degree=True) if perspective else camera.generate_intrinsics(0.9, 0.9, fov=False)
+    rng = np.random.default_rng(8)
+    images = rng.uniform(0, 1, (6, 4, 20, 28)).astype(np.float32)
+    sel = rng.uniform(0, 1, (6, 20, 28))
+    images[:, 3] = np.where(sel < 0.3, 0.0, np.where(sel < 0.6, 1.0, images[:, 3]))
+    v_rgb = rng.uniform(0, 1, verts.shape).astype(np.float32)
+    return mesh, c2ws, intr, torch.from_numpy(images), torch.from_numpy(v_rgb)
+
+
+@pytest.mark.parametrize("perspective", [True, False])
+@pytest.mark.parametrize("reference_transform", [False, True])
+def test_remapping_end_to_end_against_the_restatement(perspective, reference_transform):
+    """remapping.py on a sphere and six orbit cameras, render_size 48: the public functions against the restatement fed with the same visibility and the
+    same rendered cos_ray_normal -- every stage, both transform modes, the default weight table of six views"""
+    from unitex_amd.texturetools import camera, remapping
+    from unitex_amd.texturetools.renderer_inverse import NVDiffRendererInverse
+    mesh, c2ws, intr, images, v_rgb = _scene(perspective)
+    r = NVDiffRendererInverse(device="cuda:0", pbr_mesh=mesh)
+    kw = dict(render_size=48, perspective=perspective, reference_transform=reference_transform)
+    out, st = remapping.remapping_vertex_color(mesh, c2ws, intr, images, v_rgb, overlay_confidence=0.05, blending_confidence=0.2, inpainting_confidence=0.5,
+                                               return_stages=True, **kw)
+    weights = np.asarray(remapping.default_weights(6), np.float32)
+    acc, wacc = remapping.project_vertex_color(r, c2ws, intr, images, v_rgb, torch.from_numpy(weights), **kw)
+    assert torch.equal(acc, st["v_rgb_acc"]) and torch.equal(wacc, st["v_weight_acc"])
+    intr_b = intr.expand(6, -1, -1)
+    vis = r.get_visible_vertices(c2ws, perspective=perspective, method="raster", intrinsics=intr_b, render_size=48).cpu().numpy().astype(np.uint8)
+    ret = r.simple_rendering(c2ws, intr_b, 48, perspective=perspective, render_cos_ray_normal=True, render_camera_normal=not perspective)
+    cosn = ret["cos_ray_normal"][..., 0].cpu().numpy()
+    wm = R.weight_maps(cosn, None if perspective else ret["camera_normal"][..., 2].cpu().numpy(), 0)
+    g64 = R.weight_maps(cosn, None, 0, np.float64)["grad"]
+    assert (np.abs(g64 - float(R.GRAD_THR32)) <= R.GRAD_EDGE).mean() <= 0.005
+    xform = (c2ws if reference_transform else camera.c2w_to_w2c(c2ws)).numpy()
+    proj = camera.intr_to_proj(intr_b, perspective=perspective).numpy()
+    case = dict(v_pos=mesh.vertices.cpu().numpy(), visible=vis, xform=xform, proj=proj, images=images.numpy(), wmap=wm["out"], v_rgb=v_rgb.numpy(), weights=weights)
+    want_acc, want_w = R.vertex_project(**case)
+    e_acc, e_w = R.project_bound(**case)
+    acc, wacc = acc.cpu().numpy(), wacc.cpu().numpy()
+    # a vertex with a weight-map tap on a pixel whose alpha may fall on either side is left out; the cap is the fixture conditions' 2 % of the visible vertices
+    edge = (np.abs(g64 - float(R.GRAD_THR32)) <= R.GRAD_EDGE).astype(np.float32)
+    skip = np.zeros(acc.shape[0], bool)
+    for b in range(6):
+        g = R.ndc(case["v_pos"], xform[b], proj[b])
+        near = R.sample_zeros(R.dilate(edge[b:b + 1], 1), np.nan_to_num(g[:, 0]).clip(-2, 2), np.nan_to_num(g[:, 1]).clip(-2, 2))[0] > 0
+        skip |= near & vis[b].astype(bool)
+    assert skip.sum() <= 0.02 * vis.any(0).sum()
+    assert (np.abs(acc.astype(np.float64) - want_acc).max(1) <= 2 * e_acc)[~skip].all() and (np.abs(wacc.astype(np.float64) - want_w)[:, 0] <= 2 * e_w)[~skip].all()
+    assert (wacc > 0).any() or reference_transform      # with c2ws as the transform this scene may see nothing; that mode is pinned against G20 below
+    _, blended, mask = R.epilogue(acc, wacc, v_rgb.numpy(), 0.05, "soft", 0.2, 0.5)
+    assert np.array_equal(st["blended"].cpu().numpy(), blended) and np.array_equal(st["inpaint_mask"].cpu().numpy(), mask)
+    rowptr, col = R.csr_from_dense(R.adjacency_dense(mesh.faces.cpu().numpy(), acc.shape[0]))
+    idx = np.nonzero(mask)[0]
+    want, steps, _ = R.inpaint(rowptr, col, blended, idx, dtype=np.float64)
+    assert st["inpaint_steps"] == steps
+    d_max = int(np.diff(rowptr).max())
+    assert np.abs(out.cpu().numpy().astype(np.float64) - want).max() <= R.inpaint_bound(max(steps, 1), d_max) * max(1.0, float(np.abs(blended).max()))
+    alone = remapping.inpainting_vertex_color(mesh, st["blended"], torch.from_numpy(idx))
+    assert torch.equal(alone, out)
+    again = remapping.remapping_vertex_color(mesh, c2ws, intr, images, v_rgb, overlay_confidence=0.05, blending_confidence=0.2, inpainting_confidence=0.5, **kw)
+    assert torch.equal(again, out)      # determinism
+
+
+def test_remapping_without_colours_and_without_stages():
+    from unitex_amd.texturetools import remapping
+    mesh, c2ws, intr, images, v_rgb = _scene(True)
+    out, st = remapping.remapping_vertex_color(mesh, c2ws, intr, images, render_size=48, use_inpainting=False, return_stages=True)
+    acc, w = st["v_rgb_acc"].cpu().numpy(), st["v_weight_acc"].cpu().numpy()
+    over, blended, _ = R.epilogue(acc, w, np.zeros_like(acc), 0.2, None, 0.2, 0.2)      # v_rgb = None: zeros and no blending
+    assert np.array_equal(out.cpu().numpy(), over) and st["inpaint_steps"] == 0
+    hard = remapping.remapping_vertex_color(mesh, c2ws, intr, images, v_rgb, blending_type="hard", use_inpainting=False, use_alpha=False, render_size=48,
+                                            return_stages=True)[1]
+    _, blended, _ = R.epilogue(hard["v_rgb_acc"].cpu().numpy(), hard["v_weight_acc"].cpu().numpy(), v_rgb.numpy(), 0.2, "hard", 0.2, 0.2)
+    assert np.array_equal(hard["blended"].cpu().numpy(), blended)
+
+
+def test_initial_map_kd_is_the_composition_of_the_existing_ops():
+    from unitex_amd.texturetools import ops, remapping
+    from unitex_amd.texturetools.renderer_inverse import NVDiffRendererInverse
+    mesh, _, _, _, v_rgb = _scene(True)
+    got = remapping.initial_map_Kd_with_v_rgb(mesh, v_rgb, texture_size=48)
+    r = NVDiffRendererInverse(device="cuda:0", pbr_mesh=mesh)
+    alpha = r.compute_uv_mask(48).float()
+    rgb = r.simple_inverse_rendering(None, 48, render_v_attr=True, v_attr=v_rgb)["v_attr"][0]
+    want = torch.cat([ops.pull_push(rgb.contiguous(), (alpha[..., 0] > 0.6).to(torch.uint8).contiguous()), alpha], -1)
+    assert tuple(got.shape) == (48, 48, 4) and torch.equal(got, want)
+    inside = alpha[..., 0] > 0
+    assert 0 < float(inside.float().mean()) < 1
+    assert float(got[..., :3][~inside].abs().max()) > 0      # the texels outside the charts are filled
+
+
+# ---- against the reference's own arrays (fixture G20)
+
+def _g20_mesh(f):
+    from unitex_amd.texturetools.renderer_inverse import DeviceMesh
+    return DeviceMesh(f["verts"], f["faces"], f["uvs"], "cuda:0").set_vertex_normals(f["v_nrm"])
+
+
+@pytest.mark.parametrize("tag,perspective", VC.G20_TAGS)
+def test_ops_against_g20(tag, perspective):
+    """the kernels on the fixture's inputs: weight maps from the reference's cos_ray_normal, the projection from the reference's visibility and weight maps"""
+    f = VC.g20()
+    edge, cov = VC.g20_edge(f, tag), f["wmap_" + tag][..., 0] != 0
+    assert edge[cov].sum() <= 0.005 * cov.sum()
+    out, arccos = _ops().view_weight_maps(_cu(f["cos_ray_normal_" + tag])[..., None], r=0, want_arccos=True)
+    out = out.cpu().numpy()
+    assert np.array_equal(out[..., 1][~edge], f["wmap_" + tag][..., 1][~edge])
+    if perspective:
+        assert np.array_equal(out[..., 0], f["wmap_" + tag][..., 0])
+    a = arccos.cpu().numpy()
+    dy, dx = R._gradient(a, 1), R._gradient(a, 2)
+    assert np.abs(np.sqrt(dy * dy + dx * dx).astype(np.float64) - f["grad_" + tag]).max() <= 2 * R.ARCCOS_BOUND * np.sqrt(2) + 4 * R.U
+    keep = ~f["near_" + tag].astype(bool)
+    assert (~keep).sum() <= 0.02 * f["vis_" + tag].any(0).sum()
+    oc, bc, ic = (float(x) for x in f["conf"])
+    for mode in ("w2c", "ref"):
+        case = VC.g20_case(f, tag, perspective, mode)
+        e_acc, e_w = R.project_bound(**case)
+        for ua in (1, 0):
+            acc, w, bl, mk = _gpu_project(case, bool(ua), dict(overlay_confidence=oc, blending="soft", blending_confidence=bc, inpainting_confidence=ic))
+            key = "%s_%s_a%d" % (tag, mode, ua)
+            d_acc, d_w = np.abs(acc.astype(np.float64) - f["acc_" + key]).max(1), np.abs(w.astype(np.float64) - f["wacc_" + key])[:, 0]
+            print("G20 %s: max |gpu - reference| %.3g / %.3g" % (key, d_acc.max(), d_w.max()))
+            assert (d_acc <= 2 * e_acc)[keep].all() and (d_w <= 2 * e_w)[keep].all()
+        assert np.array_equal(mk.astype(bool), f["wacc_%s_%s_a0" % (tag, mode)][:, 0] <= np.float32(ic))
+
+
+@pytest.mark.parametrize("mode", ["w2c", "ref"])
+@pytest.mark.parametrize("tag,perspective", VC.G20_TAGS)
+def test_remapping_against_g20(tag, perspective, mode):
+    """remapping.py end to end on the fixture's mesh and cameras: visibility equal to the reference's; the accumulators and every later stage within the
+    counted bound plus what the rendered weight map's own distance from the reference's allows: cos_ray_normal carries G18's bound (20 u and the propagated
+    camera-space terms; 64 u is asserted), the weight is k cos^4 (1 - alpha), so a view adds at most k 4 |cos|^3 d cos to the weight and that times the
+    largest colour to the accumulator"""
+    from unitex_amd.texturetools import remapping
+    from unitex_amd.texturetools.renderer_inverse import NVDiffRendererInverse
+    f = VC.g20()
+    mesh = _g20_mesh(f)
+    r = NVDiffRendererInverse(device="cuda:0", pbr_mesh=mesh)
+    c2ws, intr = torch.from_numpy(f["c2ws_" + tag]), torch.from_numpy(f["intr_" + tag])
+    images, v_rgb, w3 = torch.from_numpy(f["images"][:3]), torch.from_numpy(f["v_rgb"]), torch.from_numpy(f["weights3"])
+    oc, bc, ic = (float(x) for x in f["conf"])
+    kw = dict(render_size=48, perspective=perspective, reference_transform=mode == "ref")
+    vis = r.get_visible_vertices(c2ws, perspective=perspective, method="raster", intrinsics=intr.expand(3, -1, -1), render_size=48).cpu().numpy()
+    assert np.array_equal(vis.astype(np.uint8), f["vis_" + tag])
+    ret = r.simple_rendering(c2ws, intr.expand(3, -1, -1), 48, perspective=perspective, render_cos_ray_normal=True, render_camera_normal=not perspective)
+    wm = _ops().view_weight_maps(ret["cos_ray_normal"], None if perspective else ret["camera_normal"], r=0).cpu().numpy()
+    assert np.array_equal(wm[..., 1], f["wmap_" + tag][..., 1])
+    d_cos = np.abs(wm[..., 0].astype(np.float64) - f["wmap_" + tag][..., 0]).reshape(3, -1).max(1)
+    print("G20 %s: weight map cos channel, max |gpu - reference| per view %s" % (tag, d_cos))
+    assert d_cos.max() <= 64 * R.U
+    case = VC.g20_case(f, tag, perspective, mode)
+    e_acc, e_w = R.project_bound(**case)
+    extra = float((np.abs(f["weights3"]) * 4 * d_cos).sum())
+    cmax = max(float(f["images"][:3, :3].max()), float(f["v_rgb"].max()))
+    keep = ~f["near_" + tag].astype(bool)
+    for ua in (1, 0):
+        acc, w = remapping.project_vertex_color(mesh, c2ws, intr, images, v_rgb, w3, use_alpha=bool(ua), **kw)
+        key = "%s_%s_a%d" % (tag, mode, ua)
+        assert (np.abs(acc.cpu().numpy().astype(np.float64) - f["acc_" + key]).max(1) <= 2 * e_acc + extra * cmax)[keep].all()
+        assert (np.abs(w.cpu().numpy().astype(np.float64) - f["wacc_" + key])[:, 0] <= 2 * e_w + extra)[keep].all()
+    out, st = remapping.remapping_vertex_color(mesh, c2ws, intr, images, v_rgb, weights=[2.0, 0.2, 1.0], overlay_confidence=oc, blending_confidence=bc,
+                                               inpainting_confidence=ic, return_stages=True, **kw)
+    wacc = f["wacc_%s_%s_a1" % (tag, mode)][:, 0].astype(np.float64)
+    assert np.array_equal(st["inpaint_mask"].cpu().numpy().astype(bool), wacc <= np.float32(ic))      # condition (e): no weight within 1e-6 of a threshold
+    # overlay divides by a weight above oc, the soft blending by bc: the accumulators' bound through the two quotients, plus 4 roundings
+    e_bl = (2 * e_acc + extra * cmax + (2 * e_w + extra) * cmax / np.maximum(wacc, oc)) / np.maximum(wacc, oc) / min(bc, 1.0) + 4 * R.U * cmax
+    d_bl = np.abs(st["blended"].cpu().numpy().astype(np.float64) - f["soft_%s_%s" % (tag, mode)]).max(1)
+    print("G20 %s %s: blended, max |gpu - reference| %.3g; share of the bound %.3g" % (tag, mode, d_bl.max(), (d_bl / e_bl).max()))
+    assert (d_bl <= e_bl)[keep].all()
+    assert st["inpaint_steps"] == int(f["steps_%s_%s" % (tag, mode)])
+    rowptr = _ops().vertex_adjacency(mesh.faces, acc.shape[0])[0].cpu().numpy()
+    d_fin = np.abs(out.cpu().numpy().astype(np.float64) - f["final_%s_%s" % (tag, mode)]).max()
+    assert d_fin <= e_bl.max() + R.inpaint_bound(st["inpaint_steps"], int(np.diff(rowptr).max()))      # a step is an average: it carries the input's error, no more
+
+
+def test_default_weight_table_and_initial_map_kd_against_g20():
+    from unitex_amd.texturetools import remapping
+    f = VC.g20()
+    mesh = _g20_mesh(f)
+    got = remapping.remapping_vertex_color(mesh, torch.from_numpy(f["c2ws_6"]), torch.from_numpy(f["intr_6"]), torch.from_numpy(f["images"]),
+                                           torch.from_numpy(f["v_rgb"]), render_size=48, use_inpainting=False)
+    d = np.abs(got.cpu().numpy().astype(np.float64) - f["final_6"])
+    print("G20 six views, default weights: max |gpu - reference| %.3g" % d.max())
+    assert d.max() <= 1e-5      # weights up to 2 on six views through the overlay's quotient (weights above 0.2) and the soft blending's (0.2): the bounds above, 25-fold
+    for tag, perspective in VC.G20_TAGS:
+        kd = remapping.initial_map_Kd_with_v_rgb(mesh, torch.from_numpy(f["final_%s_w2c" % tag]), texture_size=48, perspective=perspective).cpu().numpy()
+        want = f["kd_" + tag]
+        assert kd.shape == want.shape == (48, 48, 4) and np.array_equal(kd[..., 3], want[..., 3])
+        inside = want[..., 3] > 0
+        d_in, d_out = np.abs(kd[..., :3] - want[..., :3])[inside].max(), np.abs(kd[..., :3] - want[..., :3])[~inside].max()
+        print("G20 %s: initial map_Kd, max |gpu - reference| inside the charts %.3g, outside %.3g" % (tag, d_in, d_out))
+        assert d_in <= 8 * R.U and d_out <= 64 * R.U      # render_v_attr's bound of G17 (barycentric interpolation of values in [0, 1]); pull_push averages of those

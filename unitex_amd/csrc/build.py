@@ -44,6 +44,7 @@ GEOM = [
     ("pbr.hip", ["-ffp-contract=off"] + NO_PK),
     ("bvh.hip", ["-ffp-contract=off"] + NO_PK),
     ("backproject.hip", ["-ffp-contract=off"] + NO_PK),
+    ("vertex_bake.hip", ["-ffp-contract=off"] + NO_PK),      # vertex-colour bake: weight maps, per-vertex projection, graph inpainting
     ("texture_post.hip", ["-ffp-contract=off"] + NO_PK),
     ("knn.hip", ["-ffp-contract=off"]),
     ("sampling.hip", ["-ffp-contract=off"]),

@@ -434,6 +434,55 @@ int utx_uv_project(utx_ctx* ctx, const float* rast2d, const int* faces, int F, c
     UTX_CALL(ctx, me, utx_launch_uv_project(rast2d, faces, F, face_mask, v_ndc, V, B, H2D, W2D, map, Bm, Hm, Wm, C, rast_map, map ? filter : 0, bg_kind, bg_scalar, bg, uv,
                                             uv_alpha, map ? map_attr : nullptr, (hipStream_t)stream));
 }
+// ---- vertex-colour bake (vertex_bake.hip) ----
+static bool misaligned(const void* p, unsigned mask) { return ((uintptr_t)p & mask) != 0; }
+int utx_view_weight_maps(utx_ctx* ctx, const float* cos_ray_normal, const float* camera_normal, int B, int H, int W, int r, void* tmp, float* out,
+                         float* arccos_out, utx_stream stream) {
+    const char* const me = "utx_view_weight_maps";
+    if (B < 0 || H < 0 || W < 0 || r < 0) return fail(ctx, -2, me);
+    if ((long)B * H * W == 0) return 0;
+    if (H < 2 || W < 2 || !cos_ray_normal || !out || (r > 0 && !tmp)) return fail(ctx, -2, me);      // torch.gradient needs two samples per axis
+    if (misaligned(cos_ray_normal, 3) || misaligned(camera_normal, 3) || misaligned(out, 7) || misaligned(arccos_out, 3)) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_view_weight_maps(cos_ray_normal, camera_normal, B, H, W, r, tmp, out, arccos_out, (hipStream_t)stream));
+}
+static int vertex_project_checked(utx_ctx* ctx, const char* me, bool epilogue, const float* v_pos, int V, const unsigned char* visible, int B, const float* xform,
+                                  const float* proj, const float* images, int Hi, int Wi, const float* wmap, int H, int W, const float* v_rgb,
+                                  const float* weights, int use_alpha, float* acc, float* wacc, float overlay_conf, int blending, float blending_conf,
+                                  float inpainting_conf, float* blended, unsigned char* inpaint, utx_stream stream) {
+    if (V < 0 || B < 0 || Hi < 0 || Wi < 0 || H < 0 || W < 0) return fail(ctx, -2, me);
+    if (epilogue && (blending < UTX_VB_BLEND_NONE || blending > UTX_VB_BLEND_HARD)) return fail(ctx, -2, me);
+    if (V == 0) return 0;
+    if (!v_pos || !v_rgb || !wacc || (!epilogue && !acc) || (epilogue && (!blended || !inpaint))) return fail(ctx, -2, me);
+    if (B > 0 && (!visible || !xform || !proj || !images || !wmap || !weights || Hi == 0 || Wi == 0 || H == 0 || W == 0)) return fail(ctx, -2, me);
+    if (misaligned(v_pos, 3) || misaligned(xform, 3) || misaligned(proj, 3) || misaligned(images, 3) || misaligned(wmap, 7) || misaligned(v_rgb, 3) ||
+        misaligned(weights, 3) || misaligned(acc, 3) || misaligned(wacc, 3) || misaligned(blended, 3)) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_vertex_project(v_pos, V, visible, B, xform, proj, images, Hi, Wi, wmap, H, W, v_rgb, weights, use_alpha, acc, wacc, overlay_conf,
+                                                blending, blending_conf, inpainting_conf, epilogue ? blended : nullptr, inpaint, (hipStream_t)stream));
+}
+int utx_vertex_project(utx_ctx* ctx, const float* v_pos, int V, const unsigned char* visible, int B, const float* xform, const float* proj, const float* images,
+                       int Hi, int Wi, const float* wmap, int H, int W, const float* v_rgb, const float* weights, int use_alpha, float* v_rgb_acc,
+                       float* v_weight_acc, utx_stream stream) {
+    return vertex_project_checked(ctx, "utx_vertex_project", false, v_pos, V, visible, B, xform, proj, images, Hi, Wi, wmap, H, W, v_rgb, weights, use_alpha,
+                                  v_rgb_acc, v_weight_acc, 0.f, 0, 0.f, 0.f, nullptr, nullptr, stream);
+}
+int utx_vertex_project_blend(utx_ctx* ctx, const float* v_pos, int V, const unsigned char* visible, int B, const float* xform, const float* proj,
+                             const float* images, int Hi, int Wi, const float* wmap, int H, int W, const float* v_rgb, const float* weights, int use_alpha,
+                             float* v_rgb_acc, float* v_weight_acc, float overlay_confidence, int blending, float blending_confidence,
+                             float inpainting_confidence, float* blended, unsigned char* inpaint_mask, utx_stream stream) {
+    return vertex_project_checked(ctx, "utx_vertex_project_blend", true, v_pos, V, visible, B, xform, proj, images, Hi, Wi, wmap, H, W, v_rgb, weights, use_alpha,
+                                  v_rgb_acc, v_weight_acc, overlay_confidence, blending, blending_confidence, inpainting_confidence, blended, inpaint_mask, stream);
+}
+int utx_vertex_inpaint_step(utx_ctx* ctx, const int* rowptr, const int* col, const int* idx, int n, const float* rgb_in, const unsigned char* mask_in,
+                            float* rgb_out, unsigned char* mask_out, int* counter, utx_stream stream) {
+    const char* const me = "utx_vertex_inpaint_step";
+    if (n < 0) return fail(ctx, -2, me);
+    if (n == 0) return 0;
+    if (!rowptr || !col || !idx || !rgb_in || !mask_in || !rgb_out || !mask_out || !counter) return fail(ctx, -2, me);
+    if (rgb_in == rgb_out || mask_in == mask_out) return fail(ctx, -2, me);      // a step reads one pair and writes the other
+    if (misaligned(rowptr, 3) || misaligned(col, 3) || misaligned(idx, 3) || misaligned(rgb_in, 3) || misaligned(rgb_out, 3) || misaligned(counter, 3))
+        return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_vertex_inpaint_step(rowptr, col, idx, n, rgb_in, mask_in, rgb_out, mask_out, counter, (hipStream_t)stream));
+}
 int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws, int n_views, float* out, utx_stream stream) {
     if (!nrm || !c2ws || !out) return fail(ctx, -2, "utx_camera_normals");
     UTX_CALL(ctx, "utx_camera_normals", utx_launch_camera_normals(nrm, V, c2ws, n_views, out, (hipStream_t)stream));

@@ -179,6 +179,13 @@ int utx_visible_faces_rays_impl(utx_bvh* b, const float* verts, const int* faces
 int utx_launch_visible_faces_raster(const float* rast, int B, int H, int W, int F, unsigned char* mask, hipStream_t stream);
 int utx_launch_erode_faces(unsigned char* mask, const int* faces, int B, int F, int V, int depth, int* vstamp, hipStream_t stream);
 int utx_launch_visible_vertices(const unsigned char* mask, const int* faces, int B, int F, int V, unsigned char* out, hipStream_t stream);
+// vertex_bake.hip
+int utx_launch_view_weight_maps(const float* cosn, const float* cam_nrm, int B, int H, int W, int r, void* tmp, float* out, float* arccos_out, hipStream_t stream);
+int utx_launch_vertex_project(const float* v_pos, int V, const unsigned char* visible, int B, const float* xform, const float* proj, const float* images, int Hi, int Wi,
+                              const float* wmap, int H, int W, const float* v_rgb, const float* weights, int use_alpha, float* acc, float* wacc, float overlay_conf,
+                              int blending, float blending_conf, float inpainting_conf, float* blended, unsigned char* inpaint, hipStream_t stream);
+int utx_launch_vertex_inpaint_step(const int* rowptr, const int* col, const int* idx, int n, const float* rgb_in, const unsigned char* mask_in, float* rgb_out,
+                                   unsigned char* mask_out, int* counter, hipStream_t stream);
 int utx_launch_backproject(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_backproject_vis(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_composite_winner(const void* vis, int n_views, const int* order, int n_order, long T, void* winner, hipStream_t stream);

@@ -445,11 +445,12 @@ def save_ply(path, vertices, colors_u8=None):
         f.write(rec.tobytes())
 
 
-def load_ply(path, faces_required=True):
+def load_ply(path, faces_required=True, vertex_colors=False):
     """Stanford PLY, ascii / binary_little_endian / binary_big_endian: element `vertex` (x y z, optional s t | u v | texture_u texture_v; any other property is
     skipped) and element `face` (a list property vertex_indices | vertex_index; other properties skipped; polygons fanned).  Other elements before / between are
     skipped by their declared layout.  Returns (verts f32 [V,3], faces i32 [F,3], uvs f32 [V,2] | None).  A file without faces is refused unless
-    faces_required=False (point clouds: save_ply), which returns faces [0,3]."""
+    faces_required=False (point clouds: save_ply), which returns faces [0,3].  vertex_colors=True appends the per-vertex colours uint8 [V,3] (uchar red green
+    blue; None when the file has none) as a fourth value: save_ply_mesh writes them."""
     with open(path, "rb") as f:
         blob = f.read()
     end = blob.find(b"end_header")
@@ -472,7 +473,7 @@ def load_ply(path, faces_required=True):
                 elements[-1][2].append((t[2], _PLY_TYPES[t[1]], None))
     if fmt not in ("ascii", "binary_little_endian", "binary_big_endian"):
         raise ValueError("%s: PLY format %r" % (path, fmt))
-    verts = uvs = None
+    verts = uvs = colors = None
     polys = []
     if fmt == "ascii":
         tok = blob[body:].split()
@@ -490,6 +491,7 @@ def load_ply(path, faces_required=True):
                 rows.append(row)
             if name == "vertex":
                 verts, uvs = _ply_vertex_arrays(lambda k: np.asarray([r[k] for r in rows], dtype=np.float64), [p_[0] for p_ in props], count)
+                colors = _ply_vertex_colors(lambda k: np.asarray([r[k] for r in rows], dtype=np.float64), [p_[0] for p_ in props])
             elif name == "face":
                 key = next((k for k in ("vertex_indices", "vertex_index") if rows and k in rows[0]), None)
                 polys = [r[key] for r in rows] if key else []
@@ -503,6 +505,7 @@ def load_ply(path, faces_required=True):
                 pos += dt.itemsize * count
                 if name == "vertex":
                     verts, uvs = _ply_vertex_arrays(lambda k: arr[k].astype(np.float64), [p_[0] for p_ in props], count)
+                    colors = _ply_vertex_colors(lambda k: arr[k], [p_[0] for p_ in props])
                 continue
             # an element with list properties: fixed-size fast path when every list of the element has the same length (all-triangle / all-quad files), else row by row
             got = None
@@ -554,7 +557,41 @@ def load_ply(path, faces_required=True):
         faces = _fan([list(p_) for p_ in polys])
     if len(faces) == 0 and faces_required:
         raise ValueError("%s holds no faces (a point cloud cannot be textured)" % path)
-    return verts, faces, uvs
+    return (verts, faces, uvs, colors) if vertex_colors else (verts, faces, uvs)
+
+
+def _ply_vertex_colors(col, names):
+    if all(k in names for k in ("red", "green", "blue")):
+        return np.stack([col("red"), col("green"), col("blue")], -1).astype(np.uint8)
+    return None
+
+
+def save_ply_mesh(path, vertices, faces, v_rgb=None):
+    """triangle mesh with per-vertex colours as binary_little_endian PLY: element `vertex` (float x y z, uchar red green blue when v_rgb [V,3] is given: float
+    colours go through the conversion used everywhere here, clamp(0, 1) * 255 truncated; uint8 is stored as is) and element `face` (list uchar int
+    vertex_indices).  load_ply(path, vertex_colors=True) / load_mesh(path, vertex_colors=True) read it back."""
+    v = np.ascontiguousarray(vertices, dtype=np.float32).reshape(-1, 3)
+    f = np.ascontiguousarray(faces, dtype=np.int32).reshape(-1, 3)
+    fields = [("x", "<f4"), ("y", "<f4"), ("z", "<f4")]
+    head = "ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n" % len(v)
+    if v_rgb is not None:
+        c = np.asarray(v_rgb)
+        if c.shape != v.shape:
+            raise ValueError("v_rgb must be of shape %s, got %s" % (v.shape, c.shape))
+        if c.dtype != np.uint8:
+            c = (np.clip(c.astype(np.float32), 0.0, 1.0) * np.float32(255.0)).astype(np.uint8)
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        head += "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+    rec = np.empty(len(v), dtype=np.dtype(fields))
+    rec["x"], rec["y"], rec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if v_rgb is not None:
+        rec["red"], rec["green"], rec["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    frec = np.empty(len(f), dtype=np.dtype([("n", "u1"), ("i", "<i4", (3,))]))
+    frec["n"], frec["i"] = 3, f
+    with open(path, "wb") as fh:
+        fh.write((head + "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % len(f)).encode("ascii"))
+        fh.write(rec.tobytes())
+        fh.write(frec.tobytes())
 
 
 def _ply_vertex_arrays(col, names, count):
@@ -612,10 +649,13 @@ def load_off(path):
     return verts, _fan(polys)
 
 
-def load_mesh(path):
+def load_mesh(path, vertex_colors=False):
     """.obj / .glb / .gltf / .ply / .stl / .off -> (verts, faces, uvs | None [one per vertex], texture | None).  The reference hands any path to trimesh.load
     (io/mesh_loader.py:22-30); these are the formats its own tools name (mesh/structure.py:73-83, render/blender/render_blender.py:59) plus the
-    interchange formats mesh generators write."""
+    interchange formats mesh generators write.  vertex_colors=True appends a fifth value: the per-vertex colours uint8 [V,3] of a .ply that carries them, else None."""
+    if vertex_colors:
+        colors = load_ply(path, vertex_colors=True)[3] if path.lower().endswith(".ply") else None
+        return load_mesh(path) + (colors,)
     ext = path.lower().rsplit(".", 1)[-1]
     if ext == "obj":
         v, f, uv, fuv = load_obj(path)

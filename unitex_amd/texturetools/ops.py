@@ -963,3 +963,104 @@ def to_u8(img, flip=False):
     out = torch.empty(img.shape, dtype=U8, device=img.device)
     ctx.check(ctx.lib.utx_to_u8(ctx.handle, ptr(_f(img)), rows, row_elems, int(flip), ptr(out), ctx.stream()))
     return out
+
+
+# ---- the vertex-colour bake (vertex_bake.hip): project_vertex_color / remapping_vertex_color / inpainting_vertex_color of the reference
+
+VERTEX_BLENDING = {None: 0, "soft": 1, "hard": 2}      # UTX_VB_BLEND_*
+
+
+def weight_map_radius(render_size):
+    """the dilation radius of the edge alpha: the reference's kernel_size = 2 * (render_size // 512) + 1 is (2 r + 1) with r = render_size // 512"""
+    return int(render_size) // 512
+
+
+def view_weight_maps(cos_ray_normal, camera_normal=None, r=0, want_arccos=False):
+    """utx_view_weight_maps: cos_ray_normal [B,H,W,1] (or [B,H,W]) -> [B,H,W,2] = (cos term, edge alpha dilated by r), the two weight channels of
+    project_vertex_color (mesh_remapping.py:544-555).  camera_normal [B,H,W,3]: the orthographic cos term clamp(camera_normal.z, 0, 1) instead of
+    clamp(cos, -1, 0).  want_arccos: also the arccos term in [0, 1] the edge alpha is the gradient of, [B,H,W]."""
+    ctx = get_ctx(cos_ray_normal.device.index)
+    B, H, W = cos_ray_normal.shape[:3]
+    assert cos_ray_normal.numel() == B * H * W, "cos_ray_normal is [B, H, W, 1]"
+    assert camera_normal is None or tuple(camera_normal.shape) == (B, H, W, 3), "camera_normal is [B, H, W, 3]"
+    out = torch.empty(B, H, W, 2, dtype=F32, device=cos_ray_normal.device)
+    tmp = torch.empty(B * H * W, dtype=U8, device=out.device) if r > 0 else None
+    arccos = torch.empty(B, H, W, dtype=F32, device=out.device) if want_arccos else None
+    ctx.check(ctx.lib.utx_view_weight_maps(ctx.handle, ptr(_f(cos_ray_normal)), _opt(camera_normal), B, H, W, int(r), ptr(tmp), ptr(out), ptr(arccos), ctx.stream()))
+    return (out, arccos) if want_arccos else out
+
+
+def vertex_project(v_pos, visible, xform, proj, images, wmap, v_rgb, weights, use_alpha=True, epilogue=None):
+    """utx_vertex_project: v_pos [V,3], visible uint8 [B,V], xform / proj [B,4,4] (the per-view vertex transform and the projection), images
+    [B,4,Hi,Wi] rgba, wmap [B,H,W,2] (view_weight_maps), v_rgb [V,3], weights [B] -> (v_rgb_acc [V,3], v_weight_acc [V,1]): the loop of
+    project_vertex_color (:559-594), the views summed in index order.  epilogue = dict(overlay_confidence, blending (None | 'soft' | 'hard'),
+    blending_confidence, inpainting_confidence): the same launch also applies remapping_vertex_color's overlay and blending (:326-337) and returns
+    (v_rgb_acc, v_weight_acc, blended [V,3], inpaint_mask uint8 [V] = v_weight_acc <= inpainting_confidence)."""
+    ctx = get_ctx(v_pos.device.index)
+    V, B = v_pos.shape[0], visible.shape[0]
+    assert tuple(visible.shape) == (B, V) and tuple(xform.shape) == (B, 4, 4) and tuple(proj.shape) == (B, 4, 4) and tuple(weights.shape) == (B,)
+    assert images.dim() == 4 and images.shape[0] == B and images.shape[1] == 4, "images is [B, 4, Hi, Wi]"
+    assert wmap.dim() == 4 and wmap.shape[0] == B and wmap.shape[3] == 2, "wmap is [B, H, W, 2]"
+    assert tuple(v_rgb.shape) == (V, 3) and v_pos.shape[1] == 3
+    dev = v_pos.device
+    acc = torch.empty(V, 3, dtype=F32, device=dev)
+    wacc = torch.empty(V, 1, dtype=F32, device=dev)
+    head = (ctx.handle, ptr(_f(v_pos)), V, ptr(_u8(visible)), B, ptr(_f(xform)), ptr(_f(proj)), ptr(_f(images)), images.shape[2], images.shape[3], ptr(_f(wmap)),
+            wmap.shape[1], wmap.shape[2], ptr(_f(v_rgb)), ptr(_f(weights)), int(bool(use_alpha)), ptr(acc), ptr(wacc))
+    if epilogue is None:
+        ctx.check(ctx.lib.utx_vertex_project(*head, ctx.stream()))
+        return acc, wacc
+    if epilogue["blending"] not in VERTEX_BLENDING:
+        raise ValueError("vertex_project: blending %r (None, 'soft' or 'hard')" % (epilogue["blending"],))
+    blended = torch.empty(V, 3, dtype=F32, device=dev)
+    mask = torch.empty(V, dtype=U8, device=dev)
+    ctx.check(ctx.lib.utx_vertex_project_blend(*head, float(epilogue["overlay_confidence"]), VERTEX_BLENDING[epilogue["blending"]],
+                                               float(epilogue["blending_confidence"]), float(epilogue["inpainting_confidence"]), ptr(blended), ptr(mask),
+                                               ctx.stream()))
+    return acc, wacc, blended, mask
+
+
+def vertex_adjacency(faces, V):
+    """CSR vertex adjacency of a triangle mesh: faces [F,3] (any integer type, any device) -> (rowptr [V+1], col [nnz]) int32 on the faces' device; the
+    unique undirected edges, both directions, every row's neighbours ascending (the pattern of Mesh.laplacian, mesh/structure.py:743-763)."""
+    f = faces.long()
+    e = torch.cat([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]], 0)
+    e = torch.cat([e, e.flip(1)], 0)
+    e = e[e[:, 0] != e[:, 1]]
+    key = torch.unique(e[:, 0] * int(V) + e[:, 1])      # sorted: by row, then by neighbour
+    row, col = key // int(V), key % int(V)
+    rowptr = torch.zeros(int(V) + 1, dtype=torch.int64, device=faces.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(row, minlength=int(V)), 0)
+    return rowptr.to(I32).contiguous(), col.to(I32).contiguous()
+
+
+def vertex_inpaint(rowptr, col, v_rgb, v_idx, max_iters=1000, trace=None):
+    """inpainting_vertex_color (:605-627) on the adjacency of vertex_adjacency: v_rgb [V,3], v_idx [n] the vertices to fill -> (v_rgb filled, number of
+    steps).  One utx_vertex_inpaint_step launch per step, colour and mask double-buffered; after each step the host reads the 4-byte count of filled
+    vertices back and stops when it did not grow (that last step is applied, as in the reference) or at max_iters.  No vertex to fill: no launch.
+    v_idx must index the vertices (not checked here); a vertex listed twice is counted twice, which leaves the stop rule as it is.
+    trace (a list): receives each step's mask uint8 [V] (1 = valid)."""
+    ctx = get_ctx(v_rgb.device.index)
+    V, n = v_rgb.shape[0], int(v_idx.shape[0])
+    cur = _f(v_rgb).clone()
+    if n == 0 or max_iters <= 0:
+        return cur, 0
+    idx = _i(v_idx.to(I32).contiguous())
+    assert tuple(rowptr.shape) == (V + 1,), "rowptr is [V + 1]"      # the range of v_idx is the caller's to check (inpainting_vertex_color does, once)
+    mask = torch.ones(V, dtype=U8, device=cur.device)
+    mask[idx.long()] = 0
+    nxt, mask_nxt = cur.clone(), mask.clone()
+    counter = torch.zeros(1, dtype=I32, device=cur.device)
+    count, steps = 0, 0
+    for _ in range(int(max_iters)):
+        ctx.check(ctx.lib.utx_vertex_inpaint_step(ctx.handle, ptr(_i(rowptr)), ptr(_i(col)), ptr(idx), n, ptr(cur), ptr(mask), ptr(nxt), ptr(mask_nxt), ptr(counter),
+                                                  ctx.stream()))
+        cur, nxt, mask, mask_nxt = nxt, cur, mask_nxt, mask
+        steps += 1
+        if trace is not None:
+            trace.append(mask.clone())
+        now = int(counter.item())
+        if now <= count:
+            break
+        count = now
+    return cur, steps
