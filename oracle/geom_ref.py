@@ -21,6 +21,8 @@ import subprocess
 
 import numpy as np
 
+from . import pixel_ref
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _SO = os.path.join(_HERE, "_build", "libgeom_ref.so")
 _lib = None
@@ -506,17 +508,10 @@ def texture_shade(rast, uv01, tri, tex, bg=(1.0, 1.0, 1.0)):
     UV interpolation -> dr.texture(filter 'linear', wrap) -> lerp with the background by the coverage mask ->
     clamp * 255 -> uint8 (truncation).  float32 arithmetic in the order the kernel uses."""
     rast, uv01, tri, tex = _f(rast), _f(uv01), _i(tri), _f(tex)
-    H, W = rast.shape[:2]
     Ht, Wt = tex.shape[:2]
     f32 = np.float32
-    idx = rast[..., 3].astype(np.int32) - 1
-    cov = idx >= 0
-    t = tri[np.where(cov, idx, 0)]
-    u, v = rast[..., 0], rast[..., 1]
-    w = (f32(1.0) - u) - v
-    a0, a1, a2 = uv01[t[..., 0]], uv01[t[..., 1]], uv01[t[..., 2]]
-    tu = (a0[..., 0] * u + a1[..., 0] * v) + a2[..., 0] * w
-    tv = (a0[..., 1] * u + a1[..., 1] * v) + a2[..., 1] * w
+    uv, cov = pixel_ref.interp(uv01, rast, tri)
+    tu, tv = uv[..., 0], uv[..., 1]
     x = tu * f32(Wt) - f32(0.5)
     y = tv * f32(Ht) - f32(0.5)
     x0, y0 = np.floor(x), np.floor(y)

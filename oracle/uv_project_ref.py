@@ -1,18 +1,22 @@
-"""Restatement of the face / vertex visibility and of the atlas-space view projection (utx_visible_faces_rays, utx_visible_faces_raster,
+"""Restatement (TEST INFRASTRUCTURE ONLY) of the face / vertex visibility and of the atlas-space view projection (utx_visible_faces_rays, utx_visible_faces_raster,
 utx_erode_faces, utx_visible_vertices, utx_uv_project) in numpy, shared by tests/test_uv_project_cpu.py and tests/test_uv_project_gpu.py and,
-for the ray caster, by the fixture maker tests/golden/make_golden_uv_project.py.  No test lives here.
+for the ray caster, by the fixture maker tests/golden/make_golden_uv_project.py; the loader of fixture G19, its cases and their comparison.  The
+interpolation and the map lookups are oracle/pixel_ref.py's, the bound of the 'bilinear' lookup oracle/gbuffer_ref.py's map_bound.
 
 The ray caster is a brute force in float64: every ray against every triangle, Moeller-Trumbore on both sides, the hit with the smallest t >= 0, ties
 to the smallest face id.  margin() says which rays a float32 traversal may legitimately decide differently: those whose winner leads the next hit by no
 more than MARGIN in t, or that pass within MARGIN (in barycentric units) of an edge of a triangle they could hit not later than that.  With
 unit-scale geometry MARGIN = 1e-4 is about a hundred times the rounding of a float32 Moeller-Trumbore (a dozen operations at 6e-8 each on numbers
 of order 1, divided by a determinant of order 1e-2 for the triangles of the test meshes)."""
+import os
+
 import numpy as np
 
-from tests import test_simple_rendering_cpu as SC
-from tests import test_uv_maps_cpu as UC
+from .gbuffer_ref import MODES, map_bound
+from .pixel_ref import interp, sample
 
-F32, F64 = np.float32, np.float64
+GOLD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
+F32, F64, U = np.float32, np.float64, 2.0 ** -24
 MARGIN = 1e-4
 TWO_SQRT3 = 2.0 * np.sqrt(3.0)
 
@@ -167,16 +171,16 @@ def uv_project(rast2d, faces, face_mask, v_ndc, map_attr=None, rast_map=None, mo
     B = face_mask.shape[0]
     tri = rast2d[..., 3].astype(np.int64) - 1
     vis = (tri >= 0)[None] & face_mask[:, np.clip(tri, 0, None)]
-    uv = np.stack([np.where(vis[b][..., None], UC.interp(np.asarray(v_ndc[b], F32), rast2d, faces)[0], F32(-1.0)) for b in range(B)]).astype(F32)
+    uv = np.stack([np.where(vis[b][..., None], interp(np.asarray(v_ndc[b], F32), rast2d, faces)[0], F32(-1.0)) for b in range(B)]).astype(F32)
     out = {"uv": uv, "uv_alpha": vis.astype(F32)[..., None]}
     if map_attr is None:
         return out
     map_attr = np.asarray(map_attr, F32)
     Bm, Hm, Wm, C = map_attr.shape
     assert Bm in (1, B)
-    s = np.stack([SC.sample(map_attr[b if Bm > 1 else 0], uv[b], mode) for b in range(B)]).astype(F32)
+    s = np.stack([sample(map_attr[b if Bm > 1 else 0], uv[b], mode) for b in range(B)]).astype(F32)
     covmap = (np.asarray(rast_map)[..., 3:4] > 0).astype(F32)
-    cov = np.stack([SC.sample(covmap[b], uv[b], "nearest")[..., 0] for b in range(B)]) >= 1.0
+    cov = np.stack([sample(covmap[b], uv[b], "nearest")[..., 0] for b in range(B)]) >= 1.0
     alpha = vis & cov
     if background is None:
         texel00 = np.stack([map_attr[b if Bm > 1 else 0, 0, 0] for b in range(B)])[:, None, None, :]
@@ -185,3 +189,50 @@ def uv_project(rast2d, faces, face_mask, v_ndc, map_attr=None, rast_map=None, mo
         m = np.where(alpha[..., None], s, np.broadcast_to(np.asarray(background, F32), s.shape))
     out.update(map_attr=m.astype(F32), uv_alpha=alpha.astype(F32)[..., None], cov=cov)
     return out
+
+
+# ---- fixture G19 and its cases
+SETS = (("p", True), ("o", False))
+ATLAS = (48, 40)
+RASTER_SIZE = (40, 56)
+B = 3
+# (fixture key without the set, map index, per-view map, mode, background key or None)
+BACKGROUNDS = (("map_0_1_bilinear_float", 0, False, "bilinear", "bg_float"), ("map_1_b_nearest_vec", 1, True, "nearest", "bg_vec_5"),
+               ("map_0_b_nvdiffrast_dense", 0, True, "nvdiffrast", "bg_dense_3"), ("map_1_1_bilinear_vec", 1, False, "bilinear", "bg_vec_5"))
+_FIX = {}
+
+
+def load():
+    """the fixture, read once and shared (the arrays are never written to)"""
+    if not _FIX:
+        with np.load(os.path.join(GOLD, "g19_uv_project.npz"), allow_pickle=False) as f:
+            _FIX.update({k: f[k] for k in f.files})
+        for v in _FIX.values():
+            v.setflags(write=False)
+    return _FIX
+
+
+def cases(f, tag):
+    """every stored map_attr of a camera set: (fixture key, map [Bm,Hm,Wm,C], map index, mode, background or None)"""
+    out = []
+    for i in (0, 1):
+        for per_view in (False, True):
+            for mode in MODES:
+                out.append(("map_%d_%s_%s_%s" % (i, "b" if per_view else "1", mode, tag), f["map_%d" % i][:None if per_view else 1], i, mode, None))
+    for key, i, per_view, mode, bg in BACKGROUNDS:
+        out.append(("%s_%s" % (key, tag), f["map_%d" % i][:None if per_view else 1], i, mode, f[bg]))
+    return out
+
+
+def check_map(name, got, ref, mode, m):
+    """bit-exact, or within MAP_BOUND for 'bilinear'; returns the largest deviation in u"""
+    assert got.shape == ref.shape and got.dtype == ref.dtype == F32, (name, got.shape, ref.shape)
+    d = np.abs(got.astype(F64) - ref.astype(F64))
+    print("%s: max|diff| %.3g = %.2f u" % (name, d.max(), d.max() / U))
+    if mode == "bilinear":
+        for b in range(d.shape[0]):      # each view against the bound of the map it sampled
+            bound = map_bound(mode, [m[b if m.shape[0] > 1 else 0]])
+            assert (d[b] <= bound).all(), "%s view %d: %.2f u over a bound of %.2f u" % (name, b, d[b].max() / U, bound.max() / U)
+    else:
+        assert got.tobytes() == ref.tobytes(), "%s: max|diff| %.3g" % (name, d.max())
+    return d.max() / U

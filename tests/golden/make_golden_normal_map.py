@@ -7,7 +7,7 @@ unchanged):
   G16   bsdf_prepare_shading_normal(..., two_sided_shading=True, opengl=True) (TextureTools/texturetools/texture/pbr/renderutils/bsdf.py:28-51, plain torch) run
         on the CPU, its result fed to PBRModel.forward (texture/pbr/pbr.py:110-130) exactly as G15 does: the object built without its __init__, seeded lights
         of 8^2 faces uniform in [2, 4) (the contrast bound of make_golden_pbr_shade.py's header: the reference's own fp32 rounding of a lookup direction moves
-        a bilinear lookup by N / 2 * d * contrast) and a seeded 16 x 16 x 2 FG_LUT; dr.texture STUBBED by the fp64 lookups of tests/test_pbr_cpu.py.
+        a bilinear lookup by N / 2 * d * contrast) and a seeded 16 x 16 x 2 FG_LUT; dr.texture STUBBED by the fp64 lookups of oracle/pbr_ref.py.
         Inputs: a 32 x 32 image carried by four triangles around a centre vertex (five vertices).  Triangle 3 is wound the other way, so its geometric normal
         faces away from the eye (the two-sided flip).  Vertex normals and tangents are un-normalised and not orthogonal; vertex 3's tangent is parallel to its
         normal.  The barycentrics, the uvs and so the texel coordinates (0.75 i + 3) are dyadic: every fourth pixel fetches one texel exactly, the others blend
@@ -30,14 +30,15 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 from make_golden import REF, install_stubs  # noqa: E402
-from make_golden_pbr_shade import _fetch, _interp  # noqa: E402
+from make_golden_pbr_shade import _fetch  # noqa: E402
+from oracle.pixel_ref import interp  # noqa: E402
 
 F32 = np.float32
 S = 32
 
 
 def g16(out):
-    from tests import test_pbr_cpu as PC
+    from oracle import pbr_ref as PC
     P = importlib.import_module("TextureTools.texturetools.texture.pbr.pbr")
     B = importlib.import_module("TextureTools.texturetools.texture.pbr.renderutils.bsdf")
     dr = importlib.import_module("nvdiffrast.torch")
@@ -77,7 +78,7 @@ def g16(out):
     nm[12, 12] = 0.5
     fn = np.cross(verts[faces[:, 1]].astype(np.float64) - verts[faces[:, 0]], verts[faces[:, 2]].astype(np.float64) - verts[faces[:, 0]])
     fn = (fn / np.linalg.norm(fn, axis=-1, keepdims=True)).astype(F32)
-    pos_i, nrm_i, tng_i, uv_i = (_interp(a, full, faces) for a in (verts, nrm, tng, uvs))
+    pos_i, nrm_i, tng_i, uv_i = (interp(a, full, faces)[0] for a in (verts, nrm, tng, uvs))
     assert np.array_equal(uv_i[..., 0] * F32(S) - F32(0.5), F32(0.75) * np.arange(S, dtype=F32)[None, :] + F32(3.0) + 0 * yy), "texel coordinates 0.75 i + 3"
     kd_i, ks_i, nm_i = _fetch(kd, uv_i), _fetch(ks, uv_i), _fetch(nm, uv_i)
     pert = (F32(2.0) * nm_i - F32(1.0)).astype(F32)

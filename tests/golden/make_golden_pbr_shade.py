@@ -10,7 +10,7 @@ there, unchanged):
         direction error d moves a bilinear lookup on an N^2 face by N / 2 * d * (texel contrast); with N = 8 that is 1.9e-6 * contrast / maximum.  A contrast of at
         most half the maximum keeps the reference's OWN fp32 rounding under the 1e-6 to which the fp64 restatement is held (tests/test_pbr_cpu.py); with lights
         in [0, 4) that rounding alone reached 1.1e-6 at one pixel.
-        dr.texture is STUBBED by the fp64 lookups of tests/test_pbr_cpu.py (the build's own cube rule, include/unitex_hip.h, and clamp-linear for the table),
+        dr.texture is STUBBED by the fp64 lookups of oracle/pbr_ref.py (the build's own cube rule, include/unitex_hip.h, and clamp-linear for the table),
         rounded to fp32: the fixture pins the reference's arithmetic around the lookups, not nvdiffrast's sampler.
         Inputs: a 32 x 32 image carried by two triangles (four vertices with un-normalised normals, two of them facing away from the eye), interpolated
         and texture-fetched in fp32 in the kernels' operation order (utx_interpolate, utx_texture_shade) from 32^2 Kd / Ks textures whose Ks holds
@@ -29,17 +29,10 @@ ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, HERE)
 sys.path.insert(0, ROOT)
 from make_golden import REF, install_stubs  # noqa: E402
+from oracle.pixel_ref import interp  # noqa: E402
 
 F32 = np.float32
 S = 32
-
-
-def _interp(attr, rast, faces):
-    """utx_interpolate in fp32: (a0*u + a1*v) + a2*(1-u-v)"""
-    f = faces[rast[..., 3].astype(np.int64) - 1]
-    u, v = rast[..., 0:1], rast[..., 1:2]
-    w = (F32(1.0) - u) - v
-    return ((attr[f[..., 0]] * u + attr[f[..., 1]] * v) + attr[f[..., 2]] * w).astype(F32)
 
 
 def _fetch(tex, uv):
@@ -57,7 +50,7 @@ def _fetch(tex, uv):
 
 
 def g15(out):
-    from tests import test_pbr_cpu as PC
+    from oracle import pbr_ref as PC
     P = importlib.import_module("TextureTools.texturetools.texture.pbr.pbr")
     dr = importlib.import_module("nvdiffrast.torch")
     rng = np.random.default_rng(15)
@@ -82,7 +75,7 @@ def g15(out):
     ks = rng.uniform(0.0, 1.0, (S, S, 3)).astype(F32)
     ks[:8, :, 2], ks[8:16, :, 2] = 0.0, 1.0          # metallic 0 and 1
     ks[:, :8, 1], ks[:, 8:16, 1] = 0.0, 1.0          # roughness 0 and 1
-    pos_i, nrm_i, uv_i = _interp(verts, rast, faces), _interp(nrm, rast, faces), _interp(uvs, rast, faces)
+    pos_i, nrm_i, uv_i = (interp(a, rast, faces)[0] for a in (verts, nrm, uvs))
     kd_i, ks_i = _fetch(kd, uv_i), _fetch(ks, uv_i)
     log = {}
 

@@ -38,6 +38,9 @@ from make_golden import REF, _make_inverse_renderer, install_stubs  # noqa: E402
 from make_golden_reproject_variants import nvdiffrast_texture_linear_wrap  # noqa: E402
 from make_golden_uv_maps import ATLAS, N_VIEWS, SETS, _two_charts  # noqa: E402
 
+sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+from oracle.pixel_ref import grid_unnormalize  # noqa: E402
+
 SCREEN = (40, 56)                                      # (H, W)
 MODES = ("bilinear", "nearest", "nvdiffrast")
 GEOMETRY = ("z_depth", "world_normal", "camera_normal", "world_position", "camera_position", "distance", "ray_direction", "cos_ray_normal")
@@ -45,15 +48,9 @@ MAP_SHAPES = ((16, 24, 3), (8, 8, 5))
 BG_FLOAT = 0.25
 
 
-def _unnormalize(g, size):
-    """grid_sample's pixel coordinate (align_corners=False) in float32, as torch computes it"""
-    g = np.asarray(g, np.float32)
-    return ((g + np.float32(1.0)) * np.float32(size) - np.float32(1.0)) * np.float32(0.5)
-
-
 def conditions(uv, cov, Ht, Wt):
     """per filter mode, the covered pixels with a tap outside the map, and the covered 'nearest' pixels on an exact half"""
-    ix, iy = _unnormalize(uv[..., 0], Wt), _unnormalize(uv[..., 1], Ht)
+    ix, iy = grid_unnormalize(uv[..., 0], Wt), grid_unnormalize(uv[..., 1], Ht)
     x0, y0 = np.floor(ix), np.floor(iy)
     out = {"bilinear": cov & ((x0 < 0) | (x0 + 1 >= Wt) | (y0 < 0) | (y0 + 1 >= Ht))}
     nx, ny = np.rint(ix), np.rint(iy)

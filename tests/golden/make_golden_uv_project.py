@@ -41,7 +41,7 @@ from make_golden_simple_rendering import _cameras, _renderer, conditions  # noqa
 from make_golden_uv_maps import ATLAS, N_VIEWS, SETS, _two_charts  # noqa: E402
 
 sys.path.insert(0, ROOT)
-from tests import uv_project_ref as REFN  # noqa: E402
+from oracle import uv_project_ref as REFN  # noqa: E402
 
 MODES = ("bilinear", "nearest", "nvdiffrast")
 MAP_SHAPES = ((16, 24, 3), (8, 8, 5))

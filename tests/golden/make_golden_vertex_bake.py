@@ -33,7 +33,7 @@ from make_golden_uv_maps import N_VIEWS, SETS  # noqa: E402
 from make_golden_uv_project import INTRINSICS, scene  # noqa: E402
 
 sys.path.insert(0, ROOT)
-from tests import vertex_bake_ref as REFN  # noqa: E402
+from oracle import vertex_bake_ref as REFN  # noqa: E402
 
 RENDER = 48
 IMG = (20, 28)

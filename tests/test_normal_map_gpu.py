@@ -1,17 +1,16 @@
 """Tangent-space normal maps on the GPU (csrc/pbr.hip: utx_pbr_shading_normal, utx_pbr_shade_nm) against the reference's own code (fixture G16) and the fp64
-restatement of tests/test_normal_map_cpu.py, with the per-pixel bounds derived in that module's docstring (the same bounds its CPU test holds the
+restatement of oracle/pbr_ref.py, with the per-pixel bounds derived in that module's docstring (the same bounds its CPU test holds the
 reference's own fp32 result to)."""
 import numpy as np
 import pytest
 import torch
 
-from tests import test_normal_map_cpu as NC
-from tests import test_pbr_cpu as PC
-from tests import test_video_types_cpu as VC
+from oracle import pbr_ref as PC
+from oracle import video_types_ref as VC
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-U = NC.U
+U = PC.U
 
 
 def _cu(a, dtype=None):
@@ -29,7 +28,7 @@ def test_g16_shading_normal():
     """utx_pbr_shading_normal on the dense inputs the reference saw: within the derived per-pixel bound of the reference's own output (the bound is the one for
     a fp32 evaluation against the fp64 restatement; the kernel is held to it against the reference directly, which is stricter), every pixel."""
     from unitex_amd.texturetools import ops
-    f, o = NC.load_g16(), NC.g16_oracle()
+    f, o = PC.load_g16(), PC.g16_oracle()
     d = lambda k: _cu(f[k].reshape(-1, 3))
     got = ops.pbr_shading_normal(_cu(f["view_position"]), d("world_position"), d("perturbed_nrm"), d("smooth_nrm"), d("smooth_tng"), d("geom_nrm"))
     got = got.cpu().numpy().reshape(32, 32, 3)
@@ -48,7 +47,7 @@ def test_g16_fused_shade():
     """utx_pbr_shade_nm on G16's mesh-level inputs: diffuse alone and specular alone against the fp64 restatement within the per-pixel bounds (the shading
     normal's bound through the lookups, plus G15's 16 ulp of the maximum for PBRModel.forward itself), uint8 within 1, the background exact."""
     from unitex_amd.texturetools import ops
-    f, o = NC.load_g16(), NC.g16_oracle()
+    f, o = PC.load_g16(), PC.g16_oracle()
     bg = (0.25, 0.5, 0.75)
     args = (_cu(f["rast"]), _cu(f["faces"], torch.int32), _cu(f["verts"]), _cu(f["v_nrm"]), _cu(f["uvs"]), _cu(f["tex_Kd"]), _cu(f["tex_Ks"]), f["view_position"].tolist(),
             _cu(f["light_diffuse"]), _cu(f["light_specular"]), _cu(f["fg_lut"]))
@@ -125,11 +124,11 @@ def test_flat_map_on_a_torus_frame():
     interp = lambda a: a[tri[..., 0]].astype(np.float64) * u + a[tri[..., 1]].astype(np.float64) * v + a[tri[..., 2]].astype(np.float64) * (1 - u - v)
     g = fn.cpu().numpy()[np.maximum(rast[..., 3].astype(np.int64) - 1, 0)]
     p = np.broadcast_to(np.array([0.0, 0.0, 1.0]), g.shape)
-    out, parts = NC.shading_normal(eye, interp(f["verts"]), p, interp(f["v_nrm"]), interp(tng.numpy()), g, parts=True)
-    vv = NC._n(eye.astype(np.float64) - interp(f["verts"]))
-    sel = cov & (parts["gdot"] > 0) & ((vv * NC._n(interp(f["v_nrm"]))).sum(-1) >= 0.1)
+    out, parts = PC.shading_normal(eye, interp(f["verts"]), p, interp(f["v_nrm"]), interp(tng.numpy()), g, parts=True)
+    vv = PC.unit(eye.astype(np.float64) - interp(f["verts"]))
+    sel = cov & (parts["gdot"] > 0) & ((vv * PC.unit(interp(f["v_nrm"]))).sum(-1) >= 0.1)
     assert sel.sum() > 200 and (cov & ~sel).any(), "both kinds of pixel are in the frame"
-    bd, bs = NC.shade_bounds(NC.shading_normal_bound(parts), out, 8, 2.0, 2.0, 16)
+    bd, bs = PC.shade_bounds(PC.shading_normal_bound(parts), out, 8, 2.0, 2.0, 16)
     bound = bd + bs + 2 * _ulp(plain[cov][:, :3])
     e = np.abs(rgba[..., :3] - plain[..., :3]).max(-1)
     print("flat map vs no map on %d pixels: max %.3g (%.3g of the bound); elsewhere max %.3g" % (sel.sum(), e[sel].max(), (e[sel] / bound[sel]).max(), e[cov & ~sel].max()))
@@ -233,9 +232,9 @@ def test_degenerate_inputs_stay_finite():
     n[40:44], gn = 0.0, n.copy()
     gn[44:48] = 0.0
     out = ops.pbr_shading_normal(_cu(np.array([0.1, 0.2, 3.0], F32)), _cu(pos), _cu(p), _cu(n), _cu(t), _cu(gn)).cpu().numpy()
-    want = NC.shading_normal(np.array([0.1, 0.2, 3.0], F32), pos, p, n, t, gn)
+    want = PC.shading_normal(np.array([0.1, 0.2, 3.0], F32), pos, p, n, t, gn)
     assert np.isfinite(out).all() and np.isfinite(want).all()
     exact = np.r_[8:16, 32:40]          # s = 0 exactly (zero tangent with zero p; p = (0, 0, -1)): out = +-g
-    front = ((gn.astype(np.float64) * NC._n(np.array([0.1, 0.2, 3.0], F32).astype(np.float64) - pos)).sum(-1) > 0)[:, None]
+    front = ((gn.astype(np.float64) * PC.unit(np.array([0.1, 0.2, 3.0], F32).astype(np.float64) - pos)).sum(-1) > 0)[:, None]
     assert np.array_equal(out[exact], np.where(front, gn, -gn)[exact])
     assert ops.pbr_shading_normal(_cu(z[0]), _cu(z), _cu(z), _cu(z), _cu(z), _cu(z)).abs().max().item() == 0.0

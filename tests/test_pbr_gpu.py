@@ -1,4 +1,4 @@
-"""Image-based PBR shading on the GPU (csrc/pbr.hip) against the fp64 restatement of tests/test_pbr_cpu.py and the reference's own PBRModel.forward
+"""Image-based PBR shading on the GPU (csrc/pbr.hip) against the fp64 restatement of oracle/pbr_ref.py and the reference's own PBRModel.forward
 (fixture G15).  ulp = np.spacing of the named magnitude in float32."""
 import ctypes as C
 
@@ -6,8 +6,8 @@ import numpy as np
 import pytest
 import torch
 
-from tests import test_pbr_cpu as PC
-from tests import test_video_types_cpu as VC
+from oracle import pbr_ref as PC
+from oracle import video_types_ref as VC
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -148,7 +148,7 @@ def test_specular_prefilter(roughness):
 
 
 # ---------------------------------------------------------------------------------------------------------------- DFG table
-# max |fp64 twin (tests/test_pbr_cpu.py dfg_lut(256, 1024)) - the reference's bsdf_256_256.bin|, measured on the CPU: 0.012928 at (roughness row 64, cos column 0),
+# max |fp64 twin (oracle/pbr_ref.py dfg_lut(256, 1024)) - the reference's bsdf_256_256.bin|, measured on the CPU: 0.012928 at (roughness row 64, cos column 0),
 # mean 7.6e-4.  With Karis' separable k = a / 2 Smith term the difference was 0.35 (structural); the height-correlated term closed it.
 FG_LUT_TWIN_DIFFERENCE = 0.012928
 

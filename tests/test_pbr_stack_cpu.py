@@ -8,32 +8,16 @@ import pytest
 import torch
 
 from oracle import geom_ref as G
-from tests import test_perspective_cpu as PC
-from tests import test_reproject_variants_cpu as RV
+from oracle import reproject_ref as RV
+from oracle.reproject_ref import HW, N, T, check_atlas, g67s, unpack
 
 F32 = np.float32
-N, HW, T = 6, 48, 96
-
-
-def check_atlas(name, got, ref):
-    """the bounds of test_reproject_variants_gpu._check_atlas"""
-    err = np.abs(got - ref)
-    print("%s final atlas: max |d| %.3g, median %.3g, share beyond 1e-4: %.5f" % (name, err.max(), np.median(err), (err > 1e-4).mean()))
-    assert (err > 1e-4).mean() < 2e-3 and np.median(err) < 1e-6, name
-
-
-def g67s():
-    f = PC.load("g67s_pbr_stack.npz")
-    imgs = f["images"].astype(F32)
-    assert imgs.shape == (N, HW, HW, 9)
-    alpha = PC.unpack(f["alpha"], (N, HW, HW, 1)).astype(F32)
-    return f, imgs, alpha
 
 
 def test_g67s_groups_differ():
     """what the generator asserts, once more on the committed file: a build that copies group 0 cannot pass"""
     f, imgs, _ = g67s()
-    cov = PC.unpack(f["mask_2d"], (1, T, T, 1))[0, ..., 0]
+    cov = unpack(f["mask_2d"], (1, T, T, 1))[0, ..., 0]
     for key in ("color_2d_lens", "color_2d_gauss"):
         c = f[key]
         assert c.shape == (1, T, T, 9) and c.dtype == F32
@@ -49,9 +33,9 @@ def test_g67s_oracle_per_group_reproduces_the_nine_channel_reference():
     verts, faces, uvs, c2ws, intr = f["verts"], f["faces"], f["uvs"], f["c2ws"], f["intr"]
     s = RV.scene(dict(verts=verts, faces=faces, uvs=uvs, c2ws_p=c2ws, intr_p=intr), "p")
     mv_alpha = np.stack([G.rasterize(s["clip"][v], faces, HW, HW)[..., 3] > 0 for v in range(N)])
-    assert np.array_equal(mv_alpha, PC.unpack(f["mv_alpha"], (N, HW, HW, 1))[..., 0]), "view coverage"
-    ref_vis = PC.unpack(f["mask_2d_visiable"], (N, T, T, 1))[..., 0]
-    cov_ref = PC.unpack(f["mask_2d"], (1, T, T, 1))[0, ..., 0]
+    assert np.array_equal(mv_alpha, unpack(f["mv_alpha"], (N, HW, HW, 1))[..., 0]), "view coverage"
+    ref_vis = unpack(f["mask_2d_visiable"], (N, T, T, 1))[..., 0]
+    cov_ref = unpack(f["mask_2d"], (1, T, T, 1))[0, ..., 0]
     got = {"lens": [], "gauss": []}
     vis0 = None
     for g in range(3):

@@ -11,13 +11,12 @@ import numpy as np
 import pytest
 import torch
 
-from tests import test_pbr_stack_cpu as PS
-from tests import test_perspective_cpu as PC
+from oracle import reproject_ref as RV
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32 = np.float32
-N, HW, T = PS.N, PS.HW, PS.T
+N, HW, T = RV.N, RV.HW, RV.T
 
 
 def _infer(f, images, alpha, c2ws, intr, method="reproject", return_layers=False, **kw):
@@ -39,18 +38,18 @@ def _infer(f, images, alpha, c2ws, intr, method="reproject", return_layers=False
 # ------------------------------------------------------------------------------------------------ 1. the fixture through infer
 @pytest.mark.parametrize("blur,key", [("lens", "color_2d_lens"), ("gaussian", "color_2d_gauss")])
 def test_g67s_fixture_through_infer(blur, key):
-    f, imgs, alpha = PS.g67s()
+    f, imgs, alpha = RV.g67s()
     inv, (textured, mask_vis, mask_2d, color_2d) = _infer(f, imgs, alpha[..., 0], f["c2ws"], f["intr"], perspective=True, reproject_method=blur)
     assert tuple(color_2d.shape) == (1, T, T, 9)
-    assert np.array_equal(mask_2d.cpu().numpy()[0, ..., 0], PC.unpack(f["mask_2d"], (1, T, T, 1))[0, ..., 0])
-    got_vis, ref_vis = mask_vis.cpu().numpy()[..., 0], PC.unpack(f["mask_2d_visiable"], (N, T, T, 1))[..., 0]
+    assert np.array_equal(mask_2d.cpu().numpy()[0, ..., 0], RV.unpack(f["mask_2d"], (1, T, T, 1))[0, ..., 0])
+    got_vis, ref_vis = mask_vis.cpu().numpy()[..., 0], RV.unpack(f["mask_2d_visiable"], (N, T, T, 1))[..., 0]
     mism = int((got_vis != ref_vis).sum())
     print("G67s %s visibility: %d of %d texel-views differ" % (blur, mism, ref_vis.size))
     assert mism <= 2
     got, ref = color_2d.cpu().numpy()[0], f[key][0]
     for g in range(3):
-        PS.check_atlas("G67s %s group %d" % (blur, g), got[..., 3 * g:3 * g + 3], ref[..., 3 * g:3 * g + 3])
-    PS.check_atlas("G67s %s all nine" % blur, got, ref)
+        RV.check_atlas("G67s %s group %d" % (blur, g), got[..., 3 * g:3 * g + 3], ref[..., 3 * g:3 * g + 3])
+    RV.check_atlas("G67s %s all nine" % blur, got, ref)
 
 
 # ------------------------------------------------------------------------------------------------ 2. bit-identity against the 3-channel path
@@ -77,7 +76,7 @@ VARIANTS = [dict(), dict(reproject_method="gaussian"), dict(grid_interpolate_mod
 @pytest.mark.parametrize("vi", range(len(VARIANTS)))
 def test_nine_channels_equal_three_rgb_bakes_bit_for_bit_on_the_fixture_scene(persp, vi):
     from unitex_amd.texturetools import camera
-    f, imgs, alpha = PS.g67s()
+    f, imgs, alpha = RV.g67s()
     if persp:
         c2ws, intr = f["c2ws"], f["intr"]
     else:
@@ -247,9 +246,8 @@ def test_the_three_sampling_kernels_agree_where_the_surface_leaves_the_view(pers
 
 def _post_inputs(Hh, Ww, seed):
     """an atlas of 3 random channels with blobs of winners / unseen texels, a seam and coverage with holes"""
-    from tests.test_reproject_variants_gpu import _blob_winner
     from unitex_amd.texturetools import ops
-    winner, rast2d = [t.cuda().contiguous() for t in _blob_winner(Hh, Ww, seed, 40)]
+    winner, rast2d = [t.cuda().contiguous() for t in RV._blob_winner(Hh, Ww, seed, 40)]
     seam = ops.seam_mask(winner, rast2d)
     g = torch.Generator().manual_seed(seed)
     atlas3 = torch.rand(Hh, Ww, 3, generator=g).cuda()
@@ -307,7 +305,6 @@ def test_c_channel_post_processing_equals_the_numpy_restatement(Cc, size):
     chain has in test_geometry_gpu.py and test_reproject_variants_gpu.py: NN fill and pull-push exact, lens blur 2e-6 (libm's powf against the device's),
     Gaussian blur 1e-6 from the fp64 sum"""
     from oracle import geom_ref as G
-    from tests import test_reproject_variants_cpu as RV
     from unitex_amd.texturetools import ops
     Hh, Ww = size
     winner, rast2d, seam, _, pos = _post_inputs(Hh, Ww, 11 + Cc)
@@ -422,7 +419,7 @@ def test_view_sharded_nine_channel_infer_is_bit_identical_to_one_rank(world):
 @pytest.mark.parametrize("method", ["reproject", "kdtree"])
 def test_nine_channel_infer_returns_a_pbr_mesh(method, tmp_path):
     from unitex_amd.texturetools import meshes, ops
-    f, imgs, alpha = PS.g67s()
+    f, imgs, alpha = RV.g67s()
     inv, (textured, mask_vis, mask_2d, color_2d) = _infer(f, imgs, alpha[..., 0], f["c2ws"], f["intr"], method=method, perspective=True)
     assert tuple(color_2d.shape) == (1, T, T, 9)
     want = [ops.to_u8(color_2d[0, ..., 3 * g:3 * g + 3].contiguous(), flip=True).cpu().numpy() for g in range(3)]
@@ -439,7 +436,7 @@ def test_nine_channel_infer_returns_a_pbr_mesh(method, tmp_path):
 
 def test_three_channel_infer_returns_an_rgb_mesh(tmp_path):
     from unitex_amd.texturetools import meshes
-    f, imgs, alpha = PS.g67s()
+    f, imgs, alpha = RV.g67s()
     for method in ("reproject", "kdtree"):
         _, (textured, _, _, color_2d) = _infer(f, np.ascontiguousarray(imgs[..., :3]), alpha[..., 0], f["c2ws"], f["intr"], method=method, perspective=True)
         assert textured.metallic_roughness is None and textured.bump is None and color_2d.shape[-1] == 3
@@ -452,7 +449,7 @@ def test_refusals():
     from unitex_amd._lib import BackprojectDesc, ptr
     from unitex_amd.flux.ops import get_ctx
     from unitex_amd.texturetools import ops
-    f, imgs, alpha = PS.g67s()
+    f, imgs, alpha = RV.g67s()
     with pytest.raises(NotImplementedError, match="return_layers"):
         _infer(f, imgs, alpha[..., 0], f["c2ws"], f["intr"], perspective=True, return_layers=True)
     with pytest.raises(NotImplementedError, match="is not supported"):

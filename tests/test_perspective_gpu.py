@@ -1,6 +1,6 @@
 """Perspective cameras on the GPU: utx_backproject_persp / utx_view_visibility_persp through NVDiffRendererInverse.infer and
 VideoExporter.export_condition against the reference's own outputs (fixtures G67p, G11p, G9p: tests/golden/make_golden_perspective.py), and
-bit for bit against the oracle + the numpy restatement of the perspective rays (tests/test_perspective_cpu.py) at scale, on all three
+bit for bit against the oracle + the numpy restatement of the perspective rays (oracle/reproject_ref.py) at scale, on all three
 traversal modes, and under view sharding."""
 import os
 import sys
@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from oracle import geom_ref as G
-from tests import test_perspective_cpu as PC
+from oracle import reproject_ref as PC
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -11,165 +11,11 @@ import pytest
 import torch
 
 from oracle import geom_ref as G
-from tests import test_perspective_cpu as PC
+from oracle import reproject_ref as PC
+from oracle.pixel_ref import sample_wrap
+from oracle.reproject_ref import gaussian_blur_fp64, gaussian_w1, scene, seam_identity, seam_reference_loop, texel_layers, torchvision_blur, winner_of
 
 F32 = np.float32
-PRIORITY = [0, 3, 4, 1, 2, 5]
-
-
-# ---------------------------------------------------------------------------------------------------
-# restatements (the HIP kernels' formulation)
-# ---------------------------------------------------------------------------------------------------
-def _window(a, r, op, axis):
-    """op over the in-image texels of a 2r+1 window along axis (out-of-image texels skipped)"""
-    out = a.copy()
-    n = a.shape[axis]
-    for d in range(1, r + 1):
-        if d >= n:
-            break
-        lo = [slice(None)] * a.ndim
-        hi = [slice(None)] * a.ndim
-        lo[axis], hi[axis] = slice(0, n - d), slice(d, n)
-        out[tuple(lo)] = op(out[tuple(lo)], a[tuple(hi)])
-        out[tuple(hi)] = op(out[tuple(hi)], a[tuple(lo)])
-    return out
-
-
-def window2(a, r, op):
-    return _window(_window(a, r, op, 1), r, op, 0)
-
-
-def seam_identity(winner, cov, k_boundary=3, k_boundary_blur=3):
-    """utx_seam_mask_sized: bnd = the (2 rb + 1)^2 window's min or max winner differs from the texel's; seam = dilate_rd(bnd) AND erode_(rd+2)(cov)"""
-    rb, rd = k_boundary // 2, k_boundary_blur // 2
-    w = np.asarray(winner, np.int32)
-    bnd = (window2(w, rb, np.minimum) != w) | (window2(w, rb, np.maximum) != w)
-    return window2(bnd, rd, np.logical_or) & window2(np.asarray(cov, bool), rd + 2, np.logical_and)
-
-
-def seam_reference_loop(vis, cov, k_boundary=3, k_boundary_blur=3, order=PRIORITY):
-    """bake_mv_to_uv_reproject_blur's seam, restated with torch on the CPU as the reference writes it (per-view get_boundary_mask, max_pool2d)"""
-    vis = torch.from_numpy(np.asarray(vis, bool))[..., None]
-    mask_2d = torch.from_numpy(np.asarray(cov, bool))[None, ..., None]
-    mp = torch.nn.functional.max_pool2d
-
-    def get_boundary_mask(m, kernel_size):
-        a = m.to(torch.float32)
-        inner = (a - (1.0 - mp(1.0 - a.permute(0, 3, 1, 2), 2 * (kernel_size // 2) + 1, 1, kernel_size // 2)).permute(0, 2, 3, 1) > 0)
-        outer = (mp(a.permute(0, 3, 1, 2), 2 * (kernel_size // 2) + 1, 1, kernel_size // 2).permute(0, 2, 3, 1) - a > 0)
-        return torch.logical_or(inner, outer)
-    cur = torch.zeros_like(vis[:1])
-    bnd = torch.zeros_like(vis[:1])
-    for i in order:
-        extra = torch.logical_and(cur.logical_not(), vis[[i]])
-        cur = torch.logical_or(cur, extra)
-        bnd = torch.logical_or(bnd, get_boundary_mask(extra, k_boundary))
-    kbb = k_boundary_blur
-    bnd = mp(bnd.to(torch.float32).permute(0, 3, 1, 2), 2 * (kbb // 2) + 1, 1, kbb // 2).permute(0, 2, 3, 1) > 0
-    ero = 1.0 - mp(1.0 - mask_2d.to(torch.float32).permute(0, 3, 1, 2), 2 * (kbb // 2) + 5, 1, kbb // 2 + 2).permute(0, 2, 3, 1) > 0
-    return torch.logical_and(ero, bnd)[0, ..., 0].numpy()
-
-
-def winner_of(vis, order=PRIORITY):
-    w = np.full(vis.shape[1:], -1, np.int32)
-    for v in reversed(order):
-        w[vis[v]] = v
-    return w
-
-
-def gaussian_w1(k):
-    """torchvision's _get_gaussian_kernel1d with sigma = 0.15 k + 0.35, torch float32 on the CPU"""
-    sigma = k * 0.15 + 0.35
-    half = (k - 1) * 0.5
-    x = torch.linspace(-half, half, steps=k, dtype=torch.float32)
-    pdf = torch.exp(-0.5 * (x / sigma).pow(2))
-    return (pdf / pdf.sum()).numpy()
-
-
-def gaussian_blur_fp64(img_hwc, k, seam=None):
-    """utx_gaussian_blur_seam in fp64: weights w1[i] * w1[j] rounded to fp32 once, reflect padding of k // 2, depthwise; src where seam is 0"""
-    w1 = gaussian_w1(k)
-    w2 = (w1[:, None] * w1[None, :]).astype(F32).astype(np.float64)
-    r = k // 2
-    src = np.asarray(img_hwc, F32)
-    p = np.pad(src.astype(np.float64), ((r, r), (r, r), (0, 0)), mode="reflect")
-    H, W = src.shape[:2]
-    out = np.zeros(src.shape, np.float64)
-    for i in range(k):
-        for j in range(k):
-            out += w2[i, j] * p[i:i + H, j:j + W]
-    if seam is None:
-        return out
-    return np.where(np.asarray(seam, bool)[..., None], out, src.astype(np.float64))
-
-
-def torchvision_blur(img_hwc, k):
-    """torchvision's tensor path: torch.mm of the 1-D weights, F.pad(mode='reflect'), depthwise conv2d (float32, CPU)"""
-    w1 = torch.from_numpy(gaussian_w1(k))
-    kernel = torch.mm(w1[:, None], w1[None, :]).expand(3, 1, k, k)
-    x = torch.from_numpy(np.ascontiguousarray(np.asarray(img_hwc, F32).transpose(2, 0, 1)))[None]
-    x = torch.nn.functional.pad(x, [k // 2] * 4, mode="reflect")
-    return torch.nn.functional.conv2d(x, kernel, groups=3)[0].numpy().transpose(1, 2, 0)
-
-
-def sample_wrap(img, gx, gy):
-    """nvdiffrast's linear 2-D lookup with the wrap boundary in float32, the kernel's operation order: img [H,W,C], gx/gy ndc -> [..., C]"""
-    H, W = img.shape[:2]
-    gx, gy = np.asarray(gx, F32), np.asarray(gy, F32)
-    fin = np.isfinite(gx) & np.isfinite(gy)
-    u = np.where(fin, gx, F32(0)) * F32(0.5) + F32(0.5)
-    v = np.where(fin, gy, F32(0)) * F32(0.5) + F32(0.5)
-    u = u - np.floor(u)
-    v = v - np.floor(v)
-    u = u * F32(W) - F32(0.5)
-    v = v * F32(H) - F32(0.5)
-    fu0, fv0 = np.floor(u), np.floor(v)
-    fu, fv = (u - fu0)[..., None], (v - fv0)[..., None]
-    iu0, iv0 = fu0.astype(np.int64), fv0.astype(np.int64)
-    iu1, iv1 = iu0 + 1, iv0 + 1
-    iu0 = np.where(iu0 < 0, iu0 + W, iu0)
-    iv0 = np.where(iv0 < 0, iv0 + H, iv0)
-    iu1 = np.where(iu1 >= W, iu1 - W, iu1)
-    iv1 = np.where(iv1 >= H, iv1 - H, iv1)
-    lerp = lambda a, b, t: (a + t * (b - a)).astype(F32)
-    out = lerp(lerp(img[iv0, iu0], img[iv0, iu1], fu), lerp(img[iv1, iu0], img[iv1, iu1], fu), fv)
-    return np.where(fin[..., None], out, F32(0)).astype(F32)
-
-
-def backproject_nvdiff(rast2d, verts, faces, fn, vndc, images4, rayvis):
-    """utx_backproject_sampled(sample_mode=1) without the rays: colour [n,Th,Tw,3], alphaok [n,Th,Tw] u8 (rayvis comes from the ray model)"""
-    n = images4.shape[0]
-    cov = rast2d[..., 3] > 0
-    col = np.zeros((n,) + cov.shape + (3,), F32)
-    ao = np.zeros((n,) + cov.shape, np.uint8)
-    for v in range(n):
-        g = G.interpolate(np.ascontiguousarray(vndc[v], F32), rast2d, faces)[cov]      # (a0 u + a1 v) + a2 w, the kernel's order
-        s = sample_wrap(images4[v], g[:, 0], g[:, 1])
-        col[v][cov] = s[:, :3]
-        ao[v][cov] = (s[:, 3] > F32(0.999)).astype(np.uint8)
-    return col, ao
-
-
-def scene(f, tag):
-    """the G67n scene of set tag ('o' orthographic, 'p' perspective)"""
-    persp = tag == "p"
-    verts, faces, uvs, c2ws, intr = f["verts"], f["faces"], f["uvs"], f["c2ws_" + tag], f["intr_" + tag]
-    clip = G.transform_points(verts, G.mvp_matrices(c2ws, intr, perspective=persp))
-    uvclip = np.concatenate([uvs * 2 - 1, np.zeros((len(uvs), 1), F32), np.ones((len(uvs), 1), F32)], -1)
-    return dict(verts=verts, faces=faces, clip=clip, vndc=(clip[..., :2] / clip[..., 3:4]).astype(F32), uvclip=uvclip, persp=persp,
-                fn=G.face_normals(verts, faces), eyes=np.ascontiguousarray(c2ws[:, :3, 3], F32), dirs=(-c2ws[:, :3, 2]).astype(F32))
-
-
-def texel_layers(s, T, images4, angle_deg, sample):
-    """(rast2d, rayvis, alphaok, colour, dilated visibility) of uv_to_pcd; sample 'grid' (the oracle's gather) or 'nvdiff' (sample_wrap)"""
-    rast2d = G.rasterize(s["uvclip"], s["faces"], T, T)
-    bvh = G.BVH(s["verts"], s["faces"])
-    col, rv, ao = G.backproject(rast2d, s["verts"], s["faces"], s["fn"], s["vndc"], s["dirs"], images4, bvh, angle_deg=angle_deg)
-    if s["persp"]:
-        rv = PC.texel_rayvis(rast2d, s["verts"], s["faces"], s["fn"], s["eyes"], bvh, angle_deg)
-    if sample == "nvdiff":
-        col, ao = backproject_nvdiff(rast2d, s["verts"], s["faces"], s["fn"], s["vndc"], images4, rv)
-    return rast2d, rv, ao, col, G.dilate_visibility(rv, rast2d[..., 3] > 0, ao)
 
 
 # ---------------------------------------------------------------------------------------------------

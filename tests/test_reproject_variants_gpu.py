@@ -1,7 +1,7 @@
 """Back-projection variants on the GPU: reproject_method='gaussian', the seam window sizes and grid_interpolate_mode='nvdiff' through
 NVDiffRendererInverse.infer against the reference's own outputs (fixtures G67g / G67n, tests/golden/make_golden_reproject_variants.py), and the three
 new entry points (utx_seam_mask_sized, utx_gaussian_blur_seam, utx_backproject_sampled) against the numpy restatements of
-tests/test_reproject_variants_cpu.py and the oracle, at scale, on all three traversal modes, and under view sharding."""
+oracle/reproject_ref.py and the oracle, at scale, on all three traversal modes, and under view sharding."""
 import ctypes as C
 import os
 import sys
@@ -11,8 +11,7 @@ import pytest
 import torch
 
 from oracle import geom_ref as G
-from tests import test_perspective_cpu as PC
-from tests import test_reproject_variants_cpu as RV
+from oracle import reproject_ref as RV
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -55,18 +54,18 @@ def _check_atlas(name, got, ref):
 def test_g67g_gaussian_fixture_through_infer(tag, sizes):
     """infer(reproject_method='gaussian', reproject_kernel_size_*) on G67g, with the bounds of test_g67p_perspective_backprojection_fixture_through_infer;
     the seam equals the numpy restatement of the generalised identity on the run's own winner map"""
-    f = PC.load("g67g_reproject_gaussian.npz")
+    f = RV.load("g67g_reproject_gaussian.npz")
     imgs = f["images"].astype(F32)
     n, HW, T = 6, imgs.shape[1], 96
-    alpha = PC.unpack(f["alpha"], (n, HW, HW, 1))[..., 0].astype(F32)
+    alpha = RV.unpack(f["alpha"], (n, HW, HW, 1))[..., 0].astype(F32)
     kb, kbb, kblur = sizes
     inv, (textured, mask_vis, mask_2d, color_2d, layers, vis), seen = _infer(
         f, imgs, alpha, f["c2ws"], f["intr"], perspective=True, reproject_method="gaussian", reproject_kernel_size_boundary=kb,
         reproject_kernel_size_boundary_blur=kbb, reproject_kernel_size_blur=kblur)
-    assert np.array_equal(seen["mv_alpha"].cpu().numpy().astype(bool), PC.unpack(f["mv_alpha"], (n, HW, HW, 1))[..., 0])
+    assert np.array_equal(seen["mv_alpha"].cpu().numpy().astype(bool), RV.unpack(f["mv_alpha"], (n, HW, HW, 1))[..., 0])
     cov = mask_2d.cpu().numpy()[0, ..., 0]
-    assert np.array_equal(cov, PC.unpack(f["mask_2d"], (1, T, T, 1))[0, ..., 0])
-    got_vis, ref_vis = mask_vis.cpu().numpy()[..., 0], PC.unpack(f["mask_2d_visiable"], (n, T, T, 1))[..., 0]
+    assert np.array_equal(cov, RV.unpack(f["mask_2d"], (1, T, T, 1))[0, ..., 0])
+    got_vis, ref_vis = mask_vis.cpu().numpy()[..., 0], RV.unpack(f["mask_2d_visiable"], (n, T, T, 1))[..., 0]
     mism = int((got_vis != ref_vis).sum())
     print("G67g %s visibility: %d of %d texel-views differ" % (tag, mism, ref_vis.size))
     assert mism <= 2
@@ -86,15 +85,15 @@ def test_g67g_gaussian_fixture_through_infer(tag, sizes):
 
 @pytest.mark.parametrize("tag", ["o", "p"])
 def test_g67n_nvdiff_fixture_through_infer(tag):
-    f = PC.load("g67n_backprojection_nvdiff.npz")
+    f = RV.load("g67n_backprojection_nvdiff.npz")
     imgs = f["images"].astype(F32)
     n, HW, T = 6, imgs.shape[1], 96
-    alpha = PC.unpack(f["alpha_" + tag], (n, HW, HW, 1))[..., 0].astype(F32)
+    alpha = RV.unpack(f["alpha_" + tag], (n, HW, HW, 1))[..., 0].astype(F32)
     persp = tag == "p"
     inv, (textured, mask_vis, mask_2d, color_2d, layers, vis), seen = _infer(f, imgs, alpha, f["c2ws_" + tag], f["intr_" + tag], perspective=persp,
                                                                              grid_interpolate_mode="nvdiff")
-    assert np.array_equal(seen["mv_alpha"].cpu().numpy().astype(bool), PC.unpack(f["mv_alpha_" + tag], (n, HW, HW, 1))[..., 0])
-    got_vis, ref_vis = mask_vis.cpu().numpy()[..., 0], PC.unpack(f["mask_2d_visiable_" + tag], (n, T, T, 1))[..., 0]
+    assert np.array_equal(seen["mv_alpha"].cpu().numpy().astype(bool), RV.unpack(f["mv_alpha_" + tag], (n, HW, HW, 1))[..., 0])
+    got_vis, ref_vis = mask_vis.cpu().numpy()[..., 0], RV.unpack(f["mask_2d_visiable_" + tag], (n, T, T, 1))[..., 0]
     mism = int((got_vis != ref_vis).sum())
     print("G67n %s visibility: %d of %d texel-views differ" % (tag, mism, ref_vis.size))
     assert mism <= 2
@@ -108,7 +107,7 @@ def test_g67n_nvdiff_fixture_through_infer(tag):
     _, alias, _ = _infer(f, imgs, alpha, f["c2ws_" + tag], f["intr_" + tag], perspective=persp, grid_interpolate_mode="nvdiffrast")
     assert torch.equal(alias[3], color_2d) and torch.equal(alias[1], mask_vis)
     _, grid, _ = _infer(f, imgs, alpha, f["c2ws_" + tag], f["intr_" + tag], perspective=persp)
-    ref_t = PC.unpack(f["mask_2d_visiable_torch_" + tag], (n, T, T, 1))[..., 0]
+    ref_t = RV.unpack(f["mask_2d_visiable_torch_" + tag], (n, T, T, 1))[..., 0]
     assert int((grid[1].cpu().numpy()[..., 0] != ref_t).sum()) <= 2
     assert int((grid[1] != mask_vis).sum()) >= 20
 
@@ -125,35 +124,15 @@ def _seam_sized(winner, rast2d, kb, kbb):
     return seam
 
 
-def _blob_winner(H, W, seed, n_blobs):
-    """blobs of view ids 0..5 and -1 (texels no view sees), and coverage with holes; seams reach the image edge"""
-    g = torch.Generator().manual_seed(seed)
-    yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing="ij")
-    w = torch.full((H, W), -1, dtype=torch.int8)
-    for _ in range(n_blobs):
-        cy, cx = int(torch.randint(-H // 10, H + H // 10, (1,), generator=g)), int(torch.randint(-W // 10, W + W // 10, (1,), generator=g))
-        r = int(torch.randint(2, max(3, min(H, W) // 6), (1,), generator=g))
-        w[(yy - cy) ** 2 + (xx - cx) ** 2 < r * r] = int(torch.randint(-1, 6, (1,), generator=g))
-    cov = torch.ones(H, W, dtype=torch.bool)
-    for _ in range(n_blobs // 4):
-        cy, cx = int(torch.randint(0, H, (1,), generator=g)), int(torch.randint(0, W, (1,), generator=g))
-        r = int(torch.randint(1, max(2, min(H, W) // 20), (1,), generator=g))
-        cov[(yy - cy) ** 2 + (xx - cx) ** 2 < r * r] = False
-    w[~cov] = -1
-    rast = torch.zeros(H, W, 4)
-    rast[..., 3] = cov.float()
-    return w, rast
-
-
 def test_seam_mask_sized_at_3_3_is_bit_identical_to_the_default():
     from unitex_amd.texturetools import ops
-    f = PC.load("g67_backprojection.npz")
+    f = RV.load("g67_backprojection.npz")
     vis = f["mask_2d_visiable"][..., 0].astype(bool)
     cov = f["mask_2d"][0, ..., 0].astype(bool)
     rast = np.zeros(cov.shape + (4,), F32)
     rast[..., 3] = cov
     cases = [(torch.from_numpy(RV.winner_of(vis).astype(np.int8)), torch.from_numpy(rast))]
-    cases += [_blob_winner(2048, 2048, s, 400) for s in (1, 2)]
+    cases += [RV._blob_winner(2048, 2048, s, 400) for s in (1, 2)]
     for w, r in cases:
         w, r = w.cuda().contiguous(), r.cuda().contiguous()
         default = ops.seam_mask(w, r)
@@ -165,7 +144,7 @@ def test_seam_mask_sized_at_3_3_is_bit_identical_to_the_default():
 @pytest.mark.parametrize("H,W,seed", [(37, 53, 3), (257, 300, 4), (1024, 768, 5)])
 def test_seam_mask_sized_equals_the_numpy_identity(H, W, seed):
     from unitex_amd.texturetools import ops
-    w, r = _blob_winner(H, W, seed, 60)
+    w, r = RV._blob_winner(H, W, seed, 60)
     wd, rd = w.cuda().contiguous(), r.cuda().contiguous()
     cov = r[..., 3].numpy() > 0
     for kb, kbb in [(5, 5), (0, 3), (3, 0), (1, 7), (9, 4), (17, 2), (31, 31), (30, 31)]:
@@ -257,7 +236,7 @@ def test_nvdiff_sampling_bit_exact_at_scale(n_faces, persp):
     bvh_ref = G.BVH(s["verts"], s["faces"])
     col_g, rv_ref, ao_g = G.backproject(rast2d, s["verts"], s["faces"], s["fn"], s["ndc"].cpu().numpy(), s["dirs"], s["imgs"], bvh_ref, angle_deg=115.0)
     if persp:
-        rv_ref = PC.texel_rayvis(rast2d, s["verts"], s["faces"], s["fn"], s["eyes"], bvh_ref, 115.0)
+        rv_ref = RV.texel_rayvis(rast2d, s["verts"], s["faces"], s["fn"], s["eyes"], bvh_ref, 115.0)
     col_ref, ao_ref = RV.backproject_nvdiff(rast2d, s["verts"], s["faces"], s["fn"], s["ndc"].cpu().numpy(), s["imgs"], rv_ref)
     assert int((ao_ref != ao_g).sum()) > 100, "the wrap must change the alpha test along the view borders"
     bvh = ops.BVH(s["vd"], s["fd"])
@@ -370,9 +349,9 @@ def test_view_sharded_nvdiff_gaussian_infer_is_bit_identical_to_one_rank():
 
 def test_bad_arguments_fail_as_the_reference_does():
     from unitex_amd.texturetools import ops
-    f = PC.load("g67g_reproject_gaussian.npz")
+    f = RV.load("g67g_reproject_gaussian.npz")
     imgs = f["images"].astype(F32)
-    alpha = PC.unpack(f["alpha"], (6, 48, 48, 1))[..., 0].astype(F32)
+    alpha = RV.unpack(f["alpha"], (6, 48, 48, 1))[..., 0].astype(F32)
     bad = [(AssertionError, dict(reproject_method="box")), (AssertionError, dict(grid_interpolate_mode="cuda")),
            (ValueError, dict(reproject_method="gaussian", reproject_kernel_size_blur=4)),
            (ValueError, dict(reproject_method="gaussian", reproject_kernel_size_blur=0)),

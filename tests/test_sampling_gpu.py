@@ -1,5 +1,5 @@
 """GPU tests of the geometry sampling for the field stage (csrc/sampling.hip through the C ABI): exact farthest-point sampling, the equal-steps edge
-sampler and the surface sampler against the numpy restatements of tests/test_sampling_cpu.py (pinned there to the reference's run, fixture G14, to the
+sampler and the surface sampler against the numpy restatements of oracle/sampling_ref.py (pinned in tests/test_sampling_cpu.py to the reference's run, fixture G14, to the
 Random123 vectors and to a hand-worked example), and RGBTextureFullPipelineBase.sampling_on_mesh end to end.  Everything float is compared BIT FOR BIT
 unless a test says why not."""
 import os
@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import test_sampling_cpu as R
+from oracle import sampling_ref as R
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32

@@ -1,30 +1,8 @@
 """Screen-space buffers (NVDiffRendererInverse.simple_rendering / utx_screen_gbuffer), CPU side: the table of the reference's simple_rendering
 (render/nvdiffrast/renderer_base.py:101-350) restated in numpy, in the kernel's operation order, against the reference's own buffers (fixture
-G18, tests/golden/make_golden_simple_rendering.py; alpha = coverage, dr.antialias stubbed).  The GPU module (tests/test_simple_rendering_gpu.py)
-uses the restatement and the bounds of this module.
-
-Bounds (u = 2^-24; none of them was taken from the code under test):
-  * mask, alpha, world_position, camera_position, z_depth, uv, v_attr, every background form: one expression, (a0*u + a1*v) + a2*w with
-    w = (1 - u) - v, correctly rounded operations in one order on both sides, then a select: BIT-EXACT.
-  * map_attr: the sample coordinate is the bit-exact uv.
-    'nearest' is one tap: BIT-EXACT.  'nvdiffrast' is the restated lookup of G67n, a + t (b - a) along u, then along v, in torch's elementwise
-    float32 operations: BIT-EXACT.
-    'bilinear' is torch's own CPU grid_sample in the fixture, and that is NOT one fixed sequence of roundings: its vectorised kernel forms the pixel
-    coordinate as (g + 1) * (W / 2) - 0.5 and the compiler may contract that (and the blend) into fused multiply-adds, while torch's scalar and
-    device kernels -- and this build, in the back-projection sampler that G67 pins -- write ((g + 1) * W - 1) / 2, every operation rounded.  So
-    'bilinear' carries a counted bound, MAP_BOUND below:
-      coordinate  a = fl(g + 1) <= 2 is the same number on both sides.  Ours: the product a W <= 2 W rounds (<= 2 W u), the subtraction rounds
-                  (<= 2 W u), the halving is exact: <= 2 W u on the pixel coordinate.  A fused a (W / 2) - 0.5 rounds once (<= W u), an unfused one
-                  twice (<= 2 W u).  The two coordinates differ by <= 4 W u (and 4 H u along y); ix - floor(ix) is exact.  The bilinear
-                  interpolant is continuous and piecewise linear in each coordinate with slope <= R, the range of the map's values with the zero of
-                  the padding included, also where the two sides fall on different sides of a texel centre: <= 4 (W + H) u R.
-      blend       per side: a weight is two differences and a product (3 u relative), a term t w one more product (4 u), and the three additions
-                  round partial sums <= M = max |t| (the weights sum to 1): <= (4 + 3) u M.  Fused operations only remove roundings.  Two sides: 14 u M.
-      MAP_BOUND = (14 M + 4 (W + H) R) u per map: 174 u for the 16 x 24 map and 78 u for the 8 x 8 one at M = R = 1.  The largest deviation of
-      the restatement from the fixture that this module prints is 12 u (map 0) and 2 u (map 1): the coordinate term, far from its worst case.
-      The kernel is bit-identical to the restatement (tests/test_simple_rendering_gpu.py asserts that too), so its deviation is the same.
-  * world_normal, camera_normal: the project's NORMAL_ULPS = 5 u; distance, ray_direction, cos_ray_normal: the counted bounds of
-    tests/test_uv_maps_cpu.py for the same quantities (5 u * d, 7 u, 20 u), whose derivation is in that module's docstring."""
+G18, tests/golden/make_golden_simple_rendering.py; alpha = coverage, dr.antialias stubbed).  The restatement (the screen form of table), the map
+lookups (oracle/pixel_ref.py) and the bounds with their derivation (MAP_BOUND for 'bilinear', bit-exact elsewhere) are in oracle/gbuffer_ref.py;
+the GPU module (tests/test_simple_rendering_gpu.py) uses them too."""
 import os
 import subprocess
 import sys
@@ -32,159 +10,13 @@ import sys
 import numpy as np
 import pytest
 
-from tests import test_uv_maps_cpu as UC
+from oracle.gbuffer_ref import ATLAS, CHANNELS, FILL, GEOMETRY, MODES, SCREEN, SETS, UNBUILT, VIEWS, F32, F64, background_cases, bounds, check, map_bound, table, v_uv
+from oracle.gbuffer_ref import load_g18 as load
+from oracle.pixel_ref import grid_unnormalize
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F32, F64 = np.float32, np.float64
-U = 2.0 ** -24
-H, W, B = 40, 56, 3
-ATLAS = (48, 40)
-SETS = ("p", "o")
-MODES = ("bilinear", "nearest", "nvdiffrast")
-GEOMETRY = ("z_depth", "world_normal", "camera_normal", "world_position", "camera_position", "distance", "ray_direction", "cos_ray_normal")
-CHANNELS = {"z_depth": 1, "world_normal": 3, "camera_normal": 3, "world_position": 3, "camera_position": 3, "distance": 1, "ray_direction": 3,
-            "cos_ray_normal": 1, "uv": 2}
-FILL = {"z_depth": 0.0, "world_normal": -1.0, "camera_normal": -1.0, "world_position": -1.0, "camera_position": 0.0, "distance": 0.0,
-        "ray_direction": -1.0, "cos_ray_normal": -1.0, "uv": -1.0}
-EXACT = ("z_depth", "world_position", "camera_position", "uv")
-UNBUILT = ("render_voxel_attr", "render_voxel_network", "render_all_point_cloud", "render_visible_point_cloud", "render_map_network")
-_FIX = {}
-
-
-def load():
-    """the fixture, read once and shared (the arrays are never written to)"""
-    if not _FIX:
-        with np.load(os.path.join(GOLD, "g18_simple_rendering.npz"), allow_pickle=False) as f:
-            _FIX.update({k: f[k] for k in f.files})
-        for v in _FIX.values():
-            v.setflags(write=False)
-    return _FIX
-
-
-def interp_views(attr, rast, faces):
-    """attr [V,C] (one mesh) or [B,V,C] (per view), rast [B,H,W,4] -> [B,H,W,C] float32, zeros where empty"""
-    per_view = np.asarray(attr).ndim == 3
-    return np.stack([UC.interp(attr[b] if per_view else attr, rast[b], faces)[0] for b in range(rast.shape[0])])
-
-
-def _unnormalize(g, size):
-    return ((g + F32(1.0)) * F32(size) - F32(1.0)) * F32(0.5)
-
-
-def sample(tex, uv, mode):
-    """one map [Ht,Wt,C] at uv [...,2] in [-1,1], float32 in the kernel's order"""
-    Ht, Wt, _ = tex.shape
-    gx, gy = uv[..., 0], uv[..., 1]
-
-    def tap(y, x, zero_outside=True):
-        inside = (x >= 0) & (x < Wt) & (y >= 0) & (y < Ht)
-        assert zero_outside or inside.all()
-        t = tex[np.clip(y, 0, Ht - 1).astype(np.int64), np.clip(x, 0, Wt - 1).astype(np.int64)]
-        return np.where(inside[..., None], t, F32(0.0))
-    if mode in ("bilinear", "nearest"):
-        ix, iy = _unnormalize(gx, Wt), _unnormalize(gy, Ht)
-        if mode == "nearest":
-            return tap(np.rint(iy), np.rint(ix))      # halves to even
-        x0, y0 = np.floor(ix), np.floor(iy)
-        tx, ty = (ix - x0)[..., None], (iy - y0)[..., None]
-        w = ((F32(1.0) - tx) * (F32(1.0) - ty), tx * (F32(1.0) - ty), (F32(1.0) - tx) * ty, tx * ty)
-        return ((tap(y0, x0) * w[0] + tap(y0, x0 + 1) * w[1]) + tap(y0 + 1, x0) * w[2]) + tap(y0 + 1, x0 + 1) * w[3]
-    assert mode == "nvdiffrast"
-    su, sv = gx * F32(0.5) + F32(0.5), gy * F32(0.5) + F32(0.5)
-    su, sv = su - np.floor(su), sv - np.floor(sv)
-    su, sv = su * F32(Wt) - F32(0.5), sv * F32(Ht) - F32(0.5)
-    x0, y0 = np.floor(su), np.floor(sv)
-    fu, fv = (su - x0)[..., None], (sv - y0)[..., None]
-    x1, y1 = x0 + 1, y0 + 1
-    x0, y0, x1, y1 = np.where(x0 < 0, x0 + Wt, x0), np.where(y0 < 0, y0 + Ht, y0), np.where(x1 >= Wt, x1 - Wt, x1), np.where(y1 >= Ht, y1 - Ht, y1)
-    lerp = lambda a, b, t: a + (b - a) * t
-    return lerp(lerp(tap(y0, x0, False), tap(y0, x1, False), fu), lerp(tap(y1, x0, False), tap(y1, x1, False), fu), fv)
-
-
-def background_rule(value, cov, background):
-    """None leaves the value; else lerp(background, value, alpha) with alpha in {0, 1}: a select"""
-    if background is None:
-        return value
-    return np.where(cov[..., None], value, np.broadcast_to(np.asarray(background, F32), value.shape)).astype(F32)
-
-
-def table(rast, faces, v_pos=None, v_nrm=None, clip_w=None, v_pos_cam=None, v_nrm_cam=None, v_uv=None, v_attr=None, maps=(), mode="bilinear",
-          background=None):
-    """the table of utx_screen_gbuffer in the kernel's operation order: every buffer the given arrays allow, [B,H,W,C] float32, mask [B,H,W] bool"""
-    cov = np.asarray(rast)[..., 3] > 0
-    sel = lambda x, fill: np.where(cov[..., None], x, F32(fill)).astype(F32)
-    out = {"mask": cov, "alpha": cov.astype(F32)[..., None]}
-    if clip_w is not None:
-        out["z_depth"] = sel(interp_views(clip_w[..., None], rast, faces), 0.0)
-    if v_nrm is not None:
-        out["world_normal"] = sel(UC._unit(interp_views(v_nrm, rast, faces)), -1.0)
-    if v_pos is not None:
-        out["world_position"] = sel(interp_views(v_pos, rast, faces), -1.0)
-    cn = rd = None
-    if v_nrm_cam is not None:
-        cn = UC._unit(interp_views(v_nrm_cam, rast, faces))
-        out["camera_normal"] = sel(cn, -1.0)
-    if v_pos_cam is not None:
-        p = interp_views(v_pos_cam, rast, faces)
-        d = UC._len3(p)
-        rd = UC._unit(p, d)
-        out.update(camera_position=sel(p, 0.0), distance=sel(d, 0.0), ray_direction=sel(rd, -1.0))
-    if cn is not None and rd is not None:
-        out["cos_ray_normal"] = sel((cn[..., 0:1] * rd[..., 0:1] + cn[..., 1:2] * rd[..., 1:2]) + cn[..., 2:3] * rd[..., 2:3], -1.0)
-    if v_attr is not None:
-        out["v_attr"] = background_rule(interp_views(v_attr, rast, faces), cov, background)
-    if v_uv is not None:
-        out["uv"] = sel(interp_views(v_uv, rast, faces), -1.0)
-        if maps:
-            out["map_attr"] = background_rule(np.concatenate([sample(m, out["uv"], mode) for m in maps], -1).astype(F32), cov, background)
-    return out
-
-
-def bounds(key, ref_distance):
-    """absolute bound (0.0 = bit-exact) of a float32 evaluation in the kernel's order against the fixture (module docstring)"""
-    if key in ("world_normal", "camera_normal"):
-        return UC.NORMAL_ULPS * U
-    if key == "ray_direction":
-        return 2 * UC.UNIT_ULPS * U
-    if key == "distance":
-        return 2 * UC.DIST_ULPS * U * ref_distance.astype(F64)
-    if key == "cos_ray_normal":
-        return 2 * UC.COS_ULPS * U
-    return 0.0
-
-
-def map_bound(mode, maps):
-    """per-channel absolute bound [sum C_i] of map_attr against the fixture (0.0: bit-exact); module docstring"""
-    if mode != "bilinear":
-        return 0.0
-    per_map = []
-    for m in maps:
-        M = float(np.abs(m).max())
-        R = max(float(m.max()), 0.0) - min(float(m.min()), 0.0)
-        per_map.append(np.full(m.shape[2], (14.0 * M + 4.0 * (m.shape[0] + m.shape[1]) * R) * U))
-    return np.concatenate(per_map)
-
-
-def check(name, got, ref, bound, cov):
-    """UC.check over a batch of views (its coverage is [B,H,W] here as well)"""
-    return UC.check(name, got, ref, bound, cov)
-
-
-def v_uv(f):
-    return f["uvs"] * F32(2.0) - F32(1.0)
-
-
-def background_cases(f, tag):
-    """(fixture key, table keyword arguments, buffer) of every stored background form"""
-    a = f["v_attr"]
-    return (("v_attr1_" + tag, dict(v_attr=a[:, :1]), "v_attr"),
-            ("v_attr4_" + tag, dict(v_attr=a[:, :4]), "v_attr"),
-            ("v_attr4_float_" + tag, dict(v_attr=a[:, :4], background=float(f["bg_float"])), "v_attr"),
-            ("v_attr7_vec_" + tag, dict(v_attr=a, background=f["bg_vec_7"]), "v_attr"),
-            ("v_attr4_dense_" + tag, dict(v_attr=a[:, :4], background=f["bg_dense_4"]), "v_attr"),
-            ("map_0_bilinear_vec_" + tag, dict(v_uv=v_uv(f), maps=(f["map_0"],), background=f["bg_vec_3"]), "map_attr"),
-            ("map_1_nearest_dense_" + tag, dict(v_uv=v_uv(f), maps=(f["map_1"],), mode="nearest", background=f["bg_dense_5"]), "map_attr"))
+(H, W), B = SCREEN, VIEWS
 
 
 def test_fixture_is_what_the_issue_asks_for():
@@ -227,7 +59,7 @@ def test_border_taps_and_exact_halves(tag):
     uv, cov = f["uv_" + tag], f["rast_" + tag][..., 3] > 0
     for m in (f["map_0"], f["map_1"]):
         Ht, Wt, _ = m.shape
-        ix, iy = _unnormalize(uv[..., 0], Wt), _unnormalize(uv[..., 1], Ht)
+        ix, iy = grid_unnormalize(uv[..., 0], Wt), grid_unnormalize(uv[..., 1], Ht)
         x0, y0 = np.floor(ix), np.floor(iy)
         assert (cov & ((x0 < 0) | (x0 + 1 >= Wt) | (y0 < 0) | (y0 + 1 >= Ht))).any(), "bilinear"
         nx, ny = np.rint(ix), np.rint(iy)
@@ -248,7 +80,7 @@ def test_restatement_reproduces_the_fixture(tag):
     f = load()
     rast, faces = f["rast_" + tag], f["faces"]
     cov = rast[..., 3] > 0
-    got = table(rast, faces, f["verts"], f["v_nrm"], f["clip_w_" + tag], f["v_pos_cam_" + tag], f["v_nrm_cam_" + tag], v_uv(f))
+    got = table(rast, faces, f["verts"], f["v_nrm"], f["v_pos_cam_" + tag], f["v_nrm_cam_" + tag], f["clip_w_" + tag], v_uv(f))
     for k in GEOMETRY + ("uv",):
         check("%s %s" % (k, tag), got[k], f["%s_%s" % (k, tag)], bounds(k, f["distance_" + tag]), cov)
     for mode in MODES:

@@ -62,6 +62,33 @@ def test_the_audit_sees_a_shadowed_test(tmp_path):
     assert _audit(str(q)) == []
 
 
+def _test_module_imports(path):
+    """the imports of a `tests.test_*` module in this file: `import tests.test_x`, `from tests.test_x import y`, `from tests import test_x`"""
+    found = []
+    for n in ast.walk(ast.parse(open(path).read(), filename=path)):
+        if isinstance(n, ast.Import):
+            names = [a.name for a in n.names]
+        elif isinstance(n, ast.ImportFrom) and n.level == 0:
+            names = ["tests." + a.name for a in n.names] if n.module == "tests" else [n.module or ""]
+        else:
+            continue
+        found += [("%s:%d" % (os.path.relpath(path, ROOT), n.lineno), name) for name in names if name.startswith("tests.test_")]
+    return found
+
+
+def test_no_module_imports_a_test_module(tmp_path):
+    # a restatement that a second module needs lives under oracle/, once; a test module is nobody's library
+    bad = []
+    for top in ("tests", "oracle", "tools"):            # tests/golden/ is walked with tests/
+        for path in _python_files(os.path.join(ROOT, top)):
+            if os.path.basename(path) not in ("fakes.py", "conftest.py"):
+                bad += _test_module_imports(path)
+    assert not bad, "a test module imported as a library:\n" + "\n".join("  %s  %s" % b for b in bad)
+    p = tmp_path / "m.py"
+    p.write_text("from tests import fakes, test_a_cpu as A\nimport tests.test_b_gpu\n\n\ndef f():\n    from tests.test_c_cpu import g\n    from oracle import pixel_ref\n")
+    assert [name for _, name in _test_module_imports(str(p))] == ["tests.test_a_cpu", "tests.test_b_gpu", "tests.test_c_cpu"]
+
+
 def test_product_and_tool_modules_define_no_name_twice():
     # the same accident in the product package, the oracle, bench.py or a probe script would be as silent
     bad = []

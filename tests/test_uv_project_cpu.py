@@ -1,14 +1,14 @@
-"""Atlas-space view projection and face / vertex visibility, CPU side: the numpy restatement (tests/uv_project_ref.py) of utx_visible_faces_rays,
+"""Atlas-space view projection and face / vertex visibility, CPU side: the numpy restatement (oracle/uv_project_ref.py) of utx_visible_faces_rays,
 utx_visible_faces_raster, utx_erode_faces, utx_visible_vertices and utx_uv_project against the reference's own results (fixture G19,
 tests/golden/make_golden_uv_project.py), the argument handling of NVDiffRendererInverse and the C entry points' argument checks.
 
 Bounds (u = 2^-24; none of them was taken from the code under test):
   * the masks are sets of integers: EXACT.  The ray caster of the fixture is a float64 brute force and every ray of the fixture passes the margin of
-    tests/uv_project_ref.py (asserted when the fixture is made and again here), so a float32 traversal has to find the same faces.
+    oracle/uv_project_ref.py (asserted when the fixture is made and again here), so a float32 traversal has to find the same faces.
   * uv_alpha, uv: a select and utx_interpolate's one expression on the fixture's own v_ndc: BIT-EXACT.
   * map_attr in 'nearest' and 'nvdiffrast', every background form: BIT-EXACT (one tap; the restated lookup of G67n).
   * map_attr in 'bilinear': torch's CPU grid_sample in the fixture, which is not one fixed sequence of roundings.  The counted bound of
-    tests/test_simple_rendering_cpu.py, MAP_BOUND = (14 M + 4 (Wm + Hm) R) u, is a function of the map's size and range and is evaluated for the
+    oracle/gbuffer_ref.py, MAP_BOUND = (14 M + 4 (Wm + Hm) R) u, is a function of the map's size and range and is evaluated for the
     maps of this fixture by that module's map_bound(): 174 u for the 16 x 24 maps and 78 u for the 8 x 8 ones at M = R = 1."""
 import ctypes as C
 import os
@@ -18,57 +18,13 @@ import sys
 import numpy as np
 import pytest
 
-from tests import test_simple_rendering_cpu as SC
-from tests import uv_project_ref as R
+from oracle import uv_project_ref as R
+from oracle.pixel_ref import grid_unnormalize
+from oracle.uv_project_ref import ATLAS, B, MODES, RASTER_SIZE, SETS, cases, check_map, load
 
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 F32, F64, U = np.float32, np.float64, 2.0 ** -24
-SETS = (("p", True), ("o", False))
-MODES = ("bilinear", "nearest", "nvdiffrast")
-ATLAS = (48, 40)
-RASTER_SIZE = (40, 56)
-B = 3
-# (fixture key without the set, map index, per-view map, mode, background key or None)
-BACKGROUNDS = (("map_0_1_bilinear_float", 0, False, "bilinear", "bg_float"), ("map_1_b_nearest_vec", 1, True, "nearest", "bg_vec_5"),
-               ("map_0_b_nvdiffrast_dense", 0, True, "nvdiffrast", "bg_dense_3"), ("map_1_1_bilinear_vec", 1, False, "bilinear", "bg_vec_5"))
-_FIX = {}
-
-
-def load():
-    """the fixture, read once and shared (the arrays are never written to)"""
-    if not _FIX:
-        with np.load(os.path.join(GOLD, "g19_uv_project.npz"), allow_pickle=False) as f:
-            _FIX.update({k: f[k] for k in f.files})
-        for v in _FIX.values():
-            v.setflags(write=False)
-    return _FIX
-
-
-def cases(f, tag):
-    """every stored map_attr of a camera set: (fixture key, map [Bm,Hm,Wm,C], map index, mode, background or None)"""
-    out = []
-    for i in (0, 1):
-        for per_view in (False, True):
-            for mode in MODES:
-                out.append(("map_%d_%s_%s_%s" % (i, "b" if per_view else "1", mode, tag), f["map_%d" % i][:None if per_view else 1], i, mode, None))
-    for key, i, per_view, mode, bg in BACKGROUNDS:
-        out.append(("%s_%s" % (key, tag), f["map_%d" % i][:None if per_view else 1], i, mode, f[bg]))
-    return out
-
-
-def check_map(name, got, ref, mode, m):
-    """bit-exact, or within MAP_BOUND for 'bilinear'; returns the largest deviation in u"""
-    assert got.shape == ref.shape and got.dtype == ref.dtype == F32, (name, got.shape, ref.shape)
-    d = np.abs(got.astype(F64) - ref.astype(F64))
-    print("%s: max|diff| %.3g = %.2f u" % (name, d.max(), d.max() / U))
-    if mode == "bilinear":
-        for b in range(d.shape[0]):      # each view against the bound of the map it sampled
-            bound = SC.map_bound(mode, [m[b if m.shape[0] > 1 else 0]])
-            assert (d[b] <= bound).all(), "%s view %d: %.2f u over a bound of %.2f u" % (name, b, d[b].max() / U, bound.max() / U)
-    else:
-        assert got.tobytes() == ref.tobytes(), "%s: max|diff| %.3g" % (name, d.max())
-    return d.max() / U
 
 
 def test_fixture_is_what_the_issue_asks_for():
@@ -90,7 +46,7 @@ def test_fixture_is_what_the_issue_asks_for():
         assert (other & ~plate[np.clip(hit, 0, None)] & ~plate[None]).any(1).all()                   # hidden by the cylinder itself, in every view
         vis = f["uv_alpha_" + tag][..., 0] > 0
         for Hm, Wm in ((16, 24), (8, 8)):      # G18's outside-tap condition, per filter and map, on the texels the views see
-            ix, iy = SC._unnormalize(f["uv_" + tag][..., 0], Wm), SC._unnormalize(f["uv_" + tag][..., 1], Hm)
+            ix, iy = grid_unnormalize(f["uv_" + tag][..., 0], Wm), grid_unnormalize(f["uv_" + tag][..., 1], Hm)
             assert (vis & ((np.floor(ix) < 0) | (np.floor(ix) + 1 >= Wm) | (np.floor(iy) < 0) | (np.floor(iy) + 1 >= Hm))).any()         # bilinear
             assert (vis & ((np.rint(ix) < 0) | (np.rint(ix) >= Wm) | (np.rint(iy) < 0) | (np.rint(iy) >= Hm))).any()                     # nearest
             su = f["uv_" + tag] * F32(0.5) + F32(0.5)

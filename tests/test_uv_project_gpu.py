@@ -1,6 +1,6 @@
 """Atlas-space view projection and face / vertex visibility on the GPU: utx_visible_faces_rays / _raster, utx_erode_faces, utx_visible_vertices,
 utx_uv_project, their ops wrappers and the public methods of NVDiffRendererInverse against the reference's own results (fixture G19), the numpy
-restatement (tests/uv_project_ref.py), the composition of the existing ops, a float64 brute-force ray caster, and at the edges.
+restatement (oracle/uv_project_ref.py), the composition of the existing ops, a float64 brute-force ray caster, and at the edges.
 Standards: the docstring of tests/test_uv_project_cpu.py -- masks, uv_alpha, uv, 'nearest' / 'nvdiffrast' map_attr and every background form
 bit-exact on the fixture's own v_ndc and rasters; 'bilinear' map_attr within MAP_BOUND.  The kernel is bit-identical to the restatement in all
 three filters (asserted here), so its deviation from G19 is the restatement's.
@@ -15,9 +15,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import test_simple_rendering_cpu as SC
-from tests import test_uv_project_cpu as PC
-from tests import uv_project_ref as R
+from oracle import uv_project_ref as R
 
 pytestmark = pytest.mark.gpu
 F32, F64, U = np.float32, np.float64, 2.0 ** -24
@@ -49,10 +47,10 @@ def _bvh(verts, faces):
     return ops.BVH(_cu(verts), _cu(faces, torch.int32))
 
 
-@pytest.mark.parametrize("tag,perspective", PC.SETS)
+@pytest.mark.parametrize("tag,perspective", R.SETS)
 def test_ops_against_g19(tag, perspective):
     from unitex_amd.texturetools import ops
-    f = PC.load()
+    f = R.load()
     Fn, V = f["faces"].shape[0], f["verts"].shape[0]
     bvh = _bvh(f["verts"], f["faces"])
     rays = ops.visible_faces_rays(bvh, _cu(f["c2ws_" + tag]), perspective=perspective)
@@ -72,10 +70,10 @@ def test_ops_against_g19(tag, perspective):
     assert sorted(got) == ["uv", "uv_alpha"]
     assert got["uv"].tobytes() == f["uv_" + tag].tobytes() and got["uv_alpha"].tobytes() == f["uv_alpha_" + tag].tobytes()
     worst = 0.0
-    for key, m, i, mode, bg in PC.cases(f, tag):
+    for key, m, i, mode, bg in R.cases(f, tag):
         got = _project(f, tag, mask, m, i, mode, bg)
         assert got["uv"].tobytes() == f["uv_" + tag].tobytes() and got["uv_alpha"].tobytes() == f["uv_alpha_map_%d_%s" % (i, tag)].tobytes(), key
-        dev = PC.check_map(key, got["map_attr"], f[key], mode, m)
+        dev = R.check_map(key, got["map_attr"], f[key], mode, m)
         worst = max(worst, dev if mode == "bilinear" else 0.0)
         ref = R.uv_project(f["rast2d"], f["faces"], mask, f["v_ndc_" + tag], m, f["rast_map_%d_%s" % (i, tag)], mode, bg)
         assert got["map_attr"].tobytes() == ref["map_attr"].tobytes(), "%s: the kernel is not the restatement" % key
@@ -94,11 +92,11 @@ def _e2e_uv_bound(f, tag, perspective):
     return 2.0 * (per_vertex.max() + 3 * U * ndc.max())
 
 
-@pytest.mark.parametrize("tag,perspective", PC.SETS)
+@pytest.mark.parametrize("tag,perspective", R.SETS)
 def test_public_methods_against_g19(tag, perspective):
     from unitex_amd.texturetools import ops
     from unitex_amd.texturetools.renderer_inverse import NVDiffRendererInverse
-    f = PC.load()
+    f = R.load()
     inv = NVDiffRendererInverse(device="cuda:0").update_from_arrays(f["verts"], f["faces"], f["uvs"])
     c2ws, intr = torch.from_numpy(f["c2ws_" + tag].copy()), torch.from_numpy(f["intr_" + tag].copy())
     for e in (0, 1):
@@ -106,19 +104,19 @@ def test_public_methods_against_g19(tag, perspective):
         assert m.dtype == torch.bool and np.array_equal(m.cpu().numpy(), f["faces_rays_e%d_%s" % (e, tag)] > 0)
     assert np.array_equal(inv.get_visible_vertices(c2ws, perspective=perspective).cpu().numpy(), f["verts_rays_e0_" + tag] > 0)
     # the raster method runs this build's rasteriser on this build's clip coordinates: held to the restatement on the method's own raster
-    rast = inv._view_raster(c2ws, intr, PC.RASTER_SIZE, perspective)[4]
+    rast = inv._view_raster(c2ws, intr, R.RASTER_SIZE, perspective)[4]
     for e in (0, 1, 2):
         want = R.erode_faces(R.visible_faces_raster(rast.cpu().numpy(), f["faces"].shape[0]), f["faces"], f["verts"].shape[0], e)
-        got = inv.get_visible_faces(c2ws, perspective=perspective, method="raster", intrinsics=intr, render_size=PC.RASTER_SIZE, erode_neighbor=e)
+        got = inv.get_visible_faces(c2ws, perspective=perspective, method="raster", intrinsics=intr, render_size=R.RASTER_SIZE, erode_neighbor=e)
         assert np.array_equal(got.cpu().numpy(), want)
-        gotv = inv.get_visible_vertices(c2ws, perspective=perspective, method="raster", intrinsics=intr, render_size=PC.RASTER_SIZE, erode_neighbor=e)
+        gotv = inv.get_visible_vertices(c2ws, perspective=perspective, method="raster", intrinsics=intr, render_size=R.RASTER_SIZE, erode_neighbor=e)
         assert np.array_equal(gotv.cpu().numpy(), R.visible_vertices(want, f["faces"], f["verts"].shape[0]))
     bound = _e2e_uv_bound(f, tag, perspective)
     m = f["map_0"]
-    out = inv.simple_inverse_rendering(c2ws, PC.ATLAS, intrinsics=intr, perspective=perspective, map_attr=torch.from_numpy(m.copy()), render_uv=True,
+    out = inv.simple_inverse_rendering(c2ws, R.ATLAS, intrinsics=intr, perspective=perspective, map_attr=torch.from_numpy(m.copy()), render_uv=True,
                                        render_map_attr=True, grid_interpolate_mode="nearest", enable_antialis=False)
-    assert sorted(out) == ["alpha", "map_attr", "mask", "uv", "uv_alpha"] and out["map_attr"].shape == (PC.B,) + PC.ATLAS + (3,)
-    alone = inv.simple_inverse_rendering(c2ws, PC.ATLAS, intrinsics=intr, perspective=perspective, render_uv=True)
+    assert sorted(out) == ["alpha", "map_attr", "mask", "uv", "uv_alpha"] and out["map_attr"].shape == (R.B,) + R.ATLAS + (3,)
+    alone = inv.simple_inverse_rendering(c2ws, R.ATLAS, intrinsics=intr, perspective=perspective, render_uv=True)
     assert alone["uv_alpha"].cpu().numpy().tobytes() == f["uv_alpha_" + tag].tobytes()
     d = np.abs(alone["uv"].cpu().numpy().astype(F64) - f["uv_" + tag].astype(F64)).max()
     print("uv of the public method against G19, set %s: max|diff| %.3g = %.2f u (bound %.2f u)" % (tag, d, d / U, bound / U))
@@ -129,14 +127,14 @@ def test_public_methods_against_g19(tag, perspective):
     for k in ("uv", "uv_alpha", "map_attr"):
         assert out[k].cpu().numpy().tobytes() == ref[k].tobytes(), k
     # render_uv together with the camera-dependent flags equals the separate calls (the reference raises TypeError there, G19)
-    both = inv.simple_inverse_rendering(c2ws, PC.ATLAS, intrinsics=intr, perspective=perspective, render_uv=True, render_camera_position=True,
+    both = inv.simple_inverse_rendering(c2ws, R.ATLAS, intrinsics=intr, perspective=perspective, render_uv=True, render_camera_position=True,
                                         render_distance=True, render_cos_ray_normal=True)
-    geo = inv.simple_inverse_rendering(c2ws, PC.ATLAS, render_camera_position=True, render_distance=True, render_cos_ray_normal=True)
+    geo = inv.simple_inverse_rendering(c2ws, R.ATLAS, render_camera_position=True, render_distance=True, render_cos_ray_normal=True)
     for k in geo:
         assert torch.equal(both[k], geo[k]), k
     assert torch.equal(both["uv"], alone["uv"]) and torch.equal(both["uv_alpha"], alone["uv_alpha"])
     # the raster method of simple_inverse_rendering takes its size from the map
-    ras = inv.simple_inverse_rendering(c2ws, PC.ATLAS, intrinsics=intr, perspective=perspective, map_attr=torch.from_numpy(m.copy()), render_uv=True,
+    ras = inv.simple_inverse_rendering(c2ws, R.ATLAS, intrinsics=intr, perspective=perspective, map_attr=torch.from_numpy(m.copy()), render_uv=True,
                                        render_map_attr=True, visible_faces="raster", background=0.5)
     fm = R.visible_faces_raster(rast_map.cpu().numpy(), f["faces"].shape[0])
     ref = R.uv_project(f["rast2d"], f["faces"], fm, ndc.cpu().numpy(), m, rast_map.cpu().numpy(), "bilinear", F32(0.5))
@@ -148,9 +146,9 @@ def test_sentinels_around_every_output():
     """every output buffer sits between guard bytes that the launch must leave alone (the raw entry points, caller-owned memory)"""
     from unitex_amd.flux.ops import get_ctx
     from unitex_amd._lib import ptr
-    f = PC.load()
+    f = R.load()
     tag, Fn, V = "p", f["faces"].shape[0], f["verts"].shape[0]
-    H, W = PC.ATLAS
+    H, W = R.ATLAS
     ctx = get_ctx(0)
     G = 256
 
@@ -162,24 +160,24 @@ def test_sentinels_around_every_output():
         return bool((t[:G] == SENTINEL).all()) and bool((t[G + nbytes:] == SENTINEL).all())
     bvh = _bvh(f["verts"], f["faces"])
     faces, c2ws = _faces(f), _cu(f["c2ws_" + tag])
-    t_mask, mask = guarded(PC.B * Fn)
-    ctx.check(ctx.lib.utx_visible_faces_rays(ctx.handle, bvh.handle, ptr(bvh.verts), ptr(bvh.faces), Fn, ptr(c2ws), PC.B, 1, 0, ptr(mask), None, ctx.stream()))
-    assert intact(t_mask, PC.B * Fn) and np.array_equal(mask.cpu().numpy().reshape(PC.B, Fn), f["faces_rays_e0_" + tag])
-    t_v, vout = guarded(PC.B * V)
-    ctx.check(ctx.lib.utx_visible_vertices(ctx.handle, ptr(mask), ptr(faces), PC.B, Fn, V, ptr(vout), ctx.stream()))
-    assert intact(t_v, PC.B * V) and np.array_equal(vout.cpu().numpy().reshape(PC.B, V), f["verts_rays_e0_" + tag])
-    t_s, stamp = guarded(PC.B * V * 4)
-    ctx.check(ctx.lib.utx_erode_faces(ctx.handle, ptr(mask), ptr(faces), PC.B, Fn, V, 1, ptr(stamp), ctx.stream()))
-    assert intact(t_s, PC.B * V * 4) and intact(t_mask, PC.B * Fn) and np.array_equal(mask.cpu().numpy().reshape(PC.B, Fn), f["faces_rays_e1_" + tag])
-    t_r, rmask = guarded(PC.B * Fn)
+    t_mask, mask = guarded(R.B * Fn)
+    ctx.check(ctx.lib.utx_visible_faces_rays(ctx.handle, bvh.handle, ptr(bvh.verts), ptr(bvh.faces), Fn, ptr(c2ws), R.B, 1, 0, ptr(mask), None, ctx.stream()))
+    assert intact(t_mask, R.B * Fn) and np.array_equal(mask.cpu().numpy().reshape(R.B, Fn), f["faces_rays_e0_" + tag])
+    t_v, vout = guarded(R.B * V)
+    ctx.check(ctx.lib.utx_visible_vertices(ctx.handle, ptr(mask), ptr(faces), R.B, Fn, V, ptr(vout), ctx.stream()))
+    assert intact(t_v, R.B * V) and np.array_equal(vout.cpu().numpy().reshape(R.B, V), f["verts_rays_e0_" + tag])
+    t_s, stamp = guarded(R.B * V * 4)
+    ctx.check(ctx.lib.utx_erode_faces(ctx.handle, ptr(mask), ptr(faces), R.B, Fn, V, 1, ptr(stamp), ctx.stream()))
+    assert intact(t_s, R.B * V * 4) and intact(t_mask, R.B * Fn) and np.array_equal(mask.cpu().numpy().reshape(R.B, Fn), f["faces_rays_e1_" + tag])
+    t_r, rmask = guarded(R.B * Fn)
     rv = _cu(f["rast_view_" + tag])
-    ctx.check(ctx.lib.utx_visible_faces_raster(ctx.handle, ptr(rv), PC.B, rv.shape[1], rv.shape[2], Fn, ptr(rmask), ctx.stream()))
-    assert intact(t_r, PC.B * Fn) and np.array_equal(rmask.cpu().numpy().reshape(PC.B, Fn), f["faces_raster_e0_" + tag])
+    ctx.check(ctx.lib.utx_visible_faces_raster(ctx.handle, ptr(rv), R.B, rv.shape[1], rv.shape[2], Fn, ptr(rmask), ctx.stream()))
+    assert intact(t_r, R.B * Fn) and np.array_equal(rmask.cpu().numpy().reshape(R.B, Fn), f["faces_raster_e0_" + tag])
     m = _cu(f["map_1"])
-    n = PC.B * H * W
+    n = R.B * H * W
     (t_uv, uv), (t_a, alpha), (t_m, mo) = guarded(n * 2 * 4), guarded(n * 4), guarded(n * 5 * 4)
     fm, rast2d, ndc, rast_map = _cu(f["faces_rays_e0_" + tag]), _cu(f["rast2d"]), _cu(f["v_ndc_" + tag]), _cu(f["rast_map_1_" + tag])      # held until the launch has run
-    ctx.check(ctx.lib.utx_uv_project(ctx.handle, ptr(rast2d), ptr(faces), Fn, ptr(fm), ptr(ndc), V, PC.B, H, W, ptr(m), PC.B, 8, 8, 5,
+    ctx.check(ctx.lib.utx_uv_project(ctx.handle, ptr(rast2d), ptr(faces), Fn, ptr(fm), ptr(ndc), V, R.B, H, W, ptr(m), R.B, 8, 8, 5,
                                      ptr(rast_map), 2, 0, 0.0, None, ptr(uv), ptr(alpha), ptr(mo), ctx.stream()))
     assert intact(t_uv, n * 8) and intact(t_a, n * 4) and intact(t_m, n * 20)
     assert uv.cpu().numpy().tobytes() == f["uv_" + tag].tobytes() and mo.cpu().numpy().tobytes() == f["map_1_b_nvdiffrast_" + tag].tobytes()
@@ -198,14 +196,14 @@ def _synthetic(f, B, rng):
     return v_ndc, mask
 
 
-@pytest.mark.parametrize("mode", PC.MODES)
+@pytest.mark.parametrize("mode", R.MODES)
 @pytest.mark.parametrize("Bm,C_", ((1, 3), (3, 5), (1, 1)))
 def test_composition_of_existing_ops(mode, Bm, C_):
     """utx_uv_project is bit-identical to ops.interpolate + the map lookup of ops.screen_gbuffer (the map and, in 'nearest', the view's coverage) +
     torch indexing, for every filter and background form; the rasters of the coverage come from ops.rasterize"""
     from unitex_amd.texturetools import ops
-    f = PC.load()
-    B, (H, W) = 3, PC.ATLAS
+    f = R.load()
+    B, (H, W) = 3, R.ATLAS
     rng = np.random.default_rng(190 + C_)
     v_ndc, mask = _synthetic(f, B, rng)
     Hm, Wm = (8, 8) if C_ == 5 else (16, 24)
@@ -342,7 +340,7 @@ def test_error_codes_on_the_device():
     """the checks that need a live tree: a tree of another F; and the argument checks with real device memory behind the pointers"""
     from unitex_amd.flux.ops import get_ctx
     from unitex_amd._lib import ptr
-    f = PC.load()
+    f = R.load()
     ctx = get_ctx(0)
     bvh = _bvh(f["verts"], f["faces"])
     Fn, V = f["faces"].shape[0], f["verts"].shape[0]

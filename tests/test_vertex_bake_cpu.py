@@ -1,5 +1,5 @@
 """Vertex-colour bake (unitex_amd/texturetools/remapping.py, utx_view_weight_maps / utx_vertex_project / utx_vertex_inpaint_step), CPU side: the numpy
-restatement (tests/vertex_bake_ref.py) against torch's own CPU operators -- torch.gradient, max_pool2d, grid_sample with reflection and zero padding,
+restatement (oracle/vertex_bake_ref.py) against torch's own CPU operators -- torch.gradient, max_pool2d, grid_sample with reflection and zero padding,
 a sparse Laplacian product -- composed here the way mesh_remapping.py composes them; the CSR builder against a dense adjacency; the dilation radius,
 the weight tables, every refusal, the C ABI's argument checks (they return before any device call) and the .ply round trip.
 
@@ -13,38 +13,10 @@ import numpy as np
 import pytest
 import torch
 
-from tests import vertex_bake_ref as R
+from oracle import vertex_bake_ref as R
+from oracle.vertex_bake_ref import G20_TAGS, _cos_image, _grid_mesh, _hand_points, _torch_project, _torch_weight_maps, g20, g20_case, g20_edge
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _cos_image(B, H, W, seed):
-    """a cos_ray_normal-like image: smooth facing term with a few creases and a background of 0, so that both alpha classes occur"""
-    rng = np.random.default_rng(seed)
-    y, x = np.meshgrid(np.linspace(-1, 1, H), np.linspace(-1, 1, W), indexing="ij")
-    out = np.zeros((B, H, W), np.float32)
-    for b in range(B):
-        r2 = (x - rng.uniform(-0.2, 0.2)) ** 2 + (y - rng.uniform(-0.2, 0.2)) ** 2
-        c = -np.sqrt(np.clip(1 - r2 / 0.8, 0, 1))
-        c = np.where(x * rng.uniform(-1, 1) + y > 0.3, c * 0.5, c)
-        out[b] = c.astype(np.float32)
-    return out
-
-
-def _torch_weight_maps(cosn, cam_nz, r):
-    """mesh_remapping.py:544-555 with torch's CPU operators"""
-    c = torch.from_numpy(cosn)[..., None]
-    images_cos = c.clamp(-1.0, 0.0)
-    arccos = ((torch.arccos(images_cos) - torch.pi / 2) / (torch.pi / 2)).clamp(0.0, 1.0)
-    dy, dx = torch.gradient(arccos, dim=[1, 2])
-    grad = torch.sqrt(dy.square() + dx.square())
-    alpha = (grad > math.radians(10) / (math.pi / 2)).float()
-    k = 2 * r + 1
-    if k > 1:
-        alpha = torch.nn.functional.max_pool2d(alpha.permute(0, 3, 1, 2), k, 1, k // 2).permute(0, 2, 3, 1)
-    if cam_nz is not None:
-        images_cos = torch.from_numpy(cam_nz)[..., None].clamp(0.0, 1.0)
-    return torch.cat([images_cos, alpha], -1).numpy(), arccos[..., 0].numpy()
 
 
 @pytest.mark.parametrize("r,ortho", [(0, False), (1, False), (2, True)])
@@ -74,15 +46,6 @@ def test_dilation_against_max_pool2d():
         assert np.array_equal(R.dilate(a, r), want)
 
 
-def _hand_points(Hi, Wi):
-    """NDC points: exact pixel centres, exact halves between them, +-(1 - 2^-20), the outer half-pixel rim on all four sides"""
-    e = 1 - 2.0 ** -20
-    xs = [(2 * i + 1) / Wi - 1 for i in range(Wi)] + [2 * i / Wi - 1 for i in range(1, Wi)] + [-e, e, -1 + 0.5 / Wi, 1 - 0.5 / Wi, -1 + 0.25 / Wi, 1 - 0.75 / Wi, 0.0]
-    ys = [(2 * i + 1) / Hi - 1 for i in range(Hi)] + [2 * i / Hi - 1 for i in range(1, Hi)] + [-e, e, -1 + 0.5 / Hi, 1 - 0.5 / Hi, -1 + 0.25 / Hi, 1 - 0.75 / Hi, 0.0]
-    gx, gy = np.meshgrid(np.array(xs, np.float32), np.array(ys, np.float32))
-    return gx.reshape(-1), gy.reshape(-1)
-
-
 @pytest.mark.parametrize("Hi,Wi", [(5, 7), (1, 1), (1, 7), (4, 2)])
 def test_reflection_sampling_restatement_against_grid_sample(Hi, Wi):
     img = np.random.default_rng(Hi * 10 + Wi).uniform(0, 1, (4, Hi, Wi)).astype(np.float32)
@@ -92,32 +55,6 @@ def test_reflection_sampling_restatement_against_grid_sample(Hi, Wi):
         want = torch.nn.functional.grid_sample(torch.from_numpy(img)[None], grid, mode="bilinear", padding_mode=mode, align_corners=False)[0, :, :, 0].numpy()
         got = fn(img, gx, gy)
         assert np.abs(got.astype(np.float64) - want).max() <= 4 * R.U * img.max(), mode
-
-
-def _torch_project(case, use_alpha):
-    """mesh_remapping.py:557-594 with torch's CPU operators on the arrays of a synthetic case (matrices given instead of cameras)"""
-    t = {k: torch.from_numpy(v) for k, v in case.items()}
-    v_rgb, vis = t["v_rgb"], t["visible"].bool()
-    acc, wacc = torch.zeros_like(v_rgb), torch.zeros_like(v_rgb[..., [0]])
-    for b in range(vis.shape[0]):
-        v = t["v_pos"][vis[b]]
-        rgb_vis = v_rgb[vis[b]].clone()
-        w_vis = torch.zeros_like(rgb_vis[..., [0]])
-        homo = torch.cat([v, torch.ones_like(v[..., [0]])], -1) @ t["xform"][b].T
-        clip = homo @ t["proj"][b].T
-        ndc = clip[..., :2] / clip[..., [3]]
-        ok = torch.logical_and(ndc > -1, ndc < 1).prod(-1).bool()
-        g = ndc[ok][None, :, None]
-        rgba = torch.nn.functional.grid_sample(t["images"][b][None], g, padding_mode="reflection", mode="bilinear", align_corners=False)[0, :, :, 0].T
-        cw = torch.nn.functional.grid_sample(t["wmap"][b][None].permute(0, 3, 1, 2), g, padding_mode="zeros", mode="bilinear", align_corners=False)[0, :, :, 0].T
-        rgb, a = rgba[:, :3], rgba[:, 3:]
-        if not use_alpha:
-            a = torch.ones_like(a)
-        rgb_vis[ok] = rgb * a + rgb_vis[ok] * (1 - a)
-        w_vis[ok] = t["weights"][b] * cw[:, :1].square().square() * (1 - cw[:, 1:])
-        acc[vis[b]] = acc[vis[b]] + w_vis * rgb_vis
-        wacc[vis[b]] = wacc[vis[b]] + w_vis
-    return acc.numpy(), wacc.numpy()
 
 
 @pytest.mark.parametrize("use_alpha", [True, False])
@@ -152,12 +89,6 @@ def test_epilogue_restatement_has_vertices_on_both_sides_of_every_branch():
         assert np.array_equal(mask.astype(bool), (t_w[:, 0] <= 0.5).numpy())
         for thr in (0.05, 0.2, 0.5):
             assert 0 < (w > thr).mean() < 1
-
-
-def _grid_mesh(n):
-    idx = np.arange(n * n).reshape(n, n)
-    a, b, c, d = idx[:-1, :-1].ravel(), idx[:-1, 1:].ravel(), idx[1:, :-1].ravel(), idx[1:, 1:].ravel()
-    return np.concatenate([np.stack([a, b, c], -1), np.stack([b, d, c], -1)]).astype(np.int32)
 
 
 def test_csr_builder_against_a_dense_adjacency():
@@ -314,30 +245,6 @@ def test_ply_round_trip_with_vertex_colours(tmp_path):
     assert meshes.load_mesh(path, vertex_colors=True)[4] is None
     meshes.save_ply(path, v, rc)
     assert np.array_equal(meshes.load_ply(path, faces_required=False, vertex_colors=True)[3], rc)
-
-
-# ---- the reference's own arrays (tests/golden/g20_vertex_bake.npz, made by tests/golden/make_golden_vertex_bake.py)
-
-G20_TAGS = (("p", True), ("o", False))
-
-
-def g20():
-    return np.load(os.path.join(ROOT, "tests", "golden", "g20_vertex_bake.npz"))
-
-
-def g20_case(f, tag, perspective, mode):
-    """the fixture's arrays as a projection problem; the matrices come from the PRODUCT's camera functions (texturetools/camera.py)"""
-    from unitex_amd.texturetools import camera
-    c2ws = torch.from_numpy(f["c2ws_" + tag])
-    intr = torch.from_numpy(f["intr_" + tag]).expand(3, -1, -1)
-    xform = (c2ws if mode == "ref" else camera.c2w_to_w2c(c2ws)).numpy()
-    return dict(v_pos=f["verts"], visible=f["vis_" + tag], xform=xform, proj=camera.intr_to_proj(intr, perspective=perspective).numpy(), images=f["images"][:3],
-                wmap=f["wmap_" + tag], v_rgb=f["v_rgb"], weights=f["weights3"])
-
-
-def g20_edge(f, tag):
-    g64 = R.weight_maps(f["cos_ray_normal_" + tag], None, 0, np.float64)["grad"]
-    return np.abs(g64 - float(R.GRAD_THR32)) <= R.GRAD_EDGE
 
 
 @pytest.mark.parametrize("tag,perspective", G20_TAGS)

@@ -1,6 +1,6 @@
 """Vertex-colour bake on the GPU: utx_view_weight_maps, utx_vertex_project / _blend, utx_vertex_inpaint_step through the C ABI and the wrappers of
-texturetools/ops.py, and texturetools/remapping.py end to end, against the numpy restatement (tests/vertex_bake_ref.py) and torch's own CPU operators
-(the compositions of tests/test_vertex_bake_cpu.py).
+texturetools/ops.py, and texturetools/remapping.py end to end, against the numpy restatement (oracle/vertex_bake_ref.py) and torch's own CPU operators
+(the compositions of oracle/vertex_bake_ref.py).
 
 Bounds, counted (vertex_bake_ref), never fitted:
   cos channel        exact (a clamp)
@@ -19,8 +19,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import test_vertex_bake_cpu as VC
-from tests import vertex_bake_ref as R
+from oracle import vertex_bake_ref as R
 
 pytestmark = pytest.mark.gpu
 SENTINEL = 0x5A
@@ -61,9 +60,9 @@ def test_device_acosf_stays_within_the_recorded_ulps():
 @pytest.mark.parametrize("r,ortho", [(0, False), (1, False), (2, True)])
 def test_weight_maps_against_torch_and_the_restatement(r, ortho):
     B, H, W = 2, 33, 41
-    cosn = VC._cos_image(B, H, W, 3)
+    cosn = R._cos_image(B, H, W, 3)
     cam = np.random.default_rng(4).uniform(-0.2, 1.2, (B, H, W, 3)).astype(np.float32) if ortho else None
-    want, want_arccos = VC._torch_weight_maps(cosn, cam[..., 2] if ortho else None, r)
+    want, want_arccos = R._torch_weight_maps(cosn, cam[..., 2] if ortho else None, r)
     out, arccos = _ops().view_weight_maps(_cu(cosn)[..., None], _cu(cam) if ortho else None, r=r, want_arccos=True)
     out, arccos = out.cpu().numpy(), arccos.cpu().numpy()
     g64 = R.weight_maps(cosn, None, 0, np.float64)["grad"]
@@ -88,7 +87,7 @@ def test_dilation_exact_against_max_pool2d():
 @pytest.mark.parametrize("Hi,Wi", [(5, 7), (1, 1), (1, 7), (4, 2)])
 def test_reflection_sampling_on_hand_made_points(Hi, Wi):
     img = np.random.default_rng(Hi * 10 + Wi).uniform(0, 1, (1, 4, Hi, Wi)).astype(np.float32)
-    gx, gy = VC._hand_points(Hi, Wi)
+    gx, gy = R._hand_points(Hi, Wi)
     V = gx.shape[0]
     eye = np.eye(4, dtype=np.float32)[None]
     case = dict(v_pos=np.stack([gx, gy, np.zeros_like(gx)], -1), visible=np.ones((1, V), np.uint8), xform=eye, proj=eye, images=img,
@@ -123,7 +122,7 @@ def test_launch_edges_between_sentinels(V, B):
         assert np.isnan(a[0]).all() and np.isnan(a[-1]).all() and np.isfinite(a[1:-1]).all()
     assert mk[0] == SENTINEL and mk[-1] == SENTINEL
     want_acc, want_w = R.vertex_project(**case)
-    t_acc, t_w = VC._torch_project(case, True)
+    t_acc, t_w = R._torch_project(case, True)
     e_acc, e_w = R.project_bound(**case)
     for wa, ww in ((want_acc, want_w), (t_acc, t_w)):
         assert (np.abs(acc[1:-1].astype(np.float64) - wa).max(1) <= 2 * e_acc).all() and (np.abs(wacc[1:-1].astype(np.float64) - ww[:, 0]) <= 2 * e_w).all()
@@ -138,7 +137,7 @@ def test_launch_edges_between_sentinels(V, B):
 def test_projection_and_every_epilogue_against_the_restatement(use_alpha):
     case = R.synthetic_case(1000, 6, 21)
     e_acc, e_w = R.project_bound(**case)
-    t_acc, t_w = VC._torch_project(case, use_alpha)
+    t_acc, t_w = R._torch_project(case, use_alpha)
     r_acc, r_w = R.vertex_project(use_alpha=use_alpha, **case)
     first = None
     for blending in (None, "soft", "hard"):
@@ -171,7 +170,7 @@ def _gpu_inpaint(rowptr, col, rgb, idx, max_iters=1000):
 
 
 def test_inpainting_masks_steps_and_colours_on_a_mesh():
-    faces = VC._grid_mesh(9)
+    faces = R._grid_mesh(9)
     V = 81
     A = R.adjacency_dense(faces, V)
     rowptr, col = _ops().vertex_adjacency(torch.from_numpy(faces).cuda(), V)
@@ -355,11 +354,11 @@ def _g20_mesh(f):
     return DeviceMesh(f["verts"], f["faces"], f["uvs"], "cuda:0").set_vertex_normals(f["v_nrm"])
 
 
-@pytest.mark.parametrize("tag,perspective", VC.G20_TAGS)
+@pytest.mark.parametrize("tag,perspective", R.G20_TAGS)
 def test_ops_against_g20(tag, perspective):
     """the kernels on the fixture's inputs: weight maps from the reference's cos_ray_normal, the projection from the reference's visibility and weight maps"""
-    f = VC.g20()
-    edge, cov = VC.g20_edge(f, tag), f["wmap_" + tag][..., 0] != 0
+    f = R.g20()
+    edge, cov = R.g20_edge(f, tag), f["wmap_" + tag][..., 0] != 0
     assert edge[cov].sum() <= 0.005 * cov.sum()
     out, arccos = _ops().view_weight_maps(_cu(f["cos_ray_normal_" + tag])[..., None], r=0, want_arccos=True)
     out = out.cpu().numpy()
@@ -373,7 +372,7 @@ def test_ops_against_g20(tag, perspective):
     assert (~keep).sum() <= 0.02 * f["vis_" + tag].any(0).sum()
     oc, bc, ic = (float(x) for x in f["conf"])
     for mode in ("w2c", "ref"):
-        case = VC.g20_case(f, tag, perspective, mode)
+        case = R.g20_case(f, tag, perspective, mode)
         e_acc, e_w = R.project_bound(**case)
         for ua in (1, 0):
             acc, w, bl, mk = _gpu_project(case, bool(ua), dict(overlay_confidence=oc, blending="soft", blending_confidence=bc, inpainting_confidence=ic))
@@ -385,7 +384,7 @@ def test_ops_against_g20(tag, perspective):
 
 
 @pytest.mark.parametrize("mode", ["w2c", "ref"])
-@pytest.mark.parametrize("tag,perspective", VC.G20_TAGS)
+@pytest.mark.parametrize("tag,perspective", R.G20_TAGS)
 def test_remapping_against_g20(tag, perspective, mode):
     """remapping.py end to end on the fixture's mesh and cameras: visibility equal to the reference's; the accumulators and every later stage within the
     counted bound plus what the rendered weight map's own distance from the reference's allows: cos_ray_normal carries G18's bound (20 u and the propagated
@@ -393,7 +392,7 @@ def test_remapping_against_g20(tag, perspective, mode):
     largest colour to the accumulator"""
     from unitex_amd.texturetools import remapping
     from unitex_amd.texturetools.renderer_inverse import NVDiffRendererInverse
-    f = VC.g20()
+    f = R.g20()
     mesh = _g20_mesh(f)
     r = NVDiffRendererInverse(device="cuda:0", pbr_mesh=mesh)
     c2ws, intr = torch.from_numpy(f["c2ws_" + tag]), torch.from_numpy(f["intr_" + tag])
@@ -408,7 +407,7 @@ def test_remapping_against_g20(tag, perspective, mode):
     d_cos = np.abs(wm[..., 0].astype(np.float64) - f["wmap_" + tag][..., 0]).reshape(3, -1).max(1)
     print("G20 %s: weight map cos channel, max |gpu - reference| per view %s" % (tag, d_cos))
     assert d_cos.max() <= 64 * R.U
-    case = VC.g20_case(f, tag, perspective, mode)
+    case = R.g20_case(f, tag, perspective, mode)
     e_acc, e_w = R.project_bound(**case)
     extra = float((np.abs(f["weights3"]) * 4 * d_cos).sum())
     cmax = max(float(f["images"][:3, :3].max()), float(f["v_rgb"].max()))
@@ -435,14 +434,14 @@ def test_remapping_against_g20(tag, perspective, mode):
 
 def test_default_weight_table_and_initial_map_kd_against_g20():
     from unitex_amd.texturetools import remapping
-    f = VC.g20()
+    f = R.g20()
     mesh = _g20_mesh(f)
     got = remapping.remapping_vertex_color(mesh, torch.from_numpy(f["c2ws_6"]), torch.from_numpy(f["intr_6"]), torch.from_numpy(f["images"]),
                                            torch.from_numpy(f["v_rgb"]), render_size=48, use_inpainting=False)
     d = np.abs(got.cpu().numpy().astype(np.float64) - f["final_6"])
     print("G20 six views, default weights: max |gpu - reference| %.3g" % d.max())
     assert d.max() <= 1e-5      # weights up to 2 on six views through the overlay's quotient (weights above 0.2) and the soft blending's (0.2): the bounds above, 25-fold
-    for tag, perspective in VC.G20_TAGS:
+    for tag, perspective in R.G20_TAGS:
         kd = remapping.initial_map_Kd_with_v_rgb(mesh, torch.from_numpy(f["final_%s_w2c" % tag]), texture_size=48, perspective=perspective).cpu().numpy()
         want = f["kd_" + tag]
         assert kd.shape == want.shape == (48, 48, 4) and np.array_equal(kd[..., 3], want[..., 3])

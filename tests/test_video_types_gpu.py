@@ -1,5 +1,5 @@
 """Geometry-buffer video types of VideoExporter.export_orbit_video on the GPU: utx_gbuffer_shade / utx_gbuffer_range / utx_camera_normals
-against the reference's own frames (fixture G13) and, at production size, against the numpy restatement of tests/test_video_types_cpu.py
+against the reference's own frames (fixture G13) and, at production size, against the numpy restatement of oracle/video_types_ref.py
 (which that module proves against the same fixture).  Bounds: see that module's docstring -- bit-exact for the position and depth arms,
 derived ulp bounds where torch's own norm / matmul order enters; against the restatement, which is written in the kernels' operation order
 with correctly rounded numpy operations, EVERY arm is bit-exact."""
@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import test_video_types_cpu as VC
+from oracle import video_types_ref as VC
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
