@@ -670,6 +670,33 @@ int utx_vertex_project_blend(utx_ctx* ctx, const float* v_pos, int V, const unsi
 int utx_vertex_inpaint_step(utx_ctx* ctx, const int* rowptr, const int* col, const int* idx, int n, const float* rgb_in, const unsigned char* mask_in,
                             float* rgb_out, unsigned char* mask_out, int* counter, utx_stream stream);
 
+/* Blended multi-view UV texture bake: project_uv_texture / remapping_uv_texture of the reference (texture/reprojection/mesh_remapping.py:430-505, :145-270) and
+ * uv_dilation (texture/reprojection/uv_dilation.py:33-50, :80-92).  All fp32, stream-ordered, row-major, no atomics on colour, no workspace.
+ * utx_uv_bake: one thread per texel of the atlas raster rast2d [Th][Tw][4], the views b = 0 .. B-1 in index order.  Per view: vis, uv, the coverage lookup cov and
+ *   uv_alpha = vis && cov exactly as utx_uv_project defines them (faces [F][3], face_mask uint8 [B][F], v_ndc [B][V][2], rast_view [B][R][R][4] = the views rasterised
+ *   at R, only .w is read); rgba = images [B][4][R][R] (planar) and (c, e) = wmap [B][R][R][2] (utx_view_weight_maps) sampled at uv as grid_sample(bilinear, zeros,
+ *   align_corners=False), or texel [0][0] of the view's six channels where cov fails; a = use_alpha ? uv_alpha : 1; w = weights[b] ((c c) (c c)) a (1 - e);
+ *   col = (a rgba + (1 - a) map_Kd) w with map_Kd [Th][Tw][4].  acc [Th][Tw][4] = sum of col, wacc [Th][Tw] = sum of w.
+ *   epilogue != 0: the same launch also writes blended [Th][Tw][4] -- acc / wacc where wacc > overlay_confidence; then, where wacc <= blending_confidence,
+ *   UTX_VB_BLEND_SOFT: (map_Kd (blending_confidence - wacc) + acc) / blending_confidence, UTX_VB_BLEND_HARD: map_Kd, UTX_VB_BLEND_NONE: nothing -- and
+ *   inpaint_mask [Th][Tw] uint8 = (wacc <= inpainting_confidence && rast2d.w > 0); acc may be null then.  epilogue == 0: blended and inpaint_mask are not used.
+ * utx_uv_dilation_step, mode UTX_UVD_STEP: one _uv_dilation_v2 step on col_in [H][W][C] (1 <= C <= 16) and mask_in uint8 [H][W] (1 = valid) into col_out / mask_out.
+ *   A tap reads as colour * mask (the premultiplication of uv_dilation.py:41, made on every read); taps outside the image count as zero and the divisor is 9
+ *   everywhere.  S = the nine colour taps summed row by row, M = the nine mask taps.  Where M / 9 != mask: col_out = (S / 9) / (M / 9) (an invalid texel with a
+ *   valid neighbour, and a valid texel with an invalid or out-of-image neighbour, which is averaged again); elsewhere col_out = col_in, so an invalid texel out of
+ *   reach keeps its own colour.  mask_out = M > 0.  *counter (device int32, zeroed here) receives the number of texels with mask_out = 0.
+ *   mode UTX_UVD_CLAMP: col_out = clamp(col_in, 0, 1) over the whole map (uv_dilation's last line); mask_in, mask_out and counter are not used and may be null.
+ * A zero-size problem (Th Tw = 0, H W = 0) returns 0 without a launch.  -2: a negative size; B, R, F or V <= 0; C outside 1..16; a null or misaligned operand (rast2d,
+ * map_Kd, acc, blended: 16 bytes, wmap: 8, every other array: its element); an unknown blending or mode; col_in == col_out or mask_in == mask_out; outputs untouched. */
+#define UTX_UVD_STEP 0
+#define UTX_UVD_CLAMP 1
+int utx_uv_bake(utx_ctx* ctx, const float* rast2d, const int* faces, int F, const unsigned char* face_mask, const float* v_ndc, int V, int B, int Th, int Tw,
+                const float* images, const float* wmap, const float* rast_view, int R, const float* map_Kd, const float* weights, int use_alpha, float* acc,
+                float* wacc, int epilogue, float overlay_confidence, int blending, float blending_confidence, float inpainting_confidence, float* blended,
+                unsigned char* inpaint_mask, utx_stream stream);
+int utx_uv_dilation_step(utx_ctx* ctx, const float* col_in, const unsigned char* mask_in, int H, int W, int C, int mode, float* col_out, unsigned char* mask_out,
+                         int* counter, utx_stream stream);
+
 /* fused per-(view, texel) gather + visibility of uv_to_pcd (renderer_inverse.py:277-298,316-325) */
 typedef struct utx_backproject_desc {
     const void* rast2d;                 /* [T][4] f32 UV-space raster */

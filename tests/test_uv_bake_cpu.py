@@ -1,0 +1,150 @@
+"""Blended UV texture bake (unitex_amd/texturetools/remapping_uv.py, utx_uv_bake / utx_uv_dilation_step), CPU side: the numpy restatement of
+tests/uv_bake_ref.py against the reference's own arrays (fixture G21) within the counted bounds, stage by stage; uv_dilation's restatement against the
+reference's step built from torch's avg_pool2d; every refusal and the signatures; the C ABI's -2 returns before any device call."""
+import inspect
+
+import numpy as np
+import pytest
+
+from tests import uv_bake_ref as R
+
+U = R.U
+
+
+@pytest.mark.parametrize("tag", ["p", "o", "6"])
+def test_restatement_against_g21_stage_by_stage(tag):
+    f = R.g21()
+    s = R.g21_inputs(tag)
+    conf = [float(x) for x in f["conf"]]
+    for ua in ((True, False) if tag != "6" else (True,)):
+        key = "_%s_a%d" % (tag, ua) if tag != "6" else "_6"
+        d = {}
+        acc, wacc = R.uv_bake(**s, use_alpha=ua, detail=d)
+        assert (d["uv_alpha"][..., 0] == f["uv_alpha_" + tag]).all()      # reading (b): the alpha of the accumulation is uv_alpha, an integer decision
+        e_acc, e_w = R.bake_bound(s["images"], s["wmap"], s["map_Kd"], s["weights"], ua, d)
+        da, dw = np.abs(acc.astype(np.float64) - f["acc" + key]), np.abs(wacc.astype(np.float64) - f["wacc" + key])
+        print("G21 %s use_alpha=%d: acc %.2f u (bound up to %.1f u), wacc %.2f u (%.1f u)" % (tag, ua, da.max() / U, e_acc.max() / U, dw.max() / U, e_w.max() / U))
+        assert (da <= e_acc).all() and (dw <= e_w).all()
+        if not ua:      # reading (c): a texel off a view's coverage carries texel [0, 0] of the view's six channels
+            off = ~d["cov"]
+            assert off.any()
+            for b in range(off.shape[0]):
+                assert (d["s"][b][off[b]] == R.six_channels(s["images"], s["wmap"])[b, 0, 0]).all()
+    if tag == "6":
+        return
+    d = {}
+    acc, wacc = R.uv_bake(**s, use_alpha=True, detail=d)
+    e_acc, e_w = R.bake_bound(s["images"], s["wmap"], s["map_Kd"], s["weights"], True, d)
+    cmax = 1.0
+    for blending in ("soft", "hard"):
+        _, blended, mask = R.epilogue(acc, wacc, s["map_Kd"], s["rast2d"], conf[0], blending, conf[1], conf[2])
+        e_b = R.epilogue_bound(f["acc_%s_a1" % tag], f["wacc_%s_a1" % tag], s["map_Kd"], e_acc, e_w, conf[0], blending, conf[1])
+        db = np.abs(blended[..., :3].astype(np.float64) - f["blended_%s_%s" % (blending, tag)])
+        assert (db <= e_b[..., :3]).all(), "%s: %.2f u" % (blending, db.max() / U)
+        assert (mask == f["inpaint_mask_" + tag]).all()
+        if blending == "hard":
+            continue
+        trace = []
+        filled, steps = R.uv_dilation(blended[..., :3], 1 - mask, trace=trace)
+        assert steps == int(f["steps_soft_" + tag]) and steps >= 2
+        e_in = R.dilation_bound(float(e_b[..., :3].max()), steps, cmax)
+        di = np.abs(filled.astype(np.float64) - f["inpainted_soft_" + tag])
+        print("G21 %s soft: blended %.2f u (bound up to %.1f u), inpainted %.2f u (%.1f u), %d steps" % (tag, db.max() / U, e_b[..., :3].max() / U, di.max() / U, e_in / U, steps))
+        assert di.max() <= e_in
+        assert (f["final_soft_" + tag][..., 3] == (s["rast2d"][..., 3] > 0)).all()      # the returned alpha is the atlas coverage
+        cov = s["rast2d"][..., 3] > 0
+        assert np.abs(f["final_soft_" + tag][..., :3][cov] - f["inpainted_soft_" + tag][cov]).max() == 0.0      # the outpainting leaves the charts alone
+    assert str(f["map_kd_none"]).startswith("RuntimeError")      # reading (a)
+
+
+def test_dilation_restatement_is_the_reference_step_bit_for_bit():
+    rng = np.random.default_rng(0)
+    corner = np.zeros((9, 9), bool)
+    corner[0, 0] = True
+    for H, W, C, valid in [(9, 9, 3, corner), (5, 7, 4, rng.uniform(0, 1, (5, 7)) < 0.3), (1, 6, 1, rng.uniform(0, 1, (1, 6)) < 0.4), (6, 1, 16, rng.uniform(0, 1, (6, 1)) < 0.4),
+                           (12, 11, 3, np.ones((12, 11), bool)), (33, 29, 3, rng.uniform(0, 1, (33, 29)) < 0.03)]:
+        valid = valid.copy()
+        valid[0, 0] = True
+        col = rng.uniform(-0.5, 1.5, (H, W, C)).astype(np.float32)
+        a, sa = R.uv_dilation(col, valid)
+        b, sb = R.torch_reference_dilation(col, valid)
+        assert sa == sb and a.tobytes() == b.tobytes(), (H, W, C, sa, sb)
+        assert a.min() >= 0.0 and a.max() <= 1.0
+    assert R.uv_dilation(col, corner[:1, :1].repeat(33, 0).repeat(29, 1))[1] == 0
+    # the one departure: no valid texel -- the reference would not end; here one step, and the input comes back clamped
+    col = rng.uniform(-0.5, 1.5, (4, 4, 3)).astype(np.float32)
+    out, steps = R.uv_dilation(col, np.zeros((4, 4)))
+    assert steps == 1 and out.tobytes() == R.clamp01(col).tobytes()
+    # max_iters
+    out, steps = R.uv_dilation(col.repeat(3, 0).repeat(3, 1)[:9, :9], corner, max_iters=3)
+    ref, n = R.torch_reference_dilation(col.repeat(3, 0).repeat(3, 1)[:9, :9], corner, max_iters=3)
+    assert steps == n == 3 and out.tobytes() == ref.tobytes()
+
+
+def test_signatures_and_every_refusal():
+    from unitex_amd.texturetools import remapping_uv as RU
+    sig = inspect.signature(RU.remapping_uv_texture)
+    assert list(sig.parameters) == ["mesh", "c2ws", "intrinsics", "images", "map_Kd", "weights", "use_alpha", "overlay_confidence", "use_blending", "blending_type",
+                                    "blending_confidence", "use_inpainting", "use_cv_inpainting", "inpainting_confidence", "use_outpainting", "use_cv_outpainting",
+                                    "render_size", "texture_size", "visualize", "perspective", "return_stages"]
+    dflt = {k: v.default for k, v in sig.parameters.items() if v.default is not inspect.Parameter.empty}
+    assert dflt == dict(map_Kd=None, weights=None, use_alpha=True, overlay_confidence=0.2, use_blending=True, blending_type="soft", blending_confidence=0.2,
+                        use_inpainting=True, use_cv_inpainting=True, inpainting_confidence=0.2, use_outpainting=True, use_cv_outpainting=False, render_size=512,
+                        texture_size=1024, visualize=False, perspective=True, return_stages=False)
+    sig = inspect.signature(RU.project_uv_texture)
+    assert list(sig.parameters) == ["mesh", "c2ws", "intrinsics", "images", "map_Kd", "weights", "use_alpha", "render_size", "texture_size", "visualize", "perspective"]
+    assert [sig.parameters[k].default for k in ("use_alpha", "render_size", "texture_size", "visualize", "perspective")] == [True, 512, 1024, False, True]
+    assert list(inspect.signature(RU.uv_dilation).parameters)[:3] == ["map_Kd", "map_mask", "max_iters"] and inspect.signature(RU.uv_dilation).parameters["max_iters"].default == -1
+    c2ws = np.tile(np.eye(4, dtype=np.float32), (3, 1, 1))
+    args = (None, c2ws, np.eye(3, dtype=np.float32), np.zeros((3, 4, 8, 8), np.float32))
+    with pytest.raises(NotImplementedError, match="visualize"):
+        RU.remapping_uv_texture(*args, visualize=True)
+    with pytest.raises(NotImplementedError, match="visualize"):
+        RU.project_uv_texture(*args, np.zeros((8, 8, 4), np.float32), [1.0] * 3, visualize=True)
+    with pytest.raises(NotImplementedError, match="use_cv_inpainting=False"):
+        RU.remapping_uv_texture(*args)      # the reference's default
+    with pytest.raises(NotImplementedError, match="use_cv_outpainting"):
+        RU.remapping_uv_texture(*args, use_cv_inpainting=False, use_cv_outpainting=True)
+    with pytest.raises(NotImplementedError, match="poisson"):
+        RU.remapping_uv_texture(*args, use_cv_inpainting=False, blending_type="poisson")
+    with pytest.raises(ValueError, match="size mismatch: length of weights should be 3 but 2"):
+        RU.remapping_uv_texture(*args, weights=[1.0, 1.0], use_cv_inpainting=False)
+    with pytest.raises(ValueError, match="value error: linear is not supported"):
+        RU.remapping_uv_texture(*args, blending_type="linear", use_cv_inpainting=False)
+    with pytest.raises(TypeError):
+        RU.remapping_uv_texture(*args, use_cv_inpainting=False)      # mesh is neither a DeviceMesh nor a renderer
+    from unitex_amd.texturetools import remapping
+    assert "remapping_uv.py" in remapping.__doc__
+
+
+def test_c_abi_refuses_bad_arguments_before_any_device_call():
+    import ctypes as C
+    from unitex_amd import _lib
+    lib = _lib.load_library()
+    for name, nargs in (("utx_uv_bake", 27), ("utx_uv_dilation_step", 11)):
+        assert len(_lib.SYMBOLS[name][1]) == nargs
+    buf = (C.c_char * 4096)()
+    base = (C.addressof(buf) + 255) & ~255
+    p = lambda off=0: C.c_void_p(base + off)
+
+    def bake(**k):
+        a = dict(rast2d=p(), faces=p(), F=2, face_mask=p(), v_ndc=p(), V=3, B=2, Th=4, Tw=4, images=p(), wmap=p(), rast_view=p(), R=4, map_Kd=p(), weights=p(), use_alpha=1,
+                 acc=p(), wacc=p(), epilogue=1, oc=0.2, blending=1, bc=0.2, ic=0.2, blended=p(), inpaint=p())
+        a.update(k)
+        return lib.utx_uv_bake(None, *a.values(), None)
+    for bad in (dict(rast2d=None), dict(faces=None), dict(face_mask=None), dict(v_ndc=None), dict(images=None), dict(wmap=None), dict(rast_view=None), dict(map_Kd=None),
+                dict(weights=None), dict(wacc=None), dict(blended=None), dict(inpaint=None), dict(acc=None, epilogue=0), dict(rast2d=p(4)), dict(map_Kd=p(8)), dict(acc=p(4)),
+                dict(blended=p(4)), dict(wmap=p(4)), dict(images=p(2)), dict(weights=p(1)), dict(B=0), dict(B=-1), dict(R=0), dict(F=0), dict(V=0), dict(Th=-1), dict(Tw=-1),
+                dict(blending=3), dict(blending=-1)):
+        assert bake(**bad) == -2, bad
+    assert bake(Th=0) == 0 and bake(Tw=0) == 0      # a zero-size problem: nothing to launch
+
+    def step(**k):
+        a = dict(col_in=p(), mask_in=p(1024), H=4, W=4, C=3, mode=0, col_out=p(2048), mask_out=p(3072), counter=p(3584))
+        a.update(k)
+        return lib.utx_uv_dilation_step(None, *a.values(), None)
+    for bad in (dict(col_in=None), dict(mask_in=None), dict(col_out=None), dict(mask_out=None), dict(counter=None), dict(C=0), dict(C=17), dict(H=-1), dict(W=-1), dict(mode=2),
+                dict(mode=-1), dict(col_out=p()), dict(mask_out=p(1024)), dict(col_in=p(2)), dict(col_out=p(2050)), dict(counter=p(3585)), dict(mode=1, col_out=p()),
+                dict(H=0, C=17)):
+        assert step(**bad) == -2, bad
+    assert step(H=0) == 0 and step(W=0) == 0

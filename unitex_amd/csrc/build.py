@@ -45,6 +45,7 @@ GEOM = [
     ("bvh.hip", ["-ffp-contract=off"] + NO_PK),
     ("backproject.hip", ["-ffp-contract=off"] + NO_PK),
     ("vertex_bake.hip", ["-ffp-contract=off"] + NO_PK),      # vertex-colour bake: weight maps, per-vertex projection, graph inpainting
+    ("uv_bake.hip", ["-ffp-contract=off"] + NO_PK),      # blended UV texture bake: per-texel accumulation over the views, texel-space dilation
     ("texture_post.hip", ["-ffp-contract=off"] + NO_PK),
     ("knn.hip", ["-ffp-contract=off"]),
     ("sampling.hip", ["-ffp-contract=off"]),

@@ -483,6 +483,33 @@ int utx_vertex_inpaint_step(utx_ctx* ctx, const int* rowptr, const int* col, con
         return fail(ctx, -2, me);
     UTX_CALL(ctx, me, utx_launch_vertex_inpaint_step(rowptr, col, idx, n, rgb_in, mask_in, rgb_out, mask_out, counter, (hipStream_t)stream));
 }
+// ---- blended UV texture bake (uv_bake.hip) ----
+int utx_uv_bake(utx_ctx* ctx, const float* rast2d, const int* faces, int F, const unsigned char* face_mask, const float* v_ndc, int V, int B, int Th, int Tw,
+                const float* images, const float* wmap, const float* rast_view, int R, const float* map_Kd, const float* weights, int use_alpha, float* acc,
+                float* wacc, int epilogue, float overlay_confidence, int blending, float blending_confidence, float inpainting_confidence, float* blended,
+                unsigned char* inpaint_mask, utx_stream stream) {
+    const char* const me = "utx_uv_bake";
+    if (Th < 0 || Tw < 0 || B <= 0 || R <= 0 || F <= 0 || V <= 0) return fail(ctx, -2, me);
+    if (epilogue && (blending < UTX_VB_BLEND_NONE || blending > UTX_VB_BLEND_HARD)) return fail(ctx, -2, me);
+    if ((long)Th * Tw == 0) return 0;
+    if (!rast2d || !faces || !face_mask || !v_ndc || !images || !wmap || !rast_view || !map_Kd || !weights || !wacc) return fail(ctx, -2, me);
+    if ((!epilogue && !acc) || (epilogue && (!blended || !inpaint_mask))) return fail(ctx, -2, me);
+    if (misaligned(rast2d, 15) || misaligned(map_Kd, 15) || misaligned(acc, 15) || (epilogue && misaligned(blended, 15)) || misaligned(wmap, 7) ||
+        misaligned(faces, 3) || misaligned(v_ndc, 3) || misaligned(images, 3) || misaligned(rast_view, 3) || misaligned(weights, 3) || misaligned(wacc, 3))
+        return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_uv_bake(rast2d, faces, F, face_mask, v_ndc, V, B, Th, Tw, images, wmap, rast_view, R, map_Kd, weights, use_alpha, acc, wacc,
+                                         overlay_confidence, blending, blending_confidence, inpainting_confidence, epilogue ? blended : nullptr, inpaint_mask,
+                                         (hipStream_t)stream));
+}
+int utx_uv_dilation_step(utx_ctx* ctx, const float* col_in, const unsigned char* mask_in, int H, int W, int C, int mode, float* col_out, unsigned char* mask_out,
+                         int* counter, utx_stream stream) {
+    const char* const me = "utx_uv_dilation_step";
+    if (H < 0 || W < 0 || C < 1 || C > 16 || (mode != UTX_UVD_STEP && mode != UTX_UVD_CLAMP)) return fail(ctx, -2, me);
+    if ((long)H * W == 0) return 0;
+    if (!col_in || !col_out || col_in == col_out || misaligned(col_in, 3) || misaligned(col_out, 3)) return fail(ctx, -2, me);
+    if (mode == UTX_UVD_STEP && (!mask_in || !mask_out || !counter || mask_in == mask_out || misaligned(counter, 3))) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_uv_dilation_step(col_in, mask_in, H, W, C, mode, col_out, mask_out, counter, (hipStream_t)stream));
+}
 int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws, int n_views, float* out, utx_stream stream) {
     if (!nrm || !c2ws || !out) return fail(ctx, -2, "utx_camera_normals");
     UTX_CALL(ctx, "utx_camera_normals", utx_launch_camera_normals(nrm, V, c2ws, n_views, out, (hipStream_t)stream));

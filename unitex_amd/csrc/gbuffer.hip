@@ -462,22 +462,14 @@ __global__ __launch_bounds__(256) void uv_project_kernel(UvProjectArgs a) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= a.total) return;
     const long b = i / a.npix;
-    const float4 r = a.rast2d[i - b * a.npix];
-    const int id = (int)r.w - 1;
-    const bool vis = id >= 0 && id < a.F && a.face_mask[b * a.F + id] != 0;
-    float g[2] = {-1.0f, -1.0f};
-    if (vis) {
-        const float u = r.x, v = r.y, w = sd_bary_w(u, v);
-        const float* n = a.v_ndc + 2 * a.V * b;
-        sd_interp<2>(n + 2 * (long)a.tri[3 * id + 0], n + 2 * (long)a.tri[3 * id + 1], n + 2 * (long)a.tri[3 * id + 2], u, v, w, g);
-    }
+    const SdUvView s = sd_uv_view(a.rast2d[i - b * a.npix], a.tri, a.F, a.face_mask + b * a.F, a.v_ndc + 2 * a.V * b);
+    const float* g = s.g;
     a.uv[2 * i] = g[0]; a.uv[2 * i + 1] = g[1];
-    bool alpha = vis;
+    bool alpha = s.vis;
     if (a.map_attr) {
         const long msize = (long)a.Hm * a.Wm;
         const float* m = a.map + (a.Bm > 1 ? b : 0) * msize * a.C;
-        const long o = grid_nearest(a.Hm, a.Wm, g[0], g[1]);
-        const bool cov = o >= 0 && a.rast_map[4 * (b * msize + o) + 3] > 0.0f;
+        const bool cov = sd_view_coverage(a.rast_map + 4 * b * msize, a.Hm, a.Wm, g[0], g[1]);
         alpha = alpha && cov;
         float* out = a.map_attr + i * a.C;
         if (a.bg_kind != SGB_BG_NONE && !alpha) {

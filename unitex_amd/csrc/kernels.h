@@ -186,6 +186,13 @@ int utx_launch_vertex_project(const float* v_pos, int V, const unsigned char* vi
                               int blending, float blending_conf, float inpainting_conf, float* blended, unsigned char* inpaint, hipStream_t stream);
 int utx_launch_vertex_inpaint_step(const int* rowptr, const int* col, const int* idx, int n, const float* rgb_in, const unsigned char* mask_in, float* rgb_out,
                                    unsigned char* mask_out, int* counter, hipStream_t stream);
+// uv_bake.hip
+int utx_launch_uv_bake(const float* rast2d, const int* faces, int F, const unsigned char* face_mask, const float* v_ndc, int V, int B, int Th, int Tw,
+                       const float* images, const float* wmap, const float* rast_view, int R, const float* map_Kd, const float* weights, int use_alpha,
+                       float* acc, float* wacc, float overlay_conf, int blending, float blending_conf, float inpainting_conf, float* blended,
+                       unsigned char* inpaint, hipStream_t stream);
+int utx_launch_uv_dilation_step(const float* col_in, const unsigned char* mask_in, int H, int W, int C, int mode, float* col_out, unsigned char* mask_out,
+                                int* counter, hipStream_t stream);
 int utx_launch_backproject(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_backproject_vis(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_composite_winner(const void* vis, int n_views, const int* order, int n_order, long T, void* winner, hipStream_t stream);

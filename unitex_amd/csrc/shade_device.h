@@ -138,5 +138,27 @@ __device__ __forceinline__ T sample_view(const T* img, long stride, int H, int W
     }
 }
 
+// ---- one texel of the atlas raster as one view sees it (utx_uv_project and utx_uv_bake; render/nvdiffrast/renderer_base.py:513-547 of the reference)
+// r: the texel's record of the atlas raster (u, v, z/w, triangle id + 1); face_mask, v_ndc: the view's rows of [B][F] and [B][V][2].
+//   vis   the texel lies on a face the view sees
+//   g     vis ? the view's NDC of the texel's surface point : (-1, -1)
+struct SdUvView { bool vis; float g[2]; };
+__device__ __forceinline__ SdUvView sd_uv_view(float4 r, const int* tri, long F, const unsigned char* face_mask, const float* v_ndc) {
+    SdUvView o;
+    const int id = (int)r.w - 1;
+    o.vis = id >= 0 && id < F && face_mask[id] != 0;
+    o.g[0] = -1.0f; o.g[1] = -1.0f;
+    if (o.vis) {
+        const float u = r.x, v = r.y, w = sd_bary_w(u, v);
+        sd_interp<2>(v_ndc + 2 * (long)tri[3 * id + 0], v_ndc + 2 * (long)tri[3 * id + 1], v_ndc + 2 * (long)tri[3 * id + 2], u, v, w, o.g);
+    }
+    return o;
+}
+// grid_sample(nearest, zero padding) of the view's coverage rast_map.w > 0 at (gx, gy); rast_map: the view's [Hm][Wm][4] raster, only .w is read
+__device__ __forceinline__ bool sd_view_coverage(const float* rast_map, int Hm, int Wm, float gx, float gy) {
+    const long o = grid_nearest(Hm, Wm, gx, gy);
+    return o >= 0 && rast_map[4 * o + 3] > 0.0f;
+}
+
 // ---- float frame -> uint8: clamp(0, 1) * 255, truncated (astype(uint8))
 __device__ __forceinline__ unsigned char sd_to_u8(float c) { return (unsigned char)(fminf(fmaxf(c, 0.f), 1.f) * 255.0f); }

@@ -1064,3 +1064,80 @@ def vertex_inpaint(rowptr, col, v_rgb, v_idx, max_iters=1000, trace=None):
             break
         count = now
     return cur, steps
+
+
+# ---- the blended UV texture bake (uv_bake.hip): project_uv_texture / remapping_uv_texture / uv_dilation of the reference
+
+def uv_bake(rast2d, faces, face_mask, v_ndc, images, wmap, rast_view, map_Kd, weights, use_alpha=True, epilogue=None):
+    """utx_uv_bake: rast2d [Th,Tw,4] (the atlas raster), faces [F,3] int32, face_mask uint8 [B,F] (visible_faces_*), v_ndc [B,V,2], images [B,4,R,R] rgba
+    (planar, as given), wmap [B,R,R,2] (view_weight_maps), rast_view [B,R,R,4] (the views rasterised at R), map_Kd [Th,Tw,4], weights [B] ->
+    (acc [Th,Tw,4], wacc [Th,Tw,1]): project_uv_texture's sum over the views (:479-505) in index order, in one launch, without the [B,R,R,6] map, the
+    [B,Th,Tw,6] map_attr and the [B,Th,Tw,2] uv of the composition uv_project + elementwise steps, to which it is bit-identical.  epilogue =
+    dict(overlay_confidence, blending (None | 'soft' | 'hard'), blending_confidence, inpainting_confidence): the same launch also applies
+    remapping_uv_texture's overlay and blending (:205-217) and returns (acc, wacc, blended [Th,Tw,4], inpaint_mask uint8 [Th,Tw] = wacc <=
+    inpainting_confidence on the texels the atlas raster covers)."""
+    assert rast2d.dim() == 3 and rast2d.shape[2] == 4 and faces.dim() == 2 and faces.shape[1] == 3, "rast2d is [Th, Tw, 4], faces [F, 3]"
+    Th, Tw = rast2d.shape[:2]
+    F = faces.shape[0]
+    if face_mask.dim() != 2 or face_mask.shape[1] != F or face_mask.shape[0] < 1:
+        raise ValueError("uv_bake: face_mask is %s, expected [B >= 1, F = %d]" % (tuple(face_mask.shape), F))
+    B = face_mask.shape[0]
+    if v_ndc.dim() != 3 or v_ndc.shape[0] != B or v_ndc.shape[2] != 2 or v_ndc.shape[1] < 1:
+        raise ValueError("uv_bake: v_ndc is %s, expected [B = %d, V, 2]" % (tuple(v_ndc.shape), B))
+    V = v_ndc.shape[1]
+    if images.dim() != 4 or images.shape[0] != B or images.shape[1] != 4 or images.shape[2] != images.shape[3] or images.shape[2] < 1:
+        raise ValueError("uv_bake: images is %s, expected [B = %d, 4, R, R]" % (tuple(images.shape), B))
+    R = images.shape[2]
+    if tuple(wmap.shape) != (B, R, R, 2) or tuple(rast_view.shape) != (B, R, R, 4):
+        raise ValueError("uv_bake: wmap is %s and rast_view %s, expected %s and %s" % (tuple(wmap.shape), tuple(rast_view.shape), (B, R, R, 2), (B, R, R, 4)))
+    if tuple(map_Kd.shape) != (Th, Tw, 4) or tuple(weights.shape) != (B,):
+        raise ValueError("uv_bake: map_Kd is %s and weights %s, expected %s and %s" % (tuple(map_Kd.shape), tuple(weights.shape), (Th, Tw, 4), (B,)))
+    if epilogue is not None and epilogue["blending"] not in VERTEX_BLENDING:
+        raise ValueError("uv_bake: blending %r (None, 'soft' or 'hard')" % (epilogue["blending"],))
+    dev = rast2d.device
+    ctx = get_ctx(dev.index)
+    acc = torch.empty(Th, Tw, 4, dtype=F32, device=dev)
+    wacc = torch.empty(Th, Tw, 1, dtype=F32, device=dev)
+    blended = torch.empty(Th, Tw, 4, dtype=F32, device=dev) if epilogue is not None else None
+    mask = torch.empty(Th, Tw, dtype=U8, device=dev) if epilogue is not None else None
+    e = epilogue or dict(overlay_confidence=0.0, blending=None, blending_confidence=0.0, inpainting_confidence=0.0)
+    ctx.check(ctx.lib.utx_uv_bake(ctx.handle, ptr(_f(rast2d)), ptr(_i(faces)), F, ptr(_u8(face_mask)), ptr(_f(v_ndc)), V, B, Th, Tw, ptr(_f(images)), ptr(_f(wmap)),
+                                  ptr(_f(rast_view)), R, ptr(_f(map_Kd)), ptr(_f(weights)), int(bool(use_alpha)), ptr(acc), ptr(wacc), int(epilogue is not None),
+                                  float(e["overlay_confidence"]), VERTEX_BLENDING[e["blending"]], float(e["blending_confidence"]),
+                                  float(e["inpainting_confidence"]), ptr(blended), ptr(mask), ctx.stream()))
+    return (acc, wacc) if epilogue is None else (acc, wacc, blended, mask)
+
+
+def uv_dilation(map_Kd, valid, max_iters=-1, trace=None):
+    """uv_dilation (uv_dilation.py:33-50) on one image: map_Kd [H,W,C] (1 <= C <= 16), valid uint8 [H,W] (1 = keep, 0 = fill) -> (filled [H,W,C], number of
+    steps).  One utx_uv_dilation_step launch per step, colour and mask double-buffered; after each step the host reads the 4-byte count of texels that are
+    still invalid and stops at 0 (the reference's `prod() > 0`), at max_iters > 0, or when a step did not lower the count -- the one departure: with no
+    valid texel in reach the reference loops forever, here the texels out of reach keep their colour.  A last launch clamps the whole map to [0, 1],
+    also after zero steps.  trace (a list): receives each step's (colour, mask) clones."""
+    assert map_Kd.dim() == 3 and tuple(valid.shape) == tuple(map_Kd.shape[:2]), "map_Kd is [H, W, C], valid [H, W]"
+    H, W, Cc = map_Kd.shape
+    if not 1 <= Cc <= 16:
+        raise ValueError("uv_dilation: %d channels, 1 to 16 are built" % Cc)
+    ctx = get_ctx(map_Kd.device.index)
+    cur, mask = _f(map_Kd), _u8(valid)
+    out = torch.empty_like(cur)
+    steps = 0
+    if H * W == 0:
+        return out, steps
+    bufs = [torch.empty_like(cur), torch.empty_like(cur)]
+    masks = [torch.empty_like(mask), torch.empty_like(mask)]
+    counter = torch.zeros(1, dtype=I32, device=cur.device)
+    count = H * W - int(torch.count_nonzero(mask).item())
+    while count > 0 and not (max_iters > 0 and steps >= max_iters):
+        nxt, mask_nxt = bufs[steps & 1], masks[steps & 1]
+        ctx.check(ctx.lib.utx_uv_dilation_step(ctx.handle, ptr(cur), ptr(mask), H, W, Cc, 0, ptr(nxt), ptr(mask_nxt), ptr(counter), ctx.stream()))
+        cur, mask = nxt, mask_nxt
+        steps += 1
+        if trace is not None:
+            trace.append((cur.clone(), mask.clone()))
+        now = int(counter.item())
+        if now >= count:
+            break
+        count = now
+    ctx.check(ctx.lib.utx_uv_dilation_step(ctx.handle, ptr(cur), None, H, W, Cc, 1, ptr(out), None, None, ctx.stream()))
+    return out, steps

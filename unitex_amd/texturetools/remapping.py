@@ -15,7 +15,7 @@ which is what the reference executes.  Both run the same kernel; both are pinned
 False the fixture maker wraps the reference's apply_transform to invert each matrix with the reference's own c2w_to_w2c).
 
 Refused, never dropped: visualize=True everywhere (it writes cv2 debug images), use_pymeshlab=True and use_cv_outpainting=True (NotImplementedError).
-remapping_uv_texture is not built."""
+remapping_uv_texture, project_uv_texture and uv_dilation live in remapping_uv.py."""
 import numpy as np
 import torch
 
