@@ -633,6 +633,28 @@ int utx_visible_faces_raster(utx_ctx* ctx, const float* rast, int B, int H, int 
 int utx_erode_faces(utx_ctx* ctx, unsigned char* mask, const int* faces, int B, int F, int V, int depth, int* vstamp, utx_stream stream);
 int utx_visible_vertices(utx_ctx* ctx, const unsigned char* mask, const int* faces, int B, int F, int V, unsigned char* out, utx_stream stream);
 
+/* Nearest surface point: what the reference takes from cuBVH.unsigned_distance(points, return_uvw=True) [3p] (geometry/sampling/spatial_sampling.py:36,90).
+ * points [N][3] f32 -> dist [N] f32 (the distance itself, sqrtf(d2)), face [N] i32, uvw [N][3] f32, closest [N][3] f32; face, uvw, closest and visited may be null.
+ * Per triangle: tri_closest(p, v0, v1, v2) -> (d2, u, v, w), the Voronoi-region form of Ericson, Real-Time Collision Detection, 5.1.5, in fp32 with fixed
+ *   summation order (csrc/bvh_device.h; tests/closest_point_ref.py repeats it bit for bit): (u, v, w) weigh (v0, v1, v2), closest = (u v0 + v v1) + w v2,
+ *   d2 = |p - closest|^2 summed (x^2 + y^2) + z^2; every weight is >= 0; a quotient with a denominator not > 0 is 0 (a zero-length edge is its end point);
+ *   a zero-area face (interior denominator va + vb + vc not > 0) gives the nearest point of its three edge segments AB, AC, BC, the first on a tie.
+ * Per query: the face with the smallest d2, ties to the smallest face id -- independent of the order in which the triangles are met.  A subtree is skipped
+ *   only if its box's squared distance sum(max(0, lo - p, p - hi)^2) exceeds best * 1.00001f, so a tying triangle is still tested while the two
+ *   roundings differ by less than that relative margin: for a query within a few ulp * scale of the surface the computed d2 can fall to 0 and a tying face whose box
+ *   does not hold p may be skipped -- d2 is unaffected, the face named is then the smallest id among the tying faces met.  A query with a non-finite
+ *   coordinate gives face -1, dist +inf, zero uvw and closest.  Coordinates are assumed small enough that their squares and the products of two squares stay
+ *   finite in fp32 (|x| below about 1e9).
+ * One launch, one thread per query in the caller's order, on the packed tree without a stack (a greedy descent into the nearer child seeds `best`, then the
+ *   escape-link walk of utx_visible_faces_rays): no workspace, no atomics but the optional counter, no host wait, any tree depth.
+ * flags: UTX_CP_EXHAUSTIVE loops over all F triangles instead (same per-triangle function and tie rule: the test twin and the cost baseline);
+ *   UTX_CP_NO_SEED walks without the greedy descent (same result; for the node count).  visited: device counter the number of visited nodes is ADDED to.
+ * N == 0 returns 0 at once; -2 for a null tree, points or dist, N < 0, N >= 2^31, unknown flags. */
+#define UTX_CP_EXHAUSTIVE 1
+#define UTX_CP_NO_SEED 2
+int utx_bvh_closest_point(utx_ctx* ctx, utx_bvh* bvh, const float* points, long N, float* dist, int* face, float* uvw, float* closest,
+                          unsigned long long* visited, int flags, utx_stream stream);
+
 /* Vertex-colour bake from views: project_vertex_color / remapping_vertex_color / inpainting_vertex_color of the reference
  * (texture/reprojection/mesh_remapping.py:508-627, :273-350).  All fp32, stream-ordered, row-major.
  * utx_view_weight_maps: cos_ray_normal [B][H][W] (utx_screen_gbuffer) -> out [B][H][W][2] = (cos term, edge alpha).  cos term: clamp(cos, -1, 0), or with
@@ -795,6 +817,31 @@ int utx_sample_edges_equal_steps(utx_ctx* ctx, const float* verts, const int* ed
  * absolute values), w = 1 - (u + v); point = (v0 * u + v1 * v) + v2 * w.  -> samples [N][3] f32, face_index [N] i32 (optional), uvw [N][3] f32 (optional). */
 int utx_sample_surface(utx_ctx* ctx, const float* verts, const int* faces, const float* cum, int F, long N, unsigned long long seed, float* samples,
                        int* face_index, float* uvw, utx_stream stream);
+/* The random offsets of sample_spatial / sample_near_surface (spatial_sampling.py:11-37, :40-91) on the same defined stream with another stream id: counter
+ * (i, stream_id, 0, 0), stream_id 1 for sample_spatial's points, 2 for the near-surface deltas (0 is utx_sample_surface's, refused here); words 0..2 give r in [0, 1)^3.
+ * base == null: out [N][3] = r (the unit cube, as the reference's torch.rand: whatever the mesh's box is).  Otherwise base [N][3] are surface samples with
+ * face_index [N] i32 and uvw [N][3], vnormal [V][3] the vertex normals: n = (vn[f0] u + vn[f1] v) + vn[f2] w, not renormalised, and
+ * out = base + (threshold * (r * 2 - 1)) * n per component; a face_index outside [0, F) leaves the sample where it is.  uniforms [N][3] (optional) replaces the
+ * Philox words (tests feed recorded draws).  One launch.  N == 0 returns 0; -2 for N < 0, N >= 2^31, stream_id < 1, a null out or, with base, a null operand or F <= 0. */
+int utx_sample_offsets(utx_ctx* ctx, const float* base, const int* faces, int F, const int* face_index, const float* uvw, const float* vnormal, const float* uniforms,
+                       long N, unsigned long long seed, int stream_id, float threshold, float* out, utx_stream stream);
+/* PBRMesh.__call__ (mesh/structure_v2.py:105-135): n_attr <= UTX_SAMPLE_ATTRS_MAX attributes at N surface samples (face_index [N] i32, uvw [N][3]) in one launch.
+ * src_host / out_host: HOST arrays of n_attr device pointers; dims_host: HOST array [n_attr][4] = (kind, C, H, W); out k is [N][C].
+ *   UTX_ATTR_CONSTANT  src [C]: copied.
+ *   UTX_ATTR_VERTEX    src [V][C]: (src[f0] u + src[f1] v) + src[f2] w with f = faces[face_index].
+ *   UTX_ATTR_TEXTURE   src [H][W][C], C <= 4: uv = (uvs_2d[g0] u + uvs_2d[g1] v) + uvs_2d[g2] w with g = faces_2d[face_index], then torch's grid_sample as the
+ *                      reference calls it -- the uv itself is the grid coordinate (NOT mapped from [0, 1] to [-1, 1]), bilinear, align_corners=False,
+ *                      padding_mode='reflection': x = ((uv.x + 1) W - 1) / 2, reflected about -0.5 and W - 0.5, clipped to [0, W - 1]; likewise y with H.
+ * A face_index outside [0, F) gives zeros (constants are still copied).  C <= UTX_SAMPLE_ATTR_CHANNELS_MAX.  faces is needed by vertex attributes, faces_2d and
+ * uvs_2d by textures; else they may be null -- faces_2d and uvs_2d only both or neither.  -2 for a bad count, kind, channel count or size, a missing operand, or one of
+ * faces_2d / uvs_2d without the other.  Every refusal happens before any device call. */
+#define UTX_SAMPLE_ATTRS_MAX 4
+#define UTX_SAMPLE_ATTR_CHANNELS_MAX 16
+#define UTX_ATTR_CONSTANT 0
+#define UTX_ATTR_VERTEX 1
+#define UTX_ATTR_TEXTURE 2
+int utx_sample_attrs(utx_ctx* ctx, const int* faces, const int* faces_2d, const float* uvs_2d, int F, const int* face_index, const float* uvw, long N, int n_attr,
+                     const float* const* src_host, const int* dims_host, float* const* out_host, utx_stream stream);
 
 /* lens blur consumed on the seam only (image/lens_blur.py:260-280; renderer_inverse.py:620-624).
  * k49_host: HOST array, the collapsed real 7x7 kernel. src/dst [H][W][3] f32. */

@@ -220,6 +220,7 @@ SYMBOLS = {
     "utx_uv_dilation_step": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "utx_bvh_trace_count": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
     "utx_bvh_depth": (c_int, [c_void_p]),
+    "utx_bvh_closest_point": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "utx_backproject": (c_int, [c_void_p, C.POINTER(BackprojectDesc), c_void_p, c_void_p]),
     "utx_backproject_persp": (c_int, [c_void_p, C.POINTER(BackprojectDesc), c_void_p, c_void_p, c_void_p]),
     "utx_backproject_sampled": (c_int, [c_void_p, C.POINTER(BackprojectDesc), c_void_p, c_int, c_void_p, c_void_p]),
@@ -237,6 +238,9 @@ SYMBOLS = {
     "utx_fps": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "utx_sample_edges_equal_steps": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_float, c_long, c_void_p, c_void_p, c_void_p, c_void_p]),
     "utx_sample_surface": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_long, C.c_ulonglong, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "utx_sample_offsets": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_long, C.c_ulonglong, c_int, c_float, c_void_p,
+                                   c_void_p]),
+    "utx_sample_attrs": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "utx_nn_fill_workspace_bytes": (c_long, [c_long]),
     "utx_nn_fill": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "utx_lens_blur_seam": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, C.POINTER(c_float), c_void_p, c_void_p]),

@@ -248,6 +248,47 @@ __global__ __launch_bounds__(256) void visible_faces_rays_kernel(const float4* _
     }
 }
 
+// ---- nearest surface point (bvh_device.h: tri_closest, bvh_nearest_packed): one thread per query, in the caller's order.  flags & UTX_CP_EXHAUSTIVE: the same
+// per-triangle function and tie rule over all F triangles in id order (the test twin and the cost baseline); flags & UTX_CP_NO_SEED: the walk without its greedy
+// descent (for the node count).  A query with a non-finite coordinate: face -1, dist +inf, zero uvw and closest.
+__global__ __launch_bounds__(256) void bvh_closest_point_kernel(const float4* __restrict__ nodes, const float4* __restrict__ tris, int F, const float* __restrict__ points,
+                                                                long N, int flags, float* __restrict__ dist, int* __restrict__ face, float* __restrict__ uvw,
+                                                                float* __restrict__ closest, unsigned long long* visited) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned nv = 0;
+    if (i < N) {
+        const float p[3] = {points[3 * i], points[3 * i + 1], points[3 * i + 2]};
+        float best = __int_as_float(0x7f800000);
+        int hit = -1;
+        TriClosest r = {best, 0.f, 0.f, 0.f};
+        float q[3] = {0.f, 0.f, 0.f};
+        if (fabsf(p[0]) <= 3.402823466e38f && fabsf(p[1]) <= 3.402823466e38f && fabsf(p[2]) <= 3.402823466e38f) {
+            if (flags & 1) {
+                int f = 0x7fffffff;
+                for (int k = 0; k < F; ++k) cp_take(p, tris, k, best, f);
+                hit = f == 0x7fffffff ? -1 : f;
+            } else {
+                hit = bvh_nearest_packed(nodes, tris, p, !(flags & 2), best, nv);
+            }
+            if (hit >= 0) {      // the winner's weights: the same function on the same numbers, once
+                const float4 t0 = tris[3 * (long)hit], t1 = tris[3 * (long)hit + 1], t2 = tris[3 * (long)hit + 2];
+                const float v0[3] = {t0.x, t0.y, t0.z}, v1[3] = {t1.x, t1.y, t1.z}, v2[3] = {t2.x, t2.y, t2.z};
+                r = tri_closest(p, v0, v1, v2);
+#pragma unroll
+                for (int k = 0; k < 3; ++k) q[k] = (r.u * v0[k] + r.v * v1[k]) + r.w * v2[k];
+            }
+        }
+        dist[i] = sqrtf(r.d2);
+        if (face) face[i] = hit;
+        if (uvw) { uvw[3 * i] = r.u; uvw[3 * i + 1] = r.v; uvw[3 * i + 2] = r.w; }
+        if (closest) { closest[3 * i] = q[0]; closest[3 * i + 1] = q[1]; closest[3 * i + 2] = q[2]; }
+    }
+    if (visited) {      // diagnostics (tools/bench_closest_point.py: nodes visited per query): wave sum, one atomic per wave
+        for (int o = 32; o > 0; o >>= 1) nv += __shfl_xor(nv, o, 64);
+        if ((threadIdx.x & 63) == 0) atomicAdd(visited, (unsigned long long)nv);
+    }
+}
+
 // ---- face visibility by rasterisation: NVDiffRendererBase.get_visible_faces (render/nvdiffrast/renderer_base.py:77-81): the faces whose id appears in a
 // view's raster.  One thread per pixel of rast [B][H][W][4]; mask [B][F] zeroed by the launcher.
 __global__ __launch_bounds__(256) void visible_faces_raster_kernel(const float* __restrict__ rast, long npix, long total, int F, unsigned char* mask) {
@@ -458,6 +499,17 @@ extern "C" int utx_visible_faces_rays_impl(utx_bvh* b, const float* verts, const
         hipLaunchKernelGGL(visible_faces_rays_kernel<true>, g, blk, 0, stream, b->nodes, b->tris, b->info, b->aabb, verts, faces, order, F, c2ws, perspective, mask, visited);
     else
         hipLaunchKernelGGL(visible_faces_rays_kernel<false>, g, blk, 0, stream, b->nodes, b->tris, b->info, b->aabb, verts, faces, order, F, c2ws, perspective, mask, visited);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// one launch, no workspace, no host wait: the packed walk has no stack, so no depth rule applies and the tree's depth is never asked for
+extern "C" int utx_bvh_closest_point_impl(utx_bvh* b, const float* points, long N, float* dist, int* face, float* uvw, float* closest, unsigned long long* visited,
+                                          int flags, hipStream_t stream) {
+    if (!b || b->F < 1 || N < 0 || N >= (1l << 31) || (flags & ~3)) return -2;
+    if (N == 0) return 0;
+    if (!points || !dist) return -2;
+    hipLaunchKernelGGL(bvh_closest_point_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, b->nodes, b->tris, b->F, points, N, flags, dist, face, uvw,
+                       closest, visited);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 

@@ -312,3 +312,98 @@ struct utx_bvh {
     void* owned;               // the one hipMalloc of utx_bvh_build (null: the arrays live in the caller's workspace, utx_bvh_build_ws)
 };
 #define UTX_BVH_PACKED_MAX_DEPTH 60   // the reference's stack holds 64 entries and the walk keeps at most depth + 1 of them
+
+// ---- NEAREST SURFACE POINT (utx_bvh_closest_point): what the reference takes from cuBVH.unsigned_distance(points, return_uvw=True) [3p, absent]
+// (geometry/sampling/spatial_sampling.py:36,90).  A point query, no ray.
+// tri_closest: the Voronoi-region form of Ericson, Real-Time Collision Detection, 5.1.5, in fp32 with every sum in a fixed order, so that a numpy float32
+// restatement (tests/closest_point_ref.py) repeats it bit for bit.  (u, v, w) weigh (v0, v1, v2); q = (u v0 + v v1) + w v2; d2 = |p - q|^2 summed like dot3.
+// Beyond Ericson: a quotient whose denominator is not > 0 is 0 (a zero-length edge counts as its end point); the interior weights are clamped (v to [0, 1],
+// w to [0, 1 - v], u = (1 - v) - w), so every weight is >= 0; and where the interior denominator va + vb + vc (|ab x ac|^2) is not > 0 -- a zero-area face, whose
+// regions mean nothing -- the answer is the nearest of the three edge segments AB, AC, BC, the first of them on a tie.
+struct TriClosest { float d2, u, v, w; };
+__device__ __forceinline__ float cp_div(float n, float d) { return d > 0.f ? n / d : 0.f; }
+__device__ __forceinline__ float cp_eval(const float* p, const float* a, const float* b, const float* c, float u, float v, float w) {
+    float r[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) r[k] = p[k] - ((u * a[k] + v * b[k]) + w * c[k]);
+    return dot3(r, r);
+}
+__device__ __forceinline__ float cp_seg_t(const float* xp, const float* e) { return fminf(fmaxf(cp_div(dot3(xp, e), dot3(e, e)), 0.f), 1.f); }
+__device__ __forceinline__ TriClosest tri_closest(const float* p, const float* a, const float* b, const float* c) {
+    float ab[3], ac[3], bc[3], ap[3], bp[3], cp[3];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { ab[k] = b[k] - a[k]; ac[k] = c[k] - a[k]; bc[k] = c[k] - b[k]; ap[k] = p[k] - a[k]; bp[k] = p[k] - b[k]; cp[k] = p[k] - c[k]; }
+    const float d1 = dot3(ab, ap), d2 = dot3(ac, ap), d3 = dot3(ab, bp), d4 = dot3(ac, bp), d5 = dot3(ab, cp), d6 = dot3(ac, cp);
+    const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
+    const float den = (va + vb) + vc;      // |ab x ac|^2 up to rounding
+    TriClosest r;
+    if (!(den > 0.f)) {      // no area (or not a number): Ericson's regions presuppose one -- the nearest of the three edge segments
+        const float t0 = cp_seg_t(ap, ab), t1 = cp_seg_t(ap, ac), t2 = cp_seg_t(bp, bc);
+        const float e0 = cp_eval(p, a, b, c, 1.f - t0, t0, 0.f), e1 = cp_eval(p, a, b, c, 1.f - t1, 0.f, t1), e2 = cp_eval(p, a, b, c, 0.f, 1.f - t2, t2);
+        r.u = 1.f - t0; r.v = t0; r.w = 0.f;
+        float e = e0;
+        if (e1 < e) { e = e1; r.u = 1.f - t1; r.v = 0.f; r.w = t1; }
+        if (e2 < e) { r.u = 0.f; r.v = 1.f - t2; r.w = t2; }
+    }
+    else if (d1 <= 0.f && d2 <= 0.f) { r.u = 1.f; r.v = 0.f; r.w = 0.f; }
+    else if (d3 >= 0.f && d4 <= d3) { r.u = 0.f; r.v = 1.f; r.w = 0.f; }
+    else if (vc <= 0.f && d1 >= 0.f && d3 <= 0.f) { r.v = cp_div(d1, d1 - d3); r.u = 1.f - r.v; r.w = 0.f; }
+    else if (d6 >= 0.f && d5 <= d6) { r.u = 0.f; r.v = 0.f; r.w = 1.f; }
+    else if (vb <= 0.f && d2 >= 0.f && d6 <= 0.f) { r.w = cp_div(d2, d2 - d6); r.u = 1.f - r.w; r.v = 0.f; }
+    else if (va <= 0.f && d4 - d3 >= 0.f && d5 - d6 >= 0.f) { r.w = cp_div(d4 - d3, (d4 - d3) + (d5 - d6)); r.v = 1.f - r.w; r.u = 0.f; }
+    else {
+        const float inv = 1.0f / den;
+        r.v = fminf(fmaxf(vb * inv, 0.f), 1.f);
+        r.w = fminf(fmaxf(vc * inv, 0.f), 1.f - r.v);
+        r.u = (1.f - r.v) - r.w;
+    }
+    r.d2 = cp_eval(p, a, b, c, r.u, r.v, r.w);
+    return r;
+}
+// squared distance from p to a box: sum of max(0, lo - p, p - hi)^2, summed like dot3
+__device__ __forceinline__ float cp_box_d2(const float* p, const float4& a, const float4& b) {
+    const float ex[3] = {fmaxf(0.f, fmaxf(a.x - p[0], p[0] - a.w)), fmaxf(0.f, fmaxf(a.y - p[1], p[1] - b.x)), fmaxf(0.f, fmaxf(a.z - p[2], p[2] - b.y))};
+    return dot3(ex, ex);
+}
+__device__ __forceinline__ void cp_take(const float* p, const float4* __restrict__ tris, int prim, float& best, int& face) {
+    const float4 t0 = tris[3 * (long)prim], t1 = tris[3 * (long)prim + 1], t2 = tris[3 * (long)prim + 2];
+    const float v0[3] = {t0.x, t0.y, t0.z}, v1[3] = {t1.x, t1.y, t1.z}, v2[3] = {t2.x, t2.y, t2.z};
+    const float d2 = tri_closest(p, v0, v1, v2).d2;
+    if (d2 < best || (d2 == best && prim < face)) { best = d2; face = prim; }
+}
+// a subtree is skipped only if its box lies beyond the best squared distance by more than a part in 1e5 (CLOSE_LIMIT's rule, on squares): a triangle that TIES
+// with the best is still tested as long as the two roundings differ by less than that RELATIVE margin.  The limit of the rule: tri_closest's error is absolute, a few
+// u * scale on q, so for a query within a few u * scale of the surface the computed d2 may lie far below the true one (down to 0) while the box distance of a
+// tying face that does not contain p does not -- that face can then be skipped, and the walk may name another of the tying faces than the exhaustive loop does
+// (the smallest id among those it met).  d2 is the same either way; the face id is order-independent only outside that band.
+#define CP_LIMIT(best) ((best) * 1.00001f)
+// The walk over the packed tree, no stack, no LDS, no cross-lane traffic.  First a greedy descent from the root into the child whose box is nearer (a node's first
+// child is the esc of its second child), down to a leaf: that gives a finite `best` before the walk proper, which is bvh_closest_packed's esc-link walk with the
+// box test above.  The result is the face with the smallest d2, ties to the smallest id, whatever the order of the visits.  seed = false skips the descent.
+__device__ __forceinline__ int bvh_nearest_packed(const float4* __restrict__ nodes, const float4* __restrict__ tris, const float* p, bool seed, float& best, unsigned& nv) {
+    best = __int_as_float(0x7f800000);
+    int face = 0x7fffffff;
+    if (seed) {
+        int link = __float_as_int(nodes[1].z);      // of the node the descent stands on; at the root of a one-face tree it is a leaf's already
+        ++nv;
+        while (link > 0) {
+            const float4 sa = nodes[2 * (long)link], sb = nodes[2 * (long)link + 1];
+            const int first = __float_as_int(sb.w);
+            const float4 fa = nodes[2 * (long)first], fb = nodes[2 * (long)first + 1];
+            nv += 2;
+            link = __float_as_int(cp_box_d2(p, fa, fb) <= cp_box_d2(p, sa, sb) ? fb.z : sb.z);
+        }
+        cp_take(p, tris, ~link, best, face);
+    }
+    int nd = 0;
+    while (nd >= 0) {
+        const float4 a = nodes[2 * (long)nd], b = nodes[2 * (long)nd + 1];
+        const int link = __float_as_int(b.z), esc = __float_as_int(b.w);
+        ++nv;
+        if (cp_box_d2(p, a, b) > CP_LIMIT(best)) { nd = esc; continue; }
+        if (link > 0) { nd = link; continue; }
+        cp_take(p, tris, ~link, best, face);
+        nd = esc;
+    }
+    return face == 0x7fffffff ? -1 : face;
+}

@@ -610,6 +610,12 @@ int utx_visible_faces_rays(utx_ctx* ctx, utx_bvh* bvh, const float* verts, const
     if (F <= 0 || B <= 0 || B > 65535 || (flags & ~(UTX_VF_STACK_WALK | UTX_VF_FACE_ORDER))) return fail(ctx, -2, me);
     UTX_CALL(ctx, me, utx_visible_faces_rays_impl(bvh, verts, faces, F, c2ws, B, perspective, flags, mask, visited, (hipStream_t)stream));
 }
+int utx_bvh_closest_point(utx_ctx* ctx, utx_bvh* bvh, const float* points, long N, float* dist, int* face, float* uvw, float* closest, unsigned long long* visited,
+                          int flags, utx_stream stream) {
+    const char* const me = "utx_bvh_closest_point";
+    if (!bvh || N < 0 || N >= (1l << 31) || (flags & ~(UTX_CP_EXHAUSTIVE | UTX_CP_NO_SEED)) || (N > 0 && (!points || !dist))) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_bvh_closest_point_impl(bvh, points, N, dist, face, uvw, closest, visited, flags, (hipStream_t)stream));
+}
 int utx_visible_faces_raster(utx_ctx* ctx, const float* rast, int B, int H, int W, int F, unsigned char* mask, utx_stream stream) {
     if (!rast || !mask || B <= 0 || H <= 0 || W <= 0 || F <= 0) return fail(ctx, -2, "utx_visible_faces_raster");
     UTX_CALL(ctx, "utx_visible_faces_raster", utx_launch_visible_faces_raster(rast, B, H, W, F, mask, (hipStream_t)stream));
@@ -691,6 +697,15 @@ int utx_sample_surface(utx_ctx* ctx, const float* verts, const int* faces, const
                        int* face_index, float* uvw, utx_stream stream) {
     if (!verts || !faces || !cum || !samples) return fail(ctx, -2, "utx_sample_surface");
     UTX_CALL(ctx, "utx_sample_surface", utx_launch_sample_surface(verts, faces, cum, F, N, seed, samples, face_index, uvw, (hipStream_t)stream));
+}
+int utx_sample_offsets(utx_ctx* ctx, const float* base, const int* faces, int F, const int* face_index, const float* uvw, const float* vnormal, const float* uniforms,
+                       long N, unsigned long long seed, int stream_id, float threshold, float* out, utx_stream stream) {
+    UTX_CALL(ctx, "utx_sample_offsets", utx_launch_sample_offsets(base, faces, F, face_index, uvw, vnormal, uniforms, N, seed, stream_id, threshold, out,
+                                                                  (hipStream_t)stream));
+}
+int utx_sample_attrs(utx_ctx* ctx, const int* faces, const int* faces_2d, const float* uvs_2d, int F, const int* face_index, const float* uvw, long N, int n_attr,
+                     const float* const* src_host, const int* dims_host, float* const* out_host, utx_stream stream) {
+    UTX_CALL(ctx, "utx_sample_attrs", utx_launch_sample_attrs(faces, faces_2d, uvs_2d, F, face_index, uvw, N, n_attr, src_host, dims_host, out_host, (hipStream_t)stream));
 }
 long utx_nn_fill_workspace_bytes(long T) { return (long)utx_nn_fill_workspace_bytes_impl(T); }
 int utx_nn_fill(utx_ctx* ctx, const float* pos, const void* winner, const float* rast2d, long T, float* atlas, int* nn_index,

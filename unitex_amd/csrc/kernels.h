@@ -136,6 +136,10 @@ int utx_launch_sample_edges(const float* verts, const int* edges, const int* edg
                             float* samples, int* edge_index, float* edge_t, hipStream_t stream);
 int utx_launch_sample_surface(const float* verts, const int* faces, const float* cum, int F, long N, unsigned long long seed, float* samples, int* face_index,
                               float* uvw, hipStream_t stream);
+int utx_launch_sample_offsets(const float* base, const int* faces, int F, const int* face_index, const float* uvw, const float* vnormal, const float* uniforms, long N,
+                              unsigned long long seed, int stream_id, float threshold, float* out, hipStream_t stream);
+int utx_launch_sample_attrs(const int* faces, const int* faces_2d, const float* uvs_2d, int F, const int* face_index, const float* uvw, long N, int n_attr,
+                            const float* const* src_host, const int* dims_host, float* const* out_host, hipStream_t stream);
 int utx_launch_texture_shade(const float* rast, const float* uv, const int* tri, const float* tex, int Ht, int Wt, const float* bg3_host, long npix, void* out, hipStream_t stream);
 // gbuffer.hip
 int utx_launch_gbuffer_shade(int mode, const float* rast, const int* tri, const float* attr, int stride, const float* scale2, int ndc, int composite, const float* bg3_host, long npix, void* out_u8, float* out_rgba, hipStream_t stream);
@@ -176,6 +180,8 @@ int utx_bvh_trace_impl(utx_bvh* b, const float* ro, const float* rd, long R, int
 int utx_bvh_depth_impl(utx_bvh* b);
 int utx_visible_faces_rays_impl(utx_bvh* b, const float* verts, const int* faces, int F, const float* c2ws, int B, int perspective, int flags, unsigned char* mask,
                                 unsigned long long* visited, hipStream_t stream);
+int utx_bvh_closest_point_impl(utx_bvh* b, const float* points, long N, float* dist, int* face, float* uvw, float* closest, unsigned long long* visited, int flags,
+                               hipStream_t stream);
 int utx_launch_visible_faces_raster(const float* rast, int B, int H, int W, int F, unsigned char* mask, hipStream_t stream);
 int utx_launch_erode_faces(unsigned char* mask, const int* faces, int B, int F, int V, int depth, int* vstamp, hipStream_t stream);
 int utx_launch_visible_vertices(const unsigned char* mask, const int* faces, int B, int F, int V, unsigned char* out, hipStream_t stream);

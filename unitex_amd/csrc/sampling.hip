@@ -238,3 +238,138 @@ extern "C" int utx_launch_sample_surface(const float* verts, const int* faces, c
                        (unsigned)(seed >> 32), samples, face_index, uvw);
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
+
+// ---- sample_spatial / sample_near_surface (spatial_sampling.py:11-37, :40-91): the random offsets, on the defined stream of sample_surface with another stream id:
+// counter (i, stream_id, 0, 0), stream_id 1 for sample_spatial's points and 2 for the near-surface deltas (0 is sample_surface's); words 0..2 -> r in [0, 1)^3.
+//   base == null: out = r                                  (sample_spatial: torch.rand((N, 3)) -- the unit cube, whatever the mesh's box is)
+//   else:  n = (vn[f0] * u + vn[f1] * v) + vn[f2] * w       (the interpolated vertex normal, not renormalised)
+//          out = base + (threshold * (r * 2 - 1)) * n       (spatial_sampling.py:87-89, in the reference's order)
+// uniforms (optional, [N][3]): read instead of the Philox words -- for tests that hand the kernel a fixture's recorded draws.
+__global__ __launch_bounds__(256) void sample_offsets_kernel(const float* __restrict__ base, const int* __restrict__ faces, int F, const int* __restrict__ face_index,
+                                                             const float* __restrict__ uvw, const float* __restrict__ vnormal, const float* __restrict__ uniforms, long N,
+                                                             unsigned seed_lo, unsigned seed_hi, unsigned stream_id, float threshold, float* __restrict__ out) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    float r[3];
+    if (uniforms) { r[0] = uniforms[3 * i]; r[1] = uniforms[3 * i + 1]; r[2] = uniforms[3 * i + 2]; }
+    else {
+        unsigned x[4];
+        philox4x32_10((unsigned)i, stream_id, 0u, 0u, seed_lo, seed_hi, x);
+        const float sc = 1.0f / 16777216.0f;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) r[d] = (float)(x[d] >> 8) * sc;
+    }
+    if (!base) {
+#pragma unroll
+        for (int d = 0; d < 3; ++d) out[3 * i + d] = r[d];
+        return;
+    }
+    const int f = face_index[i];
+    if (f < 0 || f >= F) {      // no face, no normal: the sample stays where it is
+#pragma unroll
+        for (int d = 0; d < 3; ++d) out[3 * i + d] = base[3 * i + d];
+        return;
+    }
+    const int a = faces[3 * (long)f], b = faces[3 * (long)f + 1], c = faces[3 * (long)f + 2];
+    const float u = uvw[3 * i], v = uvw[3 * i + 1], w = uvw[3 * i + 2];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) {
+        const float n = (vnormal[3 * (long)a + d] * u + vnormal[3 * (long)b + d] * v) + vnormal[3 * (long)c + d] * w;
+        out[3 * i + d] = base[3 * i + d] + (threshold * (r[d] * 2.0f - 1.0f)) * n;
+    }
+}
+
+extern "C" int utx_launch_sample_offsets(const float* base, const int* faces, int F, const int* face_index, const float* uvw, const float* vnormal, const float* uniforms,
+                                         long N, unsigned long long seed, int stream_id, float threshold, float* out, hipStream_t stream) {
+    if (N < 0 || N >= (1l << 31) || stream_id < 1) return -2;
+    if (N == 0) return 0;
+    if (!out || (base && (!faces || F <= 0 || !face_index || !uvw || !vnormal))) return -2;
+    hipLaunchKernelGGL(sample_offsets_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, base, faces, F, face_index, uvw, vnormal, uniforms, N,
+                       (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), (unsigned)stream_id, threshold, out);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}
+
+// ---- PBRMesh.__call__ (mesh/structure_v2.py:105-135): up to four attributes at N surface samples (face_index, uvw) in one launch.  An attribute is
+//   a constant [C]                          -> copied;
+//   a per-vertex array [V][C]               -> (attr[f0] * u + attr[f1] * v) + attr[f2] * w            (torch's sum over the three corners);
+//   a texture [H][W][C], C <= 4             -> uv = (uvs_2d[g0] * u + uvs_2d[g1] * v) + uvs_2d[g2] * w with g = faces_2d[f], then grid_sample as the reference calls
+//                                              it: THE UV ITSELF IS THE GRID COORDINATE (no map of [0, 1] to [-1, 1]), bilinear, align_corners=False,
+//                                              padding_mode='reflection'.
+// The lookup below is grid_sample's own rule (unnormalise, reflect about -0.5 and size - 0.5, clip to [0, size - 1], four taps weighted by the opposite corner's
+// area); the taps of shade_device.h are zero-padding and wrap, another rule.
+struct SampleAttr { const float* src; float* out; int kind, C, H, W; };
+struct SampleAttrs { SampleAttr a[UTX_SAMPLE_ATTRS_MAX]; int n; };
+__device__ __forceinline__ float gs_reflect_coord(float g, int size) {
+    float x = ((g + 1.0f) * (float)size - 1.0f) / 2.0f;
+    const float mn = -0.5f, span = (float)size;
+    x = fabsf(x - mn);
+    const float extra = fmodf(x, span);
+    const float flips = floorf(x / span);
+    x = fmodf(flips, 2.0f) == 0.0f ? extra + mn : (span - extra) + mn;
+    return fminf((float)(size - 1), fmaxf(x, 0.0f));
+}
+__device__ __forceinline__ void gs_reflect_bilinear(const float* __restrict__ tex, int H, int W, int C, float gx, float gy, float* o) {
+    const float ix = gs_reflect_coord(gx, W), iy = gs_reflect_coord(gy, H);
+    const float x0 = floorf(ix), y0 = floorf(iy);
+    const float x1 = x0 + 1.0f, y1 = y0 + 1.0f;
+    const float nw = (x1 - ix) * (y1 - iy), ne = (ix - x0) * (y1 - iy), sw = (x1 - ix) * (iy - y0), se = (ix - x0) * (iy - y0);
+    const int jx0 = (int)x0, jy0 = (int)y0, jx1 = jx0 + 1, jy1 = jy0 + 1;      // jx0 in [0, W - 1], jy0 in [0, H - 1] after the clip
+    const bool inx1 = jx1 < W, iny1 = jy1 < H;
+    for (int c = 0; c < C; ++c) {
+        float s = tex[((long)jy0 * W + jx0) * C + c] * nw;
+        if (inx1) s += tex[((long)jy0 * W + jx1) * C + c] * ne;
+        if (iny1) s += tex[((long)jy1 * W + jx0) * C + c] * sw;
+        if (inx1 && iny1) s += tex[((long)jy1 * W + jx1) * C + c] * se;
+        o[c] = s;
+    }
+}
+__global__ __launch_bounds__(256) void sample_attrs_kernel(const int* __restrict__ faces, const int* __restrict__ faces_2d, const float* __restrict__ uvs_2d, int F,
+                                                           const int* __restrict__ face_index, const float* __restrict__ uvw, long N, SampleAttrs P) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const int f = face_index[i];
+    const bool ok = f >= 0 && f < F;
+    const float u = uvw[3 * i], v = uvw[3 * i + 1], w = uvw[3 * i + 2];
+    float gx = 0.f, gy = 0.f;
+    if (ok && faces_2d && uvs_2d) {      // the launcher admits the two only together, and a texture only with both
+        const long g0 = faces_2d[3 * (long)f], g1 = faces_2d[3 * (long)f + 1], g2 = faces_2d[3 * (long)f + 2];
+        gx = (uvs_2d[2 * g0] * u + uvs_2d[2 * g1] * v) + uvs_2d[2 * g2] * w;
+        gy = (uvs_2d[2 * g0 + 1] * u + uvs_2d[2 * g1 + 1] * v) + uvs_2d[2 * g2 + 1] * w;
+    }
+    for (int k = 0; k < P.n; ++k) {
+        const SampleAttr A = P.a[k];
+        float* o = A.out + i * A.C;
+        if (A.kind == 0) {
+            for (int c = 0; c < A.C; ++c) o[c] = A.src[c];
+        } else if (!ok) {      // a sample with no face: zeros
+            for (int c = 0; c < A.C; ++c) o[c] = 0.f;
+        } else if (A.kind == 1) {
+            const long a0 = faces[3 * (long)f], a1 = faces[3 * (long)f + 1], a2 = faces[3 * (long)f + 2];
+            for (int c = 0; c < A.C; ++c) o[c] = (A.src[a0 * A.C + c] * u + A.src[a1 * A.C + c] * v) + A.src[a2 * A.C + c] * w;
+        } else {
+            float t[4];
+            gs_reflect_bilinear(A.src, A.H, A.W, A.C, gx, gy, t);
+            for (int c = 0; c < A.C; ++c) o[c] = t[c];
+        }
+    }
+}
+
+extern "C" int utx_launch_sample_attrs(const int* faces, const int* faces_2d, const float* uvs_2d, int F, const int* face_index, const float* uvw, long N, int n_attr,
+                                       const float* const* src_host, const int* dims_host, float* const* out_host, hipStream_t stream) {
+    if (N < 0 || N >= (1l << 31) || F <= 0 || n_attr < 1 || n_attr > UTX_SAMPLE_ATTRS_MAX || !src_host || !dims_host || !out_host) return -2;
+    if ((faces_2d == nullptr) != (uvs_2d == nullptr)) return -2;      // the uv table and its index go together
+    SampleAttrs P;
+    P.n = n_attr;
+    for (int k = 0; k < n_attr; ++k) {
+        SampleAttr& A = P.a[k];
+        A.src = src_host[k]; A.out = out_host[k];
+        A.kind = dims_host[4 * k]; A.C = dims_host[4 * k + 1]; A.H = dims_host[4 * k + 2]; A.W = dims_host[4 * k + 3];
+        if (!A.src || (!A.out && N > 0) || A.kind < 0 || A.kind > 2 || A.C < 1 || A.C > UTX_SAMPLE_ATTR_CHANNELS_MAX) return -2;
+        if (A.kind == 1 && !faces) return -2;
+        if (A.kind == 2 && (A.C > 4 || A.H < 1 || A.W < 1 || !faces_2d || !uvs_2d)) return -2;
+    }
+    if (N == 0) return 0;
+    if (!face_index || !uvw) return -2;
+    hipLaunchKernelGGL(sample_attrs_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, stream, faces, faces_2d, uvs_2d, F, face_index, uvw, N, P);
+    return hipGetLastError() == hipSuccess ? 0 : -4;
+}

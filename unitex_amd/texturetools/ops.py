@@ -795,6 +795,117 @@ def sample_surface(verts, faces, cum, N, seed):
     return samples, fidx, uvw
 
 
+CLOSEST_POINT_OUTPUTS = ("dist", "face", "uvw", "closest")
+
+
+def closest_point(bvh, points, want=CLOSEST_POINT_OUTPUTS, brute=False, count=False, seed_descent=True):
+    """utx_bvh_closest_point: the nearest point of the mesh of `bvh` (ops.BVH) to every row of points [N,3] f32 -> dict of the buffers named in `want`:
+    dist [N] f32 (the distance, not its square), face [N] i32 (-1 for a query with a non-finite coordinate), uvw [N,3] f32 weighing the face's corners,
+    closest [N,3] f32.  The face with the smallest squared distance, ties to the smallest id.  brute: the exhaustive loop over all faces instead of the tree walk
+    (equal results); seed_descent=False: the walk without its greedy first descent (equal results); count: also return the number of tree nodes visited."""
+    points = _f(points)
+    if points.dim() != 2 or points.shape[1] != 3:
+        raise ValueError("closest_point: points is %s, expected [N, 3]" % (tuple(points.shape),))
+    want = tuple(want)
+    for k in want:
+        if k not in CLOSEST_POINT_OUTPUTS:
+            raise ValueError("closest_point: unknown output %r (one of %s)" % (k, ", ".join(CLOSEST_POINT_OUTPUTS)))
+    ctx, N, dev = bvh.ctx, points.shape[0], points.device
+    if not N < 2 ** 31:
+        raise ValueError("closest_point takes N < 2^31 points, got %d" % N)
+    out = {"dist": torch.empty(N, dtype=F32, device=dev)}
+    if "face" in want:
+        out["face"] = torch.empty(N, dtype=I32, device=dev)
+    for k in ("uvw", "closest"):
+        if k in want:
+            out[k] = torch.empty(N, 3, dtype=F32, device=dev)
+    visited = torch.zeros(1, dtype=torch.int64, device=dev) if count else None
+    if N > 0:
+        ctx.check(ctx.lib.utx_bvh_closest_point(ctx.handle, bvh.handle, ptr(points), N, ptr(out["dist"]), ptr(out.get("face")), ptr(out.get("uvw")),
+                                                ptr(out.get("closest")), ptr(visited) if count else None, (1 if brute else 0) | (0 if seed_descent else 2),
+                                                ctx.stream()))
+    out = {k: out[k] for k in want}
+    return (out, int(visited.item())) if count else out
+
+
+def sample_offsets(N, seed, stream_id, base=None, faces=None, face_index=None, uvw=None, vnormal=None, threshold=0.0, uniforms=None):
+    """utx_sample_offsets: N points of the random stream `stream_id` (Philox4x32-10, counter (i, stream_id, 0, 0)).  base None: the points themselves, in [0, 1)^3.
+    Otherwise base [N,3] + (threshold * (2 r - 1)) * n with n the vertex normals vnormal [V,3] interpolated by (face_index [N] i32, uvw [N,3]) over faces [F,3] i32.
+    uniforms [N,3] (tests): read in place of the stream."""
+    N = int(N)
+    some = base if base is not None else uniforms
+    dev = some.device if some is not None else torch.device("cuda", torch.cuda.current_device())
+    ctx = get_ctx(dev.index)
+    out = torch.empty(N, 3, dtype=F32, device=dev)
+    if base is not None:
+        assert tuple(base.shape) == (N, 3) and tuple(uvw.shape) == (N, 3) and tuple(face_index.shape) == (N,) and faces.dim() == 2 and vnormal.dim() == 2
+    if uniforms is not None:
+        assert tuple(uniforms.shape) == (N, 3)
+    ctx.check(ctx.lib.utx_sample_offsets(ctx.handle, ptr(_f(base)) if base is not None else None, ptr(_i(faces)) if base is not None else None,
+                                         faces.shape[0] if base is not None else 0, ptr(_i(face_index)) if base is not None else None,
+                                         ptr(_f(uvw)) if base is not None else None, ptr(_f(vnormal)) if base is not None else None,
+                                         ptr(_f(uniforms)) if uniforms is not None else None, N, int(seed) & (2 ** 64 - 1), int(stream_id), float(threshold),
+                                         ptr(out) if N else None, ctx.stream()))
+    return out
+
+
+SAMPLE_ATTRS_MAX = 4
+
+
+def sample_attrs(attrs, face_index, uvw, faces=None, faces_2d=None, uvs_2d=None):
+    """utx_sample_attrs: PBRMesh.__call__ of the reference for up to four attributes in one launch.  attrs: dict name -> f32 tensor, a constant [C], a per-vertex
+    array [V,C] (needs faces [F,3] i32) or a texture [H,W,C] with C <= 4 (needs faces_2d [F,3] i32 and uvs_2d [V2,2] f32; the interpolated uv is grid_sample's
+    grid coordinate as it stands, bilinear, align_corners=False, reflection padding).  face_index [N] i32, uvw [N,3] f32 -> dict name -> [N,C] f32."""
+    if (faces_2d is None) != (uvs_2d is None):
+        raise ValueError("sample_attrs: faces_2d and uvs_2d go together, got only %s" % ("faces_2d" if uvs_2d is None else "uvs_2d"))
+    names = list(attrs)
+    if not 1 <= len(names) <= SAMPLE_ATTRS_MAX:
+        raise ValueError("sample_attrs takes 1 to %d attributes, got %d" % (SAMPLE_ATTRS_MAX, len(names)))
+    face_index, uvw = _i(face_index), _f(uvw)
+    N, dev = face_index.shape[0], face_index.device
+    if tuple(uvw.shape) != (N, 3):
+        raise ValueError("sample_attrs: uvw is %s, expected [%d, 3]" % (tuple(uvw.shape), N))
+    ctx = get_ctx(dev.index)
+    F = None
+    for t in (faces, faces_2d):
+        if t is not None:
+            if t.dim() != 2 or t.shape[1] != 3 or (F is not None and t.shape[0] != F):
+                raise ValueError("sample_attrs: faces / faces_2d must be [F, 3] with one F")
+            F = t.shape[0]
+    src, dims, out = [], [], {}
+    for k in names:
+        a = _f(attrs[k])
+        if a.dim() == 1:
+            kind, Cc, H, W = 0, a.shape[0], 0, 0
+        elif a.dim() == 2:
+            kind, Cc, H, W = 1, a.shape[1], 0, 0
+            if faces is None:
+                raise ValueError("sample_attrs: %s is per-vertex and needs faces" % k)
+        elif a.dim() == 3:
+            kind, Cc, H, W = 2, a.shape[2], a.shape[0], a.shape[1]
+            if faces_2d is None or uvs_2d is None:
+                raise ValueError("sample_attrs: %s is a texture and needs faces_2d and uvs_2d" % k)
+            if Cc > 4 or H < 1 or W < 1:
+                raise ValueError("sample_attrs: texture %s is %s, expected [H >= 1, W >= 1, C <= 4]" % (k, tuple(a.shape)))
+        else:
+            raise NotImplementedError("invalid shape of %s: %s" % (k, tuple(a.shape)))
+        if not 1 <= Cc <= 16:
+            raise ValueError("sample_attrs: %s has %d channels, expected 1 to 16" % (k, Cc))
+        src.append(a)
+        dims += [kind, Cc, H, W]
+        out[k] = torch.empty(N, Cc, dtype=F32, device=dev)
+    if N == 0:
+        return out
+    n = len(names)
+    sp = (C.c_void_p * n)(*[a.data_ptr() for a in src])
+    op = (C.c_void_p * n)(*[out[k].data_ptr() for k in names])
+    dm = (C.c_int * (4 * n))(*[int(d) for d in dims])
+    ctx.check(ctx.lib.utx_sample_attrs(ctx.handle, ptr(_i(faces)) if faces is not None else None, ptr(_i(faces_2d)) if faces_2d is not None else None,
+                                       ptr(_f(uvs_2d)) if uvs_2d is not None else None, F if F is not None else 1, ptr(face_index), ptr(uvw), N, n, sp, dm, op,
+                                       ctx.stream()))
+    return out
+
+
 # ---- atlas post-processing.  Every image is interleaved [H,W,C] f32, 1 <= C <= CHANNELS_MAX, each channel on its own: a channel's result does not depend on
 # C or on where in the image it sits.  C == 3 goes through the 3-channel entries of the C ABI, any other C through the *_c entries (one library routine behind both).
 CHANNELS_MAX = 16

@@ -6,7 +6,9 @@ sampling are HIP kernels (csrc/sampling.hip) and need the GPU.  Two things are b
   * sample_surface's random stream -- the reference draws from the CUDA generator; here sample i reads Philox4x32-10 with key (seed_lo, seed_hi) and
     counter (i, 0, 0, 0), each word x giving (x >> 8) * 2^-24;
   * the first farthest point -- fpsample's start is not pinned (the package is absent); here it is index 0 unless the caller names another.
-Prefix sums (edge lengths, face weights) accumulate in float64 and round to float32 per element, as torch.cumsum does on the CPU."""
+Prefix sums (edge lengths, face weights) accumulate in float64 and round to float32 per element, as torch.cumsum does on the CPU.
+The second half of the file is the rest of that package: spatial_sampling.py (sample_spatial, sample_near_surface, on ops.closest_point in place of cuBVH [3p]),
+uv_sampling.py with PBRMesh.__call__ (sample_pbr_mesh, pbr_attributes) and texture_sampling of __init__.py:76-121."""
 import math
 import os
 from time import perf_counter
@@ -145,5 +147,162 @@ def geometry_sampling(input_mesh_path, sharp_path, coarse_path, scale=1.0, N=10_
     for path, pts in ((sharp_path, edge_points), (coarse_path, surface_points)):
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         meshes.save_ply(path, pts.cpu().numpy() if pts is not None else np.zeros((0, 3), np.float32))
+    time_log["export point cloud"] = perf_counter() - t0
+    return time_log
+
+
+# ---- spatial sampling (geometry/sampling/spatial_sampling.py) and material sampling (uv_sampling.py, PBRMesh.__call__, texture_sampling) ----
+# Three readings of the reference are kept as they stand, on purpose:
+#   * sample_spatial draws from [0, 1)^3 (torch.rand), whatever the mesh's bounding box is;
+#   * sample_near_surface's vertex normals are the normalised sum of the UNIT face normals (its own scatter_add), not the area weighting used elsewhere;
+#   * PBRMesh.__call__ hands the interpolated uv to grid_sample as the grid coordinate itself -- the map from [0, 1] to [-1, 1] is trimesh_to_pbr_mesh's, done once
+#     when a mesh is converted (pbr_mesh_from_textured below), not the lookup's.
+# The random stream is sample_surface's with another stream id: counter (i, 1, 0, 0) for sample_spatial, (i, 2, 0, 0) for the near-surface deltas.
+def _bvh_for(vertices, faces, bvh):
+    from . import ops
+    if bvh is not None:
+        return bvh
+    return ops.BVH(vertices.float().contiguous(), faces.to(torch.int32).contiguous())
+
+
+def _project(bvh, samples):
+    from . import ops
+    out = ops.closest_point(bvh, samples, want=("face", "uvw"))
+    return samples, out["face"].long(), out["uvw"]
+
+
+def sample_spatial(vertices, faces, bvh=None, N=10_000_000, seed=666):
+    """spatial_sampling.py:11-37: N uniform points and their projection onto the mesh.  The points are drawn from [0, 1)^3, exactly as the reference's
+    torch.rand((N, 3)) -- NOT from the mesh's bounding box; that quirk is kept.  bvh: an ops.BVH of (vertices, faces), built when None (the reference takes a
+    cuBVH [3p]).  -> samples [N,3] f32, face_index [N] int64, face_uvw [N,3] f32 (the nearest face and the weights of its corners, ops.closest_point)."""
+    from . import ops
+    bvh = _bvh_for(vertices, faces, bvh)
+    with torch.cuda.device(vertices.device):
+        samples = ops.sample_offsets(N, 666 if seed is None else seed, 1)
+    return _project(bvh, samples)
+
+
+def unit_normal_vertex_normals(vertices, faces, normals=None):
+    """spatial_sampling.py:70-76: per vertex the normalised sum of the UNIT normals of its faces (torch ops)"""
+    faces = faces.long()
+    if normals is None:
+        areas = torch.linalg.cross(vertices[faces[:, 1]] - vertices[faces[:, 0]], vertices[faces[:, 2]] - vertices[faces[:, 0]], dim=-1)
+        normals = torch.nn.functional.normalize(areas, dim=-1)
+    vn = torch.zeros((vertices.shape[0], 3, 3), dtype=vertices.dtype, device=vertices.device)
+    vn.scatter_add_(0, faces.unsqueeze(-1).expand(faces.shape[0], 3, 3), normals.unsqueeze(1).expand(faces.shape[0], 3, 3))
+    return torch.nn.functional.normalize(vn.sum(dim=1), dim=-1)
+
+
+def sample_near_surface(vertices, faces, areas=None, normals=None, bvh=None, N=10_000_000, N_radio=1.1, seed=666, distance_threhold=1.0, depth=8):
+    """spatial_sampling.py:40-91, line by line: int(N * N_radio) surface samples (sample_surface, stream 0) cut to N, each moved along the interpolated vertex
+    normal (unit_normal_vertex_normals; the interpolated normal is not renormalised) by threshold * (2 r - 1) per component, r from stream 2 and
+    threshold = distance_threhold * 2 / 2^depth; then projected back onto the mesh.  -> samples [N,3] f32, face_index [N] int64, face_uvw [N,3] f32."""
+    from . import ops
+    seed = 666 if seed is None else seed
+    threshold = distance_threhold * (2.0 / (2 ** depth))
+    v = vertices.float()
+    faces = faces.long()
+    if areas is None:
+        areas = torch.linalg.cross(v[faces[:, 1]] - v[faces[:, 0]], v[faces[:, 2]] - v[faces[:, 0]], dim=-1)
+    if normals is None:
+        normals = torch.nn.functional.normalize(areas, dim=-1)
+    vnormal = unit_normal_vertex_normals(v, faces, normals)
+    bvh = _bvh_for(v, faces, bvh)
+    base, face_index, face_uvw = sample_surface(v, faces, areas=areas, N=int(N * N_radio), seed=seed)
+    base, face_index, face_uvw = base[:N], face_index[:N], face_uvw[:N]          # maybe fewer than N, as in the reference
+    n = base.shape[0]
+    samples = ops.sample_offsets(n, seed, 2, base=base.contiguous(), faces=faces.to(torch.int32).contiguous(), face_index=face_index.to(torch.int32).contiguous(),
+                                 uvw=face_uvw.contiguous(), vnormal=vnormal.contiguous(), threshold=threshold)
+    return _project(bvh, samples)
+
+
+PBR_DEFAULT = {"albedo": (0.0, 0.0, 0.0), "metallic": (0.0,), "roughness": (1.0,), "bump": (0.0, 0.0, 0.0)}          # PBRDefault, mesh/structure_v2.py:18-22
+PBR_KEYS = ("albedo", "metallic", "roughness", "bump")
+
+
+def pbr_mesh_from_textured(mesh, device="cuda:0"):
+    """a TexturedMesh (or anything with .vertices .faces .uv .texture and optional .metallic_roughness .bump) -> the dict of arrays sample_pbr_mesh takes, as
+    trimesh_to_pbr_mesh builds a PBRMesh (mesh/structure_v2.py:282-303): uvs_2d = uv * 2 - 1, faces_2d = faces, images / 255 with the bottom row first,
+    metallic = the blue and roughness = the green channel of the metallic-roughness image."""
+    def img(a):
+        return torch.from_numpy(np.array(a)).to(device).float().div(255.0).flip(0).contiguous()
+    out = {"vertices": torch.from_numpy(np.ascontiguousarray(mesh.vertices, dtype=np.float32)).to(device),
+           "faces": torch.from_numpy(np.ascontiguousarray(mesh.faces).astype(np.int64)).to(device)}
+    if getattr(mesh, "uv", None) is not None:
+        out["uvs_2d"] = torch.from_numpy(np.ascontiguousarray(mesh.uv, dtype=np.float32)).to(device).mul(2.0).sub(1.0)
+        out["faces_2d"] = out["faces"]
+    if getattr(mesh, "texture", None) is not None:
+        out["albedo"] = img(mesh.texture)
+    if getattr(mesh, "metallic_roughness", None) is not None:
+        mr = img(mesh.metallic_roughness)
+        out["metallic"], out["roughness"] = mr[..., [2]].contiguous(), mr[..., [1]].contiguous()
+    if getattr(mesh, "bump", None) is not None:
+        out["bump"] = img(mesh.bump)
+    return out
+
+
+def pbr_attributes(mesh, face_index, face_uvw):
+    """PBRMesh.__call__ (mesh/structure_v2.py:105-135) on a dict of arrays: vertices, faces and optionally uvs_2d, faces_2d, albedo, metallic, roughness, bump --
+    each attribute a constant [C], a per-vertex array [V,C] or a texture [H,W,C]; a missing one takes PBRDefault's value.  One launch (ops.sample_attrs).
+    -> dict name -> [N,C] f32."""
+    from . import ops
+    dev = face_index.device
+    attrs = {}
+    for k in PBR_KEYS:
+        a = mesh.get(k)
+        attrs[k] = torch.tensor(PBR_DEFAULT[k], dtype=torch.float32, device=dev) if a is None else a.to(dev).float().contiguous()
+    i32 = lambda t: t.to(dev).to(torch.int32).contiguous() if t is not None else None
+    uvs, faces_2d = mesh.get("uvs_2d"), mesh.get("faces_2d")
+    if uvs is None or faces_2d is None:          # a uv table without its index (or the reverse) serves no lookup: PBRMesh reads them only for a texture, and only together
+        uvs = faces_2d = None
+    return ops.sample_attrs(attrs, face_index.to(torch.int32).contiguous(), face_uvw.float().contiguous(), faces=i32(mesh["faces"]), faces_2d=i32(faces_2d),
+                            uvs_2d=uvs.to(dev).float().contiguous() if uvs is not None else None)
+
+
+def sample_pbr_mesh(pbr_mesh, N=10_000_000, seed=666):
+    """uv_sampling.py:9-26: N surface samples (sample_surface) and the material at each.  pbr_mesh: a dict of arrays (pbr_attributes) or a TexturedMesh
+    (converted by pbr_mesh_from_textured).  A list of meshes (the reference's PBRScene) is not built.
+    -> samples [N,3] f32, face_index [N] int64, face_attr {albedo [N,3], metallic [N,1], roughness [N,1], bump [N,3]}."""
+    if isinstance(pbr_mesh, (list, tuple)):
+        raise NotImplementedError("sample_pbr_mesh takes one mesh; a list of meshes (PBRScene) is not built")
+    if not isinstance(pbr_mesh, dict):
+        pbr_mesh = pbr_mesh_from_textured(pbr_mesh)
+    v, faces = pbr_mesh["vertices"].float(), pbr_mesh["faces"].long()
+    samples, face_index, face_uvw = sample_surface(v, faces, areas=pbr_mesh.get("areas"), N=N, seed=seed)
+    return samples, face_index, pbr_attributes(pbr_mesh, face_index, face_uvw)
+
+
+def albedo_to_u8(albedo):
+    """round(clamp(albedo, 0, 1) * 255) as uint8 -- this build's rule for the colours of a point cloud"""
+    return torch.round(albedo.clamp(0.0, 1.0) * 255.0).to(torch.uint8)
+
+
+def texture_sampling(input_mesh_path, output_mesh_path, N=10_000_000, device="cuda:0"):
+    """texture_sampling (geometry/sampling/__init__.py:76-121): a coloured point cloud of a textured mesh, N surface samples with the albedo at each, written as
+    binary PLY.  The mesh is read by meshes.load_glb and its material by meshes.load_material_textures.  Colours are round(clamp(albedo, 0, 1) * 255): the
+    reference hands the float albedo to trimesh.Trimesh(vertex_colors=...), whose conversion to uint8 is third-party and unpinned."""
+    from types import SimpleNamespace
+    from . import meshes
+    time_log = dict()
+    t0 = perf_counter()
+    verts, faces, uvs, texture = meshes.load_glb(input_mesh_path)
+    if meshes._glb_chunks(input_mesh_path)[0].get("materials"):
+        tex = meshes.load_material_textures(input_mesh_path)
+    else:                                        # a file without a material is an untextured mesh: PBRDefault's values throughout
+        tex = {"metallic_roughness": None, "normal": None}
+    time_log["load scene"] = perf_counter() - t0
+    t0 = perf_counter()
+    mesh = pbr_mesh_from_textured(SimpleNamespace(vertices=verts, faces=faces, uv=uvs, texture=texture, metallic_roughness=tex["metallic_roughness"],
+                                                  bump=tex["normal"]), device=device)
+    time_log["move mesh to gpu"] = perf_counter() - t0
+    t0 = perf_counter()
+    samples, face_index, face_attr = sample_pbr_mesh(mesh, N=N, seed=666)
+    time_log["sample on mesh"] = perf_counter() - t0
+    t0 = perf_counter()
+    samples_np, colors = samples.cpu().numpy(), albedo_to_u8(face_attr["albedo"]).cpu().numpy()
+    time_log["move samples to cpu"] = perf_counter() - t0
+    t0 = perf_counter()
+    os.makedirs(os.path.dirname(os.path.abspath(output_mesh_path)), exist_ok=True)
+    meshes.save_ply(output_mesh_path, samples_np, colors_u8=colors)
     time_log["export point cloud"] = perf_counter() - t0
     return time_log
