@@ -636,7 +636,7 @@ int utx_visible_vertices(utx_ctx* ctx, const unsigned char* mask, const int* fac
 /* Nearest surface point: what the reference takes from cuBVH.unsigned_distance(points, return_uvw=True) [3p] (geometry/sampling/spatial_sampling.py:36,90).
  * points [N][3] f32 -> dist [N] f32 (the distance itself, sqrtf(d2)), face [N] i32, uvw [N][3] f32, closest [N][3] f32; face, uvw, closest and visited may be null.
  * Per triangle: tri_closest(p, v0, v1, v2) -> (d2, u, v, w), the Voronoi-region form of Ericson, Real-Time Collision Detection, 5.1.5, in fp32 with fixed
- *   summation order (csrc/bvh_device.h; tests/closest_point_ref.py repeats it bit for bit): (u, v, w) weigh (v0, v1, v2), closest = (u v0 + v v1) + w v2,
+ *   summation order (csrc/bvh_device.h; oracle/closest_point_ref.py repeats it bit for bit): (u, v, w) weigh (v0, v1, v2), closest = (u v0 + v v1) + w v2,
  *   d2 = |p - closest|^2 summed (x^2 + y^2) + z^2; every weight is >= 0; a quotient with a denominator not > 0 is 0 (a zero-length edge is its end point);
  *   a zero-area face (interior denominator va + vb + vc not > 0) gives the nearest point of its three edge segments AB, AC, BC, the first on a tie.
  * Per query: the face with the smallest d2, ties to the smallest face id -- independent of the order in which the triangles are met.  A subtree is skipped

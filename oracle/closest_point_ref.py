@@ -1,6 +1,6 @@
-"""Nearest-surface queries and the spatial / material sampling built on them (TEST INFRASTRUCTURE ONLY): the numpy restatements that
-tests/test_closest_point_gpu.py and tests/test_spatial_sampling_gpu.py hold the HIP kernels to, the float64 brute force they are both bounded against, and the
-test meshes.  tests/test_closest_point_cpu.py and tests/test_spatial_sampling_cpu.py pin them first, without a GPU.
+"""Nearest-surface queries (TEST INFRASTRUCTURE ONLY): the numpy restatement that tests/test_closest_point_gpu.py and tests/test_spatial_sampling_gpu.py hold
+the HIP kernels to, the float64 brute force they are both bounded against, and the test meshes.  tests/test_closest_point_cpu.py pins them first, without a
+GPU.  The sampling built on the queries is restated in oracle/sampling_ref.py.
 
 tri_closest_f32 repeats csrc/bvh_device.h::tri_closest operation for operation in float32 (numpy rounds every product and sum on its own, as the kernel does
 without contraction): the Voronoi-region form of Ericson, Real-Time Collision Detection, 5.1.5.  brute_f64 is NOT that formula: it drops p onto the face's plane,
@@ -21,16 +21,11 @@ The bound on | |p - q32| - d64 |.  Write u = 2^-24, S = max|p| + max|v| (every d
       | |p - q32| - d64 |  <=  11 u S + 4 * 48 u S + 4 * 12 u S  <  256 u S  =  BOUND_U * u * S.
 The same bound holds for the float64 distance from p to the returned face (it is at most |p - q32| + (a) and at least d64) and for |p - sum uvw_k v_k| evaluated
 in float64 (the returned dist without the roundings of (a))."""
-import os
-
 import numpy as np
-
-from oracle import sampling_ref as S_
 
 F32 = np.float32
 U = 2.0 ** -24
 BOUND_U = 256.0
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def scene_scale(points, verts):
@@ -269,81 +264,3 @@ def queries(name, N):
         pts[7, 1] = np.nan
         pts[N - 2, 2] = np.inf
     return pts
-
-
-# ---- the random stream and the arithmetic of sample_spatial / sample_near_surface ----
-def uniforms(N, seed, stream_id):
-    """Philox4x32-10, key (seed_lo, seed_hi), counter (i, stream_id, 0, 0): words 0..2 -> (x >> 8) * 2^-24 -> [N,3] f32"""
-    ctr = np.zeros((N, 4), np.uint32)
-    ctr[:, 0] = np.arange(N)
-    ctr[:, 1] = stream_id
-    key = np.broadcast_to(np.array([seed & 0xffffffff, (seed >> 32) & 0xffffffff], np.uint32), (N, 2))
-    return ((S_.philox4x32_10(ctr, key)[:, :3] >> np.uint32(8)).astype(F32) * F32(2.0 ** -24)).astype(F32)
-
-
-def vertex_normals_unit(verts, faces):
-    """spatial_sampling.py:70-76: the normalised sum of the UNIT face normals (torch ops in float32; compared with a tolerance where it is compared at all)"""
-    import torch
-    v, f = torch.from_numpy(np.asarray(verts, F32)), torch.from_numpy(np.asarray(faces).astype(np.int64))
-    areas = torch.linalg.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]], dim=-1)
-    normals = torch.nn.functional.normalize(areas, dim=-1)
-    vn = torch.zeros((v.shape[0], 3, 3), dtype=v.dtype)
-    vn.scatter_add_(0, f.unsqueeze(-1).expand(f.shape[0], 3, 3), normals.unsqueeze(1).expand(f.shape[0], 3, 3))
-    return torch.nn.functional.normalize(vn.sum(dim=1), dim=-1).numpy()
-
-
-def near_surface_offsets(base, faces, face_index, uvw, vnormal, r, threshold):
-    """spatial_sampling.py:87-89 in float32: n = (vn0 u + vn1 v) + vn2 w;  base + (threshold * (r * 2 - 1)) * n"""
-    f = np.asarray(faces)[face_index]
-    uvw, vn = np.asarray(uvw, F32), np.asarray(vnormal, F32)
-    n = (vn[f[:, 0]] * uvw[:, 0:1] + vn[f[:, 1]] * uvw[:, 1:2]) + vn[f[:, 2]] * uvw[:, 2:3]
-    return (np.asarray(base, F32) + (F32(threshold) * (np.asarray(r, F32) * F32(2) - F32(1))) * n).astype(F32), n.astype(F32)
-
-
-# ---- PBRMesh.__call__: the three kinds of attribute ----
-def vertex_attr(attr, faces, face_index, uvw):
-    f = np.asarray(faces)[face_index]
-    a, uvw = np.asarray(attr, F32), np.asarray(uvw, F32)
-    return ((a[f[:, 0]] * uvw[:, 0:1] + a[f[:, 1]] * uvw[:, 1:2]) + a[f[:, 2]] * uvw[:, 2:3]).astype(F32)
-
-
-def grid_reflect_coord(g, size, dtype=np.float64):
-    """grid_sample's coordinate rule for align_corners=False, padding_mode='reflection': unnormalise, reflect about -0.5 and size - 0.5, clip to [0, size - 1]"""
-    g = np.asarray(g, dtype)
-    x = ((g + dtype(1)) * dtype(size) - dtype(1)) / dtype(2)
-    x = np.abs(x - dtype(-0.5))
-    extra, flips = np.fmod(x, dtype(size)), np.floor(x / dtype(size))
-    x = np.where(np.fmod(flips, dtype(2)) == 0, extra + dtype(-0.5), (dtype(size) - extra) + dtype(-0.5))
-    return np.minimum(dtype(size - 1), np.maximum(x, dtype(0))).astype(dtype)
-
-
-def texture_attr(tex, uvs_2d, faces_2d, face_index, uvw, dtype=np.float64):
-    """uv = (uv0 u + uv1 v) + uv2 w in float32 (as the kernel forms it), then the bilinear lookup in `dtype` with the uv itself as the grid coordinate
-    -> values [N,C], and the coordinate pair (ix, iy) for the bound"""
-    g = np.asarray(faces_2d)[face_index]
-    t, uvw = np.asarray(uvs_2d, F32), np.asarray(uvw, F32)
-    uv = (t[g[:, 0]] * uvw[:, 0:1] + t[g[:, 1]] * uvw[:, 1:2]) + t[g[:, 2]] * uvw[:, 2:3]
-    tex = np.asarray(tex, dtype)
-    H, W = tex.shape[:2]
-    ix, iy = grid_reflect_coord(uv[:, 0], W, dtype), grid_reflect_coord(uv[:, 1], H, dtype)
-    x0, y0 = np.floor(ix), np.floor(iy)
-    fx, fy = ix - x0, iy - y0
-    jx0, jy0 = x0.astype(int), y0.astype(int)
-    jx1, jy1 = np.minimum(jx0 + 1, W - 1), np.minimum(jy0 + 1, H - 1)          # a tap beyond the last texel has weight 0 after the clip
-    o = dtype(1)
-    out = (tex[jy0, jx0] * ((o - fx) * (o - fy))[:, None] + tex[jy0, jx1] * (fx * (o - fy))[:, None] + tex[jy1, jx0] * ((o - fx) * fy)[:, None] +
-           tex[jy1, jx1] * (fx * fy)[:, None])
-    return out, uv, ix, iy
-
-
-# ---- fixture G22 (tests/golden/make_golden_spatial_sampling.py) ----
-def g22():
-    return np.load(os.path.join(GOLD, "g22_spatial_sampling.npz"))
-
-
-def tex_bound(tex):
-    """G18's bilinear bound (14 M + 4 (W + H) R) u -- M the largest texel, R the texels' range -- with the reflection fold added: the fold is a subtraction, a
-    quotient and a sum more on a coordinate of up to twice the size, another 4 (W + H) R u"""
-    t = np.asarray(tex, np.float64) / 255.0
-    H, W = t.shape[:2]
-    return (14.0 * np.abs(t).max() + 8.0 * (W + H) * (t.max() - t.min())) * U

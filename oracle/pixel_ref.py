@@ -1,6 +1,6 @@
 """Numpy mirror (TEST INFRASTRUCTURE ONLY) of unitex_amd/csrc/shade_device.h: each per-pixel primitive of the geometry and shading kernels once --
-barycentric interpolation, length and normalise, the grid_sample lookups (bilinear with zero padding or reflection, nearest) and nvdiffrast's wrap
-lookup.  Every function takes `dtype`: np.float32 evaluates the device expression in the device's order, every operation rounded on its own (numpy
+barycentric interpolation, length and normalise, the grid_sample lookups (bilinear with zero padding or reflection, nearest), nvdiffrast's wrap
+lookup and the overlay / blending epilogue of the two bakes.  Every function takes `dtype`: np.float32 evaluates the device expression in the device's order, every operation rounded on its own (numpy
 contracts nothing), np.float64 is the yardstick the counted bounds are measured from.
 
 The order of the roundings is the point.  torch's scalar and device grid_sample kernels unnormalise as ((g + 1) * size - 1) / 2, every operation
@@ -19,6 +19,11 @@ def bary_w(rast, dtype=F32):  # sd_bary_w
     return u, v, (dtype(1.0) - u) - v
 
 
+def interp_corners(attr, corners, u, v, w):  # sd_interp1
+    """(a0*u + a1*v) + a2*w with a_k = attr[corners[...,k]] ([...,C]) and the weights [...,1], in attr's dtype"""
+    return (attr[corners[..., 0]] * u + attr[corners[..., 1]] * v) + attr[corners[..., 2]] * w
+
+
 def interp(attr, rast, faces, dtype=F32):  # sd_interp / utx_interpolate
     """(a0*u + a1*v) + a2*((1-u)-v) in `dtype`, zeros where empty; attr [V,C] -> ([...,C], coverage [...])"""
     attr = np.asarray(attr, dtype)
@@ -26,7 +31,7 @@ def interp(attr, rast, faces, dtype=F32):  # sd_interp / utx_interpolate
     cov = tid >= 0
     f = np.asarray(faces)[np.where(cov, tid, 0)]
     u, v, w = bary_w(rast, dtype)
-    out = (attr[f[..., 0]] * u + attr[f[..., 1]] * v) + attr[f[..., 2]] * w
+    out = interp_corners(attr, f, u, v, w)
     return np.where(cov[..., None], out, dtype(0.0)).astype(dtype), cov
 
 
@@ -48,14 +53,15 @@ def grid_unnormalize(g, size, dtype=F32):  # grid_unnormalize
     return ((np.asarray(g, dtype) + dtype(1.0)) * dtype(size) - dtype(1.0)) * dtype(0.5)
 
 
-def reflect_index(g, size, dtype=F32):  # vb_reflect_index
-    """padding_mode='reflection': unnormalise, reflect about [-0.5, size - 0.5], clip to [0, size - 1]"""
-    x = np.abs(grid_unnormalize(g, size, dtype) + dtype(0.5))
+def reflect_index(g, size, dtype=F32):  # grid_reflect_index
+    """padding_mode='reflection': unnormalise, reflect about [-0.5, size - 0.5], clip to [0, size - 1]; the parity of the flips in `dtype`, fmax / fmin as fmaxf / fminf"""
     span = dtype(size)
-    extra = np.fmod(x, span)
-    flips = np.floor(x / span).astype(np.int64)
-    x = np.where(flips % 2 == 1, (span - extra) - dtype(0.5), extra - dtype(0.5)).astype(dtype)
-    return np.minimum(dtype(size - 1), np.maximum(x, dtype(0)))
+    with np.errstate(over="ignore", invalid="ignore"):
+        x = np.abs(grid_unnormalize(g, size, dtype) + dtype(0.5))
+        extra = np.fmod(x, span)
+        even = np.fmod(np.floor(x / span), dtype(2.0)) == 0
+        x = np.where(even, extra - dtype(0.5), (span - extra) - dtype(0.5)).astype(dtype)
+    return np.fmin(dtype(size - 1), np.fmax(x, dtype(0)))
 
 
 def grid_tap(img, y, x, dtype=F32):  # grid_tap
@@ -123,3 +129,19 @@ def sample_planar(img, gx, gy, padding="zeros", dtype=F32):  # the lookups of ut
     index = reflect_index if padding == "reflection" else grid_unnormalize
     hwc = np.moveaxis(img, 0, -1)
     return np.moveaxis(grid_blend(hwc, index(gx, img.shape[2], dtype), index(gy, img.shape[1], dtype), dtype), -1, 0)
+
+
+# ---- the overlay / blending epilogue of the two bakes
+def bake_epilogue(acc, wacc, base, overlay_confidence, blending, blending_confidence, dtype=F32):  # sd_bake_epilogue
+    """-> (overlay, blended): acc / wacc where wacc > overlay_confidence; then, where wacc <= blending_confidence, 'soft': (base * (conf - wacc) + overlay) / conf,
+    'hard': base.  The thresholds are float32 values in either dtype: a float32 tensor is compared with a Python number in float32"""
+    acc, wacc, base = np.asarray(acc, dtype), np.asarray(wacc, dtype), np.asarray(base, dtype)
+    oc, bc = dtype(F32(overlay_confidence)), dtype(F32(blending_confidence))
+    with np.errstate(divide="ignore", invalid="ignore"):
+        over = np.where(wacc > oc, acc / wacc, acc)
+        out = over
+        if blending == "soft":
+            out = np.where(wacc <= bc, (base * (bc - wacc) + over) / bc, over)
+        elif blending == "hard":
+            out = np.where(wacc <= bc, base, over)
+    return over.astype(dtype), out.astype(dtype)

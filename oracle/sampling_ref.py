@@ -1,11 +1,14 @@
-"""Geometry sampling for the field stage (TEST INFRASTRUCTURE ONLY): the numpy restatements that tests/test_sampling_gpu.py holds the HIP kernels to.
-Each is pinned in tests/test_sampling_cpu.py before the GPU test leans on it: the equal-steps sampler to fixture G14's captured samples
-(tests/golden/make_golden_sampling.py) bit for bit, Philox4x32-10 to the Random123 known-answer vectors, the farthest-point sampling to an example
-worked by hand."""
+"""Geometry sampling for the field stage (TEST INFRASTRUCTURE ONLY): the numpy restatements that tests/test_sampling_gpu.py and
+tests/test_spatial_sampling_gpu.py hold the HIP kernels of csrc/sampling.hip to.  Each is pinned on the CPU before a GPU test leans on it.  tests/test_sampling_cpu.py:
+the equal-steps sampler to fixture G14's captured samples (tests/golden/make_golden_sampling.py) bit for bit, Philox4x32-10 to the Random123 known-answer vectors, the
+farthest-point sampling to an example worked by hand.  tests/test_spatial_sampling_cpu.py: the near-surface offsets and the material lookup to fixture G22, the texture lookup to grid_sample."""
 import os
 
 import numpy as np
 
+from .pixel_ref import grid_blend, interp_corners, reflect_index
+
+U = 2.0 ** -24
 GOLD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 F32 = np.float32
 
@@ -66,11 +69,7 @@ def philox4x32_10(counter, key):
 
 
 def sample_surface_ref(verts, faces, cum, N, seed):
-    ctr = np.zeros((N, 4), np.uint32)
-    ctr[:, 0] = np.arange(N)
-    key = np.broadcast_to(np.array([seed & 0xffffffff, (seed >> 32) & 0xffffffff], np.uint32), (N, 2))
-    r = philox4x32_10(ctr, key)
-    u01 = (r >> np.uint32(8)).astype(F32) * F32(2.0 ** -24)
+    u01 = uniforms(N, seed, 0)
     pick = u01[:, 0] * cum[-1]
     face = np.minimum(np.searchsorted(cum, pick, side="left"), len(cum) - 1)
     u, v = u01[:, 1].copy(), u01[:, 2].copy()
@@ -112,3 +111,80 @@ def fps_ref(pos, M, mask=None, start=0):
         cand = mind >= 0
         mind[cand] = np.minimum(mind[cand], d2[cand])
     return out_idx, out_d2
+
+
+# ---- the random stream and the arithmetic of sample_spatial / sample_near_surface ----
+def uniforms(N, seed, stream_id):
+    """Philox4x32-10, key (seed_lo, seed_hi), counter (i, stream_id, 0, 0): words 0..2 -> (x >> 8) * 2^-24 -> [N,3] f32"""
+    ctr = np.zeros((N, 4), np.uint32)
+    ctr[:, 0] = np.arange(N)
+    ctr[:, 1] = stream_id
+    key = np.broadcast_to(np.array([seed & 0xffffffff, (seed >> 32) & 0xffffffff], np.uint32), (N, 2))
+    return ((philox4x32_10(ctr, key)[:, :3] >> np.uint32(8)).astype(F32) * F32(2.0 ** -24)).astype(F32)
+
+
+def vertex_normals_unit(verts, faces):
+    """spatial_sampling.py:70-76: the normalised sum of the UNIT face normals (torch ops in float32; compared with a tolerance where it is compared at all)"""
+    import torch
+    v, f = torch.from_numpy(np.asarray(verts, F32)), torch.from_numpy(np.asarray(faces).astype(np.int64))
+    areas = torch.linalg.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]], dim=-1)
+    normals = torch.nn.functional.normalize(areas, dim=-1)
+    vn = torch.zeros((v.shape[0], 3, 3), dtype=v.dtype)
+    vn.scatter_add_(0, f.unsqueeze(-1).expand(f.shape[0], 3, 3), normals.unsqueeze(1).expand(f.shape[0], 3, 3))
+    return torch.nn.functional.normalize(vn.sum(dim=1), dim=-1).numpy()
+
+
+def near_surface_offsets(base, faces, face_index, uvw, vnormal, r, threshold):
+    """spatial_sampling.py:87-89 in float32: n = (vn0 u + vn1 v) + vn2 w;  base + (threshold * (r * 2 - 1)) * n"""
+    n = vertex_attr(vnormal, faces, face_index, uvw)
+    return (np.asarray(base, F32) + (F32(threshold) * (np.asarray(r, F32) * F32(2) - F32(1))) * n).astype(F32), n.astype(F32)
+
+
+# ---- PBRMesh.__call__: the three kinds of attribute ----
+def vertex_attr(attr, faces, face_index, uvw):
+    """(attr[f0] u + attr[f1] v) + attr[f2] w in float32, f = faces[face_index]"""
+    uvw = np.asarray(uvw, F32)
+    return interp_corners(np.asarray(attr, F32), np.asarray(faces)[face_index], uvw[:, 0:1], uvw[:, 1:2], uvw[:, 2:3]).astype(F32)
+
+
+def texture_attr(tex, uvs_2d, faces_2d, face_index, uvw, dtype=np.float64):
+    """uv = (uv0 u + uv1 v) + uv2 w in float32 (as the kernel forms it), then grid_sample's reflection lookup in `dtype` with the uv itself as the grid
+    coordinate (pixel_ref.reflect_index + grid_blend; np.float32: the kernel's own bits) -> values [N,C], the uv, and the coordinate pair (ix, iy)"""
+    uv = vertex_attr(uvs_2d, faces_2d, face_index, uvw)
+    tex = np.asarray(tex, dtype)
+    H, W = tex.shape[:2]
+    ix, iy = reflect_index(uv[:, 0], W, dtype), reflect_index(uv[:, 1], H, dtype)
+    return grid_blend(tex, ix, iy, dtype), uv, ix, iy
+
+
+# ---- fixture G22 (tests/golden/make_golden_spatial_sampling.py) ----
+def g22():
+    return np.load(os.path.join(GOLD, "g22_spatial_sampling.npz"))
+
+
+def tex_bound(tex):
+    """G18's bilinear bound (14 M + 4 (W + H) R) u -- M the largest texel, R the texels' range -- with the reflection fold added: the fold is a subtraction, a
+    quotient and a sum more on a coordinate of up to twice the size, another 4 (W + H) R u"""
+    t = np.asarray(tex, np.float64) / 255.0
+    H, W = t.shape[:2]
+    return (14.0 * np.abs(t).max() + 8.0 * (W + H) * (t.max() - t.min())) * U
+
+
+# ---- the inputs of the bit-for-bit texture-lookup tests (tests/test_spatial_sampling_{cpu,gpu}.py)
+REFLECT_SIZES = ((1, 1), (1, 4), (3, 2))          # (H, W)
+REFLECT_HUGE = 1e12                                # a flip count past int32: the GPU is compared with the restatement there, torch is not asked
+
+
+def reflect_case(H, W, N=257):
+    """-> (textures {C: [H,W,C] f32} for C = 1, 3, 4, with negative texels, faces_2d [N,3], uvs_2d [N,2], face_index [N], uvw [N,3]): sample i reads uvs_2d[i] through
+    the face (i, i, i) with weights (1, 0, 0).  Per axis of S texels: the texel centres, the outer half-pixel rim (it clips onto the border texel: ix == S - 1, the
+    absent tap), the edges, two points moved one to four spans (of 2) out on either side (odd and even flips), +-REFLECT_HUGE, the rest uniform in [-7, 7]"""
+    rng = np.random.default_rng(22 + 100 * H + W)
+    tex = {C: (rng.uniform(0.1, 1.0, (H, W, C)) * np.where(np.arange(C) % 2 == 0, -1.0, 1.0)).astype(F32) for C in (1, 3, 4)}          # even channels negative
+
+    def axis(S, shift):
+        g = [(2 * i + 1) / S - 1 for i in range(S)] + [-1 + 0.5 / S, 1 - 0.5 / S, -1 + 0.25 / S, 1 - 0.25 / S, -1.0, 1.0, REFLECT_HUGE, -REFLECT_HUGE]
+        g += [b + s * 2 * k for b in (0.3, -0.55) for k in (1, 2, 3, 4) for s in (1, -1)]
+        return np.roll(np.concatenate([np.array(g, F32), rng.uniform(-7.0, 7.0, N - len(g)).astype(F32)]), shift)
+    idx = np.arange(N, dtype=np.int32)
+    return tex, np.stack([idx, idx, idx], -1), np.stack([axis(W, 0), axis(H, 40)], -1), idx, np.tile(np.array([1, 0, 0], F32), (N, 1))

@@ -21,10 +21,11 @@ import os
 
 import numpy as np
 
-from oracle import uv_project_ref as UVP
-from oracle.gbuffer_ref import map_bound
+from . import uv_project_ref as UVP
+from .gbuffer_ref import map_bound
+from .pixel_ref import bake_epilogue
 
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+GOLD = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests", "golden")
 F32, F64, U = np.float32, np.float64, 2.0 ** -24
 _FIX = {}
 
@@ -117,17 +118,9 @@ def bake_bound(images, wmap, map_Kd, weights, use_alpha, detail):
 def epilogue(acc, wacc, map_Kd, rast2d, overlay_confidence, blending, blending_confidence, inpainting_confidence):
     """remapping_uv_texture :205-228 in float32 -> (overlay, blended [Th,Tw,4], inpaint mask uint8 [Th,Tw]); blending None | 'soft' | 'hard'.  The thresholds
     are float32 values: a float32 tensor is compared with a Python number in float32"""
-    acc, wacc, kd = np.asarray(acc, F32), np.asarray(wacc, F32), np.asarray(map_Kd, F32)
-    oc, bc, ic = F32(overlay_confidence), F32(blending_confidence), F32(inpainting_confidence)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        over = np.where(wacc > oc, acc / wacc, acc)
-        out = over
-        if blending == "soft":
-            out = np.where(wacc <= bc, (kd * (bc - wacc) + over) / bc, over)
-        elif blending == "hard":
-            out = np.where(wacc <= bc, kd, over)
-    mask = (wacc[..., 0] <= ic) & (np.asarray(rast2d)[..., 3] > 0)
-    return over.astype(F32), out.astype(F32), mask.astype(np.uint8)
+    over, out = bake_epilogue(acc, wacc, map_Kd, overlay_confidence, blending, blending_confidence, F32)
+    mask = (np.asarray(wacc, F32)[..., 0] <= F32(inpainting_confidence)) & (np.asarray(rast2d)[..., 3] > 0)
+    return over, out, mask.astype(np.uint8)
 
 
 def epilogue_bound(acc, wacc, map_Kd, e_acc, e_w, overlay_confidence, blending, blending_confidence):

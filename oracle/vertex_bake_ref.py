@@ -9,7 +9,7 @@ import os
 import numpy as np
 import torch
 
-from .pixel_ref import sample_planar
+from .pixel_ref import bake_epilogue, sample_planar
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -63,15 +63,6 @@ def weight_maps(cosn, cam_nz=None, r=0, dtype=np.float32):
     return dict(out=np.stack([c0, dilate(alpha, r)], -1), arccos=a, grad=grad, alpha=alpha)
 
 
-def sample_reflect(img, gx, gy, dtype=np.float32):
-    """img [C,H,W] at NDC (gx, gy) [N] -> [C,N], grid_sample(bilinear, padding_mode='reflection', align_corners=False)"""
-    return sample_planar(img, gx, gy, "reflection", dtype)
-
-
-def sample_zeros(img, gx, gy, dtype=np.float32):
-    return sample_planar(img, gx, gy, "zeros", dtype)
-
-
 def _rows(m, p, dt):
     """m [4,4] applied to the rows of p [N,4]: ((m0 x + m1 y) + m2 z) + m3 w per output component"""
     m = m.astype(dt)
@@ -98,8 +89,8 @@ def vertex_project(v_pos, visible, xform, proj, images, wmap, v_rgb, weights, us
         vis = visible[b].astype(bool)
         on = vis & inside
         gx, gy = np.where(on, g[:, 0], 0).astype(dt), np.where(on, g[:, 1], 0).astype(dt)
-        s = sample_reflect(images[b], gx, gy, dt)
-        q = sample_zeros(np.moveaxis(wmap[b], -1, 0), gx, gy, dt)
+        s = sample_planar(images[b], gx, gy, "reflection", dt)
+        q = sample_planar(np.moveaxis(wmap[b], -1, 0), gx, gy, "zeros", dt)
         a = s[3] if use_alpha else np.ones_like(s[3])
         c = (s[:3] * a[None] + rgb0.T * (dt(1) - a)[None]).T
         cs2 = q[0] * q[0]
@@ -116,16 +107,8 @@ def vertex_project(v_pos, visible, xform, proj, images, wmap, v_rgb, weights, us
 def epilogue(acc, wacc, v_rgb, overlay_confidence, blending, blending_confidence, inpainting_confidence, dtype=np.float32):
     """remapping_vertex_color :326-343 -> (overlay, blended, inpaint mask uint8 [V]); blending None | 'soft' | 'hard'.  The thresholds are float32 values in
     either dtype: a float32 tensor is compared with a Python number in float32"""
-    dt = dtype
-    acc, wacc, rgb0 = acc.astype(dt), wacc.astype(dt), v_rgb.astype(dt)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        over = np.where(wacc > dt(np.float32(overlay_confidence)), acc / wacc, acc)
-    out = over
-    if blending == "soft":
-        out = np.where(wacc <= dt(np.float32(blending_confidence)), (rgb0 * (dt(np.float32(blending_confidence)) - wacc) + over) / dt(np.float32(blending_confidence)), over)
-    elif blending == "hard":
-        out = np.where(wacc <= dt(np.float32(blending_confidence)), rgb0, over)
-    return over, out, (wacc[:, 0] <= dt(np.float32(inpainting_confidence))).astype(np.uint8)
+    over, out = bake_epilogue(acc, wacc, v_rgb, overlay_confidence, blending, blending_confidence, dtype)
+    return over, out, (np.asarray(wacc, dtype)[:, 0] <= dtype(np.float32(inpainting_confidence))).astype(np.uint8)
 
 
 def project_bound(v_pos, visible, xform, proj, images, wmap, v_rgb, weights):

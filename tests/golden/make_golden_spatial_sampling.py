@@ -10,7 +10,7 @@
            it as grid_sample's grid coordinate as it stands, so coordinates fall outside [-1, 1] (asserted) and the reflection padding is exercised.
   G22 (b)  sample_near_surface (geometry/sampling/spatial_sampling.py:40-91) on the 80-face icosphere, N = 257, depth 4.  Seams, for the duration of the call:
            * module `cubvh` [3p, absent] is a stub whose unsigned_distance records the samples it is handed and answers with a float64 brute force
-             (tests/closest_point_ref.py::brute_f64_face: distance and face by the plane-foot formula, and whether the face is the only one within 1024 u * scale of that distance);
+             (oracle/closest_point_ref.py::brute_f64_face: distance and face by the plane-foot formula, and whether the face is the only one within 1024 u * scale of that distance);
            * torch.Generator(device='cuda') is a dummy, and torch.rand(..., device='cuda') hands back the fixture's own uniform numbers (Philox stream 2) on the CPU;
            * sample_surface is replaced by one that returns the stored surface samples (oracle/sampling_ref.py's restatement, int(N * 1.1) of them).
            Everything else -- threshold, vertex normals, the cut to N, the interpolated normal, the offset -- is the reference's own code on CPU tensors.
@@ -44,7 +44,7 @@ def _picks(F):
 
 def g22(out):
     from oracle import sampling_ref as SR
-    from tests import closest_point_ref as CR
+    from oracle import closest_point_ref as CR
     fix = {}
     # ---- (a) PBRMesh.__call__
     S2 = importlib.import_module("TextureTools.texturetools.mesh.structure_v2")
@@ -73,7 +73,7 @@ def g22(out):
     v, f = CR.icosphere(1)
     n_surf = int(N_NEAR * N_RADIO)
     base, bface, buvw = SR.sample_surface_ref(v, f, SR.face_weights_cum(v, f), n_surf, SEED)
-    r = CR.uniforms(N_NEAR, SEED, 2)
+    r = SR.uniforms(N_NEAR, SEED, 2)
     handed, named = [], []
 
     class cuBVH:

@@ -1,10 +1,10 @@
-"""CPU pins of tests/closest_point_ref.py, before the GPU tests lean on it: the float32 restatement of tri_closest against the float64 brute force (another
+"""CPU pins of oracle/closest_point_ref.py, before the GPU tests lean on it: the float32 restatement of tri_closest against the float64 brute force (another
 formula) within the bound its docstring counts, the properties the C ABI promises (weights, ties), and the Philox words of streams 1 and 2 against a
 pure-Python Philox4x32-10."""
 import numpy as np
 import pytest
 
-from tests import closest_point_ref as R
+from oracle import closest_point_ref as R, sampling_ref as S
 
 F32 = np.float32
 
@@ -73,9 +73,9 @@ def test_philox_known_answers_and_the_words_of_streams_1_and_2():
     assert _philox_py([0xffffffff] * 4, [0xffffffff] * 2) == [0x408f276d, 0x41c83b0e, 0xa20bc7c6, 0x6d5451fd]
     for seed in (666, 0x123456789abcdef0):
         for sid in (1, 2):
-            u = R.uniforms(300, seed, sid)
+            u = S.uniforms(300, seed, sid)
             for i in (0, 1, 63, 64, 255, 256, 299):
                 w = _philox_py([i, sid, 0, 0], [seed & 0xffffffff, seed >> 32])
                 assert [float(x) for x in u[i]] == [(x >> 8) * 2.0 ** -24 for x in w[:3]]
             assert (u >= 0).all() and (u < 1).all()
-    assert not (R.uniforms(64, 666, 1) == R.uniforms(64, 666, 2)).all()
+    assert not (S.uniforms(64, 666, 1) == S.uniforms(64, 666, 2)).all()

@@ -1,5 +1,5 @@
 """GPU tests of utx_bvh_closest_point (csrc/bvh_device.h, csrc/bvh.hip) through the C ABI: the tree walk, the exhaustive twin (flags & 1) and the numpy
-restatement of tests/closest_point_ref.py (pinned on the CPU in tests/test_closest_point_cpu.py) agree BIT FOR BIT; all three are bounded against a float64 brute
+restatement of oracle/closest_point_ref.py (pinned on the CPU in tests/test_closest_point_cpu.py) agree BIT FOR BIT; all three are bounded against a float64 brute
 force by another formula with the bound that module's docstring counts."""
 import ctypes as C
 import functools
@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import closest_point_ref as R
+from oracle import closest_point_ref as R
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32

@@ -1,8 +1,11 @@
-"""CPU pins of the sampling restatements of tests/closest_point_ref.py against fixture G22 (tests/golden/make_golden_spatial_sampling.py: the reference's own
+"""CPU pins of the sampling restatements of oracle/sampling_ref.py against fixture G22 (tests/golden/make_golden_spatial_sampling.py: the reference's own
 PBRMesh.__call__ and sample_near_surface on CPU tensors), before tests/test_spatial_sampling_gpu.py leans on them."""
 import numpy as np
+import pytest
+import torch
 
-from tests import closest_point_ref as R
+from oracle import closest_point_ref as CP, sampling_ref as R
+from oracle.pixel_ref import grid_unnormalize
 
 F32 = np.float32
 
@@ -31,11 +34,11 @@ def test_near_surface_arithmetic_equals_the_reference_bit_for_bit():
     assert np.abs(vn.astype(np.float64) - f["b_vertex_normals"]).max() <= 4 * R.U
     assert np.abs(np.linalg.norm(vn.astype(np.float64), axis=1) - 1).max() <= 4 * R.U
     # the faces the float64 brute force named behind the cubvh seam (another formula) are the float32 restatement's
-    dist, d2, face, uvw, q = R.closest_point_f32(f["b_samples"], f["b_verts"], f["b_faces"])
+    dist, d2, face, uvw, q = CP.closest_point_f32(f["b_samples"], f["b_verts"], f["b_faces"])
     alone = f["b_face_alone"]
     assert alone.mean() > 0.5 and (face[alone] == f["b_face"][alone]).all()
     # where several faces are nearest (outside a convex edge) either may be named: the distances agree
-    assert np.abs(dist.astype(np.float64) - R.face_dist_f64(f["b_samples"], f["b_verts"], f["b_faces"], f["b_face"])).max() <= R.BOUND_U * R.U * R.scene_scale(f["b_samples"], f["b_verts"])
+    assert np.abs(dist.astype(np.float64) - CP.face_dist_f64(f["b_samples"], f["b_verts"], f["b_faces"], f["b_face"])).max() <= CP.BOUND_U * R.U * CP.scene_scale(f["b_samples"], f["b_verts"])
 
 
 def test_material_lookup_equals_the_reference():
@@ -57,12 +60,31 @@ def test_material_lookup_equals_the_reference():
     assert np.abs(mapped - f["a_out8_albedo"]).max() > 0.05
 
 
+@pytest.mark.parametrize("H,W", R.REFLECT_SIZES)
+def test_float32_texture_lookup_against_grid_sample(H, W):
+    """the float32 restatement that tests/test_spatial_sampling_gpu.py holds utx_sample_attrs' texture lookup to bit for bit, on that test's inputs, against torch's
+    CPU grid_sample(reflection): within 4 u max|texel|, the bound of tests/test_vertex_bake_cpu.py's reflection lookup.  +-1e12 is left to the GPU test"""
+    tex, f2, uvs, fi, uvw = R.reflect_case(H, W)
+    assert len(fi) == 257 and (np.abs(uvs) == F32(R.REFLECT_HUGE)).any(1).sum() == 4
+    keep = (np.abs(uvs) < R.REFLECT_HUGE).all(1)
+    grid = torch.from_numpy(uvs[keep])[None, :, None]
+    for c, t in tex.items():
+        got, uv, ix, iy = R.texture_attr(t, uvs, f2, fi, uvw, F32)
+        assert t.shape == (H, W, c) and t.min() < 0 and np.isfinite(got).all()        # negative texels; 1e12 lands on the texture too
+        assert (_bits(uv) == _bits(uvs)).all()                                        # weights (1, 0, 0): the hand-made uv reaches the lookup as it stands
+        flips = np.floor(np.abs(grid_unnormalize(uvs[keep, 0], W) + F32(0.5)) / F32(W))
+        assert (ix[keep] == W - 1).any() and (iy[keep] == H - 1).any() and {0, 1, 2, 3, 4} <= set(flips.astype(int).tolist())      # the absent tap; odd and even flips
+        want = torch.nn.functional.grid_sample(torch.from_numpy(t).permute(2, 0, 1)[None], grid, mode="bilinear", padding_mode="reflection", align_corners=False)
+        err = np.abs(got[keep].astype(np.float64) - want[0, :, :, 0].T.numpy()).max()
+        print("%d x %d x %d: %.2f u (bound %.2f u)" % (H, W, c, err / R.U, 4 * np.abs(t).max()))
+        assert err <= 4 * R.U * np.abs(t).max()
+
+
 def test_sample_attrs_refuses_a_uv_table_without_its_index_before_any_device_call():
     """faces_2d and uvs_2d go together (the kernel reads one through the other): one without the other is -2 from the C ABI, refused before anything touches a
     device -- so it runs here, with made-up addresses that are never read -- and a ValueError from ops"""
     import ctypes as C
 
-    import pytest
     from unitex_amd import _lib
     from unitex_amd.texturetools import ops
     lib = _lib.load_library()

@@ -1,5 +1,5 @@
 """GPU tests of sample_spatial, sample_near_surface, the material lookup at surface samples and texture_sampling (csrc/sampling.hip: utx_sample_offsets,
-utx_sample_attrs; csrc/bvh.hip: utx_bvh_closest_point) through the C ABI, against the restatements of tests/closest_point_ref.py and fixture G22 (both pinned on the
+utx_sample_attrs; csrc/bvh.hip: utx_bvh_closest_point) through the C ABI, against the restatements of oracle/sampling_ref.py and fixture G22 (both pinned on the
 CPU in tests/test_spatial_sampling_cpu.py).  Everything float is compared BIT FOR BIT unless a test says why not."""
 import ctypes as C
 
@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import closest_point_ref as R
+from oracle import closest_point_ref as CP, sampling_ref as R
 
 pytestmark = pytest.mark.gpu
 g22, tex_bound = R.g22, R.tex_bound
@@ -27,7 +27,7 @@ def _bits(a):
 
 
 def _ico():
-    v, f = R.mesh("ico")
+    v, f = CP.mesh("ico")
     return v, f, _cu(v), _cu(f, torch.int64)
 
 
@@ -37,7 +37,7 @@ def _projection_is_closest_point(samples, face_index, face_uvw, vt, ft):
     o = ops.closest_point(bvh, samples, want=("face", "uvw"))
     assert face_index.dtype == torch.int64 and torch.equal(face_index, o["face"].long()) and torch.equal(face_uvw, o["uvw"])
     # and the tree walk's answer is the restatement's
-    ref = R.closest_point_f32(samples.cpu().numpy(), vt.cpu().numpy(), ft.cpu().numpy())
+    ref = CP.closest_point_f32(samples.cpu().numpy(), vt.cpu().numpy(), ft.cpu().numpy())
     assert (face_index.cpu().numpy() == ref[2]).all() and (_bits(face_uvw.cpu().numpy()) == _bits(ref[3])).all()
 
 
@@ -65,7 +65,7 @@ def test_sample_near_surface_follows_the_reference_line_by_line():
     base, bface, buvw = ops.sample_surface(vt, ft.to(torch.int32).contiguous(), cum.contiguous(), int(N * 1.1), 666)
     b2 = sampling.sample_surface(vt, ft, N=int(N * 1.1), seed=666)
     assert torch.equal(b2[0], base) and torch.equal(b2[1], bface.long()) and torch.equal(b2[2], buvw)
-    ref_base = R.S_.sample_surface_ref(v, f, cum.cpu().numpy(), int(N * 1.1), 666)
+    ref_base = R.sample_surface_ref(v, f, cum.cpu().numpy(), int(N * 1.1), 666)
     assert (_bits(base.cpu().numpy()) == _bits(ref_base[0])).all() and (bface.cpu().numpy() == ref_base[1]).all()
     # vertex normals: torch ops (a scatter_add of unit face normals, whose order of summation is torch's) -- a few u of the CPU's
     vn = sampling.unit_normal_vertex_normals(vt, ft)
@@ -121,6 +121,19 @@ def test_sample_attrs_equals_pbr_mesh_call():
     assert (bare["albedo"] == 0).all() and (bare["metallic"] == 0).all() and (bare["roughness"] == 1).all() and (bare["bump"] == 0).all()
     with pytest.raises(NotImplementedError):
         sampling.sample_pbr_mesh([mesh, mesh], N=4)
+
+
+@pytest.mark.parametrize("H,W", R.REFLECT_SIZES)
+def test_texture_lookup_is_the_float32_restatement_bit_for_bit(H, W):
+    """utx_sample_attrs' texture lookup against oracle.sampling_ref.texture_attr in float32 (pinned against torch's grid_sample in tests/test_spatial_sampling_cpu.py),
+    by uint32 view: C = 1, 3 and 4 channels in one launch, N = 257 (one block and one thread), the uv of reflect_case, +-1e12 (a flip count past int32) included"""
+    from unitex_amd.texturetools import ops
+    tex, f2, uvs, fi, uvw = R.reflect_case(H, W, N)
+    got = ops.sample_attrs({"c%d" % c: _cu(t) for c, t in tex.items()}, _cu(fi), _cu(uvw), faces_2d=_cu(f2), uvs_2d=_cu(uvs))
+    for c, t in tex.items():
+        want = R.texture_attr(t, uvs, f2, fi, uvw, F32)[0]
+        differ = np.flatnonzero((_bits(got["c%d" % c].cpu().numpy()) != _bits(want)).any(1))
+        assert want.shape == (N, c) and len(differ) == 0, (c, uvs[differ[:8]].tolist())
 
 
 def test_texture_sampling_round_trip(tmp_path):

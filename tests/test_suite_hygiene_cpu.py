@@ -89,6 +89,12 @@ def test_no_module_imports_a_test_module(tmp_path):
     assert [name for _, name in _test_module_imports(str(p))] == ["tests.test_a_cpu", "tests.test_b_gpu", "tests.test_c_cpu"]
 
 
+def test_the_top_level_of_tests_holds_test_modules_only():
+    # a restatement, a bound or a test input that a test needs is a library: it lives under oracle/, not beside the test modules
+    bad = sorted(f for f in os.listdir(HERE) if os.path.isfile(os.path.join(HERE, f)) and not (f in ("conftest.py", "fakes.py", "__init__.py") or (f.startswith("test_") and f.endswith(".py"))))
+    assert not bad, "tests/ holds only test_*.py, conftest.py, fakes.py and __init__.py at its top level: %s" % bad
+
+
 def test_product_and_tool_modules_define_no_name_twice():
     # the same accident in the product package, the oracle, bench.py or a probe script would be as silent
     bad = []

@@ -1,12 +1,12 @@
 """Blended UV texture bake (unitex_amd/texturetools/remapping_uv.py, utx_uv_bake / utx_uv_dilation_step), CPU side: the numpy restatement of
-tests/uv_bake_ref.py against the reference's own arrays (fixture G21) within the counted bounds, stage by stage; uv_dilation's restatement against the
+oracle/uv_bake_ref.py against the reference's own arrays (fixture G21) within the counted bounds, stage by stage; uv_dilation's restatement against the
 reference's step built from torch's avg_pool2d; every refusal and the signatures; the C ABI's -2 returns before any device call."""
 import inspect
 
 import numpy as np
 import pytest
 
-from tests import uv_bake_ref as R
+from oracle import uv_bake_ref as R
 
 U = R.U
 

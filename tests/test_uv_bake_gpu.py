@@ -1,11 +1,11 @@
 """Blended UV texture bake on the GPU: utx_uv_bake and utx_uv_dilation_step through the C ABI and the wrappers of ops (uv_bake, uv_dilation), and
 remapping_uv.project_uv_texture / remapping_uv_texture / uv_dilation against the reference's own arrays (fixture G21) within the counted bounds of
-tests/uv_bake_ref.py.  The kernels are held to the float32 restatement, and utx_uv_bake to the composition of the existing ops, BIT FOR BIT."""
+oracle/uv_bake_ref.py.  The kernels are held to the float32 restatement, and utx_uv_bake to the composition of the existing ops, BIT FOR BIT."""
 import numpy as np
 import pytest
 import torch
 
-from tests import uv_bake_ref as R
+from oracle import uv_bake_ref as R
 
 pytestmark = pytest.mark.gpu
 U = R.U

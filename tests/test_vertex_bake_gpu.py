@@ -300,7 +300,7 @@ def test_remapping_end_to_end_against_the_restatement(perspective, reference_tra
     skip = np.zeros(acc.shape[0], bool)
     for b in range(6):
         g = R.ndc(case["v_pos"], xform[b], proj[b])
-        near = R.sample_zeros(R.dilate(edge[b:b + 1], 1), np.nan_to_num(g[:, 0]).clip(-2, 2), np.nan_to_num(g[:, 1]).clip(-2, 2))[0] > 0
+        near = R.sample_planar(R.dilate(edge[b:b + 1], 1), np.nan_to_num(g[:, 0]).clip(-2, 2), np.nan_to_num(g[:, 1]).clip(-2, 2))[0] > 0
         skip |= near & vis[b].astype(bool)
     assert skip.sum() <= 0.02 * vis.any(0).sum()
     assert (np.abs(acc.astype(np.float64) - want_acc).max(1) <= 2 * e_acc)[~skip].all() and (np.abs(wacc.astype(np.float64) - want_w)[:, 0] <= 2 * e_w)[~skip].all()

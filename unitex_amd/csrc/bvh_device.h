@@ -316,7 +316,7 @@ struct utx_bvh {
 // ---- NEAREST SURFACE POINT (utx_bvh_closest_point): what the reference takes from cuBVH.unsigned_distance(points, return_uvw=True) [3p, absent]
 // (geometry/sampling/spatial_sampling.py:36,90).  A point query, no ray.
 // tri_closest: the Voronoi-region form of Ericson, Real-Time Collision Detection, 5.1.5, in fp32 with every sum in a fixed order, so that a numpy float32
-// restatement (tests/closest_point_ref.py) repeats it bit for bit.  (u, v, w) weigh (v0, v1, v2); q = (u v0 + v v1) + w v2; d2 = |p - q|^2 summed like dot3.
+// restatement (oracle/closest_point_ref.py) repeats it bit for bit.  (u, v, w) weigh (v0, v1, v2); q = (u v0 + v v1) + w v2; d2 = |p - q|^2 summed like dot3.
 // Beyond Ericson: a quotient whose denominator is not > 0 is 0 (a zero-length edge counts as its end point); the interior weights are clamped (v to [0, 1],
 // w to [0, 1 - v], u = (1 - v) - w), so every weight is >= 0; and where the interior denominator va + vb + vc (|ab x ac|^2) is not > 0 -- a zero-area face, whose
 // regions mean nothing -- the answer is the nearest of the three edge segments AB, AC, BC, the first of them on a tie.

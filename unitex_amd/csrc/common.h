@@ -43,6 +43,11 @@ __device__ __forceinline__ float wave_max(float v) {
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
 }
+// *counter += the number of lanes of this wave with `flag` set: one ballot, one atomic from the wave's first lane (every lane of the wave calls it)
+__device__ __forceinline__ void wave_count_add(int* counter, bool flag) {
+    const unsigned long long ballot = __ballot(flag);
+    if ((threadIdx.x & (UTX_WAVE - 1)) == 0 && ballot) atomicAdd(counter, __popcll(ballot));
+}
 
 // Bijective XCD-aware remap (8 XCDs; block b is observed to land on XCD b % 8 -- speed only,
 // never correctness). Returns the logical work id for hardware block id `bid` so that each

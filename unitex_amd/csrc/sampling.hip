@@ -11,8 +11,10 @@
 //   d2 = (dx*dx + dy*dy) + dz*dz in float32 (knn.hip's convention); arg-max with ties towards the lower index.
 // mind[i] < 0 marks a point outside the candidate set (masked out, non-finite, already picked, padding): distances are >= 0 or +inf, never NaN
 // (the coordinates of a candidate are finite), so one float carries both.
+// The numpy restatements the tests hold these kernels to are oracle/sampling_ref.py's.
 #include "common.h"
 #include "kernels.h"
+#include "shade_device.h"
 #include <float.h>
 
 #define FPS_THREADS 512
@@ -272,11 +274,10 @@ __global__ __launch_bounds__(256) void sample_offsets_kernel(const float* __rest
     }
     const int a = faces[3 * (long)f], b = faces[3 * (long)f + 1], c = faces[3 * (long)f + 2];
     const float u = uvw[3 * i], v = uvw[3 * i + 1], w = uvw[3 * i + 2];
+    float n[3];
+    sd_interp<3>(vnormal + 3 * (long)a, vnormal + 3 * (long)b, vnormal + 3 * (long)c, u, v, w, n);
 #pragma unroll
-    for (int d = 0; d < 3; ++d) {
-        const float n = (vnormal[3 * (long)a + d] * u + vnormal[3 * (long)b + d] * v) + vnormal[3 * (long)c + d] * w;
-        out[3 * i + d] = base[3 * i + d] + (threshold * (r[d] * 2.0f - 1.0f)) * n;
-    }
+    for (int d = 0; d < 3; ++d) out[3 * i + d] = base[3 * i + d] + (threshold * (r[d] * 2.0f - 1.0f)) * n[d];
 }
 
 extern "C" int utx_launch_sample_offsets(const float* base, const int* faces, int F, const int* face_index, const float* uvw, const float* vnormal, const float* uniforms,
@@ -295,34 +296,9 @@ extern "C" int utx_launch_sample_offsets(const float* base, const int* faces, in
 //   a texture [H][W][C], C <= 4             -> uv = (uvs_2d[g0] * u + uvs_2d[g1] * v) + uvs_2d[g2] * w with g = faces_2d[f], then grid_sample as the reference calls
 //                                              it: THE UV ITSELF IS THE GRID COORDINATE (no map of [0, 1] to [-1, 1]), bilinear, align_corners=False,
 //                                              padding_mode='reflection'.
-// The lookup below is grid_sample's own rule (unnormalise, reflect about -0.5 and size - 0.5, clip to [0, size - 1], four taps weighted by the opposite corner's
-// area); the taps of shade_device.h are zero-padding and wrap, another rule.
+// The interpolations are sd_interp's and the lookup is grid_reflect_taps / grid_tap / grid_blend of shade_device.h; oracle/sampling_ref.py restates them.
 struct SampleAttr { const float* src; float* out; int kind, C, H, W; };
 struct SampleAttrs { SampleAttr a[UTX_SAMPLE_ATTRS_MAX]; int n; };
-__device__ __forceinline__ float gs_reflect_coord(float g, int size) {
-    float x = ((g + 1.0f) * (float)size - 1.0f) / 2.0f;
-    const float mn = -0.5f, span = (float)size;
-    x = fabsf(x - mn);
-    const float extra = fmodf(x, span);
-    const float flips = floorf(x / span);
-    x = fmodf(flips, 2.0f) == 0.0f ? extra + mn : (span - extra) + mn;
-    return fminf((float)(size - 1), fmaxf(x, 0.0f));
-}
-__device__ __forceinline__ void gs_reflect_bilinear(const float* __restrict__ tex, int H, int W, int C, float gx, float gy, float* o) {
-    const float ix = gs_reflect_coord(gx, W), iy = gs_reflect_coord(gy, H);
-    const float x0 = floorf(ix), y0 = floorf(iy);
-    const float x1 = x0 + 1.0f, y1 = y0 + 1.0f;
-    const float nw = (x1 - ix) * (y1 - iy), ne = (ix - x0) * (y1 - iy), sw = (x1 - ix) * (iy - y0), se = (ix - x0) * (iy - y0);
-    const int jx0 = (int)x0, jy0 = (int)y0, jx1 = jx0 + 1, jy1 = jy0 + 1;      // jx0 in [0, W - 1], jy0 in [0, H - 1] after the clip
-    const bool inx1 = jx1 < W, iny1 = jy1 < H;
-    for (int c = 0; c < C; ++c) {
-        float s = tex[((long)jy0 * W + jx0) * C + c] * nw;
-        if (inx1) s += tex[((long)jy0 * W + jx1) * C + c] * ne;
-        if (iny1) s += tex[((long)jy1 * W + jx0) * C + c] * sw;
-        if (inx1 && iny1) s += tex[((long)jy1 * W + jx1) * C + c] * se;
-        o[c] = s;
-    }
-}
 __global__ __launch_bounds__(256) void sample_attrs_kernel(const int* __restrict__ faces, const int* __restrict__ faces_2d, const float* __restrict__ uvs_2d, int F,
                                                            const int* __restrict__ face_index, const float* __restrict__ uvw, long N, SampleAttrs P) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -330,11 +306,10 @@ __global__ __launch_bounds__(256) void sample_attrs_kernel(const int* __restrict
     const int f = face_index[i];
     const bool ok = f >= 0 && f < F;
     const float u = uvw[3 * i], v = uvw[3 * i + 1], w = uvw[3 * i + 2];
-    float gx = 0.f, gy = 0.f;
+    float g[2] = {0.f, 0.f};
     if (ok && faces_2d && uvs_2d) {      // the launcher admits the two only together, and a texture only with both
         const long g0 = faces_2d[3 * (long)f], g1 = faces_2d[3 * (long)f + 1], g2 = faces_2d[3 * (long)f + 2];
-        gx = (uvs_2d[2 * g0] * u + uvs_2d[2 * g1] * v) + uvs_2d[2 * g2] * w;
-        gy = (uvs_2d[2 * g0 + 1] * u + uvs_2d[2 * g1 + 1] * v) + uvs_2d[2 * g2 + 1] * w;
+        sd_interp<2>(uvs_2d + 2 * g0, uvs_2d + 2 * g1, uvs_2d + 2 * g2, u, v, w, g);
     }
     for (int k = 0; k < P.n; ++k) {
         const SampleAttr A = P.a[k];
@@ -345,11 +320,14 @@ __global__ __launch_bounds__(256) void sample_attrs_kernel(const int* __restrict
             for (int c = 0; c < A.C; ++c) o[c] = 0.f;
         } else if (A.kind == 1) {
             const long a0 = faces[3 * (long)f], a1 = faces[3 * (long)f + 1], a2 = faces[3 * (long)f + 2];
-            for (int c = 0; c < A.C; ++c) o[c] = (A.src[a0 * A.C + c] * u + A.src[a1 * A.C + c] * v) + A.src[a2 * A.C + c] * w;
+            for (int c = 0; c < A.C; ++c) o[c] = sd_interp1(A.src[a0 * A.C + c], A.src[a1 * A.C + c], A.src[a2 * A.C + c], u, v, w);
         } else {
-            float t[4];
-            gs_reflect_bilinear(A.src, A.H, A.W, A.C, gx, gy, t);
-            for (int c = 0; c < A.C; ++c) o[c] = t[c];
+            long t[4]; float tw[4];
+            grid_reflect_taps(A.H, A.W, g[0], g[1], t, tw);
+            for (int c = 0; c < A.C; ++c) {
+                const float* ch = A.src + c;
+                o[c] = grid_blend(grid_tap(ch, A.C, t[0]), grid_tap(ch, A.C, t[1]), grid_tap(ch, A.C, t[2]), grid_tap(ch, A.C, t[3]), tw);
+            }
         }
     }
 }

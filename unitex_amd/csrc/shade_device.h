@@ -1,7 +1,8 @@
-// Per-pixel device primitives of the geometry and shading kernels (raster.hip, gbuffer.hip, pbr.hip, backproject.hip): the barycentric
-// interpolation of utx_interpolate, the wrap-addressed bilinear texture fetch of utx_texture_shade, the grid_sample and nvdiffrast lookups of an
-// image at an NDC coordinate, length / normalisation with F.normalize's eps, and the float -> uint8 conversion.  These kernels are held to bit-exact parity with the oracle and with each other, so each expression
-// is written ONCE, here, with its sums in one fixed order.  Every translation unit that includes this header is compiled with
+// Per-pixel device primitives of the geometry and shading kernels (raster.hip, gbuffer.hip, pbr.hip, backproject.hip, vertex_bake.hip, uv_bake.hip,
+// sampling.hip): the barycentric interpolation of utx_interpolate, the wrap-addressed bilinear texture fetch of utx_texture_shade, the grid_sample
+// (zero padding: grid_taps; reflection padding: grid_reflect_index / grid_reflect_taps) and nvdiffrast lookups of an image at an NDC coordinate, length /
+// normalisation with F.normalize's eps, the overlay / blending epilogue of the two bakes (sd_bake_epilogue), and the float -> uint8 conversion.
+// These kernels are held to bit-exact parity with the oracle and with each other, so each expression is written ONCE, here, with its sums in one fixed order.  Every translation unit that includes this header is compiled with
 // -ffp-contract=off: each operation below is one correctly rounded fp32 operation and a value is bit-identical wherever it is computed.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -75,8 +76,8 @@ __device__ __forceinline__ void sd_tex3_wrap_const(const float k[3], int Ht, int
 // grid_sample(bilinear, zero padding, align_corners=False): the four tap offsets in pixels (x0, y0), (x0 + 1, y0), (x0, y0 + 1), (x0 + 1, y0 + 1), -1 for a
 // tap outside the view (it reads as zero), and their weights
 __device__ __forceinline__ float grid_unnormalize(float g, int size) { return ((g + 1.0f) * (float)size - 1.0f) * 0.5f; }
-__device__ __forceinline__ void grid_taps(int H, int W, float gx, float gy, long o[4], float w[4]) {
-    const float ix = grid_unnormalize(gx, W), iy = grid_unnormalize(gy, H);
+// the taps and weights around the pixel coordinate (ix, iy): both paddings end here
+__device__ __forceinline__ void grid_taps_at(int H, int W, float ix, float iy, long o[4], float w[4]) {
     const float fx = floorf(ix), fy = floorf(iy);
     const int x0 = (int)fx, y0 = (int)fy;
     const float tx = ix - fx, ty = iy - fy;
@@ -87,6 +88,18 @@ __device__ __forceinline__ void grid_taps(int H, int W, float gx, float gy, long
         o[k] = (x < 0 || x >= W || y < 0 || y >= H) ? -1 : (long)y * W + x;
     }
 }
+__device__ __forceinline__ void grid_taps(int H, int W, float gx, float gy, long o[4], float w[4]) { grid_taps_at(H, W, grid_unnormalize(gx, W), grid_unnormalize(gy, H), o, w); }
+// grid_sample(bilinear, padding_mode='reflection', align_corners=False) of one axis, as torch's GridSampler.h computes the source index: unnormalise, reflect
+// about [-0.5, size - 0.5] (|x + 0.5|, fmod by the span, an odd number of flips mirrors), back by -0.5, clip to [0, size - 1]: the outer half-pixel rim lands
+// ON the border texel.  The parity of the flips is taken in floating point: defined for every finite g (a count past 2^24 is even; overflow and NaN end on texel 0).
+__device__ __forceinline__ float grid_reflect_index(float g, int size) {
+    const float span = (float)size, in = fabsf(grid_unnormalize(g, size) + 0.5f), extra = fmodf(in, span);
+    const float r = fmodf(floorf(in / span), 2.0f) == 0.0f ? extra - 0.5f : (span - extra) - 0.5f;
+    return fminf((float)(size - 1), fmaxf(r, 0.0f));
+}
+// its taps: grid_taps' outputs, so grid_tap and grid_blend serve both paddings.  x0 + 1 == W (or y0 + 1 == H) happens on the last texel only, with weight
+// exactly 0: the tap is -1 and reads as zero (torch masks it out), so it adds +0.0 -- the sum's bits are those of skipping it unless the partial sum is -0.0
+__device__ __forceinline__ void grid_reflect_taps(int H, int W, float gx, float gy, long o[4], float w[4]) { grid_taps_at(H, W, grid_reflect_index(gx, W), grid_reflect_index(gy, H), o, w); }
 // grid_sample(nearest, zero padding, align_corners=False): the offset of the one tap, the pixel nearest to the sample with halves rounded to even
 // (rintf, as torch's round), -1 outside the image
 __device__ __forceinline__ long grid_nearest(int H, int W, float gx, float gy) {
@@ -158,6 +171,17 @@ __device__ __forceinline__ SdUvView sd_uv_view(float4 r, const int* tri, long F,
 __device__ __forceinline__ bool sd_view_coverage(const float* rast_map, int Hm, int Wm, float gx, float gy) {
     const long o = grid_nearest(Hm, Wm, gx, gy);
     return o >= 0 && rast_map[4 * o + 3] > 0.0f;
+}
+
+// ---- the overlay / blending epilogue of the two bakes (remapping_vertex_color :326-337, remapping_uv_texture :205-217 of the reference), in place on acc:
+// acc / wa where wa > overlay_conf; then, where wa <= blending_conf, blending 1 (soft): (base * (conf - wa) + acc) / conf, 2 (hard): base, 0: nothing
+template <int N>
+__device__ __forceinline__ void sd_bake_epilogue(float* acc, float wa, const float* base, float overlay_conf, int blending, float blending_conf) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+        const float a = wa > overlay_conf ? acc[k] / wa : acc[k];
+        acc[k] = !(blending && wa <= blending_conf) ? a : blending == 1 ? (base[k] * (blending_conf - wa) + a) / blending_conf : base[k];
+    }
 }
 
 // ---- float frame -> uint8: clamp(0, 1) * 255, truncated (astype(uint8))

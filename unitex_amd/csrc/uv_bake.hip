@@ -3,7 +3,7 @@
 //                         followed by the overlay / blending / inpainting-mask epilogue of remapping_uv_texture (:205-228) in the same launch
 //   utx_uv_dilation_step  one _uv_dilation_v2 step of uv_dilation (texture/reprojection/uv_dilation.py:33-50, :80-92), or its closing clamp
 // Built with -ffp-contract=off: every product and sum below is rounded on its own, in the order written, which is the order the restatement
-// (tests/uv_bake_ref.py) and the counted bounds assume.
+// (oracle/uv_bake_ref.py) and the counted bounds assume.
 #include "common.h"
 #include "kernels.h"
 #include "shade_device.h"
@@ -70,15 +70,7 @@ __global__ __launch_bounds__(256) void uv_bake_kernel(const UvBakeParams p) {
     if (p.acc) p.acc[i] = make_float4(acc[0], acc[1], acc[2], acc[3]);
     p.wacc[i] = wa;
     if constexpr (EPILOGUE) {
-        if (wa > p.overlay_conf) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc[k] = acc[k] / wa;
-        }
-        if (p.blending && wa <= p.blending_conf) {
-            const float kk = p.blending_conf - wa;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) acc[k] = p.blending == 1 ? (kd[k] * kk + acc[k]) / p.blending_conf : kd[k];      // soft / hard
-        }
+        sd_bake_epilogue<4>(acc, wa, kd, p.overlay_conf, p.blending, p.blending_conf);
         p.blended[i] = make_float4(acc[0], acc[1], acc[2], acc[3]);
         p.inpaint[i] = (unsigned char)(wa <= p.inpainting_conf && r.w > 0.0f);
     }
@@ -145,8 +137,7 @@ __global__ __launch_bounds__(256) void uv_dilation_step_kernel(const float* col_
         mask_out[i] = (unsigned char)(M > 0.0f);
         open = !(M > 0.0f);
     }
-    const unsigned long long ballot = __ballot(open);
-    if ((threadIdx.x & (UTX_WAVE - 1)) == 0 && ballot) atomicAdd(counter, __popcll(ballot));
+    wave_count_add(counter, open);
 }
 // uv_dilation's last line once the loop has ended: the whole map clamped to [0, 1] (torch.clamp: min(max(x, 0), 1), a NaN stays)
 __global__ __launch_bounds__(256) void uv_dilation_clamp_kernel(const float* col_in, long n, float* col_out) {

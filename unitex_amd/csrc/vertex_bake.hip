@@ -4,7 +4,7 @@
 //                            overlay / blending / inpainting-mask epilogue of remapping_vertex_color (:326-343) in the same launch
 //   utx_vertex_inpaint_step  one Jacobi step of inpainting_vertex_color (:617-622) on a CSR vertex adjacency
 // Built with -ffp-contract=off: every product and sum below is rounded on its own, in the order written, which is the order the restatement
-// (tests/vertex_bake_ref.py) and the counted bounds assume.
+// (oracle/vertex_bake_ref.py) and the counted bounds assume.
 #include "common.h"
 #include "kernels.h"
 #include "shade_device.h"
@@ -66,35 +66,7 @@ extern "C" int utx_launch_view_weight_maps(const float* cosn, const float* cam_n
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-// ---- projection
-// grid_sample(padding_mode='reflection', align_corners=False) of one axis, as torch's GridSampler.h computes the source index: unnormalise, reflect about
-// [-0.5, size - 0.5] (|x + 0.5|, fmod by the span, an odd number of flips mirrors), back by -0.5, then clip to [0, size - 1]: a point of the outer
-// half-pixel rim lands ON the border texel with the fractional weights of the clipped coordinate (weight 1 on the border tap).
-__device__ __forceinline__ float vb_reflect_index(float g, int size) {
-    float in = grid_unnormalize(g, size);
-    const float span = (float)size;
-    in = fabsf(in + 0.5f);
-    const float extra = fmodf(in, span);
-    const int flips = (int)floorf(in / span);
-    in = (flips & 1) ? (span - extra) - 0.5f : extra - 0.5f;
-    return fminf((float)(size - 1), fmaxf(in, 0.0f));
-}
-struct VbTaps { long o[4]; float w[4]; };
-__device__ __forceinline__ VbTaps vb_reflect_taps(int H, int W, float gx, float gy) {
-    const float ix = vb_reflect_index(gx, W), iy = vb_reflect_index(gy, H);
-    const float fx = floorf(ix), fy = floorf(iy);
-    const int x0 = (int)fx, y0 = (int)fy;
-    const float tx = ix - fx, ty = iy - fy;
-    VbTaps t;
-    t.w[0] = (1.0f - tx) * (1.0f - ty); t.w[1] = tx * (1.0f - ty); t.w[2] = (1.0f - tx) * ty; t.w[3] = tx * ty;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {      // x0 + 1 == W (or y0 + 1 == H) happens on the last texel, with weight 0: torch masks that tap out, so does this
-        const int x = x0 + (k & 1), y = y0 + (k >> 1);
-        t.o[k] = (x < 0 || x >= W || y < 0 || y >= H) ? -1 : (long)y * W + x;
-    }
-    return t;
-}
-
+// ---- projection: the image through grid_sample's reflection lookup, the weight map through its zero-padding one (both of shade_device.h)
 struct VbProjectParams {
     const float* v_pos; const unsigned char* visible; const float* xform; const float* proj; const float* images; const float2* wmap;
     const float* v_rgb; const float* weights; float* acc; float* wacc; float* blended; unsigned char* inpaint;
@@ -110,8 +82,8 @@ __global__ __launch_bounds__(256) void vb_vertex_project_kernel(const VbProjectP
     const int v = blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= p.V) return;
     const float px = p.v_pos[3 * (long)v], py = p.v_pos[3 * (long)v + 1], pz = p.v_pos[3 * (long)v + 2];
-    const float r0 = p.v_rgb[3 * (long)v], r1 = p.v_rgb[3 * (long)v + 1], r2 = p.v_rgb[3 * (long)v + 2];
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, wa = 0.f;
+    const float rgb[3] = {p.v_rgb[3 * (long)v], p.v_rgb[3 * (long)v + 1], p.v_rgb[3 * (long)v + 2]};
+    float acc[3] = {0.f, 0.f, 0.f}, wa = 0.f;
     const long plane = (long)p.Hi * p.Wi;
     for (int b = 0; b < p.B; ++b) {
         if (!p.visible[(long)b * p.V + v]) continue;
@@ -121,44 +93,39 @@ __global__ __launch_bounds__(256) void vb_vertex_project_kernel(const VbProjectP
                     hw = vb_row4(T + 12, px, py, pz, 1.0f);
         const float cw = vb_row4(P + 12, hx, hy, hz, hw);
         const float nx = vb_row4(P, hx, hy, hz, hw) / cw, ny = vb_row4(P + 4, hx, hy, hz, hw) / cw;
-        float c0 = r0, c1 = r1, c2 = r2, w = 0.0f;
+        float c[3] = {rgb[0], rgb[1], rgb[2]}, w = 0.0f;
         if (nx > -1.0f && nx < 1.0f && ny > -1.0f && ny < 1.0f) {      // strictly inside; a NaN fails
-            const VbTaps t = vb_reflect_taps(p.Hi, p.Wi, nx, ny);
+            long o[4]; float gw[4];
+            grid_reflect_taps(p.Hi, p.Wi, nx, ny, o, gw);
             const float* img = p.images + 4 * plane * b;
             float s[4];
 #pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const float* pl = img + plane * c;
-                s[c] = grid_blend(grid_tap(pl, 1, t.o[0]), grid_tap(pl, 1, t.o[1]), grid_tap(pl, 1, t.o[2]), grid_tap(pl, 1, t.o[3]), t.w);
+            for (int k = 0; k < 4; ++k) {
+                const float* pl = img + plane * k;
+                s[k] = grid_blend(grid_tap(pl, 1, o[0]), grid_tap(pl, 1, o[1]), grid_tap(pl, 1, o[2]), grid_tap(pl, 1, o[3]), gw);
             }
-            long o[4]; float gw[4];
             grid_taps(p.H, p.W, nx, ny, o, gw);
             const float2* wm = p.wmap + (long)p.H * p.W * b;
             float2 q[4];
 #pragma unroll
             for (int k = 0; k < 4; ++k) q[k] = o[k] < 0 ? make_float2(0.f, 0.f) : wm[o[k]];
-            const float cs = ((q[0].x * gw[0] + q[1].x * gw[1]) + q[2].x * gw[2]) + q[3].x * gw[3];
-            const float al = ((q[0].y * gw[0] + q[1].y * gw[1]) + q[2].y * gw[2]) + q[3].y * gw[3];
+            const float cs = grid_blend(q[0].x, q[1].x, q[2].x, q[3].x, gw), al = grid_blend(q[0].y, q[1].y, q[2].y, q[3].y, gw);
             const float a = p.use_alpha ? s[3] : 1.0f;
             const float ia = 1.0f - a;
-            c0 = s[0] * a + r0 * ia; c1 = s[1] * a + r1 * ia; c2 = s[2] * a + r2 * ia;
+#pragma unroll
+            for (int k = 0; k < 3; ++k) c[k] = s[k] * a + rgb[k] * ia;
             const float cs2 = cs * cs;
             w = (p.weights[b] * (cs2 * cs2)) * (1.0f - al);
         }
-        a0 = a0 + w * c0; a1 = a1 + w * c1; a2 = a2 + w * c2;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) acc[k] = acc[k] + w * c[k];
         wa = wa + w;
     }
-    if (p.acc) { p.acc[3 * (long)v] = a0; p.acc[3 * (long)v + 1] = a1; p.acc[3 * (long)v + 2] = a2; }
+    if (p.acc) { p.acc[3 * (long)v] = acc[0]; p.acc[3 * (long)v + 1] = acc[1]; p.acc[3 * (long)v + 2] = acc[2]; }
     p.wacc[v] = wa;
     if constexpr (EPILOGUE) {
-        if (wa > p.overlay_conf) { a0 = a0 / wa; a1 = a1 / wa; a2 = a2 / wa; }
-        if (p.blending && wa <= p.blending_conf) {
-            if (p.blending == 1) {      // soft: (v_rgb * (conf - w) + acc) / conf
-                const float k = p.blending_conf - wa;
-                a0 = (r0 * k + a0) / p.blending_conf; a1 = (r1 * k + a1) / p.blending_conf; a2 = (r2 * k + a2) / p.blending_conf;
-            } else { a0 = r0; a1 = r1; a2 = r2; }
-        }
-        p.blended[3 * (long)v] = a0; p.blended[3 * (long)v + 1] = a1; p.blended[3 * (long)v + 2] = a2;
+        sd_bake_epilogue<3>(acc, wa, rgb, p.overlay_conf, p.blending, p.blending_conf);
+        p.blended[3 * (long)v] = acc[0]; p.blended[3 * (long)v + 1] = acc[1]; p.blended[3 * (long)v + 2] = acc[2];
         p.inpaint[v] = (unsigned char)(wa <= p.inpainting_conf);
     }
 }
@@ -205,8 +172,7 @@ __global__ __launch_bounds__(256) void vb_inpaint_step_kernel(const int* rowptr,
         else { rgb_out[3 * v] = rgb_in[3 * v]; rgb_out[3 * v + 1] = rgb_in[3 * v + 1]; rgb_out[3 * v + 2] = rgb_in[3 * v + 2]; }
         mask_out[v] = (unsigned char)valid;
     }
-    const unsigned long long ballot = __ballot(valid);
-    if ((threadIdx.x & (UTX_WAVE - 1)) == 0 && ballot) atomicAdd(counter, __popcll(ballot));
+    wave_count_add(counter, valid);
 }
 // arguments checked by utx_vertex_inpaint_step (capi.cpp); zeroes *counter, then one launch.  n == 0 launches nothing (and leaves the counter alone).
 extern "C" int utx_launch_vertex_inpaint_step(const int* rowptr, const int* col, const int* idx, int n, const float* rgb_in, const unsigned char* mask_in,

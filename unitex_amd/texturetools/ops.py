@@ -1101,6 +1101,14 @@ def view_weight_maps(cos_ray_normal, camera_normal=None, r=0, want_arccos=False)
     return (out, arccos) if want_arccos else out
 
 
+def _epilogue_args(epilogue, who):
+    """the `epilogue` dict of vertex_project / uv_bake, checked -> its four C arguments (overlay_conf, blending, blending_conf, inpainting_conf); None: zeros"""
+    e = dict(overlay_confidence=0.0, blending=None, blending_confidence=0.0, inpainting_confidence=0.0) if epilogue is None else epilogue
+    if e["blending"] not in VERTEX_BLENDING:
+        raise ValueError("%s: blending %r (None, 'soft' or 'hard')" % (who, e["blending"]))
+    return float(e["overlay_confidence"]), VERTEX_BLENDING[e["blending"]], float(e["blending_confidence"]), float(e["inpainting_confidence"])
+
+
 def vertex_project(v_pos, visible, xform, proj, images, wmap, v_rgb, weights, use_alpha=True, epilogue=None):
     """utx_vertex_project: v_pos [V,3], visible uint8 [B,V], xform / proj [B,4,4] (the per-view vertex transform and the projection), images
     [B,4,Hi,Wi] rgba, wmap [B,H,W,2] (view_weight_maps), v_rgb [V,3], weights [B] -> (v_rgb_acc [V,3], v_weight_acc [V,1]): the loop of
@@ -1121,13 +1129,10 @@ def vertex_project(v_pos, visible, xform, proj, images, wmap, v_rgb, weights, us
     if epilogue is None:
         ctx.check(ctx.lib.utx_vertex_project(*head, ctx.stream()))
         return acc, wacc
-    if epilogue["blending"] not in VERTEX_BLENDING:
-        raise ValueError("vertex_project: blending %r (None, 'soft' or 'hard')" % (epilogue["blending"],))
+    args = _epilogue_args(epilogue, "vertex_project")
     blended = torch.empty(V, 3, dtype=F32, device=dev)
     mask = torch.empty(V, dtype=U8, device=dev)
-    ctx.check(ctx.lib.utx_vertex_project_blend(*head, float(epilogue["overlay_confidence"]), VERTEX_BLENDING[epilogue["blending"]],
-                                               float(epilogue["blending_confidence"]), float(epilogue["inpainting_confidence"]), ptr(blended), ptr(mask),
-                                               ctx.stream()))
+    ctx.check(ctx.lib.utx_vertex_project_blend(*head, *args, ptr(blended), ptr(mask), ctx.stream()))
     return acc, wacc, blended, mask
 
 
@@ -1203,19 +1208,16 @@ def uv_bake(rast2d, faces, face_mask, v_ndc, images, wmap, rast_view, map_Kd, we
         raise ValueError("uv_bake: wmap is %s and rast_view %s, expected %s and %s" % (tuple(wmap.shape), tuple(rast_view.shape), (B, R, R, 2), (B, R, R, 4)))
     if tuple(map_Kd.shape) != (Th, Tw, 4) or tuple(weights.shape) != (B,):
         raise ValueError("uv_bake: map_Kd is %s and weights %s, expected %s and %s" % (tuple(map_Kd.shape), tuple(weights.shape), (Th, Tw, 4), (B,)))
-    if epilogue is not None and epilogue["blending"] not in VERTEX_BLENDING:
-        raise ValueError("uv_bake: blending %r (None, 'soft' or 'hard')" % (epilogue["blending"],))
+    args = _epilogue_args(epilogue, "uv_bake")
     dev = rast2d.device
     ctx = get_ctx(dev.index)
     acc = torch.empty(Th, Tw, 4, dtype=F32, device=dev)
     wacc = torch.empty(Th, Tw, 1, dtype=F32, device=dev)
     blended = torch.empty(Th, Tw, 4, dtype=F32, device=dev) if epilogue is not None else None
     mask = torch.empty(Th, Tw, dtype=U8, device=dev) if epilogue is not None else None
-    e = epilogue or dict(overlay_confidence=0.0, blending=None, blending_confidence=0.0, inpainting_confidence=0.0)
     ctx.check(ctx.lib.utx_uv_bake(ctx.handle, ptr(_f(rast2d)), ptr(_i(faces)), F, ptr(_u8(face_mask)), ptr(_f(v_ndc)), V, B, Th, Tw, ptr(_f(images)), ptr(_f(wmap)),
                                   ptr(_f(rast_view)), R, ptr(_f(map_Kd)), ptr(_f(weights)), int(bool(use_alpha)), ptr(acc), ptr(wacc), int(epilogue is not None),
-                                  float(e["overlay_confidence"]), VERTEX_BLENDING[e["blending"]], float(e["blending_confidence"]),
-                                  float(e["inpainting_confidence"]), ptr(blended), ptr(mask), ctx.stream()))
+                                  *args, ptr(blended), ptr(mask), ctx.stream()))
     return (acc, wacc) if epilogue is None else (acc, wacc, blended, mask)
 
 
