@@ -143,11 +143,11 @@ typedef struct utx_gemm_desc {
     const void* A2; long lda2;    /* optional LoRA segment: [M, nseg*K2] = s * x A_lora^T */
     const void* B2; long ldb2;    /* [N,K2] LoRA up weight */
     int M, N, K, K2;              /* K, K2 multiples of 64; N multiple of 8 */
-    int lora_n_limit;             /* output columns < limit take the LoRA segment */
+    int lora_n_limit;             /* output columns < limit take the LoRA segment; >= N or a multiple of 128 (else -2) */
     int lora_seg_n;               /* A2 column block for column n is (n / lora_seg_n) * K2 */
     float alpha;
     const void* bias;             /* [N] bf16 or NULL */
-    int gelu_from;                /* columns >= gelu_from get GELU(tanh); N for none */
+    int gelu_from;                /* columns >= gelu_from get GELU(tanh); N for none; below N a multiple of 4 (else -2) */
     const void* gate;             /* [N] bf16 or NULL: out = res + gate * y */
     const void* res; long ldres;  /* residual [M,N] bf16 (may alias C) */
     void* C; long ldc;

@@ -110,3 +110,21 @@ def test_smaller_grids_and_margins():
     _lib.set_option("UTX_GEMM_STREAMK", 60)               # a margin of 60 K-tiles: K = 3072 (49 K-tiles per tile) can never clear it
     assert ops.gemm_plan(13376, 3072, K=3072, K2=64)["tail_tiles"] == 0
     assert ops.gemm_plan(13376, 3072, K=12288, K2=64)["tail_tiles"] == 124
+
+
+def test_plan_refuses_column_boundaries_no_kernel_can_honour():
+    """gelu_from inside the 4 columns a lane owns, a LoRA limit inside a 128-column tile: -2 from utx_gemm_plan under every kernel selector (utx_gemm_bf16 answers the
+    same, with the output untouched: tests/test_gemm_edges_gpu.py); the neighbouring boundaries a kernel can honour are planned"""
+    for tile in (0, 128, 2564):
+        _lib.set_option("UTX_GEMM_TILE", tile)
+        for gf in (1, 2, 130, 258, 263):
+            with pytest.raises(ValueError):
+                ops.gemm_plan(200, 264, K=64, gelu_from=gf)
+        for gf in (0, 4, 132, 136, 260, 264):
+            assert ops.gemm_plan(200, 264, K=64, gelu_from=gf)["kernel"] == "128x128"
+        for lim in (8, 200, 257):
+            with pytest.raises(ValueError):
+                ops.gemm_plan(200, 384, K=64, K2=64, lora_seg_n=128, lora_n_limit=lim)
+        for lim in (128, 256, 384, 392):
+            assert ops.gemm_plan(200, 384, K=64, K2=64, lora_seg_n=128, lora_n_limit=lim)["tiles"] > 0
+        assert ops.gemm_plan(200, 384, K=64, K2=0, lora_n_limit=200)["tiles"] > 0          # no LoRA segment: the limit is not read

@@ -406,14 +406,25 @@ static bool gemm_tile_known() {
     return t == 0 || t == 128 || t == 2564;
 }
 
+// Column boundaries that no kernel can honour, refused by utx_gemm_plan and utx_launch_gemm_bf16 alike (-2), never rounded to the next boundary that a kernel can:
+//   gelu_from inside the 4 consecutive columns a lane owns (phase 1 of the epilogue decides GELU once per such group, by its first column: with gelu_from = 130 the
+//   columns 130 and 131 would leave without GELU) -- every kernel here owns columns in groups of 4 that start on a multiple of 4;
+//   a LoRA limit inside a 128-column tile (the K loop takes the LoRA segment per tile, by the tile's first column: the columns from lora_n_limit to the tile's end
+//   would get the segment too).  lora_seg_n has always been checked the same way.
+static bool gemm_column_boundaries_ok(const GemmParams& p) {
+    if (p.gelu_from < p.N && (p.gelu_from % 4)) return false;
+    if (p.K2 > 0 && p.lora_n_limit > 0 && p.lora_n_limit < p.N && (p.lora_n_limit % 128)) return false;
+    return true;
+}
+
 // Which kernel a descriptor goes to, and how the one-wave-per-SIMD kernel would cut its last round -- pure host arithmetic (no HIP call), shared by
 // the launcher below and by utx_gemm_plan (C ABI: the host side and the CPU tests read the decision instead of restating it).
 // kernel: 0 = 128^2 (incl. the implicit convolution / MX fp8 forms), 1 = one wave per SIMD (gemm_w4.hip); 2, 3 and 4 were the retired 256^2 kernels and are
-// never returned.  Returns -2 for an unknown UTX_GEMM_TILE; shape validation stays in the launcher.
+// never returned.  Returns -2 for an unknown UTX_GEMM_TILE and for a column boundary no kernel can honour (above); the rest of the shape validation stays in the launcher.
 extern "C" int utx_gemm_plan_impl(const GemmParams* pp, int ncu, int sk_has_work, int out[4]) {
     const GemmParams& p = *pp;
     const int tile_env = g_utx_opt.gemm_tile;
-    if (!gemm_tile_known()) return -2;
+    if (!gemm_tile_known() || !gemm_column_boundaries_ok(p)) return -2;
     out[0] = 0; out[1] = ((p.M + 127) / 128) * ((p.N + 127) / 128); out[2] = 0; out[3] = 0;
     if (p.conv_Wo > 0 || p.mx8 == 1) return 0;
     if (p.mx8 != 2) {
@@ -449,6 +460,7 @@ extern "C" int utx_launch_gemm_bf16(const GemmParams* hp, hipStream_t stream) {
     if (p.K2 > 0 && (!p.A2 || !p.B2 || (p.lda2 & 7) || (p.ldb2 & 7) || p.lora_seg_n <= 0 || (p.lora_seg_n % 128))) return -2;
     if (p.gate && (!p.res || (p.ldres & 7))) return -2;
     if (p.n_split < p.N && (!p.C1 || (p.n_split % 128) || (p.ldc1 & 7))) return -2;
+    if (!gemm_column_boundaries_ok(p)) return -2;
     const int group_env = g_utx_opt.gemm_group_m;
     if (!gemm_tile_known()) return -2;         // for every form, the convolution / MX ones included (they never read the option): the same answer as utx_gemm_plan
     // fused q / k post-processing exists only in the bf16 one-wave-per-SIMD kernel: refuse every other form here, in front of the early returns of
