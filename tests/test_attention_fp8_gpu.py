@@ -127,6 +127,7 @@ def test_fluxdit_with_fp8_attention_runs_the_fp8_kernel_and_stays_close_to_the_b
     """FluxDiT(fp8_attention=True): the plan carries the three quantiser passes and utx_attn_fwd_fp8 per block (also in the pruned last block and with the
     de-duplicated text tokens' key weight); a tiny 2 + 2-block forward stays within 6 % of max|out| of the bf16 forward (mean <= 1 %)."""
     from oracle import dit_ref
+    from unitex_amd.flux.step_plan import walk
     from unitex_amd.flux.transformer import FluxDiT, FluxShape
     cfg = dit_ref.tiny_config(heads=2, double=2, single=2, joint_dim=64, pooled_dim=64)
     sd = dit_ref.make_synthetic_state_dict(cfg, seed=0)
@@ -143,8 +144,10 @@ def test_fluxdit_with_fp8_attention_runs_the_fp8_kernel_and_stays_close_to_the_b
         m.set_output_rows(192)
         m.set_conditioning(enc, pooled, 3.5)
         if kw:
-            kinds = [fn for fn, _ in next(iter(m._plans.values()))["plan"] if isinstance(fn, str)]
-            assert kinds.count("attn8") == 4 and kinds.count("quant_qk") == 8 and kinds.count("quant_vt") == 4 and m.key_bias_log2 > 0
+            kinds = [op.kind for op, _ in walk(next(iter(m._plans.values()))["plan"])]
+            at = [i for i, k in enumerate(kinds) if k == "attn8"]      # the head-major Q and K rows go through the plain MX quantiser (no kind of their own)
+            assert all(kinds[i - 3: i + 1] == ["quant_mx8", "quant_mx8", "quant_vt", "attn8"] for i in at)
+            assert kinds.count("attn8") == 4 and kinds.count("quant_mx8") == 8 and kinds.count("quant_vt") == 4 and m.key_bias_log2 > 0
         outs[name] = m.forward(lat, 0.5)[:192].float().cpu()
         torch.cuda.synchronize()
         if kw:      # the default launch path is the C replay (utx_plan_add_quant_vt_mx8 / utx_plan_add_attn_fp8); the Python launch list gives the same bits

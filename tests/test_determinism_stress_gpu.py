@@ -196,7 +196,7 @@ def test_two_stream_fp8_pruned_plan_600_back_to_back_forwards():
     m.set_positions(torch.zeros(S_txt, 3), img_ids)
     m.set_output_rows(4096)
     m.set_conditioning(enc, pooled, 3.5)
-    assert m.overlap_text and any(fn == "par" for fn, _ in next(iter(m._plans.values()))["plan"])
+    assert m.overlap_text and any(op.kind == "par" for op in next(iter(m._plans.values()))["plan"])
     ref = m.forward(lat, 0.5)[:4096].clone()
     bad = []
     for i in range(600):

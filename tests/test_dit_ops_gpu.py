@@ -823,7 +823,8 @@ def test_c_side_plan_replay_is_bit_identical_to_the_python_launch_list(fp8):
     p = next(iter(m._plans.values()))
     assert p.get("cplan") is not None and m.overlap_text, "the plan was not compiled into a utx_plan"
     n_c = m.lib.utx_plan_size(p["cplan"])
-    n_py = sum((len(d[0]) + len(d[1]) + 2) if (isinstance(fn, str) and fn == "par") else 1 for fn, d in p["plan"])
+    from unitex_amd.flux.step_plan import walk
+    n_py = sum(1 for _ in walk(p["plan"])) + 2 * sum(1 for op in p["plan"] if op.kind == "par")
     assert n_c == n_py and n_c > 40      # fork + join entries per two-stream section
     a1 = m.forward(lat, 0.5).clone(); a2 = m.forward(lat2, 0.25).clone()
     torch.cuda.synchronize()
@@ -929,6 +930,44 @@ def test_c_built_dit_plan_equals_the_python_built_one(full_width, lora, rows, fp
         assert torch.equal(got.view(torch.int16), ref.view(torch.int16))
     finally:
         m.lib.utx_plan_free(h)
+
+
+@pytest.mark.parametrize("fp8_attention", [False, True])
+def test_event_lists_send_forward_down_the_eager_plan_and_get_one_entry_per_timed_launch(fp8_attention):
+    """what bench.py's per-kernel timing relies on: with `attn_events` / `gemm_events` set, forward() walks the Python launch list by itself (the compiled C plan
+    stays in place), computes the same bits, and appends (start, end) per attention launch and (start, end, FLOPs) per main-stream GEMM with M >= 4096, where
+    FLOPs = 2 M N (K + K2 min(lora_n_limit, N) / N).  S_img = 4096 is the smallest shape with such GEMMs; the fp8-attention case checks the attention count only."""
+    from unitex_amd.flux.step_plan import walk
+    from unitex_amd.flux.transformer import FluxDiT, FluxShape
+    cfg = dit_ref.tiny_config(heads=2, double=1, single=2, joint_dim=64, pooled_dim=64)
+    sd = dit_ref.make_synthetic_state_dict(cfg, seed=0)
+    shape = FluxShape(num_heads=2, num_double=1, num_single=2, joint_dim=64, pooled_dim=64)
+    S_txt, img_ids = 64, dit_ref.latent_image_ids(64, 64)
+    g = torch.Generator().manual_seed(21)
+    lat = torch.randn(img_ids.shape[0], 64, generator=g).to(BF).cuda()
+    enc = (0.5 * torch.randn(S_txt, 64, generator=g)).to(BF).cuda(); pooled = (0.5 * torch.randn(1, 64, generator=g)).to(BF).cuda()
+    m = FluxDiT(sd, shape, device="cuda:0", fp8_attention=fp8_attention)
+    if not fp8_attention:
+        m.set_lora([(dit_ref.make_synthetic_lora(cfg, sd, rank=16, seed=2), 1.0)])      # K2 > 0 in the FLOP count
+    m.set_positions(torch.zeros(S_txt, 3), img_ids)
+    m.set_conditioning(enc, pooled, 3.5)
+    p = next(iter(m._plans.values()))
+    assert p.get("cplan") is not None
+    plain = m.forward(lat, 0.5).clone()
+    m.attn_events, m.gemm_events = [], []
+    timed = m.forward(lat, 0.5).clone()
+    torch.cuda.synchronize()
+    assert p.get("cplan") is not None and torch.equal(plain.view(torch.int16), timed.view(torch.int16))
+    flat = list(walk(p["plan"]))
+    n_attn = sum(1 for op, _ in flat if op.kind in ("attn", "attn8"))
+    assert n_attn == 3 and len(m.attn_events) == n_attn and all(len(e) == 2 for e in m.attn_events)
+    if fp8_attention:
+        return
+    big = [op.args for op, side in flat if op.kind == "gemm" and side == 0 and op.args.M >= 4096]
+    assert big and any(d.K2 > 0 for d in big) and len(m.gemm_events) == len(big)
+    for (_, _, flops), d in zip(m.gemm_events, big):
+        k2 = d.K2 * min(d.lora_n_limit, d.N) / d.N if (d.K2 > 0 and d.lora_n_limit > 0) else 0.0
+        assert flops == 2.0 * d.M * d.N * (d.K + k2), (d.M, d.N, d.K, d.K2, flops)
 
 
 @pytest.mark.parametrize("S", [2830, 4096])

@@ -324,13 +324,8 @@ def test_mx8_packed_form_refuses_what_it_cannot_do():
 
 
 def _flat(m):
-    def walk(ops_):
-        for fn, d in ops_:
-            if isinstance(fn, str) and fn == "par":
-                yield from walk(d[0]); yield from walk(d[1])
-            else:
-                yield fn, d
-    return list(walk(next(iter(m._plans.values()))["plan"]))
+    from unitex_amd.flux.step_plan import walk
+    return [op for op, _ in walk(next(iter(m._plans.values()))["plan"])]
 
 
 @pytest.mark.parametrize("fp8_attention", [False, True])
@@ -371,8 +366,8 @@ def test_sequence_parallel_single_blocks_run_their_projection_in_fp8(fp8_attenti
             m.set_conditioning(enc, pooled, 3.5)
             assert m.fp8_attention == fp8_attention
             if fp8_attention and not sp:
-                assert sum(1 for fn, _ in _flat(m) if isinstance(fn, str) and fn == "attn8") == 3
-            descs = [d for fn, d in _flat(m) if fn is m.lib.utx_gemm_bf16 and d.M >= 4096]
+                assert sum(1 for kind, _ in _flat(m) if kind == "attn8") == 3
+            descs = [d for kind, d in _flat(m) if kind == "gemm" and d.M >= 4096]
             big = [d for d in descs if d.N in (9216, 12288, 21504)]
             if sp:
                 # per single block: the q|k|v half (N = 9216) and the MLP half (N = 12288), both on MX operands with tile-packed scales; the MLP half hands

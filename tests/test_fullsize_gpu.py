@@ -378,13 +378,13 @@ def test_full_width_dit_blocks_at_config1_shape_match_oracle():
     assert (out - ref).abs().mean().item() < 0.004 * max(mx, 1.0)
     # the forward above ran with q / k post-processing fused into the QKV projections (these shapes take the one-wave-per-SIMD GEMM);
     # GEMM -> utx_qkv_post must give the same bits
-    fused_gemms = sum(1 for fn, d in _flat_plan(m) if fn is m.lib.utx_gemm_bf16 and d.qk_cols > 0)
+    fused_gemms = sum(1 for kind, d in _flat_plan(m) if kind == "gemm" and d.qk_cols > 0)
     assert fused_gemms == 2, "expected the image-stream QKV projection of the double block and the single block's projection to be fused, got %d" % fused_gemms
     def rerun(fused):
         m.fuse_qk = fused
         m._drop_plans()
         m.set_conditioning(enc.cuda(), pooled.cuda(), 3.5)
-        assert (sum(1 for fn, d in _flat_plan(m) if fn is m.lib.utx_gemm_bf16 and d.qk_cols > 0) == 2) == fused
+        assert (sum(1 for kind, d in _flat_plan(m) if kind == "gemm" and d.qk_cols > 0) == 2) == fused
         o_ = m.forward(lat.cuda(), 0.4375).float().cpu()
         torch.cuda.synchronize()
         return o_
@@ -407,13 +407,8 @@ def test_full_width_dit_blocks_at_config1_shape_match_oracle():
 
 
 def _flat_plan(m):
-    def walk(ops_):
-        for fn, d in ops_:
-            if fn == "par":
-                yield from walk(d[0]); yield from walk(d[1])
-            else:
-                yield fn, d
-    return list(walk(next(iter(m._plans.values()))["plan"]))
+    from unitex_amd.flux.step_plan import walk
+    return [op for op, _ in walk(next(iter(m._plans.values()))["plan"])]
 
 
 def test_address_arithmetic_beyond_32_bit_offsets():

@@ -4,6 +4,8 @@ block boundaries, stream-ordered, no host synchronisation), so the first buffer 
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import dit_ref
+from unitex_amd.flux import step_plan
+from unitex_amd.flux.step_plan import Op
 from unitex_amd.flux.transformer import FluxDiT, FluxShape
 BF = torch.bfloat16
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 1200
@@ -27,41 +29,36 @@ m.set_conditioning(enc, pooled, 3.5)
 p = next(iter(m._plans.values()))
 m.lib.utx_plan_free(p["cplan"]); p["cplan"] = None
 ws, plan = p["ws"], p["plan"]
-orig_launch = FluxDiT._launch
-def launch(self, fn, d, st, timed=True):
-    if fn == "dbg_copy":
-        d[1].copy_(d[0]); return
-    if fn == "dbg_flush":
-        junk2.fill_(7); return
-    return orig_launch(self, fn, d, st, timed)
-FluxDiT._launch = launch
+# the tool's own kinds: one more row each in the step plan's table (eager only)
+step_plan.DEVICE["dbg_copy"] = (lambda dit, d, st: (d[1].copy_(d[0]), 0)[1], None)
+step_plan.DEVICE["dbg_flush"] = (lambda dit, d, st: (junk2.fill_(7), 0)[1], None)
 # find the block boundaries: a top-level utx_ln_mod entry over all S rows starts a single block; the first "par" entry is the double block's first half
 S = p["S_txt"] + p["S_img"]
 snaps = {}
 def snap_entry(name, t):
     snaps[name] = torch.empty_like(t)
-    return ("dbg_copy", (t, snaps[name]))
+    return Op("dbg_copy", (t, snaps[name]))
 new, n_ln, n_par = [], 0, 0
 for e in plan:
     fn, d = e
-    if fn is m.lib.utx_ln_mod and d.n_tok == S:
+    if fn == "ln_mod" and d.n_tok == S:
         new.append(snap_entry("h before single block %d" % n_ln, ws["h"])); n_ln += 1
     if fn == "par":
         if n_par == 0:
             new.append(snap_entry("mod (all AdaLN vectors)", ws["mod"])); new.append(snap_entry("h after the embedders", ws["h"]))
         n_par += 1
-    if fn is m.lib.utx_attn_fwd_bf16_ws:
+    if fn == "attn":
         if MODE == "flush":
-            new.append(("dbg_flush", None))
+            new.append(Op("dbg_flush"))
         first_attn = not any(n_.startswith("Kh BEFORE") for n_ in snaps)
         if MODE == "kv" and first_attn:
             new.append(snap_entry("Qh BEFORE attention 0", ws["Qh"])); new.append(snap_entry("Kh BEFORE attention 0", ws["Kh"])); new.append(snap_entry("Vt BEFORE attention 0", ws["Vt"]))
     new.append(e)
-    if fn is m.lib.utx_attn_fwd_bf16_ws and MODE == "kv" and first_attn:
+    if fn == "attn" and MODE == "kv" and first_attn:
         new.append(snap_entry("Qh AFTER attention 0", ws["Qh"])); new.append(snap_entry("Kh AFTER attention 0", ws["Kh"])); new.append(snap_entry("Vt AFTER attention 0", ws["Vt"]))
     if fn == "par" and n_par == 1:
         new.append(snap_entry("qkv after the double block's first half", ws["qkv"]))
-    if fn is m.lib.utx_attn_fwd_bf16_ws:
+    if fn == "attn":
         k = sum(1 for n_ in snaps if n_.startswith("attention output"))
         new.append(snap_entry("attention output %d" % k, ws["attn"] if k == 0 else ws["cat"][:, :3072]))
 new.append(snap_entry("out", ws["out"]))

@@ -5,6 +5,7 @@ import collections, math, os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ctypes as C
 from unitex_amd.flux import ops
+from unitex_amd.flux.step_plan import walk
 from unitex_amd.flux.synthetic import SyntheticFluxStateDict, synthetic_lora
 from unitex_amd.flux.transformer import FluxDiT, FluxShape
 dev = "cuda:0"
@@ -18,17 +19,12 @@ S_txt, S_img = 512, 2 * HL * WL + (dual // 16) ** 2
 model.set_positions(torch.zeros(S_txt, 3), torch.zeros(S_img, 3))
 model.set_conditioning(torch.zeros(S_txt, shape.joint_dim, device=dev), torch.zeros(1, shape.pooled_dim, device=dev), 3.5)
 plan = next(iter(model._plans.values()))["plan"]
-gemm_fn = model.lib.utx_gemm_bf16
 cnt = collections.Counter(); side = collections.Counter()
-def walk(ops_, on_side):
-    for fn, d in ops_:
-        if fn == "par":
-            walk(d[0], False); walk(d[1], True)
-        elif fn is gemm_fn or (hasattr(fn, "__name__") and getattr(fn, "__name__", "") == "utx_gemm_bf16"):
-            key = (d.M, d.N, d.K, d.K2, bool(d.gate), d.gelu_from < d.N, d.n_split < d.N)
-            cnt[key] += 1
-            if on_side: side[key] += 1
-walk(plan, False)
+for (kind, d), on_side in walk(plan):
+    if kind == "gemm":
+        key = (d.M, d.N, d.K, d.K2, bool(d.gate), d.gelu_from < d.N, d.n_split < d.N)
+        cnt[key] += 1
+        if on_side: side[key] += 1
 def kernel_of(M, N, K, K2):
     tiles = ((M + 255) // 256) * ((N + 255) // 256)
     return "pers256" if (N % 256 == 0 and tiles >= 192) else "128x128"

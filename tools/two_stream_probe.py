@@ -11,6 +11,7 @@ from unitex_amd import _lib
 if os.environ.get("UTX_LIB"):
     _lib.LIB_PATH = os.path.abspath(os.environ["UTX_LIB"])      # A/B of a differently built library (e.g. dit_elementwise.hip without packed fp32 instructions)
 from oracle import dit_ref
+from unitex_amd.flux.step_plan import Op
 from unitex_amd.flux.transformer import FluxDiT, FluxShape
 BF = torch.bfloat16
 reps = int(sys.argv[1]) if len(sys.argv) > 1 else 2500
@@ -35,27 +36,28 @@ for arm in ARMS:
     p = next(iter(m._plans.values()))
     m.lib.utx_plan_free(p["cplan"]); p["cplan"] = None
     new, done = [], False
-    for fn, d in p["plan"]:
+    for op in p["plan"]:
+        fn, d = op
         if fn == "par" and not done and arm in ("post_main", "gemm_main"):
             main_ops, side_ops, e0, e1 = d
             keep = 1 if arm == "gemm_main" else len(side_ops) - 1
-            new.append(("par", (main_ops, side_ops[:keep], e0, e1)))
+            new.append(Op("par", (main_ops, side_ops[:keep], e0, e1)))
             new.extend(side_ops[keep:])
             done = True
         elif fn == "par" and not done and arm == "qkv_main":
             # side = ln_mod + LoRA-down GEMM; the text half's QKV GEMM (the MX fp8 small-M kernel in this plan) + qkv_post run behind the join on the main stream
             main_ops, side_ops, e0, e1 = d
-            new.append(("par", (main_ops, side_ops[:2], e0, e1)))
+            new.append(Op("par", (main_ops, side_ops[:2], e0, e1)))
             new.extend(side_ops[2:])
             done = True
         elif fn == "par" and not done and arm == "lora_down_main":
             # side = ln_mod, QKV GEMM, qkv_post; the LoRA-down GEMM (side_ops[1]) runs on the main stream IN FRONT of the section
             main_ops, side_ops, e0, e1 = d
             new.append(side_ops[1])
-            new.append(("par", (main_ops, [side_ops[0]] + side_ops[2:], e0, e1)))
+            new.append(Op("par", (main_ops, [side_ops[0]] + side_ops[2:], e0, e1)))
             done = True
         else:
-            new.append((fn, d))
+            new.append(op)
     p["plan"] = new
     ref = m.forward(lat, 0.5)[:4096].clone()
     bad = 0

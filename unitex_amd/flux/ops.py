@@ -209,26 +209,28 @@ def gemm(A, B, bias=None, out=None, **kw):
     return out
 
 
-def gemv(x, W, bias=None, silu_in=False, silu_out=False, out=None):
-    ctx = get_ctx(x.device.index)
-    M, K = x.shape
-    N = W.shape[0]
-    if out is None:
-        out = torch.empty(M, N, dtype=torch.bfloat16, device=x.device)
+def make_gemv_desc(x, W, bias, y, silu_in=False, silu_out=False):
     d = GemvDesc()
     d.x, d.ldx, d.W, d.ldw, d.bias = ptr(_bf(x)), x.stride(0), ptr(_bf(W)), W.stride(0), ptr(bias)
-    d.y, d.ldy, d.M, d.N, d.K = ptr(out), out.stride(0), M, N, K
+    d.y, d.ldy, d.M, d.N, d.K = ptr(y), y.stride(0), x.shape[0], W.shape[0], W.shape[1]
     d.silu_in, d.silu_out = int(silu_in), int(silu_out)
+    return d
+
+
+def gemv(x, W, bias=None, silu_in=False, silu_out=False, out=None):
+    ctx = get_ctx(x.device.index)
+    if out is None:
+        out = torch.empty(x.shape[0], W.shape[0], dtype=torch.bfloat16, device=x.device)
+    d = make_gemv_desc(x, W, bias, out, silu_in, silu_out)
     ctx.check(ctx.lib.utx_gemv_bf16(ctx.handle, C.byref(d), ctx.stream()))
     return out
 
 
-def qkv_post(qkv, q_col, k_col, v_col, wq, wk, cos, sin, Qh, Kh, Vt, n_tok, tok_off, H, eps=1e-6, q_scale=1.0,
-             heads_per_group=0, group_stride=0, head_stride=None, row_stride_v=None, skip_qk=False, sub_heads=0, sub_stride=0):
+def make_qkv_post_desc(qkv, q_col, k_col, v_col, wq, wk, cos, sin, Qh, Kh, Vt, n_tok, tok_off, H, eps=1e-6, q_scale=1.0,
+                       heads_per_group=0, group_stride=0, head_stride=None, row_stride_v=None, skip_qk=False, sub_heads=0, sub_stride=0):
     """heads_per_group > 0: Qh / Kh / Vt are flat bases of a grouped layout (the sequence-parallel send buffer, ulysses.py):
     head h at (h // g) * group_stride + (h % g) * head_stride, V^T rows row_stride_v apart; with sub_heads = s > 0 the heads of a
     group are cut once more: (h // g) * group_stride + ((h % g) // s) * sub_stride + (h % s) * head_stride."""
-    ctx = get_ctx(qkv.device.index)
     d = QkvPostDesc()
     d.qkv, d.ld = ptr(_bf(qkv)), qkv.stride(0)
     d.q_col, d.k_col, d.v_col = q_col, k_col, v_col
@@ -244,17 +246,32 @@ def qkv_post(qkv, q_col, k_col, v_col, wq, wk, cos, sin, Qh, Kh, Vt, n_tok, tok_
         d.hs_qk, d.hs_v, d.S_pad = Qh.stride(0), Vt.stride(0), Vt.shape[2]
     d.n_tok, d.tok_off, d.H, d.eps, d.q_scale = n_tok, tok_off, H, eps, q_scale
     d.skip_qk = int(bool(skip_qk))      # q / k came out of the GEMM's fused epilogue (make_gemm_desc(qk_post=...)): V transpose only
-    ctx.check(ctx.lib.utx_qkv_post(ctx.handle, C.byref(d), ctx.stream()))
+    return d
+
+
+def qkv_post(qkv, *args, **kw):
+    """utx_qkv_post on the current stream; arguments as make_qkv_post_desc"""
+    ctx = get_ctx(qkv.device.index)
+    ctx.check(ctx.lib.utx_qkv_post(ctx.handle, C.byref(make_qkv_post_desc(qkv, *args, **kw)), ctx.stream()))
+
+
+def make_ln_mod_desc(x, shift, scale, y, eps=1e-6, mxq=None):
+    """mxq = (aq uint8 scratch rows, packed scale buffer): the result leaves as MX fp8 into aq[:n_tok, :D] + tile-packed scales instead of bf16 into y
+    (utx_ln_mod_desc.q: the activation operand of the fp8 GEMM behind it, without the bf16 round trip and the quantiser's pass)."""
+    d = LnModDesc()
+    d.x, d.ldx, d.shift, d.scale = ptr(_bf(x)), x.stride(0), ptr(_bf(shift)), ptr(_bf(scale))
+    d.y, d.ldy, d.n_tok, d.D, d.eps = ptr(y), y.stride(0), x.shape[0], x.shape[1], eps
+    if mxq is not None:
+        aq, asp = mxq
+        d.q, d.ldq, d.qs, d.qs_row_blocks = ptr(aq), aq.stride(0), ptr(asp), asp.stride(0) // 512
+    return d
 
 
 def ln_mod(x, shift, scale, out=None, eps=1e-6):
     ctx = get_ctx(x.device.index)
     if out is None:
         out = torch.empty_like(x)
-    d = LnModDesc()
-    d.x, d.ldx, d.shift, d.scale = ptr(_bf(x)), x.stride(0), ptr(_bf(shift)), ptr(_bf(scale))
-    d.y, d.ldy, d.n_tok, d.D, d.eps = ptr(out), out.stride(0), x.shape[0], x.shape[1], eps
-    ctx.check(ctx.lib.utx_ln_mod(ctx.handle, C.byref(d), ctx.stream()))
+    ctx.check(ctx.lib.utx_ln_mod(ctx.handle, C.byref(make_ln_mod_desc(x, shift, scale, out, eps)), ctx.stream()))
     return out
 
 

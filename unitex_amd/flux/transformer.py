@@ -2,7 +2,7 @@
 
 Mirrors the call signature of diffusers' FluxTransformer2DModel.forward as used by the reference
 (/root/reference/flux_piplines/texturing/pipeline.py:646-656) for batch size 1.  All compute is HIP:
-the forward is a pre-built *plan* -- a flat list of (C-ABI entry point, descriptor) pairs over
+the forward is a pre-built *plan* -- a list of step_plan.Op records (kind, the C entry point's final arguments) over
 pre-allocated HBM workspaces -- replayed once per denoise step (and capturable into a hipGraph, since
 every launch is ordered on torch's current stream and nothing synchronises).
 
@@ -21,8 +21,9 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from .._lib import GemvDesc, LnModDesc, QkvPostDesc, ptr
-from . import ops
+from .._lib import ptr
+from . import ops, step_plan
+from .step_plan import Op, quant_mx8_op
 
 BF16 = torch.bfloat16
 
@@ -390,7 +391,7 @@ class FluxDiT:
                 asv = as_[:M, : K // 32]
             nq = int(opt.get("quant_cols", K))
             if nq > 0:      # columns [0, nq) of A are quantised here; the rest (0 = all of it) was written as fp8 by its producer (ln_mod / a GELU epilogue)
-                plan.append(("quant_mx8", (A[:, :nq], aqv[:, :nq], PackedScales(as_[c0 // 128:], M, nq) if hasattr(Ws, "row_blocks") else asv)))
+                plan.append(quant_mx8_op(A[:, :nq], aqv[:, :nq], PackedScales(as_[c0 // 128:], M, nq) if hasattr(Ws, "row_blocks") else asv))
             kw = dict(kw, a_scale=asv, b_scale=Ws)
             if opt.get("q_out") is not None:
                 kw["q_out"] = opt["q_out"]
@@ -401,75 +402,59 @@ class FluxDiT:
         if lora is not None:
             A_cat, B_cat, alpha, Rp = lora
             Tv = T[: A.shape[0], : A_cat.shape[0]]
-            d0 = ops.make_gemm_desc(A, A_cat, Tv, alpha=alpha)
-            plan.append((self.lib.utx_gemm_bf16, d0))
+            plan.append(Op("gemm", ops.make_gemm_desc(A, A_cat, Tv, alpha=alpha)))
             d = ops.make_gemm_desc(A_main, B_main, Cout, bias=bias, A2=Tv, B2=B_cat, lora_n_limit=lora_n_limit,
                                    lora_seg_n=lora_seg_n, **kw)
         else:
             d = ops.make_gemm_desc(A_main, B_main, Cout, bias=bias, **kw)
-        plan.append((self.lib.utx_gemm_bf16, d))
+        plan.append(Op("gemm", d))
 
     def _par(self, plan, main_ops, side_ops):
         """two independent op lists: side by side on two streams (fork / join events) or one after the other."""
         if self.overlap_text and side_ops:
-            plan.append(("par", (main_ops, side_ops, torch.cuda.Event(), torch.cuda.Event())))
+            plan.append(Op("par", (main_ops, side_ops, torch.cuda.Event(), torch.cuda.Event())))
         else:
             plan.extend(main_ops)
             plan.extend(side_ops)
 
     def _lnmod(self, plan, x, y, shift, scale, mxq=None):
-        """mxq = (aq uint8 scratch rows, packed scale buffer): the result leaves as MX fp8 into aq[:n_tok, :D] + tile-packed scales instead of bf16 into y
-        (utx_ln_mod_desc.q: the activation operand of the fp8 GEMM behind it, without the bf16 round trip and the quantiser's pass)."""
-        d = LnModDesc()
-        d.x, d.ldx, d.shift, d.scale = ptr(x), x.stride(0), ptr(shift), ptr(scale)
-        d.y, d.ldy, d.n_tok, d.D, d.eps = ptr(y), y.stride(0), x.shape[0], x.shape[1], 1e-6
-        if mxq is not None:
-            aq, asp = mxq
-            d.q, d.ldq, d.qs, d.qs_row_blocks = ptr(aq), aq.stride(0), ptr(asp), asp.stride(0) // 512
-        plan.append((self.lib.utx_ln_mod, d))
+        plan.append(Op("ln_mod", ops.make_ln_mod_desc(x, shift, scale, y, mxq=mxq)))
 
     def _qkvpost(self, plan, qkv, wq, wk, ws, n_tok, tok_off, skip_qk=False):
-        sh, D = self.shape, self.shape.dim
-        d = QkvPostDesc()
-        d.qkv, d.ld, d.q_col, d.k_col, d.v_col = ptr(qkv), qkv.stride(0), 0, D, 2 * D
-        d.wq, d.wk, d.cosb, d.sinb = ptr(wq), ptr(wk), ptr(ws["cos"]), ptr(ws["sin"])
-        if self.sp is not None:
-            # sequence parallel: write Q, K, V^T straight into the all-to-all send buffer [G][P][3][Hg][S_loc*128] (no pack pass)
-            ex = self.ex
-            d.Qh, d.Kh, d.Vt = ptr(ex.send_base(0)), ptr(ex.send_base(1)), ptr(ex.send_base(2))
-            d.hs_qk, d.hs_v, d.S_pad = ex.E, ex.E, ex.S_loc
-            d.heads_per_group, d.gs_qk, d.gs_v = ex.Hp, ex.dest_stride, ex.dest_stride       # level 1: destination rank
-            d.sub_heads, d.gs2_qk, d.gs2_v = ex.Hg, ex.group_stride, ex.group_stride        # level 2: head group (pipelined exchanges)
+        D, ex = self.shape.dim, self.ex if self.sp is not None else None
+        if ex is not None:
+            # sequence parallel: write Q, K, V^T straight into the all-to-all send buffer [G][P][3][Hg][S_loc*128] (no pack pass):
+            # level 1 = destination rank, level 2 = head group (pipelined exchanges)
+            out = (ex.send_base(0), ex.send_base(1), ex.send_base(2))
+            grouped = dict(heads_per_group=ex.Hp, group_stride=ex.dest_stride, head_stride=ex.E, row_stride_v=ex.S_loc, sub_heads=ex.Hg, sub_stride=ex.group_stride)
         else:
-            d.Qh, d.Kh, d.Vt = ptr(ws["Qh"]), ptr(ws["Kh"]), ptr(ws["Vt"])
-            d.hs_qk, d.hs_v, d.S_pad = ws["Qh"].stride(0), ws["Vt"].stride(0), ws["Vt"].shape[2]
-        d.n_tok, d.tok_off, d.H, d.eps = n_tok, tok_off, sh.num_heads, 1e-6
-        d.q_scale = (1.0 / math.sqrt(128.0)) * 1.4426950408889634   # scores become base-2 exponents (attention scale=0)
-        d.skip_qk = int(bool(skip_qk))
-        plan.append((self.lib.utx_qkv_post, d))
+            out, grouped = (ws["Qh"], ws["Kh"], ws["Vt"]), {}
+        q_scale = (1.0 / math.sqrt(128.0)) * 1.4426950408889634   # scores become base-2 exponents (attention scale=0)
+        plan.append(Op("qkv_post", ops.make_qkv_post_desc(qkv, 0, D, 2 * D, wq, wk, ws["cos"], ws["sin"], *out, n_tok, tok_off, self.shape.num_heads,
+                                                          q_scale=q_scale, skip_qk=skip_qk, **grouped)))
 
     def _attn(self, plan, ws, out, S, q_rows=None):
         if self.sp is not None:
             # exchange 1 was started by an earlier "sp_start" entry; here, head group by head group: wait + unpack, attention over the group's
             # heads x the full sequence, start its return exchange -- the fabric works beside the next group's attention (ulysses.py)
-            plan.append(("sp_attn", out[:, : self.shape.dim]))
+            plan.append(Op("sp_attn", out[:, : self.shape.dim]))
             return
         sh = self.shape
         Qh, Kh, Vt = ws["Qh"], ws["Kh"], ws["Vt"]
         r0, r1 = (0, S) if q_rows is None else q_rows     # q_rows: queries = token rows [r0, r1) only (last-block pruning); `out` starts at row r0 as well
+        # the key bias is frozen into the op here: the plan cache key (set_conditioning) carries key_bias_log2, key_bias_period and the shapes
+        wk = self._attn_work(ws, sh.num_heads, r1 - r0, S)      # scratch of the key-split tail round (the fp8 kernel splits its last round like the bf16 one)
+        tail = (float(self.key_bias_log2), int(self.key_bias_period), ptr(wk), 0 if wk is None else wk.numel())
         if self.fp8_attention:
-            plan.append(("quant_qk", (Qh, ws["Q8"], ws["Q8s"])))
-            plan.append(("quant_qk", (Kh, ws["K8"], ws["K8s"])))
-            plan.append(("quant_vt", (Vt, ws["V8"], ws["V8s"])))
-            wk8 = self._attn_work(ws, sh.num_heads, r1 - r0, S)      # scratch of the key-split tail round (round 6: the fp8 kernel splits its last round like the bf16 one)
-            plan.append(("attn8", (ws["Q8"][:, r0:], ws["Q8s"][:, r0:], ws["K8"], ws["K8s"], ws["V8"], ws["V8s"], out, r1 - r0, S, Qh.shape[1], wk8)))
+            H, S_pad = Qh.shape[:2]
+            for x, x8, xs in ((Qh, ws["Q8"], ws["Q8s"]), (Kh, ws["K8"], ws["K8s"])):      # head-major Q / K rows: the quantiser over the [H * S_pad, 128] view
+                plan.append(Op("quant_mx8", (ptr(x), 128, ptr(x8), 128, ptr(xs), 4, H * S_pad, 128, 0)))
+            plan.append(Op("quant_vt", (ptr(Vt), ptr(ws["V8"]), ptr(ws["V8s"]), H, S_pad)))
+            plan.append(Op("attn8", (ptr(ws["Q8"][:, r0:]), ptr(ws["Q8s"][:, r0:]), ptr(ws["K8"]), ptr(ws["K8s"]), ptr(ws["V8"]), ptr(ws["V8s"]), ptr(out), out.stride(0),
+                                     sh.num_heads, r1 - r0, S, S_pad) + tail))
             return
-        Qs = Qh[:, r0:]
-        wk = self._attn_work(ws, sh.num_heads, r1 - r0, S)
-        args = (ptr(Qs), ptr(Kh), ptr(Vt), ptr(out), Qh.stride(0), Qh.stride(1), Kh.stride(0), Kh.stride(1),
-                Vt.stride(0), Vt.stride(1), out.stride(0), sh.num_heads, r1 - r0, S, 0.0, float(self.key_bias_log2), int(self.key_bias_period),
-                ptr(wk), 0 if wk is None else wk.numel())
-        plan.append((self.lib.utx_attn_fwd_bf16_ws, args))
+        plan.append(Op("attn", (ptr(Qh[:, r0:]), ptr(Kh), ptr(Vt), ptr(out), Qh.stride(0), Qh.stride(1), Kh.stride(0), Kh.stride(1),
+                                Vt.stride(0), Vt.stride(1), out.stride(0), sh.num_heads, r1 - r0, S, 0.0) + tail))
 
     def _attn_work(self, ws, H, S_q, S_kv):
         """scratch of the attention tail split (utx_attn_fwd_bf16_ws: caller-owned, nothing allocated on the launch path, capture-safe): one buffer per
@@ -486,11 +471,7 @@ class FluxDiT:
         return ws["attn_ws"]
 
     def _gemv(self, plan, x, W, b, y, silu_in=False, silu_out=False):
-        d = GemvDesc()
-        d.x, d.ldx, d.W, d.ldw, d.bias = ptr(x), x.stride(0), ptr(W), W.stride(0), ptr(b)
-        d.y, d.ldy, d.M, d.N, d.K = ptr(y), y.stride(0), x.shape[0], W.shape[0], W.shape[1]
-        d.silu_in, d.silu_out = int(silu_in), int(silu_out)
-        plan.append((self.lib.utx_gemv_bf16, d))
+        plan.append(Op("gemv", ops.make_gemv_desc(x, W, b, y, silu_in, silu_out)))
 
     def _build(self, S_txt, S_img):
         sh, D, H, dev = self.shape, self.shape.dim, self.shape.num_heads, self.device
@@ -576,7 +557,7 @@ class FluxDiT:
             self._gemv(plan, ws["e1"], W[k % ("guidance_embedder", "linear_2") + ".w"], W[k % ("guidance_embedder", "linear_2") + ".b"], ws["e_g"])
         self._gemv(plan, ws["pooled"], W[k % ("text_embedder", "linear_1") + ".w"], W[k % ("text_embedder", "linear_1") + ".b"], ws["e1"], silu_out=True)
         self._gemv(plan, ws["e1"], W[k % ("text_embedder", "linear_2") + ".w"], W[k % ("text_embedder", "linear_2") + ".b"], ws["e_p"])
-        plan.append(("temb_sum", None))
+        plan.append(Op("temb_sum", (ws["e_t"], ws["e_g"] if sh.guidance_embeds else None, ws["e_p"], ws["temb"])))
         # every AdaLN modulation vector of the step in one weight-streaming pass
         self._gemv(plan, ws["temb"], W["mod.w"], W["mod.b"], ws["mod"], silu_in=True)
         # ---- embedders
@@ -613,7 +594,7 @@ class FluxDiT:
             self._qkvpost(pc, qkv[:S_txt], b["naq"], b["nak"], ws, S_txt, 0)
             self._par(plan, px, pc)
             if self.sp is not None:
-                plan.append(("sp_start", None))
+                plan.append(Op("sp_start"))
             self._attn(plan, ws, attn, S)
             px, pc = [], []
             self._gemm(px, attn[S_txt:], b["out_x.w"], h_x, bias=b["out_x.b"], lora=b.get("lora.out_x"), T=T,
@@ -665,20 +646,20 @@ class FluxDiT:
                         ws["asp2"] = packed_scale_buffer(n_out, Kmax, dev)
                     Wq, Wsp = b["qkvm.q"], b["qkvm.sp"]
                     a_all = PackedScales(ws["asp"], S, D)
-                    plan.append(("quant_mx8", (xn, ws["aq"][:S, :D], a_all)))
-                    plan.append((self.lib.utx_gemm_bf16, ops.make_gemm_desc(ws["aq"][:S, :D], Wq[D: 3 * D], qkv[:, D: 3 * D], bias=bm[D: 3 * D],
+                    plan.append(quant_mx8_op(xn, ws["aq"][:S, :D], a_all))
+                    plan.append(Op("gemm", ops.make_gemm_desc(ws["aq"][:S, :D], Wq[D: 3 * D], qkv[:, D: 3 * D], bias=bm[D: 3 * D],
                                                                             a_scale=a_all, b_scale=Wsp.row_slice(D, 3 * D))))
                     a_q = PackedScales(ws["asp2"], n_out, D)
-                    plan.append(("quant_mx8", (xn[r0:r1], ws["aq2"][:, :D], a_q)))
-                    plan.append((self.lib.utx_gemm_bf16, ops.make_gemm_desc(ws["aq2"][:, :D], Wq[:D], qkv[r0:r1, :D], bias=bm[:D],
+                    plan.append(quant_mx8_op(xn[r0:r1], ws["aq2"][:, :D], a_q))
+                    plan.append(Op("gemm", ops.make_gemm_desc(ws["aq2"][:, :D], Wq[:D], qkv[r0:r1, :D], bias=bm[:D],
                                                                             a_scale=a_q, b_scale=Wsp.row_slice(0, D))))
-                    plan.append((self.lib.utx_gemm_bf16, ops.make_gemm_desc(ws["aq2"][:, :D], Wq[3 * D:], cat[r0:r1, D:], bias=bm[3 * D:], gelu_from=0,
+                    plan.append(Op("gemm", ops.make_gemm_desc(ws["aq2"][:, :D], Wq[3 * D:], cat[r0:r1, D:], bias=bm[3 * D:], gelu_from=0,
                                                                             a_scale=a_q, b_scale=Wsp.row_slice(3 * D, Wq.shape[0]))))
                     self._qkvpost(plan, qkv, b["nq"], b["nk"], ws, S, 0)
                     self._attn(plan, ws, cat[r0:], S, q_rows=(r0, r1))
                     a_o = PackedScales(ws["asp2"], n_out, Kmax)
-                    plan.append(("quant_mx8", (cat[r0:r1], ws["aq2"], a_o)))
-                    plan.append((self.lib.utx_gemm_bf16, ops.make_gemm_desc(ws["aq2"], b["out.q"], h[r0:r1], bias=b["out.b"], gate=g_, res=h[r0:r1],
+                    plan.append(quant_mx8_op(cat[r0:r1], ws["aq2"], a_o))
+                    plan.append(Op("gemm", ops.make_gemm_desc(ws["aq2"], b["out.q"], h[r0:r1], bias=b["out.b"], gate=g_, res=h[r0:r1],
                                                                             a_scale=a_o, b_scale=b["out.sp"])))
                     continue
                 lora = b.get("lora.qkvm")
@@ -687,15 +668,15 @@ class FluxDiT:
                     A_cat, B_cat, alpha, _rp = lora
                     R = A_cat.shape[0] // 3
                     Tv = T[:S, : 3 * R]
-                    plan.append((self.lib.utx_gemm_bf16, ops.make_gemm_desc(xn, A_cat, Tv, alpha=alpha)))
+                    plan.append(Op("gemm", ops.make_gemm_desc(xn, A_cat, Tv, alpha=alpha)))
                     kw_kv = dict(A2=Tv[:, R:], B2=B_cat[D: 3 * D], lora_n_limit=2 * D, lora_seg_n=D)
                     kw_q = dict(A2=Tv[r0:r1, :R], B2=B_cat[:D], lora_n_limit=D, lora_seg_n=D)
-                plan.append((self.lib.utx_gemm_bf16, ops.make_gemm_desc(xn, Wm[D: 3 * D], qkv[:, D: 3 * D], bias=bm[D: 3 * D], **kw_kv)))
-                plan.append((self.lib.utx_gemm_bf16, ops.make_gemm_desc(xn[r0:r1], Wm[:D], qkv[r0:r1, :D], bias=bm[:D], **kw_q)))
-                plan.append((self.lib.utx_gemm_bf16, ops.make_gemm_desc(xn[r0:r1], Wm[3 * D:], cat[r0:r1, D:], bias=bm[3 * D:], gelu_from=0)))
+                plan.append(Op("gemm", ops.make_gemm_desc(xn, Wm[D: 3 * D], qkv[:, D: 3 * D], bias=bm[D: 3 * D], **kw_kv)))
+                plan.append(Op("gemm", ops.make_gemm_desc(xn[r0:r1], Wm[:D], qkv[r0:r1, :D], bias=bm[:D], **kw_q)))
+                plan.append(Op("gemm", ops.make_gemm_desc(xn[r0:r1], Wm[3 * D:], cat[r0:r1, D:], bias=bm[3 * D:], gelu_from=0)))
                 self._qkvpost(plan, qkv, b["nq"], b["nk"], ws, S, 0)      # Q rows outside [r0, r1) are stale (finite) and never read
                 self._attn(plan, ws, cat[r0:], S, q_rows=(r0, r1))
-                plan.append((self.lib.utx_gemm_bf16, ops.make_gemm_desc(cat[r0:r1], b["out.w"], h[r0:r1], bias=b["out.b"], gate=g_, res=h[r0:r1])))
+                plan.append(Op("gemm", ops.make_gemm_desc(cat[r0:r1], b["out.w"], h[r0:r1], bias=b["out.b"], gate=g_, res=h[r0:r1])))
                 continue
             if self.sp is None:
                 # one GEMM for [q|k|v|proj_mlp]: qkv -> qkv buffer, GELU(mlp) -> cat[:, D:]
@@ -719,7 +700,7 @@ class FluxDiT:
                 self._gemm(plan, xn, b["qkvm.w"][: 3 * D], qkv, bias=b["qkvm.b"][: 3 * D], lora=b.get("lora.qkvm"),
                            lora_n_limit=3 * D, lora_seg_n=D, T=T, mx8=m_a)
                 self._qkvpost(plan, qkv, b["nq"], b["nk"], ws, S, 0)
-                plan.append(("sp_start", None))
+                plan.append(Op("sp_start"))
                 self._gemm(plan, xn, b["qkvm.w"][3 * D:], cat[:, D:], bias=b["qkvm.b"][3 * D:], gelu_from=0, mx8=m_b)
             self._attn(plan, ws, cat, S)  # attention output lands in cat[:, :D] (row stride 5D)
             self._gemm(plan, cat, b["out.w"], h, bias=b["out.b"], gate=g_, res=h, mx8=m_out)
@@ -740,18 +721,12 @@ class FluxDiT:
         out = {}
         arr = (C.c_int * 4)()
 
-        def walk(entries):
-            for e in entries:
-                if e[0] == "par":
-                    walk(e[1][0]); walk(e[1][1])
-                elif e[0] is self.lib.utx_gemm_bf16:
-                    if self.lib.utx_gemm_plan(C.byref(e[1]), int(n_cus), C.byref(arr)) != 0:
-                        continue
-                    k = ops.GEMM_KERNELS[arr[0]]
-                    out[k] = out.get(k, 0) + 1
-                    if arr[2] > 0:
-                        out["w4_split_tail"] = out.get("w4_split_tail", 0) + 1
-        walk(next(iter(self._plans.values()))["plan"])
+        for op, _ in step_plan.walk(next(iter(self._plans.values()))["plan"]):
+            if op.kind == "gemm" and self.lib.utx_gemm_plan(C.byref(op.args), int(n_cus), C.byref(arr)) == 0:
+                k = ops.GEMM_KERNELS[arr[0]]
+                out[k] = out.get(k, 0) + 1
+                if arr[2] > 0:
+                    out["w4_split_tail"] = out.get("w4_split_tail", 0) + 1
         return out
 
     def _assign_streamk(self, plan, ws):
@@ -759,14 +734,7 @@ class FluxDiT:
         are ordered among themselves; the text-side ops of a "par" entry run beside them on the second stream and get none (their GEMMs are
         far below the size where the tail is split).  UTX_GEMM_STREAMK=0 at library level switches the split off."""
         ncu = torch.cuda.get_device_properties(self.device).multi_processor_count
-
-        def main_gemms(entries):
-            for e in entries:
-                if e[0] is self.lib.utx_gemm_bf16:
-                    yield e[1]
-                elif e[0] == "par":
-                    yield from main_gemms(e[1][0])
-        descs = list(main_gemms(plan))
+        descs = [op.args for op, side in step_plan.walk(plan) if op.kind == "gemm" and side == 0]
         # only launches with more 256 x 256 tiles than CUs can have a partly filled LAST round (small models never pay for the buffer)
         if not any(((d.M + 255) // 256) * (d.N // 256) > ncu for d in descs):
             return
@@ -873,105 +841,47 @@ class FluxDiT:
         g1000 = _bf16_scalar(_bf16_scalar(guidance) * 1000.0)  # guidance.to(dtype) * 1000 in bf16 [3p]
         ws["gproj"].copy_(_timestep_proj(g1000))
 
-    def _launch(self, fn, d, st, timed=True):
-        """one stream-ordered launch of a plan entry that is a C-ABI call: (entry point, descriptor) or the MX fp8 quantiser"""
-        gev = self.gemm_events
-        if gev is not None and timed and fn is self.lib.utx_gemm_bf16 and d.M >= 4096:
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            rc = fn(self.ctx.handle, C.byref(d), st)
-            b.record()
+    def _launch(self, op, st, timed=True):
+        """THE eager launch of a device op, ordered on stream `st` (step_plan.DEVICE); timed: a large-M GEMM is bracketed for `gemm_events`"""
+        launch, d = step_plan.DEVICE[op.kind][0], op.args
+        if self.gemm_events is not None and timed and op.kind == "gemm" and d.M >= 4096:
             k2 = d.K2 * min(d.lora_n_limit, d.N) / d.N if (d.K2 > 0 and d.lora_n_limit > 0) else 0.0     # the LoRA K-segment runs on the columns < lora_n_limit
-            gev.append((a, b, 2.0 * d.M * d.N * (d.K + k2)))
-            if rc:
-                self.ctx.check(rc)
-            return
-        if fn == "quant_qk":
-            ops.quant_qk_mx8(d[0], out=(d[1], d[2]))
-            return
-        if fn == "quant_vt":
-            ops.quant_vt_mx8(d[0], out=(d[1], d[2]))
-            return
-        if fn == "attn8":
-            q8, qs, k8, ks, v8, vs, out, n_q, S_kv, S_pad, wk8 = d
-            ev = getattr(self, "attn_events", None)
-            if ev is not None:
-                a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                a.record()
-            rc = self.lib.utx_attn_fwd_fp8_ws(self.ctx.handle, ptr(q8), ptr(qs), ptr(k8), ptr(ks), ptr(v8), ptr(vs), ptr(out), out.stride(0), self.shape.num_heads,
-                                              int(n_q), int(S_kv), int(S_pad), float(self.key_bias_log2), int(self.key_bias_period), ptr(wk8), 0 if wk8 is None else wk8.numel(), st)
-            if ev is not None:
-                b.record()
-                ev.append((a, b))
-            if rc:
-                self.ctx.check(rc)
-            return
-        if fn == "quant_mx8":
-            x_, q_, s_ = d
-            if hasattr(s_, "row_blocks"):
-                rc = self.lib.utx_quant_mx8_packed(self.ctx.handle, ptr(x_), x_.stride(0), ptr(q_), q_.stride(0), ptr(s_.data), s_.row_blocks,
-                                                   x_.shape[0], x_.shape[1], st)
-            else:
-                rc = self.lib.utx_quant_mx8(self.ctx.handle, ptr(x_), x_.stride(0), ptr(q_), q_.stride(0), ptr(s_), s_.stride(0),
-                                            x_.shape[0], x_.shape[1], st)
+            rc = step_plan.timed(self.gemm_events, (2.0 * d.M * d.N * (d.K + k2),), lambda: launch(self, d, st))
         else:
-            rc = fn(self.ctx.handle, C.byref(d), st)
+            rc = launch(self, d, st)
         if rc:
             self.ctx.check(rc)
 
     def run_plan(self, p):
-        h, st = self.ctx.handle, self.ctx.stream()
-        lib, ws = self.lib, p["ws"]
-        for fn, d in p["plan"]:
-            if fn == "par":
-                main_ops, side_ops, ev_fork, ev_join = d
+        st, ws = self.ctx.stream(), p["ws"]
+        for op in p["plan"]:
+            if op.kind == "par":
+                main_ops, side_ops, ev_fork, ev_join = op.args
                 main = torch.cuda.current_stream(self.device)
                 ev_fork.record(main)
                 self._side.wait_event(ev_fork)
                 st2 = C.c_void_p(self._side.cuda_stream)
-                for f2, d2 in side_ops:
-                    self._launch(f2, d2, st2, timed=False)
-                for f2, d2 in main_ops:
-                    self._launch(f2, d2, st)
+                for o in side_ops:
+                    self._launch(o, st2, timed=False)
+                for o in main_ops:
+                    self._launch(o, st)
                 ev_join.record(self._side)
                 main.wait_event(ev_join)
-            elif fn in ("quant_mx8", "quant_qk", "quant_vt", "attn8"):
-                self._launch(fn, d, st)
-            elif fn == "temb_sum":
-                # conditioning = (timesteps_emb + guidance_emb) + pooled_projections, bf16 adds [3p]
-                t = ws["e_t"]
-                if self.shape.guidance_embeds:
-                    t = t + ws["e_g"]
-                torch.add(t, ws["e_p"], out=ws["temb"])
-            elif fn == "sp_start" or fn == "sp_attn":
-                self._sp_entry(fn, d, ws, st)
-            elif fn is lib.utx_attn_fwd_bf16_ws:
-                ev = getattr(self, "attn_events", None)
-                if ev is not None:  # bench.py: HIP events on the launch stream around the dominant kernel
-                    a = torch.cuda.Event(enable_timing=True)
-                    b = torch.cuda.Event(enable_timing=True)
-                    a.record()
-                    rc = fn(h, *d, st)
-                    b.record()
-                    ev.append((a, b))
-                else:
-                    rc = fn(h, *d, st)
-                if rc:
-                    self.ctx.check(rc)
+            elif op.kind in step_plan.HOST_KINDS:
+                self._sp_entry(op, ws, st)
             else:
-                self._launch(fn, d, st)
+                self._launch(op, st)
 
-    def _sp_entry(self, fn, d, ws, st):
+    def _sp_entry(self, op, ws, st):
         """the host-side entries of a sequence-parallel plan: start of the Q / K / V exchange; per head group wait + unpack, attention, start of the return
         exchange, then the waits + unpacks of the return exchanges (ulysses.py)"""
         lib, h = self.lib, self.ctx.handle
-        if fn == "sp_start":
+        if op.kind == "sp_start":
             self._sp_work = self.ex.start_heads_in()
             return
-        if fn == "sp_attn":
+        if op.kind == "sp_attn":
             ex = self.ex
             works, self._sp_work = self._sp_work, None
-            ev = getattr(self, "attn_events", None)
             wk = self._attn_work(ws, ex.Hg, ex.S, ex.S_k)      # S queries over S_k keys (S_k < S: the ranks' identical text rows kept once)
             back = []
             for g in range(ex.G):
@@ -982,32 +892,25 @@ class FluxDiT:
                     for src, d8, s8 in ((q, ws["Q8"], ws["Q8s"]), (k, ws["K8"], ws["K8s"])):
                         self.ctx.check(lib.utx_quant_mx8(h, ptr(src), 128, ptr(d8), 128, ptr(s8), 4, ex.Hg * ex.S, 128, st))
                     self.ctx.check(lib.utx_quant_vt_mx8(h, ptr(vt), ptr(ws["V8"]), ptr(ws["V8s"]), ex.Hg, ex.S, st))
-                if ev is not None:
-                    a = torch.cuda.Event(enable_timing=True)
-                    b = torch.cuda.Event(enable_timing=True)
-                    a.record()
-                if hd is None:
-                    # zero copy: Q / K / V^T read from the receive buffer of the all-to-all, one block of S_loc tokens per source rank (utx_attn_fwd_bf16_blk)
-                    qp, kp, vp, hs, bs, rows = ex.heads_blocks(g)
-                    rc = lib.utx_attn_fwd_bf16_blk(h, C.c_void_p(qp), C.c_void_p(kp), C.c_void_p(vp), ptr(og), hs, 128, hs, 128, hs, rows, og.stride(0),
-                                                   ex.Hg, ex.S, ex.S, 0.0, float(self.key_bias_log2), int(self.key_bias_period), ptr(wk),
-                                                   0 if wk is None else wk.numel(), rows, bs, bs, bs, st)
-                elif self.fp8_attention:
-                    rc = lib.utx_attn_fwd_fp8(h, ptr(ws["Q8"]), ptr(ws["Q8s"]), ptr(ws["K8"]), ptr(ws["K8s"]), ptr(ws["V8"]), ptr(ws["V8s"]), ptr(og), og.stride(0),
-                                              ex.Hg, ex.S, ex.S, ex.S, float(self.key_bias_log2), int(self.key_bias_period), st)
-                else:
+
+                def attention():
+                    if hd is None:
+                        # zero copy: Q / K / V^T read from the receive buffer of the all-to-all, one block of S_loc tokens per source rank (utx_attn_fwd_bf16_blk)
+                        qp, kp, vp, hs, bs, rows = ex.heads_blocks(g)
+                        return lib.utx_attn_fwd_bf16_blk(h, C.c_void_p(qp), C.c_void_p(kp), C.c_void_p(vp), ptr(og), hs, 128, hs, 128, hs, rows, og.stride(0),
+                                                         ex.Hg, ex.S, ex.S, 0.0, float(self.key_bias_log2), int(self.key_bias_period), ptr(wk),
+                                                         0 if wk is None else wk.numel(), rows, bs, bs, bs, st)
+                    if self.fp8_attention:
+                        return lib.utx_attn_fwd_fp8(h, ptr(ws["Q8"]), ptr(ws["Q8s"]), ptr(ws["K8"]), ptr(ws["K8s"]), ptr(ws["V8"]), ptr(ws["V8s"]), ptr(og), og.stride(0),
+                                                    ex.Hg, ex.S, ex.S, ex.S, float(self.key_bias_log2), int(self.key_bias_period), st)
                     q, k, vt = hd
-                    rc = lib.utx_attn_fwd_bf16_ws(h, ptr(q), ptr(k), ptr(vt), ptr(og), q.stride(0), q.stride(1), k.stride(0), k.stride(1),
-                                                  vt.stride(0), vt.stride(1), og.stride(0), ex.Hg, ex.S, ex.S_k, 0.0, float(self.key_bias_log2),
-                                                  int(self.key_bias_period), ptr(wk), 0 if wk is None else wk.numel(), st)
-                if ev is not None:
-                    b.record()
-                    ev.append((a, b))
-                if rc:
-                    self.ctx.check(rc)
+                    return lib.utx_attn_fwd_bf16_ws(h, ptr(q), ptr(k), ptr(vt), ptr(og), q.stride(0), q.stride(1), k.stride(0), k.stride(1),
+                                                    vt.stride(0), vt.stride(1), og.stride(0), ex.Hg, ex.S, ex.S_k, 0.0, float(self.key_bias_log2),
+                                                    int(self.key_bias_period), ptr(wk), 0 if wk is None else wk.numel(), st)
+                self.ctx.check(step_plan.timed(self.attn_events, (), attention))
                 back.append(ex.start_tokens_out_group(g))
             for g in range(ex.G):
-                ex.finish_tokens_out_group(g, back[g], d)
+                ex.finish_tokens_out_group(g, back[g], op.args)
 
     # ------------------------------------------------------------------ C-side replay (utx_plan)
     def compile_plan(self, p=None):
@@ -1017,7 +920,7 @@ class FluxDiT:
         replayed range by range (p["segments"], utx_plan_run_range).  Not used while per-kernel events are requested (bench.py's roofline timing walks the
         Python list).  Returns the handle, or None when the plan has entries C cannot replay."""
         p = next(iter(self._plans.values())) if p is None else p
-        lib, ws = self.lib, p["ws"]
+        lib = self.lib
         h = C.c_void_p()
         self.ctx.check(lib.utx_plan_create(self.ctx.handle, C.byref(h)))
         # sequence parallel (round 4): the collectives stay torch.distributed calls of the host, the launches BETWEEN them are replayed by ranges
@@ -1025,49 +928,20 @@ class FluxDiT:
         # its 2 G collectives + 3 G exchange-side launches per layer instead of one ctypes call per kernel (~1000 per step)
         segments, seg_begin = ([] if self.sp is not None else None), 0
 
-        def add(fn, d):
-            if fn is lib.utx_gemm_bf16:
-                return lib.utx_plan_add_gemm(h, C.byref(d))
-            if fn is lib.utx_gemv_bf16:
-                return lib.utx_plan_add_gemv(h, C.byref(d))
-            if fn is lib.utx_ln_mod:
-                return lib.utx_plan_add_ln_mod(h, C.byref(d))
-            if fn is lib.utx_qkv_post:
-                return lib.utx_plan_add_qkv_post(h, C.byref(d))
-            if fn is lib.utx_attn_fwd_bf16_ws:
-                return lib.utx_plan_add_attn(h, *d)
-            if isinstance(fn, str) and fn == "quant_mx8":
-                x_, q_, s_ = d
-                if hasattr(s_, "row_blocks"):
-                    return lib.utx_plan_add_quant_mx8(h, ptr(x_), x_.stride(0), ptr(q_), q_.stride(0), ptr(s_.data), s_.row_blocks, x_.shape[0], x_.shape[1], 1)
-                return lib.utx_plan_add_quant_mx8(h, ptr(x_), x_.stride(0), ptr(q_), q_.stride(0), ptr(s_), s_.stride(0), x_.shape[0], x_.shape[1], 0)
-            if isinstance(fn, str) and fn == "quant_qk":      # head-major Q / K rows: utx_quant_mx8 over the [H * S_pad, 128] view (ops.quant_qk_mx8)
-                x_, q_, s_ = d
-                return lib.utx_plan_add_quant_mx8(h, ptr(x_), 128, ptr(q_), 128, ptr(s_), 4, x_.shape[0] * x_.shape[1], 128, 0)
-            if isinstance(fn, str) and fn == "quant_vt":
-                x_, q_, s_ = d
-                return lib.utx_plan_add_quant_vt_mx8(h, ptr(x_), ptr(q_), ptr(s_), x_.shape[0], x_.shape[2])
-            if isinstance(fn, str) and fn == "attn8":
-                q8, qs, k8, ks, v8, vs, out, n_q, S_kv, S_pad, wk8 = d
-                return lib.utx_plan_add_attn_fp8_ws(h, ptr(q8), ptr(qs), ptr(k8), ptr(ks), ptr(v8), ptr(vs), ptr(out), out.stride(0), self.shape.num_heads,
-                                                    int(n_q), int(S_kv), int(S_pad), float(self.key_bias_log2), int(self.key_bias_period), ptr(wk8), 0 if wk8 is None else wk8.numel())
-            if isinstance(fn, str) and fn == "temb_sum":
-                g = ws["e_g"] if self.shape.guidance_embeds else None
-                return lib.utx_plan_add_add3(h, ptr(ws["e_t"]), ptr(g), ptr(ws["e_p"]), ptr(ws["temb"]), ws["temb"].numel())
-            return -100
+        def add(op):
+            return step_plan.DEVICE[op.kind][1](lib, h, op.args)
         ok = True
-        for fn, d in p["plan"]:
-            if isinstance(fn, str) and fn == "par":
-                main_ops, side_ops = d[0], d[1]
-                rcs = [lib.utx_plan_fork(h)] + [add(f2, d2) for f2, d2 in side_ops] + [lib.utx_plan_main(h)] + \
-                      [add(f2, d2) for f2, d2 in main_ops] + [lib.utx_plan_join(h)]
-            elif segments is not None and isinstance(fn, str) and fn in ("sp_start", "sp_attn"):
+        for op in p["plan"]:
+            if op.kind == "par":
+                main_ops, side_ops = op.args[:2]
+                rcs = [lib.utx_plan_fork(h)] + [add(o) for o in side_ops] + [lib.utx_plan_main(h)] + [add(o) for o in main_ops] + [lib.utx_plan_join(h)]
+            elif op.kind in step_plan.HOST_KINDS:
                 n = int(lib.utx_plan_size(h))
-                segments.append((seg_begin, n, (fn, d)))
+                segments.append((seg_begin, n, op))
                 seg_begin = n
                 rcs = [0]
             else:
-                rcs = [add(fn, d)]
+                rcs = [add(op)]
             if any(rc != 0 for rc in rcs):
                 ok = False
                 break
@@ -1093,7 +967,7 @@ class FluxDiT:
                 if rc:
                     raise RuntimeError("utx_plan_run_range [%d, %d): entry %d failed with code %d" % (b0, b1, bad.value, rc))
             if host_op is not None:
-                self._sp_entry(host_op[0], host_op[1], ws, st)
+                self._sp_entry(host_op, ws, st)
 
     def build_c_dit_plan(self, p=None):
         """The same step built by the C-side builder (utx_dit_load, csrc/dit_plan.cpp): this object's packed weights and the plan's workspaces are
@@ -1202,7 +1076,7 @@ class FluxDiT:
         under capture.  Positions, conditioning and LoRA scales are read from device buffers, so they can change between
         replays; a new sequence length or adapter set builds a new plan and drops the graph."""
         p = next(iter(self._plans.values()))
-        if getattr(self, "attn_events", None) is not None:
+        if self.attn_events is not None:
             raise RuntimeError("per-kernel event timing and graph replay are exclusive")
         if warm:        # skip when the plan has already run eagerly (the denoise loop captures after its first step)
             self.run_plan(p)
