@@ -503,7 +503,7 @@ int utx_uv_project(utx_ctx* ctx, const float* rast2d, const int* faces, int F, c
  * 0 (1, -fy, -fx)  1 (-1, -fy, fx)  2 (fx, 1, fy)  3 (fx, -1, -fy)  4 (fx, -fy, 1)  5 (-fx, -fy, -1); texel i has its centre at f = 2 (i + 0.5) / N - 1.
  * Everything is fp32 data, stream-ordered, without host synchronisation; a bad size returns -2.
  *
- * Cube lookup rule (utx_cube_sample, utx_pbr_forward, utx_pbr_shade, utx_pbr_shade_nm; this library's own -- nvdiffrast's boundary_mode='cube' is third-party):
+ * Cube lookup rule (utx_cube_sample, utx_pbr_forward, utx_pbr_shade, utx_pbr_shade_nm, utx_scene_render, utx_cubemap_to_latlong; this library's own -- nvdiffrast's boundary_mode='cube' is third-party):
  *   1. face = the component of largest magnitude, ties to x, then y (a zero vector looks up the centre of face 0); (fx, fy) = the other two
  *      components over that magnitude;
  *   2. t = (f + 1) * N / 2 - 0.5, base = floor(t), fraction = t - base; a fraction within N * 2^-21 of a texel centre snaps to it (four times
@@ -580,6 +580,38 @@ int utx_pbr_shade_nm(utx_ctx* ctx, const float* rast, const int* tri, const floa
                      const float* kd, int Hk, int Wk, const float* ks_or_null, int Hs, int Ws, const float* nm, int Hn, int Wn, const float* eye3_host,
                      const float* light_diffuse, int Nd, const float* light_specular, int Ns, const float* fg_lut, int R, float lambda_diffuse, float lambda_specular,
                      const float* bg3_host, long npix, void* out_u8, float* out_rgba_or_null, utx_stream stream);
+
+/* Environment renderer: the per-pixel paths of NVDiffRendererScene (render/nvdiffrast/renderer_scene.py).  Cubemaps are [6][N][N][C], panoramas
+ * [Hi][Wi][C], 1 <= C <= 4, fp32.  A cubemap is read by the cube lookup rule above (N even, N <= 8192), a panorama linearly with wrap addressing in both
+ * axes (texel centres at +0.5, blended as t00 (1 - fx) + t01 fx: utx_texture_shade's fetch), a view image as grid_sample(bilinear, zero padding,
+ * align_corners=False).  One thread per pixel / texel, every sum in a fixed order: results are identical from run to run.
+ *
+ * utx_scene_render (perspective_rendering, :288-317): c2ws [B][4][4], intrinsics [B][3][3] (intr_stride 9) or one [3][3] (intr_stride 0), normalised.
+ * Pixel (x, y) of camera b: n = 2 ((x, y) + 0.5) / (W, H) - 1;  p = ((n.x + (2cx - 1)) / (2fx), ((2cy - 1) - n.y) / (2fy), -1) (the point at depth 1 under
+ * intr_to_proj's matrix, its second row flipped);  d = normalize((R p + t) - t) with normalize(v) = v / max(|v|, 1e-12).  Each requested output is written,
+ * a NULL output is skipped (at least one is required):
+ *   rays_d [B][H][W][3] = d;   cubemap_attr [B][H][W][C] = the cube lookup at d;   uv [B][H][W][2] = (atan2(d.x, -d.z) / 2pi + 0.5, acos(clamp(d.y)) / pi);
+ *   latlong_attr [B][H][W][C] = the panorama at uv (computed whether or not uv itself is requested).
+ * Returns -2 for a null c2ws / intrinsics, a size <= 0, intr_stride not in {0, 9}, no output at all, cubemap_attr without a cubemap (or N odd, N > 8192),
+ * latlong_attr without a panorama, C outside 1 .. 4 when a lookup is requested. */
+int utx_scene_render(utx_ctx* ctx, const float* c2ws, const float* intrinsics, int intr_stride, int B, int H, int W, const float* cubemap_or_null, int N,
+                     const float* latlong_or_null, int Hi, int Wi, int C, float* rays_d_or_null, float* cubemap_attr_or_null, float* uv_or_null,
+                     float* latlong_attr_or_null, utx_stream stream);
+
+/* cubemap_to_latlong (:148-172): texel (x, y) of out [Ht][Wt][C]: g = 2 ((x, y) + 0.5) / (Wt, Ht) - 1, psi = g.x pi, theta = g.y pi / 2 + pi / 2,
+ * d = (sin theta sin psi, cos theta, -sin theta cos psi), angles and direction in fp64 and rounded once; out = the cube lookup at d.
+ * Not the inverse of utx_latlong_to_cubemap (neither is it in the reference).  Returns -2 for a null pointer, a size <= 0, N odd or > 8192, C outside 1 .. 4. */
+int utx_cubemap_to_latlong(utx_ctx* ctx, const float* cubemap, int N, int C, int Ht, int Wt, float* out, utx_stream stream);
+
+/* perspective_inverse_rendering_torch (:373-430): M views images [M][H][W][C] baked into one panorama [Ht][Wt][C].  w2cs, projections: [M][4][4] row-major,
+ * the two matrices the reference applies one after the other (inverse of c2w; intr_to_proj), each row evaluated as ((m0 x + m1 y) + m2 z) + m3 w.
+ * Per texel, d as in utx_cubemap_to_latlong, and per view in index order: clip = projection (w2c (d, 1)) -- the direction taken as a POINT of the unit
+ * sphere, so the camera's translation counts, as in the reference;  uv = clip.xy / clip.w;  alpha = (-1 <= uv <= 1 on both axes) and clip.w > 0;
+ * sum += alpha * grid_sample(images[m], uv), count += alpha.  latlong_attr = clamp(sum / count, 0, 1), exactly 0 where no view sees the texel.
+ * Outputs (NULL = skipped, at least one required): uv [M][Ht][Wt][2], uv_alpha [M][Ht][Wt][1] (0 or 1), latlong_attr [Ht][Wt][C].
+ * Returns -2 for a null matrix pointer, M, Ht or Wt <= 0, no output at all, latlong_attr without images (or H, W <= 0, C outside 1 .. 4). */
+int utx_scene_bake_latlong(utx_ctx* ctx, const float* w2cs, const float* projections, const float* images_or_null, int M, int H, int W, int C, int Ht, int Wt,
+                           float* uv_or_null, float* uv_alpha_or_null, float* latlong_attr_or_null, utx_stream stream);
 
 /* LBVH ray-mesh intersector (raytracing/__init__.py:12-83 RayTracing / rt_aprmis APRMISRayTracing; the build the
  * reference runs per mesh: raytracing/rt_aprmis/bvhhelpers.py:20-84).  verts/faces are borrowed and must stay alive while

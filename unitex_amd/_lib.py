@@ -197,6 +197,10 @@ SYMBOLS = {
     "utx_pbr_shade_nm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int,
                                  c_void_p, c_int, c_int, C.POINTER(c_float), c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_float, c_float, C.POINTER(c_float),
                                  c_long, c_void_p, c_void_p, c_void_p]),
+    "utx_scene_render": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                 c_void_p, c_void_p]),
+    "utx_cubemap_to_latlong": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "utx_scene_bake_latlong": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "utx_bvh_build": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, C.POINTER(c_void_p), c_void_p]),
     "utx_bvh_workspace_bytes": (C.c_size_t, [c_int]),
     "utx_bvh_build_ws": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, C.c_size_t, C.POINTER(c_void_p), c_void_p]),

@@ -42,6 +42,7 @@ GEOM = [
     ("raster.hip", ["-ffp-contract=off"]),
     ("gbuffer.hip", ["-ffp-contract=off"] + NO_PK),      # screen- and atlas-space geometry buffers: sums of products that would form the packed pair
     ("pbr.hip", ["-ffp-contract=off"] + NO_PK),
+    ("scene.hip", ["-ffp-contract=off"] + NO_PK),      # environment renderer: shares the cube lookup (cube_device.h) with pbr.hip, same flags
     ("bvh.hip", ["-ffp-contract=off"] + NO_PK),
     ("backproject.hip", ["-ffp-contract=off"] + NO_PK),
     ("vertex_bake.hip", ["-ffp-contract=off"] + NO_PK),      # vertex-colour bake: weight maps, per-vertex projection, graph inpainting

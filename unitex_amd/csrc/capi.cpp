@@ -576,6 +576,25 @@ int utx_pbr_shade_nm(utx_ctx* ctx, const float* rast, const int* tri, const floa
                                                               out_rgba_or_null, (hipStream_t)stream));
 }
 
+// ---- environment renderer (scene.hip) ----
+int utx_scene_render(utx_ctx* ctx, const float* c2ws, const float* intrinsics, int intr_stride, int B, int H, int W, const float* cubemap_or_null, int N,
+                     const float* latlong_or_null, int Hi, int Wi, int C, float* rays_d_or_null, float* cubemap_attr_or_null, float* uv_or_null,
+                     float* latlong_attr_or_null, utx_stream stream) {
+    if (!c2ws || !intrinsics) return fail(ctx, -2, "utx_scene_render");
+    UTX_CALL(ctx, "utx_scene_render", utx_launch_scene_render(c2ws, intrinsics, intr_stride, B, H, W, cubemap_or_null, N, latlong_or_null, Hi, Wi, C, rays_d_or_null,
+                                                              cubemap_attr_or_null, uv_or_null, latlong_attr_or_null, (hipStream_t)stream));
+}
+int utx_cubemap_to_latlong(utx_ctx* ctx, const float* cubemap, int N, int C, int Ht, int Wt, float* out, utx_stream stream) {
+    if (!cubemap || !out) return fail(ctx, -2, "utx_cubemap_to_latlong");
+    UTX_CALL(ctx, "utx_cubemap_to_latlong", utx_launch_cubemap_to_latlong(cubemap, N, C, Ht, Wt, out, (hipStream_t)stream));
+}
+int utx_scene_bake_latlong(utx_ctx* ctx, const float* w2cs, const float* projections, const float* images_or_null, int M, int H, int W, int C, int Ht, int Wt,
+                           float* uv_or_null, float* uv_alpha_or_null, float* latlong_attr_or_null, utx_stream stream) {
+    if (!w2cs || !projections) return fail(ctx, -2, "utx_scene_bake_latlong");
+    UTX_CALL(ctx, "utx_scene_bake_latlong", utx_launch_scene_bake_latlong(w2cs, projections, images_or_null, M, H, W, C, Ht, Wt, uv_or_null, uv_alpha_or_null,
+                                                                          latlong_attr_or_null, (hipStream_t)stream));
+}
+
 int utx_condition_shade(utx_ctx* ctx, const float* rast, const float* nrm, const float* pos, const float* bg3_host, long npix,
                         void* out_normal, void* out_ccm, void* out_alpha, utx_stream stream) {
     if (!rast || !nrm || !pos || !bg3_host || !out_normal || !out_ccm || !out_alpha) return fail(ctx, -2, "utx_condition_shade");

@@ -171,6 +171,12 @@ int utx_launch_pbr_shade_nm(const float* rast, const int* tri, const float* vpos
                             int Wk, const float* ks, int Hs, int Ws, const float* nm, int Hn, int Wn, const float* eye3_host, const float* light_diffuse, int Nd,
                             const float* light_specular, int Ns, const float* lut, int R, float lambda_diffuse, float lambda_specular, const float* bg3_host, long npix,
                             void* out_u8, float* out_rgba, hipStream_t stream);
+// scene.hip
+int utx_launch_scene_render(const float* c2ws, const float* intr, int intr_stride, int B, int H, int W, const float* cube, int N, const float* lat, int Hi, int Wi, int C,
+                            float* rays_d, float* cube_attr, float* uv, float* lat_attr, hipStream_t stream);
+int utx_launch_cubemap_to_latlong(const float* cube, int N, int C, int Ht, int Wt, float* out, hipStream_t stream);
+int utx_launch_scene_bake_latlong(const float* w2cs, const float* projs, const float* images, int M, int H, int W, int C, int Ht, int Wt, float* uv, float* uv_alpha,
+                                  float* out, hipStream_t stream);
 int utx_bvh_build_impl(const float* verts, int V, const int* faces, int F, utx_bvh** out, hipStream_t stream);
 size_t utx_bvh_workspace_bytes_impl(int F);
 int utx_bvh_build_ws_impl(const float* verts, int V, const int* faces, int F, void* work, size_t work_bytes, utx_bvh** out, hipStream_t stream);

@@ -483,6 +483,58 @@ def cube_sample(cube, dirs):
     return out.reshape(dirs.shape)
 
 
+def scene_render(c2ws, intrinsics, H, W, cubemap=None, latlong=None, want=("rays_d",)):
+    """cameras c2ws [B,4,4], intrinsics [3,3] or [B,3,3] looking into cubemap [6,N,N,C] / latlong [Hi,Wi,C] (utx_scene_render) -> a dict with the
+    requested ones of rays_d [B,H,W,3], cubemap_attr [B,H,W,C], uv [B,H,W,2], latlong_map_attr [B,H,W,C], all from one launch"""
+    ctx = get_ctx(c2ws.device.index)
+    B, dev = c2ws.shape[0], c2ws.device
+    unknown = set(want) - {"rays_d", "cubemap_attr", "uv", "latlong_map_attr"}
+    if unknown or not want:
+        raise ValueError("scene_render: want must name some of rays_d, cubemap_attr, uv, latlong_map_attr, got %r" % (tuple(want),))
+    if "cubemap_attr" in want and cubemap is None:
+        raise ValueError("scene_render: cubemap_attr needs a cubemap")
+    if "latlong_map_attr" in want and latlong is None:
+        raise ValueError("scene_render: latlong_map_attr needs a lat-long map")
+    assert c2ws.shape == (B, 4, 4) and intrinsics.shape in ((3, 3), (B, 3, 3))
+    Cs = {int(m.shape[-1]) for m, k in ((cubemap, "cubemap_attr"), (latlong, "latlong_map_attr")) if k in want}
+    if len(Cs) > 1:
+        raise ValueError("scene_render: the cubemap and the lat-long map must have the same number of channels")
+    Cc = Cs.pop() if Cs else 3
+    if cubemap is not None:
+        assert cubemap.ndim == 4 and cubemap.shape[0] == 6 and cubemap.shape[1] == cubemap.shape[2]
+    shapes = {"rays_d": 3, "cubemap_attr": Cc, "uv": 2, "latlong_map_attr": Cc}
+    out = {k: torch.empty(B, H, W, shapes[k], dtype=F32, device=dev) for k in shapes if k in want}
+    ctx.check(ctx.lib.utx_scene_render(ctx.handle, ptr(_f(c2ws)), ptr(_f(intrinsics)), 9 if intrinsics.ndim == 3 else 0, B, H, W, _opt(cubemap),
+                                       cubemap.shape[1] if cubemap is not None else 0, _opt(latlong), latlong.shape[0] if latlong is not None else 0,
+                                       latlong.shape[1] if latlong is not None else 0, Cc, ptr(out.get("rays_d")), ptr(out.get("cubemap_attr")), ptr(out.get("uv")),
+                                       ptr(out.get("latlong_map_attr")), ctx.stream()))
+    return out
+
+
+def cubemap_to_latlong(cubemap, Ht, Wt):
+    """cubemap [6,N,N,C] -> panorama [Ht,Wt,C] (utx_cubemap_to_latlong)"""
+    ctx = get_ctx(cubemap.device.index)
+    assert cubemap.ndim == 4 and cubemap.shape[0] == 6 and cubemap.shape[1] == cubemap.shape[2]
+    out = torch.empty(Ht, Wt, cubemap.shape[3], dtype=F32, device=cubemap.device)
+    ctx.check(ctx.lib.utx_cubemap_to_latlong(ctx.handle, ptr(_f(cubemap)), cubemap.shape[1], cubemap.shape[3], Ht, Wt, ptr(out), ctx.stream()))
+    return out
+
+
+def scene_bake_latlong(w2cs, projections, Ht, Wt, images=None):
+    """M views (w2cs, projections [M,4,4]; images [M,H,W,C] or None) into one panorama (utx_scene_bake_latlong)
+    -> (uv [M,Ht,Wt,2], uv_alpha [M,Ht,Wt,1], latlong_map_attr [Ht,Wt,C] or None without images)"""
+    ctx = get_ctx(w2cs.device.index)
+    M, dev = w2cs.shape[0], w2cs.device
+    assert w2cs.shape == (M, 4, 4) and projections.shape == (M, 4, 4) and (images is None or (images.ndim == 4 and images.shape[0] == M))
+    uv = torch.empty(M, Ht, Wt, 2, dtype=F32, device=dev)
+    alpha = torch.empty(M, Ht, Wt, 1, dtype=F32, device=dev)
+    H, W, Cc = (images.shape[1], images.shape[2], images.shape[3]) if images is not None else (0, 0, 0)
+    out = torch.empty(Ht, Wt, Cc, dtype=F32, device=dev) if images is not None else None
+    ctx.check(ctx.lib.utx_scene_bake_latlong(ctx.handle, ptr(_f(w2cs)), ptr(_f(projections)), _opt(images), M, H, W, Cc, Ht, Wt, ptr(uv), ptr(alpha), ptr(out),
+                                             ctx.stream()))
+    return uv, alpha, out
+
+
 def pbr_forward(view_pos, world_pos, world_nrm, kd, ks, light_diffuse, light_specular, fg_lut):
     """dense PBRModel.forward (utx_pbr_forward): view_pos [3] or [npix,3], world_pos / world_nrm [npix,3], kd [npix,>=3], ks [npix,3]
     -> (diffuse, specular) [npix,3]"""
