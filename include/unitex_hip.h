@@ -687,6 +687,38 @@ int utx_visible_vertices(utx_ctx* ctx, const unsigned char* mask, const int* fac
 int utx_bvh_closest_point(utx_ctx* ctx, utx_bvh* bvh, const float* points, long N, float* dist, int* face, float* uvw, float* closest,
                           unsigned long long* visited, int flags, utx_stream stream);
 
+/* Ray queries on the tree: RayTracing.intersects_closest of the reference (raytracing/__init__.py: hit, front, tri_idx, loc, uv) for arbitrary rays, and the
+ * queries raytracing/check_visibility.py builds from it (self_rt, cross_rt, sphere_rt).  Each is ONE launch, no workspace, no host wait, no atomics but the
+ * optional counter `visited` (device word the number of visited nodes is ADDED to; may be null).  Walks and depth rule of utx_visible_faces_rays: the packed
+ * walk up to a depth of 60, the stack walk beyond it or with UTX_RC_STACK_WALK (equal results).  All fp32, stream-ordered; csrc/raycast.hip.
+ * utx_bvh_intersect: rays_o, rays_d [R][3]; directions are NOT normalised, t is in units of |d|.  The hit with the smallest t >= 0 wins, both triangle sides
+ *   count, ties in t go to the smallest face id, a zero direction component is replaced by 1e-30 in the box test -- the closest hit of utx_visible_faces_rays,
+ *   so tid is what that function finds for the same ray, and none of utx_bvh_trace's quirks.  Outputs, each may be null: tid [R] i32 (-1: miss), t [R] (+inf: miss),
+ *   loc [R][3] = o + t d (a rounded product, then a rounded sum), uv [R][2] = Moeller-Trumbore's (u, v) of the winner (u weighs v1, v weighs v2),
+ *   front [R] u8 = 1 iff dot(d, (v1 - v0) x (v2 - v0)) < 0 (this library's rule: the reference's backends leave it unpinned), face_mask [F] u8: the byte of
+ *   every hit face is set to 1 (not cleared here: the caller zeroes it, or accumulates).  A miss: loc = 0, uv = 0, front = 0.  A ray with d = (0, 0, 0) or a
+ *   NaN in o or d is a miss (it may visit every node once; it never faults and always ends).
+ * utx_bvh_occluded: segments from [R][3] -> to [R][3]; blocked [R] u8 = 1 iff some triangle is hit with 0 <= t < 1 along d = to - from (strict, no
+ *   normalisation).  The walk leaves at the first such hit and enters no box beyond t = 1.  A zero-length segment is not blocked.
+ * utx_points_enclosed: inner [N] u8 = 1 iff each of the n_rays (1 .. 1024) rays from points[i] has a hit with t >= 0 (any hit).  Ray j of point i has the
+ *   direction sphere(i, j): Philox4x32-10, key (seed low word, seed high word), counter (i, j, attempt, stream_id); x1 = 2 u0 - 1, x2 = 2 u1 - 1 with
+ *   u = (word >> 8) 2^-24 from words 0 and 1; while s = x1^2 + x2^2 >= 1 the next attempt (at most 64, then d = (0, 0, 1)); d = (2 x1 q, 2 x2 q, 1 - 2 s),
+ *   q = sqrt(1 - s) correctly rounded (Marsaglia 1972) -- independent of the launch geometry, repeated bit for bit by numpy.  dirs_or_null [N][n_rays][3]: read
+ *   instead of the generator.  min(64, next power of two >= n_rays) lanes serve a point and stop at the point's first completed miss;
+ *   UTX_RC_NO_EARLY_EXIT walks every ray (same inner).  hits [N] i32 (may be null): the number of rays that hit, exact only with UTX_RC_NO_EARLY_EXIT.
+ * utx_sphere_directions: out [n_points][n_rays][3] = sphere(i, j) of the same device function (n_points * n_rays < 2^31).
+ * R == 0, N == 0 or an empty direction table return 0 at once.  -2 for a null tree or a null required operand (rays, segments, blocked, points, inner, out),
+ *   a negative count, a count >= 2^31, n_rays outside 1 .. 1024, unknown flags, and a tree deeper than 94 levels on the stack walk. */
+#define UTX_RC_STACK_WALK 1
+#define UTX_RC_NO_EARLY_EXIT 2
+int utx_bvh_intersect(utx_ctx* ctx, utx_bvh* bvh, const float* rays_o, const float* rays_d, long R, int* tid, float* t, float* loc, float* uv, unsigned char* front,
+                      unsigned char* face_mask, unsigned long long* visited, int flags, utx_stream stream);
+int utx_bvh_occluded(utx_ctx* ctx, utx_bvh* bvh, const float* from, const float* to, long R, unsigned char* blocked, unsigned long long* visited, int flags,
+                     utx_stream stream);
+int utx_points_enclosed(utx_ctx* ctx, utx_bvh* bvh, const float* points, long N, int n_rays, unsigned long long seed, unsigned stream_id, const float* dirs_or_null,
+                        unsigned char* inner, int* hits, unsigned long long* visited, int flags, utx_stream stream);
+int utx_sphere_directions(utx_ctx* ctx, long n_points, long n_rays, unsigned long long seed, unsigned stream_id, float* out, utx_stream stream);
+
 /* Vertex-colour bake from views: project_vertex_color / remapping_vertex_color / inpainting_vertex_color of the reference
  * (texture/reprojection/mesh_remapping.py:508-627, :273-350).  All fp32, stream-ordered, row-major.
  * utx_view_weight_maps: cos_ray_normal [B][H][W] (utx_screen_gbuffer) -> out [B][H][W][2] = (cos term, edge alpha).  cos term: clamp(cos, -1, 0), or with

@@ -225,6 +225,10 @@ SYMBOLS = {
     "utx_bvh_trace_count": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
     "utx_bvh_depth": (c_int, [c_void_p]),
     "utx_bvh_closest_point": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "utx_bvh_intersect": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long] + [c_void_p] * 7 + [c_int, c_void_p]),
+    "utx_bvh_occluded": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_int, c_void_p]),
+    "utx_points_enclosed": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_int, C.c_ulonglong, C.c_uint, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "utx_sphere_directions": (c_int, [c_void_p, c_long, c_long, C.c_ulonglong, C.c_uint, c_void_p, c_void_p]),
     "utx_backproject": (c_int, [c_void_p, C.POINTER(BackprojectDesc), c_void_p, c_void_p]),
     "utx_backproject_persp": (c_int, [c_void_p, C.POINTER(BackprojectDesc), c_void_p, c_void_p, c_void_p]),
     "utx_backproject_sampled": (c_int, [c_void_p, C.POINTER(BackprojectDesc), c_void_p, c_int, c_void_p, c_void_p]),

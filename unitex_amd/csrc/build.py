@@ -44,6 +44,7 @@ GEOM = [
     ("pbr.hip", ["-ffp-contract=off"] + NO_PK),
     ("scene.hip", ["-ffp-contract=off"] + NO_PK),      # environment renderer: shares the cube lookup (cube_device.h) with pbr.hip, same flags
     ("bvh.hip", ["-ffp-contract=off"] + NO_PK),
+    ("raycast.hip", ["-ffp-contract=off"] + NO_PK),      # ray queries on the LBVH: t, uv, loc and the direction stream are compared bit for bit
     ("backproject.hip", ["-ffp-contract=off"] + NO_PK),
     ("vertex_bake.hip", ["-ffp-contract=off"] + NO_PK),      # vertex-colour bake: weight maps, per-vertex projection, graph inpainting
     ("uv_bake.hip", ["-ffp-contract=off"] + NO_PK),      # blended UV texture bake: per-texel accumulation over the views, texel-space dilation

@@ -213,8 +213,8 @@ __device__ __forceinline__ bool close_box(const CloseRay& r, float limit, const 
     }
     return tmin <= tmax;
 }
-// Moeller-Trumbore, both sides; t >= 0 only
-__device__ __forceinline__ bool close_tri(const CloseRay& r, const float* v0, const float* v1, const float* v2, float& t_out) {
+// Moeller-Trumbore, both sides; t >= 0 only.  close_tri_uv also hands out the barycentrics (u weighs v1, v and v2) of a hit; close_tri is the same arithmetic
+__device__ __forceinline__ bool close_tri_uv(const CloseRay& r, const float* v0, const float* v1, const float* v2, float& t_out, float& u_out, float& v_out) {
     const float E1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]};
     const float E2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
     float P[3]; cross3(r.d, E2, P);
@@ -229,8 +229,12 @@ __device__ __forceinline__ bool close_tri(const CloseRay& r, const float* v0, co
     if (!(v >= 0.f && u + v <= 1.f)) return false;
     const float t = dot3(E2, Q) * inv;
     if (!(t >= 0.f)) return false;
-    t_out = t;
+    t_out = t; u_out = u; v_out = v;
     return true;
+}
+__device__ __forceinline__ bool close_tri(const CloseRay& r, const float* v0, const float* v1, const float* v2, float& t_out) {
+    float u, v;
+    return close_tri_uv(r, v0, v1, v2, t_out, u, v);
 }
 __device__ __forceinline__ void close_take(float t, int prim, float& closest, int& hit) {
     if (t < closest || (t == closest && prim < hit)) { closest = t; hit = prim; }

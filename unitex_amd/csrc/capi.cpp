@@ -635,6 +635,28 @@ int utx_bvh_closest_point(utx_ctx* ctx, utx_bvh* bvh, const float* points, long 
     if (!bvh || N < 0 || N >= (1l << 31) || (flags & ~(UTX_CP_EXHAUSTIVE | UTX_CP_NO_SEED)) || (N > 0 && (!points || !dist))) return fail(ctx, -2, me);
     UTX_CALL(ctx, me, utx_bvh_closest_point_impl(bvh, points, N, dist, face, uvw, closest, visited, flags, (hipStream_t)stream));
 }
+int utx_bvh_intersect(utx_ctx* ctx, utx_bvh* bvh, const float* rays_o, const float* rays_d, long R, int* tid, float* t, float* loc, float* uv, unsigned char* front,
+                      unsigned char* face_mask, unsigned long long* visited, int flags, utx_stream stream) {
+    const char* const me = "utx_bvh_intersect";
+    if (!bvh || R < 0 || R >= (1l << 31) || (flags & ~UTX_RC_STACK_WALK) || (R > 0 && (!rays_o || !rays_d))) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_bvh_intersect_impl(bvh, rays_o, rays_d, R, tid, t, loc, uv, front, face_mask, visited, flags, (hipStream_t)stream));
+}
+int utx_bvh_occluded(utx_ctx* ctx, utx_bvh* bvh, const float* from, const float* to, long R, unsigned char* blocked, unsigned long long* visited, int flags,
+                     utx_stream stream) {
+    const char* const me = "utx_bvh_occluded";
+    if (!bvh || R < 0 || R >= (1l << 31) || (flags & ~UTX_RC_STACK_WALK) || (R > 0 && (!from || !to || !blocked))) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_bvh_occluded_impl(bvh, from, to, R, blocked, visited, flags, (hipStream_t)stream));
+}
+int utx_points_enclosed(utx_ctx* ctx, utx_bvh* bvh, const float* points, long N, int n_rays, unsigned long long seed, unsigned stream_id, const float* dirs_or_null,
+                        unsigned char* inner, int* hits, unsigned long long* visited, int flags, utx_stream stream) {
+    const char* const me = "utx_points_enclosed";
+    if (!bvh || N < 0 || N >= (1l << 31) || n_rays < 1 || n_rays > 1024 || (flags & ~(UTX_RC_STACK_WALK | UTX_RC_NO_EARLY_EXIT)) || (N > 0 && (!points || !inner)))
+        return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_points_enclosed_impl(bvh, points, N, n_rays, seed, stream_id, dirs_or_null, inner, hits, visited, flags, (hipStream_t)stream));
+}
+int utx_sphere_directions(utx_ctx* ctx, long n_points, long n_rays, unsigned long long seed, unsigned stream_id, float* out, utx_stream stream) {
+    UTX_CALL(ctx, "utx_sphere_directions", utx_launch_sphere_directions(n_points, n_rays, seed, stream_id, out, (hipStream_t)stream));
+}
 int utx_visible_faces_raster(utx_ctx* ctx, const float* rast, int B, int H, int W, int F, unsigned char* mask, utx_stream stream) {
     if (!rast || !mask || B <= 0 || H <= 0 || W <= 0 || F <= 0) return fail(ctx, -2, "utx_visible_faces_raster");
     UTX_CALL(ctx, "utx_visible_faces_raster", utx_launch_visible_faces_raster(rast, B, H, W, F, mask, (hipStream_t)stream));

@@ -189,6 +189,13 @@ int utx_visible_faces_rays_impl(utx_bvh* b, const float* verts, const int* faces
 int utx_bvh_closest_point_impl(utx_bvh* b, const float* points, long N, float* dist, int* face, float* uvw, float* closest, unsigned long long* visited, int flags,
                                hipStream_t stream);
 int utx_launch_visible_faces_raster(const float* rast, int B, int H, int W, int F, unsigned char* mask, hipStream_t stream);
+// raycast.hip
+int utx_bvh_intersect_impl(utx_bvh* b, const float* ro, const float* rd, long R, int* tid, float* t, float* loc, float* uv, unsigned char* front, unsigned char* face_mask,
+                           unsigned long long* visited, int flags, hipStream_t stream);
+int utx_bvh_occluded_impl(utx_bvh* b, const float* from, const float* to, long R, unsigned char* blocked, unsigned long long* visited, int flags, hipStream_t stream);
+int utx_points_enclosed_impl(utx_bvh* b, const float* points, long N, int n_rays, unsigned long long seed, unsigned stream_id, const float* dirs, unsigned char* inner,
+                             int* hits, unsigned long long* visited, int flags, hipStream_t stream);
+int utx_launch_sphere_directions(long n_points, long n_rays, unsigned long long seed, unsigned stream_id, float* out, hipStream_t stream);
 int utx_launch_erode_faces(unsigned char* mask, const int* faces, int B, int F, int V, int depth, int* vstamp, hipStream_t stream);
 int utx_launch_visible_vertices(const unsigned char* mask, const int* faces, int B, int F, int V, unsigned char* out, hipStream_t stream);
 // vertex_bake.hip

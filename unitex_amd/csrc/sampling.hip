@@ -14,6 +14,7 @@
 // The numpy restatements the tests hold these kernels to are oracle/sampling_ref.py's.
 #include "common.h"
 #include "kernels.h"
+#include "philox_device.h"
 #include "shade_device.h"
 #include <float.h>
 
@@ -195,19 +196,8 @@ extern "C" int utx_launch_sample_edges(const float* verts, const int* edges, con
     return hipGetLastError() == hipSuccess ? 0 : -4;
 }
 
-// ---- sample_surface (surface_sampling.py:24-35) on a defined random stream: Philox4x32-10 (Salmon et al., SC'11; Random123), key (seed_lo, seed_hi),
+// ---- sample_surface (surface_sampling.py:24-35) on a defined random stream: Philox4x32-10 (philox_device.h), key (seed_lo, seed_hi),
 // counter (i, 0, 0, 0) for sample i; a word x becomes (x >> 8) * 2^-24 in [0, 1).  Word 0 picks the face, words 1 and 2 are (u, v).
-__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0, unsigned k1, unsigned out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0, p1 = (unsigned long long)0xCD9E8D57u * c2;
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1, n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
-        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
-
 __global__ __launch_bounds__(256) void sample_surface_kernel(const float* __restrict__ verts, const int* __restrict__ faces, const float* __restrict__ cum, int F, long N,
                                                              unsigned seed_lo, unsigned seed_hi, float* __restrict__ samples, int* __restrict__ face_index,
                                                              float* __restrict__ uvw) {

@@ -588,6 +588,9 @@ def pbr_shade(rast, tri, v_pos, v_nrm, v_uv, kd, ks, eye, light_diffuse, light_s
     return (out, rgba) if want_rgba else out
 
 
+INTERSECT_OUTPUTS = ("tid", "t", "loc", "uv", "front")
+
+
 class BVH:
     """utx_bvh handle (RayTracing / APRMISRayTracing of the reference)."""
 
@@ -648,6 +651,96 @@ class BVH:
     def depth(self):
         """longest root-to-leaf path of the tree (<= 60: the stackless packed traversal is in use)"""
         return int(self.ctx.lib.utx_bvh_depth(self.handle))
+
+    # ---- ray queries (csrc/raycast.hip): closest hit with every output, occlusion of segments, enclosed points
+    def _rows(self, what, x, tail=(3,)):
+        """x as a contiguous float32 [..., *tail] tensor on the tree's device, or a named ValueError"""
+        if not torch.is_tensor(x) or not x.is_floating_point():
+            raise ValueError("%s must be a floating-point tensor, got %s" % (what, x.dtype if torch.is_tensor(x) else type(x).__name__))
+        if x.dim() != 1 + len(tail) or tuple(x.shape[1:]) != tuple(tail):
+            raise ValueError("%s is %s, expected [N, %s]" % (what, tuple(x.shape), ", ".join(str(t) for t in tail)))
+        if x.device != self.verts.device:
+            raise ValueError("%s is on %s, the tree on %s" % (what, x.device, self.verts.device))
+        if not x.shape[0] < 2 ** 31:
+            raise ValueError("%s has %d rows, at most 2^31 - 1 are taken" % (what, x.shape[0]))
+        return _f(x.to(F32).contiguous())
+
+    def intersect(self, rays_o, rays_d, want=INTERSECT_OUTPUTS, force_stack=False, count=False, face_mask=None):
+        """utx_bvh_intersect: the closest hit of the rays rays_o, rays_d [R,3] f32 (directions not normalised: t in units of |d|) -> dict of the buffers named in
+        `want`: tid [R] i32 (-1: miss), t [R] f32 (+inf: miss), loc [R,3] = o + t d, uv [R,2] (Moeller-Trumbore's u, v of the winner), front [R] u8
+        (dot(d, (v1 - v0) x (v2 - v0)) < 0).  The smallest t >= 0 wins, both sides count, ties to the smallest face id: the hit of visible_faces_rays, not the
+        quirk-preserving id of trace().  A miss has loc = uv = front = 0.  face_mask [F] u8: the hit faces are set to 1 in it (not cleared).  count: also the
+        number of tree nodes visited."""
+        ro, rd = self._rows("intersect: rays_o", rays_o), self._rows("intersect: rays_d", rays_d)
+        if ro.shape != rd.shape:
+            raise ValueError("intersect: rays_o is %s, rays_d %s" % (tuple(ro.shape), tuple(rd.shape)))
+        want = tuple(want)
+        for k in want:
+            if k not in INTERSECT_OUTPUTS:
+                raise ValueError("intersect: unknown output %r (one of %s)" % (k, ", ".join(INTERSECT_OUTPUTS)))
+        if face_mask is not None and (face_mask.dtype != torch.uint8 or tuple(face_mask.shape) != (self.faces.shape[0],) or not face_mask.is_contiguous()
+                                      or face_mask.device != ro.device):
+            raise ValueError("intersect: face_mask must be a contiguous uint8 [F = %d] tensor on the tree's device" % self.faces.shape[0])
+        R, dev = ro.shape[0], ro.device
+        spec = {"tid": ((R,), I32), "t": ((R,), F32), "loc": ((R, 3), F32), "uv": ((R, 2), F32), "front": ((R,), torch.uint8)}
+        out = {k: torch.empty(spec[k][0], dtype=spec[k][1], device=dev) for k in want}
+        visited = torch.zeros(1, dtype=torch.int64, device=dev) if count else None
+        if R > 0:
+            self.ctx.check(self.ctx.lib.utx_bvh_intersect(self.ctx.handle, self.handle, ptr(ro), ptr(rd), R, ptr(out.get("tid")), ptr(out.get("t")), ptr(out.get("loc")),
+                                                          ptr(out.get("uv")), ptr(out.get("front")), ptr(face_mask), ptr(visited), 1 if force_stack else 0,
+                                                          self.ctx.stream()))
+        return (out, int(visited.item())) if count else out
+
+    def occluded(self, a, b, force_stack=False, count=False):
+        """utx_bvh_occluded: blocked [R] u8 for the segments a -> b ([R,3] each): 1 iff some triangle is hit with 0 <= t < 1 along b - a"""
+        a, b = self._rows("occluded: a", a), self._rows("occluded: b", b)
+        if a.shape != b.shape:
+            raise ValueError("occluded: a is %s, b %s" % (tuple(a.shape), tuple(b.shape)))
+        R = a.shape[0]
+        blocked = torch.empty(R, dtype=torch.uint8, device=a.device)
+        visited = torch.zeros(1, dtype=torch.int64, device=a.device) if count else None
+        if R > 0:
+            self.ctx.check(self.ctx.lib.utx_bvh_occluded(self.ctx.handle, self.handle, ptr(a), ptr(b), R, ptr(blocked), ptr(visited), 1 if force_stack else 0,
+                                                         self.ctx.stream()))
+        return (blocked, int(visited.item())) if count else blocked
+
+    def points_enclosed(self, points, n_rays, seed, dirs=None, early_exit=True, stream_id=0, want_hits=False, force_stack=False):
+        """utx_points_enclosed: inner [N] u8 = 1 iff each of the point's n_rays (1 .. 1024) rays hits the mesh (t >= 0, any hit).  The directions are the stream
+        of sphere_directions(N, n_rays, seed, stream_id) -- or dirs [N,n_rays,3], read in its place.  early_exit: a point's remaining rays are dropped at its
+        first miss (same inner).  want_hits: also hits [N] i32, the number of rays that hit -- exact only with early_exit=False."""
+        points = self._rows("points_enclosed: points", points)
+        n_rays = int(n_rays)
+        if not 1 <= n_rays <= 1024:
+            raise ValueError("points_enclosed: n_rays is %d, expected 1 .. 1024" % n_rays)
+        N = points.shape[0]
+        if dirs is not None:
+            dirs = self._rows("points_enclosed: dirs", dirs, (n_rays, 3))
+            if dirs.shape[0] != N:
+                raise ValueError("points_enclosed: dirs is %s for %d points" % (tuple(dirs.shape), N))
+        inner = torch.empty(N, dtype=torch.uint8, device=points.device)
+        hits = torch.empty(N, dtype=I32, device=points.device) if want_hits else None
+        if N > 0:
+            self.ctx.check(self.ctx.lib.utx_points_enclosed(self.ctx.handle, self.handle, ptr(points), N, n_rays, int(seed) & (2 ** 64 - 1), int(stream_id) & 0xffffffff,
+                                                            ptr(dirs), ptr(inner), ptr(hits), None, (1 if force_stack else 0) | (0 if early_exit else 2),
+                                                            self.ctx.stream()))
+        return (inner, hits) if want_hits else inner
+
+    def sphere_directions(self, n_points, n_rays, seed, stream_id=0):
+        """utx_sphere_directions: [n_points, n_rays, 3] f32, the unit directions points_enclosed draws for (point, ray) under (seed, stream_id)"""
+        return sphere_directions(n_points, n_rays, seed, stream_id, device=self.verts.device)
+
+
+def sphere_directions(n_points, n_rays, seed, stream_id=0, device=None):
+    """utx_sphere_directions: [n_points, n_rays, 3] f32 -- Philox4x32-10 keyed by seed, counter (point, ray, attempt, stream_id), Marsaglia's rejection method"""
+    n_points, n_rays = int(n_points), int(n_rays)
+    if n_points < 0 or n_rays < 0 or not n_points * n_rays < 2 ** 31:
+        raise ValueError("sphere_directions: %d x %d directions, expected counts >= 0 with a product < 2^31" % (n_points, n_rays))
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    ctx = get_ctx(dev.index)
+    out = torch.empty(n_points, n_rays, 3, dtype=F32, device=dev)
+    if out.numel() > 0:
+        ctx.check(ctx.lib.utx_sphere_directions(ctx.handle, n_points, n_rays, int(seed) & (2 ** 64 - 1), int(stream_id) & 0xffffffff, ptr(out), ctx.stream()))
+    return out
 
 
 def backproject(rast2d, verts, faces, fnormal, vndc, dirs, images, bvh, angle_deg=100.0, view_begin=0, view_count=None,
