@@ -50,6 +50,8 @@ def _run_attn(q, k, v, prescaled=False):
 @pytest.mark.parametrize("H,S,spike", [(1, 64, False), (2, 256, False), (3, 200, False), (2, 1000, True),
                                        (2, 2304, True), (24, 512, False)])
 def test_attention_matches_oracle(H, S, spike):
+    """finiteness and gross agreement at plain and large shapes; the flat max-abs bound is as large as the outputs themselves (about 1 / sqrt(S)) -- the values at the
+    kernels' edges are held to a counted float64 interval by tests/test_attention_edges_gpu.py"""
     q, k, v = _mk_attn_inputs(H, S, seed=S + H, spike=spike)
     ref = dit_ref.sdpa(q.float(), k.float(), v.float(), em=False)
     out = _run_attn(q, k, v)
@@ -675,7 +677,8 @@ def test_sequence_parallel_two_ranks_match_unsharded_forward(world, zero_text, g
 def test_attention_more_queries_than_keys(H, S_k, extra, kb):
     """S_q > S_kv (round 6: a sequence-parallel rank attends with ALL P x S_loc query rows over keys that carry the ranks' identical text rows once,
     utx_sp_unpack_qkv_dedup): q and k / vt are separate arrays, nothing ties a query row to a key row.  Against the oracle softmax with the key weight on
-    tile 0, through both kernels (4 x 64 stream where it takes the shape, 8 x 32 loop), and row for row bit-identical to the S_q = S_kv launch."""
+    tile 0, through both kernels (4 x 64 stream where it takes the shape, 8 x 32 loop), and row for row bit-identical to the S_q = S_kv launch.
+    (max-abs only: a bias on the wrong tile would pass here; tests/test_attention_edges_gpu.py holds S_q != S_kv and the key multiplicity to a counted interval.)"""
     from unitex_amd import _lib
     ops = _ops()
     g = torch.Generator().manual_seed(S_k + extra)
@@ -714,7 +717,9 @@ def test_attention_more_queries_than_keys(H, S_k, extra, kb):
 
 def test_attention_running_max_keeps_growing():
     """pathological order for the sum-checked softmax: the scores of every query grow steadily along the key axis, so the
-    running max has to be re-centred again and again (slow path on most tiles, in either 32-key block)."""
+    running max has to be re-centred again and again (slow path on most tiles, in either 32-key block).
+    (As the scores come out, this ramp spans about 9 base-2 units, below the 2^13 sum check: oracle/attention_fp64.py states the range, and
+    tests/test_attention_edges_gpu.py runs a ramp of 45 through the 8 x 32 kernel, which does re-centre, against a counted interval.)"""
     H, S = 2, 1536
     g = torch.Generator().manual_seed(11)
     q = torch.randn(H, S, 128, generator=g).to(BF)
@@ -736,7 +741,8 @@ def test_attention_running_max_keeps_growing():
 def test_attention_q64_kernel_and_repair_pass(S, ramp_max):
     """the 4 x 64 kernel (UTX_ATTN_Q64=1, the default since round 6; whole 64-key tiles, pre-scaled Q) against the oracle: plain inputs, the growing
     running maximum (45 log2-units above the first block: inside its 2^96 headroom, no re-centring at all), and ramps steep enough to leave the headroom
-    (110: finite row sums beyond 2^96, 150: fp32 overflow inside the kernel) so that the repair pass with the 8 x 32 kernel has to rewrite the query blocks."""
+    (110: finite row sums beyond 2^96, 150: fp32 overflow inside the kernel) so that the repair pass with the 8 x 32 kernel has to rewrite the query blocks.
+    (max-abs only; that the repair pass ran, and repaired next to untouched blocks, is asserted in tests/test_attention_edges_gpu.py against a counted interval.)"""
     H = 2
     g = torch.Generator().manual_seed(S + int(ramp_max))
     q = torch.randn(H, S, 128, generator=g)
@@ -974,7 +980,8 @@ def test_event_lists_send_forward_down_the_eager_plan_and_get_one_entry_per_time
 def test_attention_tail_split_matches_oracle_and_unsplit_launch(S):
     """more workgroups than CUs: the partly filled last round is cut along the keys (partial outputs + log-sum-exp, merged by
     a second kernel).  Rows of the full rounds must be bit-identical to the unsplit launch, tail rows within the usual
-    tolerance of the oracle (one more bf16 rounding of the partial outputs)."""
+    tolerance of the oracle (one more bf16 rounding of the partial outputs).
+    (The split boundaries, the merge and a ragged or shorter last range are held to a counted interval in tests/test_attention_edges_gpu.py.)"""
     H = 24
     q, k, v = _mk_attn_inputs(H, S, seed=S, spike=True)
     from unitex_amd import _lib
