@@ -193,7 +193,10 @@ typedef struct utx_gemm_desc {
      * (FLUX: GELU(ff.net.0) feeds ff.net.2; GELU(proj_mlp) feeds proj_out) -- instead of bf16: bytes q_out [M][ldq_out] at column n - gelu_from,
      * tile-packed scales qs_out (qs_out_rb row blocks per K-tile slab), K-tile q_out_kt0 + (n - gelu_from) / 128.  Bit-identical to the bf16
      * epilogue followed by utx_quant_mx8_packed (rounded to bf16, then quantised per block of 32 columns); C / C1 are not written for those
-     * columns.  (N - gelu_from) % 128 == 0, ldq_out % 8 == 0.  The split tail round is not used by such a launch. */
+     * columns.  (N - gelu_from) % 128 == 0, ldq_out % 8 == 0.  The split tail round is not used by such a launch.  As with utx_quant_mx8_packed, rows >= M
+     * are not written: neither their bytes in q_out nor their scales in the last row block of qs_out, nor any K-tile slab outside q_out_kt0 ..
+     * q_out_kt0 + (N - gelu_from) / 128 - 1 or row block >= ceil(M / 128).  With row-major scales (mx8 = 1), a gate, gelu_from off a 128 multiple or
+     * qs_out_rb < ceil(M / 128) the launch is refused (-2) and nothing is written (tests/test_gemm_mx_edges_gpu.py). */
     void* q_out; long ldq_out;
     void* qs_out; long qs_out_rb;
     int q_out_kt0;

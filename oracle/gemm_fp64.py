@@ -215,16 +215,16 @@ def _rbf32(x):
     return bf16(np.asarray(x, dtype=np.float32).astype(F64)).astype(np.float32)
 
 
-def emulate(case, inp, defect=None):
-    """what the kernels compute, in numpy float32: K-tiles of 64 accumulated in float32, y = bf16(alpha * acc + bias), GELU by the kernels' expression, bf16(gate * y),
-    bf16(res + .).  defect: one of DEFECTS, the mistake of that name; None: none.  -> [M, N] float64 of bf16 values (SENT where nothing was written)."""
-    assert defect is None or defect in DEFECTS
+def gelu_f32(x):
+    """the kernels' GELU expression on float32 x, not yet rounded to bf16"""
     f = np.float32
-    A, B = inp["A"].astype(f), inp["B"].astype(f)
-    (M, K), N, K2 = A.shape, B.shape[0], case["K2"]
-    acc = np.zeros((M, N), dtype=f)
-    for kt in range(K // 64 - (1 if defect == "drop_last_k_tile" else 0)):
-        acc += A[:, 64 * kt: 64 * kt + 64] @ B[:, 64 * kt: 64 * kt + 64].T
+    with np.errstate(over="ignore"):
+        return x * (f(1) / (f(1) + np.exp(f(-2) * (f(K0) * (x + f(K1) * x * x * x)))))
+
+
+def emulate_lora(acc, case, inp, defect=None):
+    """adds the bf16 LoRA segments to the float32 accumulators acc [M, N] in place, K2 in tiles of 64"""
+    f, N, K2 = np.float32, acc.shape[1], case["K2"]
     if K2:
         A2, B2 = inp["A2"].astype(f), inp["B2"].astype(f)
         for s, (cols, ks) in enumerate(_lora_segments(N, K2, case["lora_seg_n"], case["lora_n_limit"])):
@@ -234,6 +234,12 @@ def emulate(case, inp, defect=None):
                 ks = slice(0, K2)
             for kt in range(K2 // 64):
                 acc[:, cols] += A2[:, ks][:, 64 * kt: 64 * kt + 64] @ B2[cols][:, 64 * kt: 64 * kt + 64].T
+    return acc
+
+
+def emulate_epilogue(acc, case, inp, defect=None):
+    """float32 accumulators -> [M, N] float64 of bf16 values: y = bf16(alpha * acc + bias), GELU by the kernels' expression, bf16(gate * y), bf16(res + .)"""
+    f, N = np.float32, acc.shape[1]
     alpha = f(case["alpha"])
     b = np.zeros(N, dtype=f) if inp["bias"] is None else inp["bias"].astype(f)
     if defect == "alpha_on_bias":
@@ -245,9 +251,7 @@ def emulate(case, inp, defect=None):
     gf = N if case["gelu_from"] is None else case["gelu_from"]
     gf += 4 if defect == "gelu_4_late" else 0
     if gf < N:
-        x = y[:, gf:]
-        u = f(K0) * (x + f(K1) * x * x * x)
-        y[:, gf:] = _rbf32(x * (f(1) / (f(1) + np.exp(f(-2) * u))))
+        y[:, gf:] = _rbf32(gelu_f32(y[:, gf:]))
     if case["gate"]:
         t = inp["gate"].astype(f) * y              # a product of two bf16 values: exact in float32
         y = _rbf32(inp["res"].astype(f) + (t if defect == "gate_y_unrounded" else _rbf32(t)))
@@ -255,3 +259,16 @@ def emulate(case, inp, defect=None):
     if defect == "n_tail_group_unwritten":
         out[:, N - 8:] = SENT
     return out
+
+
+def emulate(case, inp, defect=None):
+    """what the kernels compute, in numpy float32: K-tiles of 64 accumulated in float32, y = bf16(alpha * acc + bias), GELU by the kernels' expression, bf16(gate * y),
+    bf16(res + .).  defect: one of DEFECTS, the mistake of that name; None: none.  -> [M, N] float64 of bf16 values (SENT where nothing was written)."""
+    assert defect is None or defect in DEFECTS
+    f = np.float32
+    A, B = inp["A"].astype(f), inp["B"].astype(f)
+    (M, K), N = A.shape, B.shape[0]
+    acc = np.zeros((M, N), dtype=f)
+    for kt in range(K // 64 - (1 if defect == "drop_last_k_tile" else 0)):
+        acc += A[:, 64 * kt: 64 * kt + 64] @ B[:, 64 * kt: 64 * kt + 64].T
+    return emulate_epilogue(emulate_lora(acc, case, inp, defect), case, inp, defect)

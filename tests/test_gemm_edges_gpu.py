@@ -6,18 +6,16 @@ at most 1.41 % of the intervals hold more than one bf16 value and that eight ker
 Cases, operands and references come from the oracle module (one copy, shared with the CPU test).  The one-wave-per-SIMD kernel is reached with a handful of
 tiles through UTX_GEMM_TILE=2564 / UTX_GEMM_PERS_GRID / UTX_GEMM_STREAMK=1000+S; every option a test sets is put back in a `finally`.  Outputs are preallocated
 with a sentinel, two rows and (where the case says so) some columns larger than the contract writes: the sentinel must be gone inside M x N and intact outside."""
-import contextlib
-
 import numpy as np
 import pytest
 import torch
 
 from oracle import dit_ref
 from oracle import gemm_fp64 as G
+from tests.support.gemm_gpu import _bits, _options, _sent
 
 pytestmark = pytest.mark.gpu
 BF = torch.bfloat16
-_DEFAULTS = (("UTX_GEMM_TILE", 0), ("UTX_GEMM_FASTK", 1), ("UTX_GEMM_STREAMK", 1), ("UTX_GEMM_PERS_GRID", 0), ("UTX_GEMM_GROUP_M", 0))
 _CACHE = {}
 
 
@@ -26,33 +24,12 @@ def _ops():
     return ops
 
 
-@contextlib.contextmanager
-def _options(**kw):
-    """UTX_GEMM_<name> = value inside the block; every GEMM option back at its default behind it, whatever happened"""
-    from unitex_amd import _lib
-    try:
-        for k, v in kw.items():
-            _lib.set_option("UTX_GEMM_" + k, int(v))
-        yield
-    finally:
-        for k, v in _DEFAULTS:
-            _lib.set_option(k, v)
-
-
 def _case_data(case):
     """(inputs, reference): built once per case, shared by every launch of it, never modified"""
     if case["name"] not in _CACHE:
         inp = G.make_inputs(case)
         _CACHE[case["name"]] = (inp, G.reference(case, inp))
     return _CACHE[case["name"]]
-
-
-def _sent(rows, cols):
-    return torch.full((rows, cols), G.SENT16, dtype=torch.int16).view(BF)
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int16).numpy()
 
 
 def _bf(a, pad=0, fill=3.0e38):

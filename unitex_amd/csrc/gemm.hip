@@ -422,9 +422,10 @@ static bool gemm_column_boundaries_ok(const GemmParams& p) {
 // kernel: 0 = 128^2 (incl. the implicit convolution / MX fp8 forms), 1 = one wave per SIMD (gemm_w4.hip); 2, 3 and 4 were the retired 256^2 kernels and are
 // never returned.  Returns -2 for an unknown UTX_GEMM_TILE and for a column boundary no kernel can honour (above); the rest of the shape validation stays in the launcher.
 extern "C" int utx_gemm_plan_impl(const GemmParams* pp, int ncu, int sk_has_work, int out[4]) {
-    const GemmParams& p = *pp;
+    GemmParams p = *pp;
     const int tile_env = g_utx_opt.gemm_tile;
     if (!gemm_tile_known() || !gemm_column_boundaries_ok(p)) return -2;
+    if (p.mx8) p.K /= 2;      // a caller's descriptor counts fp8 elements; the launcher halves K before it asks for the split, so a K range of an MX launch is 128 of them
     out[0] = 0; out[1] = ((p.M + 127) / 128) * ((p.N + 127) / 128); out[2] = 0; out[3] = 0;
     if (p.conv_Wo > 0 || p.mx8 == 1) return 0;
     if (p.mx8 != 2) {

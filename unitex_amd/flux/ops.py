@@ -159,14 +159,14 @@ def streamk_workspace(device, stream=None, shared=True):
 GEMM_KERNELS = ("128x128", "w4")
 
 
-def gemm_plan(M, N, K=3072, K2=0, n_split=None, gelu_from=None, lora_seg_n=None, lora_n_limit=None, sk=True, n_cus=256):
+def gemm_plan(M, N, K=3072, K2=0, n_split=None, gelu_from=None, lora_seg_n=None, lora_n_limit=None, sk=True, n_cus=256, mx8=0):
     """what utx_gemm_bf16 does with this shape under the current launch options (utx_gemm_plan: the library's own dispatch arithmetic, no device
     needed): dict(kernel=one of GEMM_KERNELS, tiles, tail_tiles, ranges) -- tail_tiles > 0 when the one-wave-per-SIMD kernel cuts its last round
-    along K into `ranges` ranges per tile (needs scratch: sk)."""
+    along K into `ranges` ranges per tile (needs scratch: sk).  mx8 = 1 / 2: the MX fp8 forms (utx_gemm_desc.mx8; K counts fp8 elements)."""
     lib = _lib.load_library()
     d = GemmDesc()
     d.A = d.B = d.C = 1                       # never dereferenced by the plan
-    d.M, d.N, d.K, d.K2 = int(M), int(N), int(K), int(K2)
+    d.M, d.N, d.K, d.K2, d.mx8 = int(M), int(N), int(K), int(K2), int(mx8)
     d.lora_n_limit = (N if lora_n_limit is None else lora_n_limit) if K2 else 0
     d.lora_seg_n = (N if lora_seg_n is None else lora_seg_n) if K2 else 128
     d.n_split = N if n_split is None else n_split
