@@ -786,6 +786,30 @@ int utx_uv_bake(utx_ctx* ctx, const float* rast2d, const int* faces, int F, cons
 int utx_uv_dilation_step(utx_ctx* ctx, const float* col_in, const unsigned char* mask_in, int H, int W, int C, int mode, float* col_out, unsigned char* mask_out,
                          int* counter, utx_stream stream);
 
+/* Scattered-sample UV bake: NVDiffRendererBase.global_inverse_rendering of the reference (render/nvdiffrast/renderer_base.py:562-743), the two stages that are
+ * not already here.  All fp32, stream-ordered, row-major, no workspace.
+ * utx_view_samples: one thread per pixel of rast [B][H][W][4] (one utx_rasterize per view).  For a covered pixel on triangle (i0, i1, i2) of faces [F][3] with the
+ *   raster's weights: tex_to_pos [B][H][W][2] = the interpolation of v_uv [V][2] (vertex UVs in [-1, 1]); tex_to_pos_cam [B][H][W][6] = the interpolation of
+ *   (v_pos_cam[b][i] / max(|v_pos_cam[b][i]|, 1e-12), v_nrm_cam[b][i]) with v_pos_cam / v_nrm_cam [B][V][3] (utx_transform_points with M = w2c; utx_camera_normals,
+ *   which normalises): the position direction is normalised per VERTEX, before the interpolation, and nothing is normalised after it.  An uncovered pixel holds zeros.
+ *   mask [B][H][W] uint8 = covered && (exclude_boundary: the pixels above, below, left and right are covered, the image wrapping round at its edges as torch.roll
+ *   does) && (use_normal_threshold: tex_to_pos_cam[5] > cos_normal) && (use_ray_threshold: dot(tex_to_pos_cam[0:3], tex_to_pos_cam[3:6]) > cos_ray) &&
+ *   (image_mask [B][H][W] uint8, optional: non-zero).
+ * utx_knn_inpaint_step: one Jacobi sweep over M points (the covered texels) on their neighbour lists idx / d2 [M][k] (utx_knn with the set as source and query:
+ *   ascending squared distance, so the point itself leads its list), nrm [M][3], col_in [M][C], pending_in [M] uint8 (non-zero: no colour yet).  A pending point
+ *   whose list holds fewer than k - 1 pending entries takes col_out = sum_j (m_j w_j) col_in[j] / sum_j (m_j w_j) in list order, m_j = 0 for a pending neighbour
+ *   and 1 otherwise, w_j = (r_j / max(sum_j |r_j|, 1e-12)) cos(nrm_j, nrm_i), r_j = 1 / sqrt(d2_j) with +inf replaced by FLT_MAX and NaN by 0
+ *   (torch.nan_to_num), cos(a, b) = a.b / max(|a| |b|, 1e-8), and pending_out = 0; every other point copies its colour and flag.  Nothing guards the arithmetic:
+ *   two zero distances in one list overflow the sum, the weights vanish and the point becomes NaN and known.  A list entry outside [0, M) is not read and weighs
+ *   0.  *counter (device int32, zeroed here) receives the number of points filled.  One launch; no block waits for another.
+ * A zero-size problem (B H W = 0, M = 0) returns 0 without a launch.  -2: a negative size; F or V <= 0; M > 2^31 - 1; k outside 1..32; C outside 1..16; a null or
+ * misaligned operand (rast: 16 bytes, tex_to_pos: 8, every other array: its element); col_in == col_out or pending_in == pending_out; outputs untouched. */
+int utx_view_samples(utx_ctx* ctx, const float* rast, const int* faces, int F, const float* v_uv, const float* v_pos_cam, const float* v_nrm_cam, int V, int B,
+                     int H, int W, int exclude_boundary, int use_normal_threshold, float cos_normal, int use_ray_threshold, float cos_ray,
+                     const unsigned char* image_mask, float* tex_to_pos, float* tex_to_pos_cam, unsigned char* mask, utx_stream stream);
+int utx_knn_inpaint_step(utx_ctx* ctx, const int* idx, const float* d2, const float* nrm, const float* col_in, const unsigned char* pending_in, long M, int k, int C,
+                         float* col_out, unsigned char* pending_out, int* counter, utx_stream stream);
+
 /* fused per-(view, texel) gather + visibility of uv_to_pcd (renderer_inverse.py:277-298,316-325) */
 typedef struct utx_backproject_desc {
     const void* rast2d;                 /* [T][4] f32 UV-space raster */

@@ -510,6 +510,30 @@ int utx_uv_dilation_step(utx_ctx* ctx, const float* col_in, const unsigned char*
     if (mode == UTX_UVD_STEP && (!mask_in || !mask_out || !counter || mask_in == mask_out || misaligned(counter, 3))) return fail(ctx, -2, me);
     UTX_CALL(ctx, me, utx_launch_uv_dilation_step(col_in, mask_in, H, W, C, mode, col_out, mask_out, counter, (hipStream_t)stream));
 }
+// ---- scattered-sample UV bake (global_bake.hip) ----
+int utx_view_samples(utx_ctx* ctx, const float* rast, const int* faces, int F, const float* v_uv, const float* v_pos_cam, const float* v_nrm_cam, int V, int B,
+                     int H, int W, int exclude_boundary, int use_normal_threshold, float cos_normal, int use_ray_threshold, float cos_ray,
+                     const unsigned char* image_mask, float* tex_to_pos, float* tex_to_pos_cam, unsigned char* mask, utx_stream stream) {
+    const char* const me = "utx_view_samples";
+    if (B < 0 || H < 0 || W < 0 || F <= 0 || V <= 0) return fail(ctx, -2, me);
+    if ((long)B * H * W == 0) return 0;
+    if (!rast || !faces || !v_uv || !v_pos_cam || !v_nrm_cam || !tex_to_pos || !tex_to_pos_cam || !mask) return fail(ctx, -2, me);
+    if (misaligned(rast, 15) || misaligned(tex_to_pos, 7) || misaligned(faces, 3) || misaligned(v_uv, 3) || misaligned(v_pos_cam, 3) || misaligned(v_nrm_cam, 3) ||
+        misaligned(tex_to_pos_cam, 3)) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_view_samples(rast, faces, F, v_uv, v_pos_cam, v_nrm_cam, V, B, H, W, exclude_boundary != 0, use_normal_threshold != 0, cos_normal,
+                                              use_ray_threshold != 0, cos_ray, image_mask, tex_to_pos, tex_to_pos_cam, mask, (hipStream_t)stream));
+}
+int utx_knn_inpaint_step(utx_ctx* ctx, const int* idx, const float* d2, const float* nrm, const float* col_in, const unsigned char* pending_in, long M, int k, int C,
+                         float* col_out, unsigned char* pending_out, int* counter, utx_stream stream) {
+    const char* const me = "utx_knn_inpaint_step";
+    if (M < 0 || M > 0x7fffffffL || k < 1 || k > 32 || C < 1 || C > 16) return fail(ctx, -2, me);      // the neighbour ids are int32
+    if (M == 0) return 0;
+    if (!idx || !d2 || !nrm || !col_in || !pending_in || !col_out || !pending_out || !counter) return fail(ctx, -2, me);
+    if (col_in == col_out || pending_in == pending_out) return fail(ctx, -2, me);      // a step reads one pair and writes the other
+    if (misaligned(idx, 3) || misaligned(d2, 3) || misaligned(nrm, 3) || misaligned(col_in, 3) || misaligned(col_out, 3) || misaligned(counter, 3))
+        return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_knn_inpaint_step(idx, d2, nrm, col_in, pending_in, M, k, C, col_out, pending_out, counter, (hipStream_t)stream));
+}
 int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws, int n_views, float* out, utx_stream stream) {
     if (!nrm || !c2ws || !out) return fail(ctx, -2, "utx_camera_normals");
     UTX_CALL(ctx, "utx_camera_normals", utx_launch_camera_normals(nrm, V, c2ws, n_views, out, (hipStream_t)stream));

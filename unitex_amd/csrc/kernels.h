@@ -212,6 +212,12 @@ int utx_launch_uv_bake(const float* rast2d, const int* faces, int F, const unsig
                        unsigned char* inpaint, hipStream_t stream);
 int utx_launch_uv_dilation_step(const float* col_in, const unsigned char* mask_in, int H, int W, int C, int mode, float* col_out, unsigned char* mask_out,
                                 int* counter, hipStream_t stream);
+// global_bake.hip
+int utx_launch_view_samples(const float* rast, const int* faces, int F, const float* v_uv, const float* v_pos_cam, const float* v_nrm_cam, int V, int B, int H, int W,
+                            int exclude_boundary, int use_normal, float cos_normal, int use_ray, float cos_ray, const unsigned char* image_mask,
+                            float* tex_to_pos, float* tex_to_pos_cam, unsigned char* mask, hipStream_t stream);
+int utx_launch_knn_inpaint_step(const int* idx, const float* d2, const float* nrm, const float* col_in, const unsigned char* pend_in, long M, int k, int C,
+                                float* col_out, unsigned char* pend_out, int* counter, hipStream_t stream);
 int utx_launch_backproject(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_backproject_vis(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_composite_winner(const void* vis, int n_views, const int* order, int n_order, long T, void* winner, hipStream_t stream);

@@ -1399,3 +1399,84 @@ def uv_dilation(map_Kd, valid, max_iters=-1, trace=None):
         count = now
     ctx.check(ctx.lib.utx_uv_dilation_step(ctx.handle, ptr(cur), None, H, W, Cc, 1, ptr(out), None, None, ctx.stream()))
     return out, steps
+
+
+# ---- the scattered-sample UV bake (global_bake.hip): global_inverse_rendering of the reference
+
+KNN_INPAINT_K_MAX = 32      # utx_knn's and utx_knn_inpaint_step's cap
+
+
+def _cos_threshold(degrees):
+    """(use, cos) of an angle threshold in degrees, None = off; the cosine is rounded to float32, as the reference's comparison with a float32 tensor does"""
+    return (0, 0.0) if degrees is None else (1, float(np.float32(math.cos(math.radians(float(degrees))))))
+
+
+def view_samples(rast, faces, v_uv, v_pos_cam, v_nrm_cam, exclude_boundary=True, normal_angle_degree_threshold=None, ray_angle_degree_threshold=None,
+                 image_mask=None):
+    """utx_view_samples: rast [B,H,W,4] (the views' rasters), faces [F,3] int32, v_uv [V,2] in [-1,1], v_pos_cam / v_nrm_cam [B,V,3] (_camera_arrays: camera-space
+    positions, NOT normalised, and normalised camera-space normals) -> (tex_to_pos [B,H,W,2], tex_to_pos_cam [B,H,W,6], mask uint8 [B,H,W]) of
+    global_inverse_rendering (renderer_base.py:624-654) in one launch: the pixel's UV, the interpolation of the per-vertex normalised position direction and
+    normal, and the sample mask -- coverage, the four torch.roll neighbours (wrapping round the edge), the two optional angle thresholds in degrees and the
+    optional image_mask [B,H,W] (or [B,H,W,1]; non-zero = keep)."""
+    if rast.dim() != 4 or rast.shape[3] != 4 or faces.dim() != 2 or faces.shape[1] != 3 or faces.shape[0] < 1:
+        raise ValueError("view_samples: rast is %s and faces %s, expected [B, H, W, 4] and [F >= 1, 3]" % (tuple(rast.shape), tuple(faces.shape)))
+    B, H, W = rast.shape[:3]
+    if v_uv.dim() != 2 or v_uv.shape[1] != 2 or v_uv.shape[0] < 1:
+        raise ValueError("view_samples: v_uv is %s, expected [V >= 1, 2]" % (tuple(v_uv.shape),))
+    V = v_uv.shape[0]
+    for name, a in (("v_pos_cam", v_pos_cam), ("v_nrm_cam", v_nrm_cam)):
+        if B > 0 and (a is None or tuple(a.shape) != (B, V, 3)):
+            raise ValueError("view_samples: %s is %s, expected %s" % (name, None if a is None else tuple(a.shape), (B, V, 3)))
+    dev = rast.device
+    if image_mask is not None:
+        image_mask = torch.as_tensor(image_mask).to(dev)
+        if image_mask.numel() != B * H * W:
+            raise ValueError("view_samples: image_mask is %s, expected %s" % (tuple(image_mask.shape), (B, H, W)))
+        image_mask = (image_mask.reshape(B, H, W) != 0).to(U8).contiguous()
+    use_n, cos_n = _cos_threshold(normal_angle_degree_threshold)
+    use_r, cos_r = _cos_threshold(ray_angle_degree_threshold)
+    tex_to_pos = torch.empty(B, H, W, 2, dtype=F32, device=dev)
+    tex_to_pos_cam = torch.empty(B, H, W, 6, dtype=F32, device=dev)
+    mask = torch.empty(B, H, W, dtype=U8, device=dev)
+    if B * H * W == 0:
+        return tex_to_pos, tex_to_pos_cam, mask
+    ctx = get_ctx(dev.index)
+    ctx.check(ctx.lib.utx_view_samples(ctx.handle, ptr(_f(rast)), ptr(_i(faces)), faces.shape[0], ptr(_f(v_uv)), ptr(_f(v_pos_cam)), ptr(_f(v_nrm_cam)), V, B, H, W,
+                                       int(bool(exclude_boundary)), use_n, cos_n, use_r, cos_r, ptr(image_mask) if image_mask is not None else None,
+                                       ptr(tex_to_pos), ptr(tex_to_pos_cam), ptr(mask), ctx.stream()))
+    return tex_to_pos, tex_to_pos_cam, mask
+
+
+def knn_inpaint(idx, d2, nrm, col, pending, n_iters_max=1000, trace=None):
+    """The propagation loop of global_inverse_rendering (renderer_base.py:702-722) on M points: idx int32 / d2 [M,k] (knn_gather(pos, pos, k, want_index=True)),
+    nrm [M,3], col [M,C] (1 <= C <= 16), pending uint8 [M] (non-zero: to fill) -> (col, pending, steps).  One utx_knn_inpaint_step launch per step, colour and
+    flag double-buffered; after each launch the host reads the 4-byte count of points it filled and stops at 0 (that launch changed nothing and is not a
+    step) or after n_iters_max steps.  Points that never qualify stay pending with the colour they came with.  trace (a list): receives each step's pending
+    flags (a clone)."""
+    if idx.dim() != 2 or tuple(d2.shape) != tuple(idx.shape):
+        raise ValueError("knn_inpaint: idx is %s and d2 %s, expected [M, k] both" % (tuple(idx.shape), tuple(d2.shape)))
+    M, k = idx.shape
+    if not 1 <= k <= KNN_INPAINT_K_MAX:
+        raise ValueError("knn_inpaint: %d neighbours, 1 to %d are built" % (k, KNN_INPAINT_K_MAX))
+    if col.dim() != 2 or col.shape[0] != M or not 1 <= col.shape[1] <= CHANNELS_MAX:
+        raise ValueError("knn_inpaint: col is %s, expected [M = %d, 1 <= C <= %d]" % (tuple(col.shape), M, CHANNELS_MAX))
+    if tuple(nrm.shape) != (M, 3) or tuple(pending.shape) != (M,):
+        raise ValueError("knn_inpaint: nrm is %s and pending %s, expected %s and %s" % (tuple(nrm.shape), tuple(pending.shape), (M, 3), (M,)))
+    Cc = col.shape[1]
+    cur, pend = _f(col).clone(), _u8(pending).clone()
+    steps = 0
+    if M == 0 or n_iters_max <= 0:
+        return cur, pend, steps
+    ctx = get_ctx(col.device.index)
+    nxt, pend_nxt = torch.empty_like(cur), torch.empty_like(pend)
+    counter = torch.zeros(1, dtype=I32, device=col.device)
+    p_idx, p_d2, p_nrm = ptr(_i(idx)), ptr(_f(d2)), ptr(_f(nrm))      # checked once: the lists do not change over the steps
+    while steps < int(n_iters_max):
+        ctx.check(ctx.lib.utx_knn_inpaint_step(ctx.handle, p_idx, p_d2, p_nrm, ptr(cur), ptr(pend), M, k, Cc, ptr(nxt), ptr(pend_nxt), ptr(counter), ctx.stream()))
+        if int(counter.item()) == 0:
+            break
+        cur, nxt, pend, pend_nxt = nxt, cur, pend_nxt, pend
+        steps += 1
+        if trace is not None:
+            trace.append(pend.clone())
+    return cur, pend, steps

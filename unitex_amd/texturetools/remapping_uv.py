@@ -2,6 +2,7 @@
 
     project_uv_texture      (:430-505)  the views' colours accumulated per atlas texel with facing weights
     remapping_uv_texture    (:145-270)  ... then overlay, blending against the given atlas, inpainting of the unseen texels, outpainting of the rest
+    remapping_uv_texture_v2 (:25-142)   the scattered-sample bake (NVDiffRendererInverse.global_inverse_rendering), then outpainting
     uv_dilation             (texture/reprojection/uv_dilation.py:33-50, step :80-92)  texel-space dilation
 
 Names, argument names, argument order and defaults are the reference's.  `mesh` is what the inverse renderer holds: a renderer_inverse.DeviceMesh, or an
@@ -121,6 +122,42 @@ def remapping_uv_texture(mesh, c2ws, intrinsics, images, map_Kd=None, weights=No
     if return_stages:
         return out, dict(map_Kd_rgb_acc=acc, map_Kd_weight_acc=wacc, blended=blended, inpaint_mask=mask, inpainted=inpainted, inpaint_steps=steps, map_Kd=out)
     return out
+
+
+def remapping_uv_texture_v2(mesh, c2ws, intrinsics, images, map_Kd=None, use_outpainting=True, use_cv_outpainting=False, render_size=512, texture_size=1024,
+                            angle_degree_threshold=45.0, visualize=False, visualize_detail=False, perspective=True, grid_interpolate_mode="nearest"):
+    """remapping_uv_texture_v2 (:25-142): images [B,4,render_size,render_size] rgba baked through global_inverse_rendering -- every view pixel a sample at its
+    own UV, the texels some view sees take their nearest sample, the texels no view sees are filled along the surface (n_neighbors = 10, at most 1000
+    steps) --, then outpainting of the texels the atlas does not cover (alpha <= 0.6; ops.pull_push) -> [T,T,4] = rgb and the atlas coverage.
+    render_size above 768 resamples the images to 768 x 768 (F.interpolate, nearest) first, as the reference does.  angle_degree_threshold (None: off) is
+    the ray-angle threshold of a perspective bake and the normal-angle threshold of an orthographic one.  map_Kd is ignored, as in the reference.
+    grid_interpolate_mode is this build's one keyword: 'nearest' here, where the reference passes nothing and so runs its 'linear' (a scipy Delaunay
+    interpolator on the host, not built; 'linear' and 'barycentric' raise NotImplementedError naming 'nearest').  Refused, never dropped
+    (NotImplementedError): use_cv_outpainting=True, visualize=True, visualize_detail=True."""
+    _refuse_visualize("remapping_uv_texture_v2", visualize)
+    if visualize_detail:
+        raise NotImplementedError("remapping_uv_texture_v2(visualize_detail=True) is not built: it writes cv2 debug images")
+    if use_outpainting and use_cv_outpainting:
+        raise NotImplementedError("remapping_uv_texture_v2(use_cv_outpainting=True) is not built (cv2.inpaint): the outpainting is pull_push")
+    r = _renderer(mesh)
+    if isinstance(render_size, (tuple, list)) or isinstance(texture_size, (tuple, list)):
+        raise ValueError("remapping_uv_texture_v2: render_size and texture_size are one number each")
+    R, T = int(render_size), int(texture_size)
+    images = torch.as_tensor(images, dtype=torch.float32).to(r.device)
+    B = torch.as_tensor(c2ws).shape[0]
+    if tuple(images.shape) != (B, 4, R, R):
+        raise ValueError("remapping_uv_texture_v2: images is %s, expected [%d, 4, render_size = %d, %d] rgba" % (tuple(images.shape), B, R, R))
+    if R > 768:      # "before using a faster interpolation algorithm, downsample images to 768*768" (:44-47)
+        images = torch.nn.functional.interpolate(images, (768, 768))
+        R = 768
+    intrinsics = torch.as_tensor(intrinsics, dtype=torch.float32).cpu().expand(B, -1, -1)
+    thr = dict(ray_angle_degree_threshold=angle_degree_threshold) if perspective else dict(normal_angle_degree_threshold=angle_degree_threshold)
+    ret = r.global_inverse_rendering(images.permute(0, 2, 3, 1).contiguous(), c2ws, intrinsics, R, T, grid_interpolate_mode=grid_interpolate_mode,
+                                     perspective=perspective, **thr)
+    rgb, alpha = ret["map_attr"][..., :3].contiguous(), ret["map_alpha"]
+    if use_outpainting:
+        rgb = ops.pull_push(rgb, (alpha[..., 0] > 0.6).to(torch.uint8).contiguous())
+    return torch.cat([rgb, alpha], dim=-1)
 
 
 def uv_dilation(map_Kd, map_mask, max_iters=-1, return_steps=False):

@@ -532,6 +532,155 @@ class NVDiffRendererInverse:
         out["mask"] = out["mask"].bool()[..., None]
         return out
 
+    def geometry_rendering(self, c2ws, intrinsics, render_size, render_all_point_cloud=False, render_visible_point_cloud=False, render_z_depth=True,
+                           render_distance=True, render_world_normal=True, render_camera_normal=True, render_world_position=True,
+                           render_camera_position=True, render_ray_direction=True, render_cos_ray_normal=True, render_uv=True, background=None, **kwargs):
+        """NVDiffRendererBase.geometry_rendering (renderer_base.py:745-780): simple_rendering with every geometry buffer on by default and neither v_attr nor
+        map_attr.  The two point-cloud flags default to False, what simple_rendering builds (the reference's True); True raises as it does there, and so does
+        every other keyword simple_rendering refuses."""
+        return self.simple_rendering(c2ws, intrinsics, render_size, render_all_point_cloud=render_all_point_cloud,
+                                     render_visible_point_cloud=render_visible_point_cloud, render_z_depth=render_z_depth, render_distance=render_distance,
+                                     render_world_normal=render_world_normal, render_camera_normal=render_camera_normal,
+                                     render_world_position=render_world_position, render_camera_position=render_camera_position,
+                                     render_ray_direction=render_ray_direction, render_cos_ray_normal=render_cos_ray_normal, render_v_attr=False,
+                                     render_uv=render_uv, render_map_attr=False, background=background, **kwargs)
+
+    def vertex_rendering(self, v_rgb, c2ws, intrinsics, render_size, render_rgb=True, render_all_point_cloud=False, render_visible_point_cloud=False,
+                         render_z_depth=False, render_distance=False, render_world_normal=False, render_camera_normal=False, render_world_position=False,
+                         render_camera_position=False, render_ray_direction=False, render_cos_ray_normal=False, background=None, **kwargs):
+        """NVDiffRendererBase.vertex_rendering (renderer_base.py:782-820): simple_rendering of the per-vertex colour v_rgb [V,C]; 'rgb' is 'v_attr'."""
+        out = self.simple_rendering(c2ws, intrinsics, render_size, v_attr=v_rgb, render_all_point_cloud=render_all_point_cloud,
+                                    render_visible_point_cloud=render_visible_point_cloud, render_z_depth=render_z_depth, render_distance=render_distance,
+                                    render_world_normal=render_world_normal, render_camera_normal=render_camera_normal,
+                                    render_world_position=render_world_position, render_camera_position=render_camera_position,
+                                    render_ray_direction=render_ray_direction, render_cos_ray_normal=render_cos_ray_normal, render_v_attr=render_rgb,
+                                    render_uv=False, render_map_attr=False, background=background, **kwargs)
+        if render_rgb:
+            out["rgb"] = out["v_attr"]
+        return out
+
+    def uv_rendering(self, map_Kd, c2ws, intrinsics, render_size, render_rgb=True, render_all_point_cloud=False, render_visible_point_cloud=False,
+                     render_z_depth=False, render_distance=False, render_world_normal=False, render_camera_normal=False, render_world_position=False,
+                     render_camera_position=False, render_ray_direction=False, render_cos_ray_normal=False, background=None, **kwargs):
+        """NVDiffRendererBase.uv_rendering (renderer_base.py:822-860): simple_rendering of the texture map_Kd ([Ht,Wt,C], [1,Ht,Wt,C] or a tuple of maps) with
+        'uv' always on, as in the reference; 'rgb' is 'map_attr'."""
+        out = self.simple_rendering(c2ws, intrinsics, render_size, map_attr=map_Kd, render_all_point_cloud=render_all_point_cloud,
+                                    render_visible_point_cloud=render_visible_point_cloud, render_z_depth=render_z_depth, render_distance=render_distance,
+                                    render_world_normal=render_world_normal, render_camera_normal=render_camera_normal,
+                                    render_world_position=render_world_position, render_camera_position=render_camera_position,
+                                    render_ray_direction=render_ray_direction, render_cos_ray_normal=render_cos_ray_normal, render_v_attr=False,
+                                    render_uv=True, render_map_attr=render_rgb, background=background, **kwargs)
+        if render_rgb:
+            out["rgb"] = out["map_attr"]
+        return out
+
+    GLOBAL_INTERPOLATE_MODES = ("nearest", "linear", "barycentric")
+
+    def global_inverse_rendering(self, image_attr, c2ws, intrinsics, render_size, texture_size, image_mask=None, image_mask_exclude_boundary=True,
+                                 texture_attr=None, texture_mask=None, ray_angle_degree_threshold=None, normal_angle_degree_threshold=None,
+                                 grid_interpolate_mode="linear", inpainting_occlusion=True, n_neighbors=10, n_iters_max=1000, perspective=True, **kwargs):
+        """NVDiffRendererBase.global_inverse_rendering (render/nvdiffrast/renderer_base.py:562-743) on the mesh of update_from_file / update_from_arrays:
+        the views image_attr [B,H,W,C] of the cameras c2ws [B,4,4] / intrinsics [B,3,3] baked into an atlas of texture_size (int or (H, W)) from scattered
+        samples.  Every view pixel that passes the sample mask -- coverage, its four neighbours covered (image_mask_exclude_boundary; the image wraps
+        round, as torch.roll), normal_angle_degree_threshold on the interpolated camera-space normal's z, ray_angle_degree_threshold on the dot of
+        the interpolated direction and normal, image_mask [B,H,W,1] -- is a sample (its UV, its colour) (ops.view_samples, one launch).  The texels
+        predicted are those on a face that get_visible_faces(method='rays') reports for some view, minus texture_mask; each takes the colour of its
+        nearest sample in UV ('nearest' = scipy's NearestNDInterpolator: ops.knn_gather with k = 1 on a zero third coordinate; ties go to the lower
+        sample index).  inpainting_occlusion then fills the covered texels no view sees along the SURFACE: k = n_neighbors nearest covered texels in
+        3-D (ops.knn_gather on the set itself), weight = L1-normalised reciprocal distance times the cosine between the normals (arXiv 2411.02336
+        section 3.2), one Jacobi sweep per step (ops.knn_inpaint) until a step fills nothing or n_iters_max; a texel with k - 1 or more unknown
+        neighbours waits, and one that never qualifies keeps colour 0 and stays out of map_mask.  The reference's arithmetic is mirrored where it is
+        odd (duplicate positions give NaN, which the closing nan_to_num turns into 0).
+        Returns the reference's dict: map_attr [Ht,Wt,C], map_alpha [Ht,Wt,1] (the atlas coverage), map_mask bool [Ht,Wt,1] (predicted or given), samples_u
+        [Ns,2], samples_v [Ns,C], predicts_u [Np,2], predicts_v [Np,C], samples_x [M,6] / samples_y [M,C] (the covered texels' position + normal and
+        final colour; None without inpainting_occlusion), tex_to_pos [B,H,W,2], tex_to_pos_cam [B,H,W,6], world_to_tex [Ht,Wt,6].  Atlas row 0 is v = 0.
+        texture_attr [Ht,Wt,C] / texture_mask [Ht,Wt,1] (both or neither): the texels of texture_mask keep texture_attr and are not predicted.
+        perspective replaces the reference's enable_perspective() / enable_orthogonal() state.
+        grid_interpolate_mode keeps the reference's default 'linear', which -- like 'barycentric' -- is a scipy Delaunay interpolator on the host and is
+        refused (NotImplementedError): pass 'nearest'.  An unknown mode, texture_attr without texture_mask (or the reverse), n_neighbors outside 1..32 or
+        above the number of covered texels, and a call in which no pixel passes the sample mask raise ValueError; an unknown keyword is a TypeError."""
+        who = "global_inverse_rendering"
+        for k_ in kwargs:
+            raise TypeError("%s() got an unexpected keyword argument %r" % (who, k_))
+        if grid_interpolate_mode not in self.GLOBAL_INTERPOLATE_MODES:
+            raise ValueError("%s(grid_interpolate_mode=%r): one of %s" % (who, grid_interpolate_mode, ", ".join(self.GLOBAL_INTERPOLATE_MODES)))
+        if grid_interpolate_mode != "nearest":
+            raise NotImplementedError("%s(grid_interpolate_mode=%r) is not built (scipy's Delaunay interpolators on the host): pass grid_interpolate_mode='nearest'"
+                                      % (who, grid_interpolate_mode))
+        if (texture_attr is None) != (texture_mask is None):
+            raise ValueError("%s: texture_attr and texture_mask come together" % who)
+        if not 1 <= int(n_neighbors) <= ops.KNN_INPAINT_K_MAX:
+            raise ValueError("%s(n_neighbors=%r): 1 to %d" % (who, n_neighbors, ops.KNN_INPAINT_K_MAX))
+        m, dev = self.pbr_mesh, self.device
+        assert m is not None, "update_from_file first"
+        image_attr = torch.as_tensor(image_attr, dtype=torch.float32).to(dev)
+        Ht, Wt = (texture_size, texture_size) if isinstance(texture_size, int) else texture_size
+        with self._stage("view_raster"):
+            _, c2ws_cpu, _, _, rast = self._view_raster(c2ws, intrinsics, render_size, perspective)
+        B, H, W = rast.shape[:3]
+        if image_attr.dim() != 4 or tuple(image_attr.shape[:3]) != (B, H, W) or not 1 <= image_attr.shape[3] <= ops.CHANNELS_MAX:
+            raise ValueError("%s: image_attr is %s, expected [%d, %d, %d, 1 <= C <= %d]" % (who, tuple(image_attr.shape), B, H, W, ops.CHANNELS_MAX))
+        Cc = image_attr.shape[3]
+        rast2d = self._uv_raster(int(Ht), int(Wt))
+        covered = rast2d[..., 3] > 0
+        with self._stage("visible_faces"):
+            seen = self._visible_faces(c2ws_cpu, perspective, "rays", None, 0).bool().any(dim=0)
+        predicts_mask = covered & seen[(rast2d[..., 3].long() - 1).clamp_(min=0)]
+        if texture_mask is not None:
+            texture_attr = torch.as_tensor(texture_attr, dtype=torch.float32).to(dev)
+            texture_mask = torch.as_tensor(texture_mask).to(dev).bool()
+            if tuple(texture_attr.shape) != (Ht, Wt, Cc) or tuple(texture_mask.shape) != (Ht, Wt, 1):
+                raise ValueError("%s: texture_attr is %s and texture_mask %s, expected %s and %s" % (who, tuple(texture_attr.shape), tuple(texture_mask.shape),
+                                                                                                     (Ht, Wt, Cc), (Ht, Wt, 1)))
+            predicts_mask = predicts_mask & ~texture_mask[..., 0]
+        with self._stage("samples"):
+            v_pos_cam, v_nrm_cam = ops._camera_arrays(m.vertices, m.vertex_normals, c2ws_cpu, B, True, True, None, None)
+            tex_to_pos, tex_to_pos_cam, smask = ops.view_samples(rast, m.faces, m.uvs_2d, v_pos_cam, v_nrm_cam, image_mask_exclude_boundary,
+                                                                 normal_angle_degree_threshold, ray_angle_degree_threshold, image_mask)
+            world_to_tex = ops.interpolate(torch.cat([m.vertices, m.vertex_normals], dim=-1).contiguous(), rast2d, m.faces)
+            smask = smask.bool()
+            samples_u, samples_v = tex_to_pos[smask], image_attr[smask]
+            # undiscretize (camera/conversion.py:183-197): the texel centres in [-1, 1], x first
+            gx = (torch.arange(Wt, dtype=torch.float32, device=dev) + 0.5) / Wt * 2.0 - 1.0
+            gy = (torch.arange(Ht, dtype=torch.float32, device=dev) + 0.5) / Ht * 2.0 - 1.0
+            tex_to_tex = torch.stack([gx[None, :].expand(Ht, Wt), gy[:, None].expand(Ht, Wt)], dim=-1)
+            predicts_u = tex_to_tex[predicts_mask]
+        if samples_u.shape[0] == 0:
+            raise ValueError("%s: no pixel of any view passes the sample mask" % who)
+        with self._stage("nearest"):
+            if predicts_u.shape[0] > 0:
+                z = lambda t: torch.cat([t, torch.zeros_like(t[:, :1])], dim=-1).contiguous()
+                predicts_v = ops.knn_gather(z(samples_u), z(predicts_u), 1, src_attr=samples_v.contiguous())
+            else:
+                predicts_v = torch.zeros(0, Cc, dtype=torch.float32, device=dev)
+        map_attr = torch.zeros(Ht, Wt, Cc, dtype=torch.float32, device=dev)
+        map_attr[predicts_mask] = predicts_v
+        map_mask = predicts_mask & ~torch.isnan(map_attr).any(dim=-1)
+        map_attr = torch.nan_to_num(map_attr, nan=0.0).clamp_(0.0, 1.0)
+        if texture_mask is not None:
+            map_attr = torch.where(texture_mask, texture_attr, map_attr)
+            map_mask = covered & (map_mask | texture_mask[..., 0])
+        samples_x = samples_y = None
+        self.last = {"rast2d": rast2d, "view_mask": smask, "inpaint_steps": 0}
+        if inpainting_occlusion:
+            samples_x = world_to_tex[covered]
+            M = samples_x.shape[0]
+            if M < int(n_neighbors):
+                raise ValueError("%s(n_neighbors=%d): the atlas covers %d texels only" % (who, n_neighbors, M))
+            with self._stage("knn"):
+                pos = samples_x[:, :3].contiguous()
+                _, idx, d2 = ops.knn_gather(pos, pos, int(n_neighbors), want_index=True)
+            with self._stage("propagation"):
+                samples_y, _, steps = ops.knn_inpaint(idx, d2, samples_x[:, 3:].contiguous(), map_attr[covered], (~map_mask)[covered].to(torch.uint8),
+                                                      n_iters_max=n_iters_max)
+            self.last["inpaint_steps"] = steps
+            map_attr = torch.zeros_like(map_attr)
+            map_attr[covered] = samples_y
+            map_attr = torch.nan_to_num(map_attr, nan=0.0).clamp_(0.0, 1.0)
+        return {"map_attr": map_attr, "map_alpha": covered[..., None].to(torch.float32), "map_mask": map_mask[..., None], "samples_u": samples_u,
+                "samples_v": samples_v, "predicts_u": predicts_u, "predicts_v": predicts_v, "samples_x": samples_x, "samples_y": samples_y,
+                "tex_to_pos": tex_to_pos, "tex_to_pos_cam": tex_to_pos_cam, "world_to_tex": world_to_tex}
+
     def compute_uv_mask(self, texture_size=2048):
         """Mesh.compute_uv_mask (mesh/structure.py:786-799): the atlas coverage, bool [H,W,1]"""
         return self.simple_inverse_rendering(None, texture_size, enable_antialis=False)["mask"][0]
