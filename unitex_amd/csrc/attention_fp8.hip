@@ -6,8 +6,8 @@
 // column: in-register softmax), sum-checked softmax with rare exact re-centring, accumulators start at -m -- on OCP MX operands:
 //   Q8, K8  [H][S_pad][128] e4m3 bytes + one dword of four E8M0 scales per row (the 32-channel blocks of d)      <- utx_quant_mx8 of the head-major Q / K
 //   V8^T    [H][128][S_pad] e4m3 bytes + E8M0 per (channel, block of 32 KEYS), stored [H][S_pad/32][32][4]      <- utx_quant_vt_mx8 (this file)
-//   P       e4m3 with the unit scale: the sum check keeps every p <= 256 (< 448); p below 2^-9 flush to zero (the published fp8 attention kernels accept
-//           the same: a weight that small relative to the running maximum)
+//   P       e4m3 with the unit scale: the sum check keeps every p <= 256 (< 448); round to nearest even with gradual underflow, so p <= 2^-10 becomes zero and
+//           2^-10 < p < 1.5 * 2^-9 becomes 2^-9 (the published fp8 attention kernels accept the same: a weight that small relative to the running maximum)
 // so the MFMA's block scales carry the dynamic range of Q, K and V and no amax pass over a tensor is needed.
 // Operand layout of the 32 x 32 x 64 MFMA (gemm_w4.hip, tools/mx_probe.hip): lane (row, h) holds k = 16 h .. 16 h + 15 of the first 32-element scale
 // block in bytes 0-15 and k = 32 + 16 h .. of the second in bytes 16-31; block-0 scales come from lanes 0-31, block-1 scales from lanes 32-63 (byte
