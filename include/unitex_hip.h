@@ -813,6 +813,28 @@ int utx_view_samples(utx_ctx* ctx, const float* rast, const int* faces, int F, c
 int utx_knn_inpaint_step(utx_ctx* ctx, const int* idx, const float* d2, const float* nrm, const float* col_in, const unsigned char* pending_in, long M, int k, int C,
                          float* col_out, unsigned char* pending_out, int* counter, utx_stream stream);
 
+/* Poisson image fusion: image_fusion of the reference (image/image_fusion.py:12-58), which hands uint8 images to OpenCV's seamlessClone(NORMAL_CLONE) [3p] on the
+ * host.  The rule is this library's (DESIGN 8 "Poisson image fusion"); everything runs on the device in fp32, stream-ordered, row-major, bit-reproducible.
+ * utx_mask_morph: mask_in / mask_out / tmp uint8 [H][W].  n > 0: grey erosion (minimum) over an n x n box, n < 0: grey dilation (maximum) over |n| x |n|; the box
+ *   covers the offsets -(|n| / 2) .. |n| - 1 - |n| / 2 in both axes and taps outside the image are left out.  Two separable passes through tmp.  1 <= |n| <= 31.
+ * utx_mask_bbox: rect (DEVICE int32 [4]) = (x1, y1, w, h), the tight bounding rectangle of mask > 0; four zeros for an empty mask.  The caller reads the 16 bytes
+ *   back: the rectangle sizes the solver's levels on the host.
+ * utx_image_fusion: src, dst, out uint8 [H][W][3], mask uint8 [H][W], the rectangle (x1, y1, w, h) inside the image (HOST integers).  w < 3 or h < 3: out = dst.
+ *   Otherwise, inside the rectangle: s = src where mask > 0, else 0; m = mask / 255 eroded three times by a 3 x 3 box (pixels outside the rectangle left out);
+ *   v = m grad(s) + (1 - m) grad(dst) with forward differences and m at (x, y); f = the backward divergence of v on the (w - 2) x (h - 2) interior; I has the
+ *   5-point Laplacian f there and equals dst on the rectangle's one-pixel ring.  Solved for u = I - dst (zero boundary values, right-hand side div(m grad(s - dst)))
+ *   by `cycles` multigrid V-cycles (0: utx_image_fusion_cycles(w, h), fixed per size; no data-dependent stop, no read-back); every cycle iterates on the residual of
+ *   that exact system.  out = clamp(round_half_even(dst + u), 0, 255) on the interior and dst elsewhere; out_f float32 [H][W][3] (optional) = dst + u unrounded
+ *   and unclamped on the interior, dst elsewhere.  work: utx_image_fusion_workspace_bytes(w, h) bytes (0 when there is no interior), 4-byte aligned.
+ * -2, outputs untouched: H, W <= 0; n = 0 or |n| > 31; a null operand (out_f excepted); tmp equal to mask_in or mask_out; a rectangle with a negative member or
+ * reaching outside the image; cycles outside 0 .. 64; with an interior, a null, misaligned or short workspace. */
+int utx_mask_morph(utx_ctx* ctx, const unsigned char* mask_in, int H, int W, int n, unsigned char* tmp, unsigned char* mask_out, utx_stream stream);
+int utx_mask_bbox(utx_ctx* ctx, const unsigned char* mask, int H, int W, int* rect, utx_stream stream);
+int utx_image_fusion_cycles(int w, int h);
+long utx_image_fusion_workspace_bytes(int w, int h);
+int utx_image_fusion(utx_ctx* ctx, const unsigned char* src, const unsigned char* dst, const unsigned char* mask, int H, int W, int x1, int y1, int w, int h,
+                     int cycles, unsigned char* out, float* out_f, void* work, long work_bytes, utx_stream stream);
+
 /* fused per-(view, texel) gather + visibility of uv_to_pcd (renderer_inverse.py:277-298,316-325) */
 typedef struct utx_backproject_desc {
     const void* rast2d;                 /* [T][4] f32 UV-space raster */

@@ -225,6 +225,11 @@ SYMBOLS = {
     "utx_view_samples": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_float,
                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "utx_knn_inpaint_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "utx_mask_morph": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "utx_mask_bbox": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "utx_image_fusion_cycles": (c_int, [c_int, c_int]),
+    "utx_image_fusion_workspace_bytes": (c_long, [c_int, c_int]),
+    "utx_image_fusion": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p] + [c_int] * 7 + [c_void_p, c_void_p, c_void_p, c_long, c_void_p]),
     "utx_bvh_trace_count": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
     "utx_bvh_depth": (c_int, [c_void_p]),
     "utx_bvh_closest_point": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

@@ -49,6 +49,7 @@ GEOM = [
     ("vertex_bake.hip", ["-ffp-contract=off"] + NO_PK),      # vertex-colour bake: weight maps, per-vertex projection, graph inpainting
     ("uv_bake.hip", ["-ffp-contract=off"] + NO_PK),      # blended UV texture bake: per-texel accumulation over the views, texel-space dilation
     ("global_bake.hip", ["-ffp-contract=off"] + NO_PK),      # scattered-sample UV bake: per-pixel sample pass, surface-space propagation step
+    ("image_fusion.hip", ["-ffp-contract=off"] + NO_PK),      # Poisson image fusion: mask morphology, right-hand side, multigrid V-cycles; bit-reproducible
     ("texture_post.hip", ["-ffp-contract=off"] + NO_PK),
     ("knn.hip", ["-ffp-contract=off"]),
     ("sampling.hip", ["-ffp-contract=off"]),

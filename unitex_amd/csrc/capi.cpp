@@ -534,6 +534,28 @@ int utx_knn_inpaint_step(utx_ctx* ctx, const int* idx, const float* d2, const fl
         return fail(ctx, -2, me);
     UTX_CALL(ctx, me, utx_launch_knn_inpaint_step(idx, d2, nrm, col_in, pending_in, M, k, C, col_out, pending_out, counter, (hipStream_t)stream));
 }
+// ---- Poisson image fusion (image_fusion.hip) ----
+int utx_mask_morph(utx_ctx* ctx, const unsigned char* mask_in, int H, int W, int n, unsigned char* tmp, unsigned char* mask_out, utx_stream stream) {
+    const char* const me = "utx_mask_morph";
+    if (H <= 0 || W <= 0 || n == 0 || n > 31 || n < -31) return fail(ctx, -2, me);
+    if (!mask_in || !tmp || !mask_out || tmp == mask_in || tmp == mask_out) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_mask_morph(mask_in, H, W, n, tmp, mask_out, (hipStream_t)stream));
+}
+int utx_mask_bbox(utx_ctx* ctx, const unsigned char* mask, int H, int W, int* rect, utx_stream stream) {
+    const char* const me = "utx_mask_bbox";
+    if (H <= 0 || W <= 0 || !mask || !rect || misaligned(rect, 3)) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_mask_bbox(mask, H, W, rect, (hipStream_t)stream));
+}
+int utx_image_fusion_cycles(int w, int h) { return utx_image_fusion_cycles_impl(w, h); }
+long utx_image_fusion_workspace_bytes(int w, int h) { return (long)utx_image_fusion_workspace_bytes_impl(w, h); }
+int utx_image_fusion(utx_ctx* ctx, const unsigned char* src, const unsigned char* dst, const unsigned char* mask, int H, int W, int x1, int y1, int w, int h,
+                     int cycles, unsigned char* out, float* out_f, void* work, long work_bytes, utx_stream stream) {
+    const char* const me = "utx_image_fusion";
+    if (H <= 0 || W <= 0 || x1 < 0 || y1 < 0 || w < 0 || h < 0 || w > W - x1 || h > H - y1 || cycles < 0 || cycles > 64) return fail(ctx, -2, me);
+    if (!src || !dst || !mask || !out || misaligned(out_f, 3)) return fail(ctx, -2, me);
+    if (w >= 3 && h >= 3 && (!work || misaligned(work, 3) || work_bytes < (long)utx_image_fusion_workspace_bytes_impl(w, h))) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_image_fusion(src, dst, mask, H, W, x1, y1, w, h, cycles, out, out_f, work, (hipStream_t)stream));
+}
 int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws, int n_views, float* out, utx_stream stream) {
     if (!nrm || !c2ws || !out) return fail(ctx, -2, "utx_camera_normals");
     UTX_CALL(ctx, "utx_camera_normals", utx_launch_camera_normals(nrm, V, c2ws, n_views, out, (hipStream_t)stream));

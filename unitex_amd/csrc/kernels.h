@@ -218,6 +218,13 @@ int utx_launch_view_samples(const float* rast, const int* faces, int F, const fl
                             float* tex_to_pos, float* tex_to_pos_cam, unsigned char* mask, hipStream_t stream);
 int utx_launch_knn_inpaint_step(const int* idx, const float* d2, const float* nrm, const float* col_in, const unsigned char* pend_in, long M, int k, int C,
                                 float* col_out, unsigned char* pend_out, int* counter, hipStream_t stream);
+// image_fusion.hip
+int utx_launch_mask_morph(const unsigned char* mask_in, int H, int W, int n, unsigned char* tmp, unsigned char* mask_out, hipStream_t stream);
+int utx_launch_mask_bbox(const unsigned char* mask, int H, int W, int* rect, hipStream_t stream);
+int utx_image_fusion_cycles_impl(int w, int h);
+size_t utx_image_fusion_workspace_bytes_impl(int w, int h);
+int utx_launch_image_fusion(const unsigned char* src, const unsigned char* dst, const unsigned char* mask, int H, int W, int x1, int y1, int w, int h, int cycles,
+                            unsigned char* out, float* out_f, void* work, hipStream_t stream);
 int utx_launch_backproject(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_backproject_vis(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_composite_winner(const void* vis, int n_views, const int* order, int n_order, long T, void* winner, hipStream_t stream);

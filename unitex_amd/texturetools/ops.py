@@ -1480,3 +1480,58 @@ def knn_inpaint(idx, d2, nrm, col, pending, n_iters_max=1000, trace=None):
         if trace is not None:
             trace.append(pend.clone())
     return cur, pend, steps
+
+
+# ---- Poisson image fusion (image_fusion.hip): image_fusion of the reference; the rule is DESIGN 8 "Poisson image fusion"
+
+MASK_MORPH_MAX = 31      # utx_mask_morph's cap on the box size
+
+
+def mask_morph(mask, n):
+    """mask uint8 [H,W]; n > 0: grey erosion over an n x n box, n < 0: grey dilation over |n| x |n| (offsets -(|n| // 2) .. |n| - 1 - |n| // 2, taps outside the
+    image left out), n = 0: a copy.  Two separable launches (utx_mask_morph)."""
+    n = int(n)
+    if abs(n) > MASK_MORPH_MAX:
+        raise ValueError("mask_morph: a box of %d, at most %d is built" % (abs(n), MASK_MORPH_MAX))
+    if mask.dim() != 2:
+        raise ValueError("mask_morph: mask is %s, expected [H, W]" % (tuple(mask.shape),))
+    H, W = mask.shape
+    if n == 0 or H * W == 0:
+        return _u8(mask).clone()
+    ctx = get_ctx(mask.device.index)
+    tmp, out = torch.empty_like(mask), torch.empty_like(mask)
+    ctx.check(ctx.lib.utx_mask_morph(ctx.handle, ptr(_u8(mask)), H, W, n, ptr(tmp), ptr(out), ctx.stream()))
+    return out
+
+
+def mask_bbox(mask):
+    """(x1, y1, w, h): the tight bounding rectangle of mask > 0 (uint8 [H,W]), zeros for an empty mask.  One reduction and a 16-byte read-back (utx_mask_bbox)."""
+    H, W = mask.shape
+    if H * W == 0:
+        return 0, 0, 0, 0
+    ctx = get_ctx(mask.device.index)
+    rect = torch.empty(4, dtype=I32, device=mask.device)
+    ctx.check(ctx.lib.utx_mask_bbox(ctx.handle, ptr(_u8(mask)), H, W, ptr(rect), ctx.stream()))
+    return tuple(int(v) for v in rect.cpu().tolist())
+
+
+def image_fusion_u8(src_u8, dst_u8, mask_u8, n_erode_pix=0, return_float=False, cycles=0):
+    """Poisson fusion of one image: src_u8, dst_u8 uint8 [H,W,3], mask_u8 uint8 [H,W] -> uint8 [H,W,3] (with return_float=True also the unrounded float32 result).
+    The mask is resized by n_erode_pix (mask_morph), its bounding rectangle read back (the one host round trip: it sizes the multigrid levels), and
+    utx_image_fusion solves for the correction on the rectangle's interior with a fixed number of V-cycles (cycles = 0: the library's count for the size)."""
+    if src_u8.dim() != 3 or src_u8.shape[-1] != 3 or tuple(dst_u8.shape) != tuple(src_u8.shape) or tuple(mask_u8.shape) != tuple(src_u8.shape[:2]):
+        raise ValueError("image_fusion_u8: src %s, dst %s, mask %s; expected [H, W, 3], [H, W, 3], [H, W]" %
+                         (tuple(src_u8.shape), tuple(dst_u8.shape), tuple(mask_u8.shape)))
+    H, W = mask_u8.shape
+    out = torch.empty_like(_u8(dst_u8))
+    out_f = torch.empty(H, W, 3, dtype=F32, device=out.device) if return_float else None
+    if H * W == 0:
+        return (out, out_f) if return_float else out
+    ctx = get_ctx(src_u8.device.index)
+    mask = mask_morph(mask_u8, n_erode_pix) if n_erode_pix else _u8(mask_u8)
+    x1, y1, w, h = mask_bbox(mask)
+    wb = int(ctx.lib.utx_image_fusion_workspace_bytes(w, h))
+    work = torch.empty(max(wb, 4), dtype=U8, device=out.device)
+    ctx.check(ctx.lib.utx_image_fusion(ctx.handle, ptr(_u8(src_u8)), ptr(_u8(dst_u8)), ptr(mask), H, W, x1, y1, w, h, int(cycles), ptr(out), ptr(out_f), ptr(work),
+                                       wb, ctx.stream()))
+    return (out, out_f) if return_float else out

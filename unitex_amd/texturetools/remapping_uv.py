@@ -19,7 +19,13 @@ Three readings of the reference, recorded by the fixture (tests/golden/g21_uv_ba
 One departure: uv_dilation stops when a step fills nothing more (the reference loops forever when no valid texel is in reach).
 
 Refused, never dropped (NotImplementedError): visualize=True (cv2 debug images), use_cv_inpainting=True -- the reference's DEFAULT, cv2.inpaint (Telea):
-pass use_cv_inpainting=False --, use_cv_outpainting=True, blending_type='poisson'."""
+pass use_cv_inpainting=False --, use_cv_outpainting=True, blending_type='poisson'.
+
+blending_type='poisson' is still refused HERE, but its solver is built (texturetools/image_fusion.py, csrc/image_fusion.hip); until the refusal is lifted a caller
+composes the branch (:213) as the reference does:
+    acc, wacc = project_uv_texture(mesh, c2ws, intrinsics, images, map_Kd, weights)
+    overlay = torch.where(wacc > overlay_confidence, acc / wacc, acc)
+    rgb = image_fusion(overlay[None, ..., :3], map_Kd[None, ..., :3], (wacc > blending_confidence).float()[None])[0]"""
 import numpy as np
 import torch
 
