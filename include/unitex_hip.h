@@ -835,6 +835,33 @@ long utx_image_fusion_workspace_bytes(int w, int h);
 int utx_image_fusion(utx_ctx* ctx, const unsigned char* src, const unsigned char* dst, const unsigned char* mask, int H, int W, int x1, int y1, int w, int h,
                      int cycles, unsigned char* out, float* out_f, void* work, long work_bytes, utx_stream stream);
 
+/* Telea inpainting: what the reference's uv_dilation_cv / remapping_uv_texture(use_cv_inpainting=True) hand to OpenCV's cv2.inpaint(INPAINT_TELEA) [3p] on the host.
+ * The rule is this library's (DESIGN 8 "Telea inpainting": Telea's 2004 estimate on an exact distance map, not OpenCV's heap order, which nothing here can pin);
+ * everything runs on the device in fp32, stream-ordered, row-major, bit-reproducible.  H, W in 1 .. UTX_INPAINT_SIDE_MAX.
+ * utx_inpaint_distance: hole uint8 [H][W] (non-zero: fill) -> d2 int32 [H][W]: the exact squared Euclidean distance of a hole pixel to the nearest in-image
+ *   pixel outside the hole, 0 outside the hole, UTX_INPAINT_NONE everywhere when the whole image is a hole.  tmp: int32 [H][W] (the column scan).
+ * utx_inpaint_telea_step: one sweep on col_in float [H][W][C] (1 <= C <= 4), done_in uint8 [H][W] (1: the pixel has its value; every pixel outside the hole) and
+ *   d2 into col_out / done_out.  With T = sqrt(float(d2)) and eps = radius (1 .. UTX_INPAINT_RADIUS_MAX): a hole pixel p that is not done computes itself once
+ *   every pixel of its read set -- the disc |q - p|^2 <= eps^2 and the 4-neighbours of the disc's pixels -- with d2 < d2(p) is done.  Per channel, q row-major
+ *   over the (2 eps + 1)^2 window, in the image, inside the disc, with d2(q) < d2(p) (strict, on integers), r = p - q:
+ *     w = ((1 / (|r|^2 |r|)) (1 / (1 + |T(q) - T(p)|))) max(|r . gT(p)|, 1e-6);  v = sum w (I(q) + gI(q) . r) / sum w
+ *   gT: central difference of T where both neighbours are in the image, one-sided at the image border, 0 on an axis of length 1.  gI(q) per axis over the
+ *   neighbours n of q in the image with d2(n) < d2(p): central with both, one-sided with one, 0 with none.  Every other hole pixel copies its colour and flag;
+ *   pixels OUTSIDE the hole are not written: col_out / done_out must already hold col_in / done_in there (the caller initialises both buffers alike).  A pixel
+ *   with d2 = UTX_INPAINT_NONE is never computed.  *counter (device int32) is INCREASED by the number of pixels computed in this sweep; the caller zeroes it,
+ *   so it may be read back once every few sweeps.  One launch; no block waits for another; no workspace.
+ * utx_inpaint_finish: out uint8 [H][W][C] = round_half_even(min(max(col, 0), 255)); out_f float [H][W][C] (optional) = col, unclamped and unrounded.
+ * -2, outputs untouched: a null operand (out_f excepted) or one not aligned to its element; H or W outside 1 .. UTX_INPAINT_SIDE_MAX; C outside 1 .. 4; radius
+ * outside 1 .. UTX_INPAINT_RADIUS_MAX (a caller's radius <= 0, OpenCV's clamp to 1, is normalised above the C ABI); tmp == d2; col_in == col_out or
+ * done_in == done_out; col == out_f. */
+#define UTX_INPAINT_RADIUS_MAX 8
+#define UTX_INPAINT_SIDE_MAX 16384
+#define UTX_INPAINT_NONE 2147483647
+int utx_inpaint_distance(utx_ctx* ctx, const unsigned char* hole, int H, int W, int* tmp, int* d2, utx_stream stream);
+int utx_inpaint_telea_step(utx_ctx* ctx, const float* col_in, const unsigned char* done_in, const int* d2, int H, int W, int C, int radius, float* col_out,
+                           unsigned char* done_out, int* counter, utx_stream stream);
+int utx_inpaint_finish(utx_ctx* ctx, const float* col, int H, int W, int C, unsigned char* out, float* out_f, utx_stream stream);
+
 /* fused per-(view, texel) gather + visibility of uv_to_pcd (renderer_inverse.py:277-298,316-325) */
 typedef struct utx_backproject_desc {
     const void* rast2d;                 /* [T][4] f32 UV-space raster */

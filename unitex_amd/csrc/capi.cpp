@@ -556,6 +556,29 @@ int utx_image_fusion(utx_ctx* ctx, const unsigned char* src, const unsigned char
     if (w >= 3 && h >= 3 && (!work || misaligned(work, 3) || work_bytes < (long)utx_image_fusion_workspace_bytes_impl(w, h))) return fail(ctx, -2, me);
     UTX_CALL(ctx, me, utx_launch_image_fusion(src, dst, mask, H, W, x1, y1, w, h, cycles, out, out_f, work, (hipStream_t)stream));
 }
+// ---- Telea inpainting (inpaint.hip) ----
+int utx_inpaint_distance(utx_ctx* ctx, const unsigned char* hole, int H, int W, int* tmp, int* d2, utx_stream stream) {
+    const char* const me = "utx_inpaint_distance";
+    if (H <= 0 || W <= 0 || H > UTX_INPAINT_SIDE_MAX || W > UTX_INPAINT_SIDE_MAX) return fail(ctx, -2, me);
+    if (!hole || !tmp || !d2 || tmp == d2 || misaligned(tmp, 3) || misaligned(d2, 3)) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_inpaint_distance(hole, H, W, tmp, d2, (hipStream_t)stream));
+}
+int utx_inpaint_telea_step(utx_ctx* ctx, const float* col_in, const unsigned char* done_in, const int* d2, int H, int W, int C, int radius, float* col_out,
+                           unsigned char* done_out, int* counter, utx_stream stream) {
+    const char* const me = "utx_inpaint_telea_step";
+    if (H <= 0 || W <= 0 || H > UTX_INPAINT_SIDE_MAX || W > UTX_INPAINT_SIDE_MAX || C < 1 || C > 4 || radius < 1 || radius > UTX_INPAINT_RADIUS_MAX)
+        return fail(ctx, -2, me);
+    if (!col_in || !done_in || !d2 || !col_out || !done_out || !counter) return fail(ctx, -2, me);
+    if (col_in == col_out || done_in == done_out) return fail(ctx, -2, me);      // a sweep reads one pair and writes the other
+    if (misaligned(col_in, 3) || misaligned(col_out, 3) || misaligned(d2, 3) || misaligned(counter, 3)) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_inpaint_telea_step(col_in, done_in, d2, H, W, C, radius, col_out, done_out, counter, (hipStream_t)stream));
+}
+int utx_inpaint_finish(utx_ctx* ctx, const float* col, int H, int W, int C, unsigned char* out, float* out_f, utx_stream stream) {
+    const char* const me = "utx_inpaint_finish";
+    if (H <= 0 || W <= 0 || H > UTX_INPAINT_SIDE_MAX || W > UTX_INPAINT_SIDE_MAX || C < 1 || C > 4) return fail(ctx, -2, me);
+    if (!col || !out || misaligned(col, 3) || misaligned(out_f, 3) || col == out_f) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_inpaint_finish(col, H, W, C, out, out_f, (hipStream_t)stream));
+}
 int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws, int n_views, float* out, utx_stream stream) {
     if (!nrm || !c2ws || !out) return fail(ctx, -2, "utx_camera_normals");
     UTX_CALL(ctx, "utx_camera_normals", utx_launch_camera_normals(nrm, V, c2ws, n_views, out, (hipStream_t)stream));

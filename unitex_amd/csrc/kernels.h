@@ -225,6 +225,11 @@ int utx_image_fusion_cycles_impl(int w, int h);
 size_t utx_image_fusion_workspace_bytes_impl(int w, int h);
 int utx_launch_image_fusion(const unsigned char* src, const unsigned char* dst, const unsigned char* mask, int H, int W, int x1, int y1, int w, int h, int cycles,
                             unsigned char* out, float* out_f, void* work, hipStream_t stream);
+// inpaint.hip
+int utx_launch_inpaint_distance(const unsigned char* hole, int H, int W, int* tmp, int* d2, hipStream_t stream);
+int utx_launch_inpaint_telea_step(const float* col_in, const unsigned char* done_in, const int* d2, int H, int W, int C, int eps, float* col_out,
+                                  unsigned char* done_out, int* counter, hipStream_t stream);
+int utx_launch_inpaint_finish(const float* col, int H, int W, int C, unsigned char* out, float* out_f, hipStream_t stream);
 int utx_launch_backproject(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_backproject_vis(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_composite_winner(const void* vis, int n_views, const int* order, int n_order, long T, void* winner, hipStream_t stream);

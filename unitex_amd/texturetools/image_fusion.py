@@ -7,10 +7,10 @@ round trip is the 16-byte bounding rectangle per image, which sizes the solver's
 not pinned against OpenCV, which is not available to the tests.
 
 Built: image_fusion, image_fusion_hybrid.  Refused by name (NotImplementedError): color_transfer=True (an HSV histogram transfer through cv2.cvtColor),
-smooth_fusion (cv2.inpaint) and the boundary_color_shift experiments (cv2 contours and inpainting, scipy interpolators and k-d trees), image_soft_fusion
+smooth_fusion and the boundary_color_shift experiments (beside cv2.inpaint, which ops.inpaint_telea now covers, cv2 contours, scipy interpolators and k-d trees), image_soft_fusion
 (a 175-tap cv2.GaussianBlur).
 
-The blended UV bake composes with it as its 'poisson' branch does (mesh_remapping.py:213), until remapping_uv_texture itself takes blending_type='poisson':
+The blended UV bake's 'poisson' branch (mesh_remapping.py:213) runs in remapping_uv.remapping_uv_texture_cv (remapping_uv_texture keeps refusing it) as the composition:
     acc, wacc = project_uv_texture(mesh, c2ws, intrinsics, images, map_Kd, weights)
     overlay = torch.where(wacc > overlay_confidence, acc / wacc, acc)
     rgb = image_fusion(overlay[None, ..., :3], map_Kd[None, ..., :3], (wacc > blending_confidence).float()[None])[0]

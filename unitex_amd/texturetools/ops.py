@@ -1535,3 +1535,84 @@ def image_fusion_u8(src_u8, dst_u8, mask_u8, n_erode_pix=0, return_float=False, 
     ctx.check(ctx.lib.utx_image_fusion(ctx.handle, ptr(_u8(src_u8)), ptr(_u8(dst_u8)), ptr(mask), H, W, x1, y1, w, h, int(cycles), ptr(out), ptr(out_f), ptr(work),
                                        wb, ctx.stream()))
     return (out, out_f) if return_float else out
+
+
+# ---- Telea inpainting (inpaint.hip): cv2.inpaint(INPAINT_TELEA) of the reference; the rule is DESIGN 8 "Telea inpainting"
+
+INPAINT_RADIUS_MAX = 8      # utx_inpaint_telea_step's cap on the radius
+INPAINT_SIDE_MAX = 16384      # ... and on the image's sides (the squared distances stay inside int32)
+INPAINT_NONE = 2147483647      # the distance where the whole image is a hole
+INPAINT_READBACK = 4      # sweeps between two read-backs of the 4-byte counter (DESIGN 8 "Telea inpainting": measured at 1, 4 and 16)
+
+
+def _inpaint_shape(who, H, W):
+    if H > INPAINT_SIDE_MAX or W > INPAINT_SIDE_MAX:
+        raise ValueError("%s: an image of %d x %d, sides up to %d are built" % (who, H, W, INPAINT_SIDE_MAX))
+
+
+def inpaint_distance(hole):
+    """hole uint8 [H,W] (non-zero: fill) -> int32 [H,W]: the exact squared Euclidean distance of every hole pixel to the nearest pixel outside the hole, 0 outside
+    the hole, INPAINT_NONE everywhere when the whole image is a hole.  Two launches (utx_inpaint_distance): a column scan, then a per-pixel minimum over the row."""
+    if hole.dim() != 2:
+        raise ValueError("inpaint_distance: hole is %s, expected [H, W]" % (tuple(hole.shape),))
+    H, W = hole.shape
+    _inpaint_shape("inpaint_distance", H, W)
+    d2 = torch.empty(H, W, dtype=I32, device=hole.device)
+    if H * W == 0:
+        return d2
+    ctx = get_ctx(hole.device.index)
+    tmp = torch.empty_like(d2)
+    ctx.check(ctx.lib.utx_inpaint_distance(ctx.handle, ptr(_u8(hole)), H, W, ptr(tmp), ptr(d2), ctx.stream()))
+    return d2
+
+
+def inpaint_telea(img_u8, hole_u8, radius=1, return_float=False, trace=None, readback=None):
+    """Telea inpainting of one image: img_u8 uint8 [H,W,C] (1 <= C <= 4), hole_u8 uint8 [H,W] (non-zero: fill), radius 1 .. 8 (<= 0 means 1, as OpenCV clamps
+    the reference's -1) -> (uint8 [H,W,C], sweeps), with return_float=True (uint8, float32 [H,W,C] unrounded and unclamped, sweeps).  The distance map
+    (inpaint_distance), then one utx_inpaint_telea_step launch per sweep on a float32 working image, colour and done flags double-buffered; every `readback`
+    sweeps (None: INPAINT_READBACK) the host reads the 4-byte count of pixels computed since the last read and stops once every hole pixel is done, so up to
+    readback - 1 sweeps that change nothing may be launched -- the result does not depend on it.  utx_inpaint_finish rounds once at the end.  An empty image,
+    an empty hole and an all-hole image return a copy and 0 sweeps.  trace (a list): receives each sweep's done flags (a clone)."""
+    if img_u8.dim() != 3 or not 1 <= img_u8.shape[2] <= 4 or tuple(hole_u8.shape) != tuple(img_u8.shape[:2]):
+        raise ValueError("inpaint_telea: img is %s and hole %s, expected [H, W, 1 <= C <= 4] and [H, W]" % (tuple(img_u8.shape), tuple(hole_u8.shape)))
+    if img_u8.dtype != U8:
+        raise ValueError("inpaint_telea: img is %s, expected uint8" % img_u8.dtype)
+    radius = max(int(radius), 1)
+    if radius > INPAINT_RADIUS_MAX:
+        raise ValueError("inpaint_telea: a radius of %d, at most %d is built" % (radius, INPAINT_RADIUS_MAX))
+    k = INPAINT_READBACK if readback is None else int(readback)
+    if k < 1:
+        raise ValueError("inpaint_telea: readback is %d, expected >= 1" % k)
+    H, W, Cc = img_u8.shape
+    _inpaint_shape("inpaint_telea", H, W)
+    img = img_u8.contiguous()
+    pending = int(torch.count_nonzero(hole_u8).item()) if H * W else 0
+    if pending == 0 or pending == H * W:      # nothing to fill, or nothing to fill from
+        out = img.clone()
+        return (out, out.to(F32), 0) if return_float else (out, 0)
+    ctx = get_ctx(img.device.index)
+    hole = _u8(hole_u8)
+    d2 = inpaint_distance(hole)
+    cur = img.to(F32)
+    nxt = cur.clone()      # a sweep writes hole pixels only: both buffers hold the image outside the hole
+    done = (hole == 0).to(U8)
+    done_nxt = done.clone()
+    counter = torch.zeros(1, dtype=I32, device=img.device)
+    p_d2 = ptr(d2)
+    sweeps = 0
+    while pending > 0:
+        for _ in range(k):
+            ctx.check(ctx.lib.utx_inpaint_telea_step(ctx.handle, ptr(cur), ptr(done), p_d2, H, W, Cc, radius, ptr(nxt), ptr(done_nxt), ptr(counter), ctx.stream()))
+            cur, nxt, done, done_nxt = nxt, cur, done_nxt, done
+            sweeps += 1
+            if trace is not None:
+                trace.append(done.clone())
+        filled = int(counter.item())
+        counter.zero_()
+        if filled == 0:
+            raise RuntimeError("inpaint_telea: %d sweeps filled nothing with %d pixels pending" % (k, pending))
+        pending -= filled
+    out = torch.empty_like(img)
+    out_f = torch.empty(H, W, Cc, dtype=F32, device=img.device) if return_float else None
+    ctx.check(ctx.lib.utx_inpaint_finish(ctx.handle, ptr(cur), H, W, Cc, ptr(out), ptr(out_f), ctx.stream()))
+    return (out, out_f, sweeps) if return_float else (out, sweeps)

@@ -18,14 +18,19 @@ Three readings of the reference, recorded by the fixture (tests/golden/g21_uv_ba
       (simple_inverse_rendering's rule for background=None).  Reproduced, not repaired.
 One departure: uv_dilation stops when a step fills nothing more (the reference loops forever when no valid texel is in reach).
 
-Refused, never dropped (NotImplementedError): visualize=True (cv2 debug images), use_cv_inpainting=True -- the reference's DEFAULT, cv2.inpaint (Telea):
-pass use_cv_inpainting=False --, use_cv_outpainting=True, blending_type='poisson'.
+Refused, never dropped (NotImplementedError): visualize=True (cv2 debug images) everywhere; in remapping_uv_texture also use_cv_inpainting=True -- the
+reference's DEFAULT, cv2.inpaint (Telea): pass use_cv_inpainting=False --, use_cv_outpainting=True and blending_type='poisson', whose refusals its tests pin.
 
-blending_type='poisson' is still refused HERE, but its solver is built (texturetools/image_fusion.py, csrc/image_fusion.hip); until the refusal is lifted a caller
-composes the branch (:213) as the reference does:
-    acc, wacc = project_uv_texture(mesh, c2ws, intrinsics, images, map_Kd, weights)
-    overlay = torch.where(wacc > overlay_confidence, acc / wacc, acc)
-    rgb = image_fusion(overlay[None, ..., :3], map_Kd[None, ..., :3], (wacc > blending_confidence).float()[None])[0]"""
+Those three branches run under new names:
+    uv_dilation_cv          (uv_dilation.py:15-29)  the reference's quantisation around ops.inpaint_telea (csrc/inpaint.hip): Telea inpainting on the device,
+                            by this library's own rule (DESIGN 8 "Telea inpainting"), not OpenCV's heap order [3p]
+    remapping_uv_texture_cv the reference's signature and defaults with use_cv_inpainting, use_cv_outpainting and blending_type='poisson' running; the 'poisson'
+                            branch (:213) is the composition
+                                acc, wacc = project_uv_texture(mesh, c2ws, intrinsics, images, map_Kd, weights)
+                                overlay = torch.where(wacc > overlay_confidence, acc / wacc, acc)
+                                rgb = image_fusion(overlay[None, ..., :3], map_Kd[None, ..., :3], (wacc > blending_confidence).float()[None])[0]
+                            With the cv flags off and 'soft' / 'hard' it returns remapping_uv_texture's bytes (one shared body).
+remapping_uv_texture_v2 and initial_map_Kd_with_v_rgb keep refusing use_cv_outpainting=True."""
 import numpy as np
 import torch
 
@@ -82,6 +87,58 @@ def project_uv_texture(mesh, c2ws, intrinsics, images, map_Kd, weights, use_alph
     return _bake("project_uv_texture", mesh, c2ws, intrinsics, images, map_Kd, weights, use_alpha, render_size, texture_size, perspective, None)[2]
 
 
+def _remapping_uv_texture(who, cv, mesh, c2ws, intrinsics, images, map_Kd, weights, use_alpha, overlay_confidence, use_blending, blending_type,
+                          blending_confidence, use_inpainting, use_cv_inpainting, inpainting_confidence, use_outpainting, use_cv_outpainting, render_size,
+                          texture_size, visualize, perspective, return_stages):
+    """the one body of remapping_uv_texture and remapping_uv_texture_cv; cv=False keeps the three refusals of the former"""
+    _refuse_visualize(who, visualize)
+    batch_size = torch.as_tensor(c2ws).shape[0]
+    if weights is not None and len(weights) != batch_size:
+        raise ValueError("size mismatch: length of weights should be %d but %d" % (batch_size, len(weights)))
+    if blending_type not in ("poisson", "soft", "hard"):
+        raise ValueError("value error: %s is not supported" % (blending_type,))
+    if not cv:
+        if blending_type == "poisson":
+            raise NotImplementedError("remapping_uv_texture(blending_type='poisson') is not built: 'soft' or 'hard'")
+        if use_inpainting and use_cv_inpainting:
+            raise NotImplementedError("remapping_uv_texture(use_cv_inpainting=True) is not built (cv2.inpaint): pass use_cv_inpainting=False for uv_dilation")
+        if use_outpainting and use_cv_outpainting:
+            raise NotImplementedError("remapping_uv_texture(use_cv_outpainting=True) is not built (cv2.inpaint): the outpainting is pull_push")
+    r = _renderer(mesh)
+    T = int(texture_size)
+    if map_Kd is None:
+        map_Kd = torch.zeros(T, T, 4, dtype=torch.float32, device=r.device)
+        use_blending = False
+    if weights is None:
+        weights = default_weights(batch_size)
+    weights = torch.as_tensor(np.asarray(weights, dtype=np.float32))
+    poisson = bool(use_blending) and blending_type == "poisson"      # the overlay stage alone comes from the launch; the fusion follows it (:213)
+    epilogue = dict(overlay_confidence=overlay_confidence, blending=blending_type if use_blending and not poisson else None,
+                    blending_confidence=blending_confidence, inpainting_confidence=inpainting_confidence)
+    rast2d, kd4, (acc, wacc, blended, mask) = _bake(who, r, c2ws, intrinsics, images, map_Kd, weights, use_alpha, render_size, T, perspective, epilogue)
+    covered = (rast2d[..., 3] > 0).to(torch.uint8).contiguous()      # compute_uv_mask: the coverage of the same raster
+    rgb, steps = blended[..., :3].contiguous(), 0
+    if poisson:
+        from .image_fusion import image_fusion
+        rgb = image_fusion(rgb[None], kd4[None, ..., :3], (wacc > blending_confidence).to(torch.float32)[None])[0].contiguous()
+        blended = torch.cat([rgb, blended[..., 3:]], dim=-1)
+    if use_inpainting:
+        if use_cv_inpainting:
+            rgb = uv_dilation_cv(rgb.permute(2, 0, 1)[None], mask[None, None] != 0)[0].permute(1, 2, 0).contiguous()
+        else:
+            rgb, steps = ops.uv_dilation(rgb, (1 - mask).contiguous())
+    inpainted = rgb
+    if use_outpainting:
+        if use_cv_outpainting:
+            rgb = uv_dilation_cv(rgb.permute(2, 0, 1)[None], (covered == 0)[None, None])[0].permute(1, 2, 0).contiguous()
+        else:
+            rgb = ops.pull_push(rgb, covered)
+    out = torch.cat([rgb, covered[..., None].to(torch.float32)], dim=-1)
+    if return_stages:
+        return out, dict(map_Kd_rgb_acc=acc, map_Kd_weight_acc=wacc, blended=blended, inpaint_mask=mask, inpainted=inpainted, inpaint_steps=steps, map_Kd=out)
+    return out
+
+
 def remapping_uv_texture(mesh, c2ws, intrinsics, images, map_Kd=None, weights=None, use_alpha=True, overlay_confidence=0.2, use_blending=True,
                          blending_type="soft", blending_confidence=0.2, use_inpainting=True, use_cv_inpainting=True, inpainting_confidence=0.2,
                          use_outpainting=True, use_cv_outpainting=False, render_size=512, texture_size=1024, visualize=False, perspective=True,
@@ -92,42 +149,24 @@ def remapping_uv_texture(mesh, c2ws, intrinsics, images, map_Kd=None, weights=No
     rgb with the atlas coverage as alpha.  map_Kd=None: zeros and no blending.  weights=None: the reference's table for 8 / 6 / 4 / 2 views, ones
     otherwise.  Returns [T,T,4]; with return_stages=True a dict of every stage as well (map_Kd_rgb_acc, map_Kd_weight_acc, blended, inpaint_mask,
     inpainted, inpaint_steps, map_Kd).  A weights of the wrong length and an unknown blending_type raise ValueError (the reference's two assertions);
-    see the module docstring for what is refused."""
-    _refuse_visualize("remapping_uv_texture", visualize)
-    batch_size = torch.as_tensor(c2ws).shape[0]
-    if weights is not None and len(weights) != batch_size:
-        raise ValueError("size mismatch: length of weights should be %d but %d" % (batch_size, len(weights)))
-    if blending_type not in ("poisson", "soft", "hard"):
-        raise ValueError("value error: %s is not supported" % (blending_type,))
-    if blending_type == "poisson":
-        raise NotImplementedError("remapping_uv_texture(blending_type='poisson') is not built: 'soft' or 'hard'")
-    if use_inpainting and use_cv_inpainting:
-        raise NotImplementedError("remapping_uv_texture(use_cv_inpainting=True) is not built (cv2.inpaint): pass use_cv_inpainting=False for uv_dilation")
-    if use_outpainting and use_cv_outpainting:
-        raise NotImplementedError("remapping_uv_texture(use_cv_outpainting=True) is not built (cv2.inpaint): the outpainting is pull_push")
-    r = _renderer(mesh)
-    T = int(texture_size)
-    if map_Kd is None:
-        map_Kd = torch.zeros(T, T, 4, dtype=torch.float32, device=r.device)
-        use_blending = False
-    if weights is None:
-        weights = default_weights(batch_size)
-    weights = torch.as_tensor(np.asarray(weights, dtype=np.float32))
-    epilogue = dict(overlay_confidence=overlay_confidence, blending=blending_type if use_blending else None, blending_confidence=blending_confidence,
-                    inpainting_confidence=inpainting_confidence)
-    rast2d, _, (acc, wacc, blended, mask) = _bake("remapping_uv_texture", r, c2ws, intrinsics, images, map_Kd, weights, use_alpha, render_size, T, perspective,
-                                                  epilogue)
-    covered = (rast2d[..., 3] > 0).to(torch.uint8).contiguous()      # compute_uv_mask: the coverage of the same raster
-    rgb, steps = blended[..., :3].contiguous(), 0
-    if use_inpainting:
-        rgb, steps = ops.uv_dilation(rgb, (1 - mask).contiguous())
-    inpainted = rgb
-    if use_outpainting:
-        rgb = ops.pull_push(rgb, covered)
-    out = torch.cat([rgb, covered[..., None].to(torch.float32)], dim=-1)
-    if return_stages:
-        return out, dict(map_Kd_rgb_acc=acc, map_Kd_weight_acc=wacc, blended=blended, inpaint_mask=mask, inpainted=inpainted, inpaint_steps=steps, map_Kd=out)
-    return out
+    see the module docstring for what is refused -- remapping_uv_texture_cv runs those branches."""
+    return _remapping_uv_texture("remapping_uv_texture", False, mesh, c2ws, intrinsics, images, map_Kd, weights, use_alpha, overlay_confidence, use_blending,
+                                 blending_type, blending_confidence, use_inpainting, use_cv_inpainting, inpainting_confidence, use_outpainting,
+                                 use_cv_outpainting, render_size, texture_size, visualize, perspective, return_stages)
+
+
+def remapping_uv_texture_cv(mesh, c2ws, intrinsics, images, map_Kd=None, weights=None, use_alpha=True, overlay_confidence=0.2, use_blending=True,
+                            blending_type="soft", blending_confidence=0.2, use_inpainting=True, use_cv_inpainting=True, inpainting_confidence=0.2,
+                            use_outpainting=True, use_cv_outpainting=False, render_size=512, texture_size=1024, visualize=False, perspective=True,
+                            return_stages=False):
+    """remapping_uv_texture with the reference's signature and defaults and every branch but visualize=True running: use_cv_inpainting=True (the reference's
+    default) fills the inpainting mask with uv_dilation_cv, use_cv_outpainting=True the texels the atlas does not cover, and blending_type='poisson' takes the
+    overlay stage (the launch's epilogue with no blending) through image_fusion(overlay rgb, map_Kd rgb, weight > blending_confidence) (:213).  The `blended`
+    stage of return_stages is the fused image then.  With use_cv_inpainting=False, use_cv_outpainting=False and 'soft' / 'hard' the result is
+    remapping_uv_texture's, bit for bit: the two share one body."""
+    return _remapping_uv_texture("remapping_uv_texture_cv", True, mesh, c2ws, intrinsics, images, map_Kd, weights, use_alpha, overlay_confidence, use_blending,
+                                 blending_type, blending_confidence, use_inpainting, use_cv_inpainting, inpainting_confidence, use_outpainting,
+                                 use_cv_outpainting, render_size, texture_size, visualize, perspective, return_stages)
 
 
 def remapping_uv_texture_v2(mesh, c2ws, intrinsics, images, map_Kd=None, use_outpainting=True, use_cv_outpainting=False, render_size=512, texture_size=1024,
@@ -183,3 +222,28 @@ def uv_dilation(map_Kd, map_mask, max_iters=-1, return_steps=False):
     out, steps = ops.uv_dilation(map_Kd[0].permute(1, 2, 0).contiguous(), (map_mask[0, 0] == 0).to(torch.uint8).contiguous(), max_iters=max_iters)
     out = out.permute(2, 0, 1)[None]
     return (out, steps) if return_steps else out
+
+
+def uv_dilation_cv(map_Kd, map_mask, max_iters=-1):
+    """uv_dilation_cv of the reference (uv_dilation.py:15-29): map_Kd [N,C,H,W] float (1 <= C <= 4), map_mask [N,1,H,W] bool (true: the texels to fill) ->
+    [N,C,H,W] in map_Kd's dtype.  Each image is quantised as the reference does -- clamp(0, 1) * 255 truncated to uint8 --, filled on its own by
+    ops.inpaint_telea with max_iters as the RADIUS, exactly as the reference passes it to cv2.inpaint (-1, its default, is clamped to 1), and divided by 255.
+    The fill is this library's Telea rule (DESIGN 8 "Telea inpainting"), not OpenCV's heap order [3p].  A new tensor is returned; the reference writes into
+    map_Kd as well."""
+    map_Kd = torch.as_tensor(map_Kd)
+    if not map_Kd.is_floating_point():
+        raise ValueError("uv_dilation_cv: map_Kd is %s, a float tensor in [0, 1] is expected" % map_Kd.dtype)
+    if not map_Kd.is_cuda:
+        map_Kd = map_Kd.to("cuda")
+    map_mask = torch.as_tensor(map_mask).to(map_Kd.device)
+    if map_Kd.dim() != 4 or map_mask.dim() != 4 or tuple(map_mask.shape) != (map_Kd.shape[0], 1) + tuple(map_Kd.shape[2:]):
+        raise ValueError("uv_dilation_cv: map_Kd is %s and map_mask %s, expected [N, C, H, W] and [N, 1, H, W]" % (tuple(map_Kd.shape), tuple(map_mask.shape)))
+    if not 1 <= map_Kd.shape[1] <= 4:
+        raise ValueError("uv_dilation_cv: %d channels, 1 to 4 are built" % map_Kd.shape[1])
+    q = map_Kd.permute(0, 2, 3, 1).clamp(0, 1).mul(255).to(torch.uint8).contiguous()
+    m = map_mask.to(torch.bool).permute(0, 2, 3, 1)[..., 0].to(torch.uint8).mul(255).contiguous()
+    res = torch.empty_like(map_Kd)
+    for i in range(map_Kd.shape[0]):
+        out = ops.inpaint_telea(q[i], m[i], radius=max_iters)[0]
+        res[i] = out.to(map_Kd.dtype).div(255).permute(2, 0, 1)
+    return res
