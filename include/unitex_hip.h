@@ -329,7 +329,11 @@ int utx_transform_points(utx_ctx* ctx, const float* verts, int V, const float* m
                          float* clip, float* ndc, utx_stream stream);
 
 /* dr.rasterize replacement (renderer_inverse.py:183,273): pos [V][4] clip space, tri [F][3] int32,
- * rast [H][W][4] = (u, v, z/w, triangle_id + 1), 0 = empty.  work: utx_rasterize_workspace_bytes. */
+ * rast [H][W][4] = (u, v, z/w, triangle_id + 1), 0 = empty.  work: utx_rasterize_workspace_bytes.
+ * Accepted range: a triangle is drawn only if x, y, w of its three vertices are finite, every w > 0, and every snapped
+ * coordinate s = floor((x / w * 0.5 + 0.5) * size * 256 + 0.5) has |s| <= 2^30; H, W <= 2^22.  Any other triangle is skipped
+ * whole (no clipping).  Inside the range every int64 edge function and the area are exact (at most 4 * (2^30)^2 = 2^62).
+ * A pixel whose z/w is NaN or outside [-1, 1] is not covered. */
 long utx_rasterize_workspace_bytes(int F, int H, int W);
 int utx_rasterize(utx_ctx* ctx, const float* pos, const int* tri, int F, int H, int W, float* rast,
                   void* work, utx_stream stream);

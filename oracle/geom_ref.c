@@ -23,6 +23,10 @@
  *    the coverage rule.  The rule implemented here is this project's own, documented in DESIGN.md:
  *    8-bit sub-pixel snapping, inclusive int64 edge functions, pixel centres, nearest z/w wins,
  *    ties -> lowest triangle id; output (u, v, z/w, id+1) with u,v the weights of vertices 0 and 1.
+ *    Accepted range: a triangle is drawn only if x, y, w of its three vertices are finite, every w > 0, and every snapped
+ *    coordinate s = floor((x / w * 0.5 + 0.5) * size * 256 + 0.5) has |s| <= 2^30; H, W <= 2^22.  Any other triangle is skipped
+ *    whole (no clipping).  Inside the range every int64 edge function and the area are exact (at most 4 * (2^30)^2 = 2^62).
+ *    A pixel whose z/w is NaN or outside [-1, 1] is not covered.
  */
 #include <math.h>
 #include <stdint.h>
@@ -30,15 +34,19 @@
 #include <string.h>
 
 #define SUBPIX 256
+#define SNAP_RANGE 1073741824.0 /* 2^30: largest |snapped coordinate| of a triangle that is drawn */
 
 /* ------------------------------------------------------------------------------------------- */
 /* rasteriser                                                                                   */
 /* ------------------------------------------------------------------------------------------- */
-static inline int64_t snap(float ndc, int size) {
-    /* (ndc*0.5+0.5)*size*SUBPIX rounded to nearest (ties away from zero via floor(x+0.5)) */
+static inline double snap(float ndc, int size) {
+    /* (ndc*0.5+0.5)*size*SUBPIX rounded to nearest (half-units round up: floor(x+0.5)); a double holding an integer, or
+     * inf / NaN: converted to int64 only after the range test */
     double v = ((double)ndc * 0.5 + 0.5) * (double)size * (double)SUBPIX;
-    return (int64_t)floor(v + 0.5);
+    return floor(v + 0.5);
 }
+static inline int in_range(double s) { return fabs(s) <= SNAP_RANGE; } /* false for NaN */
+static inline int finite_xyw(const float* p) { return isfinite(p[0]) && isfinite(p[1]) && isfinite(p[3]); }
 
 /* pos: [V][4] clip-space; tri: [F][3]; rast out: [H][W][4] floats (u, v, z/w, id+1), zero = empty */
 void utxref_rasterize(const float* pos, int V, const int32_t* tri, int F, int H, int W, float* rast) {
@@ -52,10 +60,14 @@ void utxref_rasterize(const float* pos, int V, const int32_t* tri, int F, int H,
         const float* p1 = pos + 4 * (size_t)tri[3 * f + 1];
         const float* p2 = pos + 4 * (size_t)tri[3 * f + 2];
         if (!(p0[3] > 0.f) || !(p1[3] > 0.f) || !(p2[3] > 0.f)) continue; /* no clipping: skip */
+        if (!finite_xyw(p0) || !finite_xyw(p1) || !finite_xyw(p2)) continue;
         float iw0 = 1.0f / p0[3], iw1 = 1.0f / p1[3], iw2 = 1.0f / p2[3];
-        int64_t x0 = snap(p0[0] * iw0, W), y0 = snap(p0[1] * iw0, H);
-        int64_t x1 = snap(p1[0] * iw1, W), y1 = snap(p1[1] * iw1, H);
-        int64_t x2 = snap(p2[0] * iw2, W), y2 = snap(p2[1] * iw2, H);
+        double dx0 = snap(p0[0] * iw0, W), dy0 = snap(p0[1] * iw0, H);
+        double dx1 = snap(p1[0] * iw1, W), dy1 = snap(p1[1] * iw1, H);
+        double dx2 = snap(p2[0] * iw2, W), dy2 = snap(p2[1] * iw2, H);
+        if (!(in_range(dx0) && in_range(dy0) && in_range(dx1) && in_range(dy1) && in_range(dx2) && in_range(dy2)))
+            continue; /* outside the accepted range: skip */
+        int64_t x0 = (int64_t)dx0, y0 = (int64_t)dy0, x1 = (int64_t)dx1, y1 = (int64_t)dy1, x2 = (int64_t)dx2, y2 = (int64_t)dy2;
         int64_t area = (x1 - x0) * (y2 - y0) - (y1 - y0) * (x2 - x0);
         if (area == 0) continue;
         int64_t minx = x0 < x1 ? x0 : x1; if (x2 < minx) minx = x2;
@@ -92,7 +104,7 @@ void utxref_rasterize(const float* pos, int V, const int32_t* tri, int F, int H,
                     float s = (a0 + a1) + a2;
                     u = a0 / s; v = a1 / s;
                 }
-                if (zw < -1.0f || zw > 1.0f) continue;
+                if (!(zw >= -1.0f && zw <= 1.0f)) continue; /* also a NaN z/w: it never claims a pixel */
                 size_t pi = (size_t)py * W + px;
                 /* triangles are visited in increasing id: strict '<' keeps the lowest id on ties */
                 if (zw < zbuf[pi]) {

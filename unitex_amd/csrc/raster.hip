@@ -10,6 +10,10 @@
 //   * nearest z/w wins, ties -> lowest triangle id (64-bit atomicMin on {sortable(z/w), id});
 //   * output per pixel (u, v, z/w, id + 1) with u, v the weights of vertices 0 and 1; 0 = empty;
 //     row r <-> y_ndc = (r + 0.5) / H * 2 - 1 (the reference's projection already flips y).
+// Accepted range: a triangle is drawn only if x, y, w of its three vertices are finite, every w > 0, and every snapped
+// coordinate s = floor((x / w * 0.5 + 0.5) * size * 256 + 0.5) has |s| <= 2^30; H, W <= 2^22.  Any other triangle is skipped
+// whole (no clipping).  Inside the range every int64 edge function and the area are exact (at most 4 * (2^30)^2 = 2^62).
+// A pixel whose z/w is NaN or outside [-1, 1] is not covered.
 // HBM-bound integer/byte work: one thread per triangle scans its bounding box (triangles of a 50k-200k
 // face mesh on a 2048^2 atlas cover ~15-80 texels each); large triangles are queued and scanned by a
 // whole workgroup.  A resolve pass turns the depth/id buffer into the (u, v, z/w, id+1) record.
@@ -21,6 +25,8 @@
 
 #define SUBPIX 256
 #define BIG_BBOX 2048  // bbox area (pixels) above which a triangle goes to the cooperative path
+#define SNAP_RANGE 1073741824.0  // 2^30: largest |snapped coordinate| of a triangle that is drawn
+#define MAX_IMAGE_SIZE (1 << 22)  // pixel centres stay within 256 * 2^22 = 2^30
 
 struct TriSetup {
     long long x0, y0, x1, y1, x2, y2, area;
@@ -29,10 +35,13 @@ struct TriSetup {
     bool ok;
 };
 
-__device__ __forceinline__ long long snap_fx(float ndc, int size) {
+// the snapped coordinate as a double (an integer value, or inf / NaN); converted only after the range test
+__device__ __forceinline__ double snap_fx(float ndc, int size) {
     double v = ((double)ndc * 0.5 + 0.5) * (double)size * (double)SUBPIX;
-    return (long long)floor(v + 0.5);
+    return floor(v + 0.5);
 }
+__device__ __forceinline__ bool in_range(double s) { return fabs(s) <= SNAP_RANGE; }  // false for NaN
+__device__ __forceinline__ bool finite_xyw(const float* p) { return fabsf(p[0]) < INFINITY && fabsf(p[1]) < INFINITY && fabsf(p[3]) < INFINITY; }
 
 __device__ __forceinline__ TriSetup tri_setup(const float* pos, const int* tri, int f, int H, int W) {
     TriSetup s;
@@ -41,10 +50,15 @@ __device__ __forceinline__ TriSetup tri_setup(const float* pos, const int* tri, 
     const float* p1 = pos + 4 * (long)tri[3 * f + 1];
     const float* p2 = pos + 4 * (long)tri[3 * f + 2];
     if (!(p0[3] > 0.f) || !(p1[3] > 0.f) || !(p2[3] > 0.f)) return s;
+    if (!finite_xyw(p0) || !finite_xyw(p1) || !finite_xyw(p2)) return s;
     s.iw0 = 1.0f / p0[3]; s.iw1 = 1.0f / p1[3]; s.iw2 = 1.0f / p2[3];
-    s.x0 = snap_fx(p0[0] * s.iw0, W); s.y0 = snap_fx(p0[1] * s.iw0, H);
-    s.x1 = snap_fx(p1[0] * s.iw1, W); s.y1 = snap_fx(p1[1] * s.iw1, H);
-    s.x2 = snap_fx(p2[0] * s.iw2, W); s.y2 = snap_fx(p2[1] * s.iw2, H);
+    const double dx0 = snap_fx(p0[0] * s.iw0, W), dy0 = snap_fx(p0[1] * s.iw0, H);
+    const double dx1 = snap_fx(p1[0] * s.iw1, W), dy1 = snap_fx(p1[1] * s.iw1, H);
+    const double dx2 = snap_fx(p2[0] * s.iw2, W), dy2 = snap_fx(p2[1] * s.iw2, H);
+    if (!(in_range(dx0) && in_range(dy0) && in_range(dx1) && in_range(dy1) && in_range(dx2) && in_range(dy2))) return s;  // outside the accepted range: skip
+    s.x0 = (long long)dx0; s.y0 = (long long)dy0;
+    s.x1 = (long long)dx1; s.y1 = (long long)dy1;
+    s.x2 = (long long)dx2; s.y2 = (long long)dy2;
     s.area = (s.x1 - s.x0) * (s.y2 - s.y0) - (s.y1 - s.y0) * (s.x2 - s.x0);
     if (s.area == 0) return s;
     long long minx = min(s.x0, min(s.x1, s.x2)), maxx = max(s.x0, max(s.x1, s.x2));
@@ -74,7 +88,7 @@ __device__ __forceinline__ bool tri_eval(const TriSetup& s, int px, int py, floa
     b1 = (float)((double)e1 / (double)s.area);
     b2 = (1.0f - b0) - b1;
     zw = (b0 * s.z0 + b1 * s.z1) + b2 * s.z2;
-    return !(zw < -1.0f || zw > 1.0f);
+    return zw >= -1.0f && zw <= 1.0f;  // false for a NaN z/w: it never claims a pixel
 }
 
 __device__ __forceinline__ unsigned long long depth_key(float zw, int f) {
@@ -149,7 +163,7 @@ __global__ __launch_bounds__(256) void raster_resolve_kernel(const float* pos, c
 
 extern "C" int utx_launch_rasterize(const float* pos, const int* tri, int F, int H, int W, float* rast, void* work,
                                     hipStream_t stream) {
-    if (F <= 0 || H <= 0 || W <= 0) return -1;
+    if (F <= 0 || H <= 0 || W <= 0 || H > MAX_IMAGE_SIZE || W > MAX_IMAGE_SIZE) return -1;
     unsigned long long* zb = (unsigned long long*)work;
     const long npix = (long)H * W;
     int* big_count = (int*)(zb + npix);
