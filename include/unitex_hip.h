@@ -866,6 +866,33 @@ int utx_inpaint_telea_step(utx_ctx* ctx, const float* col_in, const unsigned cha
                            unsigned char* done_out, int* counter, utx_stream stream);
 int utx_inpaint_finish(utx_ctx* ctx, const float* col, int H, int W, int C, unsigned char* out, float* out_f, utx_stream stream);
 
+/* Sliced optimal-transport colour transfer: CTSOT of the reference (image/color_transfer_ot.py), which loops over numpy argsorts on the host and regularises with
+ * OpenCV's cv2.bilateralFilter [3p].  DESIGN 8 "Colour transfer".  All fp32, stream-ordered, row-major, bit-reproducible; no read-back, no host synchronisation.
+ * utx_color_transfer_ot: src, dst, out [N][C] (1 <= C <= 4, 1 <= N < UTX_COLOR_TRANSFER_N_MAX), dirs [steps * batch_size][C] (DEVICE; unit directions, one per
+ *   step and batch in that order).  cur = src; per step, for each batch b in order with d = its direction: p(x) = ((x0 d0 + x1 d1) + x2 d2) + x3 d3, each product
+ *   and sum rounded to float32; the projections of cur and of dst are sorted by the total order of their bit patterns (-0 before +0; equal source projections
+ *   keep ascending pixel order: a stable radix sort); advect[i] = advect[i] + (pt_sorted[r] - ps_sorted[r]) * d for the pixel i of source rank r.  After the
+ *   last batch cur = cur + advect / float(batch_size), advect = 0.  out = cur after the last step; steps = 0: out = src.  This is the reference's loop bit for
+ *   bit wherever no two projections of a batch are equal (tests/golden/g26_color_transfer_ot.npz).  Non-finite values are not looked for.
+ *   work: utx_color_transfer_ot_workspace_bytes(N, C) bytes (0 for arguments the call would refuse); not read when steps = 0.
+ * utx_bilateral_filter: img, out [H][W][C], C 1 or 3.  The rule is this library's on OpenCV's documented parameters with d = 0: the circular support
+ *   dx^2 + dy^2 <= radius^2 (the caller's max(1, rint(1.5 sigmaSpace)), 1 .. UTX_BILATERAL_RADIUS_MAX), space_weights (DEVICE, [radius + 1][radius + 1],
+ *   indexed [|dy|][|dx|]: the caller's exp(-(dx^2 + dy^2) / (2 sigmaSpace^2))), colour weight expf((sum_c |v_c(q) - v_c(p)|)^2 * color_coef) with
+ *   color_coef = -1 / (2 sigmaColor^2) <= 0, reflect-101 borders applied repeatedly (an axis of length 1 maps to index 0).  Taps row-major over the window, one
+ *   running sum per channel and one of the weights w = space * colour: out = sum(w v) / sum(w).  One launch, a 16 x 16 tile with its halo in LDS:
+ *   utx_bilateral_lds_bytes(radius, C) bytes, which UTX_BILATERAL_RADIUS_MAX keeps within the 65536 a launch gets without asking for more.
+ * -2, outputs untouched: a null or misaligned operand (dirs and work only with steps > 0); out equal to an input; N, C, steps < 0, batch_size < 1, H, W
+ *   (1 .. UTX_BILATERAL_SIDE_MAX, H W < UTX_COLOR_TRANSFER_N_MAX), radius or a positive or NaN color_coef outside the above; a short workspace. */
+#define UTX_COLOR_TRANSFER_N_MAX 1073741824L
+#define UTX_BILATERAL_RADIUS_MAX 27
+#define UTX_BILATERAL_SIDE_MAX 32768
+long utx_color_transfer_ot_workspace_bytes(long N, int C);
+int utx_color_transfer_ot(utx_ctx* ctx, const float* src, const float* dst, const float* dirs, long N, int C, int steps, int batch_size, float* out, void* work,
+                          long work_bytes, utx_stream stream);
+int utx_bilateral_lds_bytes(int radius, int C);
+int utx_bilateral_filter(utx_ctx* ctx, const float* img, int H, int W, int C, int radius, const float* space_weights, float color_coef, float* out,
+                         utx_stream stream);
+
 /* fused per-(view, texel) gather + visibility of uv_to_pcd (renderer_inverse.py:277-298,316-325) */
 typedef struct utx_backproject_desc {
     const void* rast2d;                 /* [T][4] f32 UV-space raster */

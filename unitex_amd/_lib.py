@@ -233,6 +233,10 @@ SYMBOLS = {
     "utx_inpaint_distance": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "utx_inpaint_telea_step": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "utx_inpaint_finish": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "utx_color_transfer_ot_workspace_bytes": (c_long, [c_long, c_int]),
+    "utx_color_transfer_ot": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_int, c_int, c_int, c_void_p, c_void_p, c_long, c_void_p]),
+    "utx_bilateral_lds_bytes": (c_int, [c_int, c_int]),
+    "utx_bilateral_filter": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p]),
     "utx_bvh_trace_count": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p]),
     "utx_bvh_depth": (c_int, [c_void_p]),
     "utx_bvh_closest_point": (c_int, [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),

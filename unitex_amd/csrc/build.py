@@ -51,6 +51,7 @@ GEOM = [
     ("global_bake.hip", ["-ffp-contract=off"] + NO_PK),      # scattered-sample UV bake: per-pixel sample pass, surface-space propagation step
     ("image_fusion.hip", ["-ffp-contract=off"] + NO_PK),      # Poisson image fusion: mask morphology, right-hand side, multigrid V-cycles; bit-reproducible
     ("inpaint.hip", ["-ffp-contract=off"] + NO_PK),      # Telea inpainting: exact distance map, propagation sweeps through an LDS tile, rounding; bit-reproducible
+    ("color_transfer.hip", ["-ffp-contract=off"] + NO_PK),      # sliced-OT colour transfer: projection, rocPRIM sorts, scatter; bilateral filter through an LDS tile; bit-reproducible
     ("texture_post.hip", ["-ffp-contract=off"] + NO_PK),
     ("knn.hip", ["-ffp-contract=off"]),
     ("sampling.hip", ["-ffp-contract=off"]),

@@ -579,6 +579,28 @@ int utx_inpaint_finish(utx_ctx* ctx, const float* col, int H, int W, int C, unsi
     if (!col || !out || misaligned(col, 3) || misaligned(out_f, 3) || col == out_f) return fail(ctx, -2, me);
     UTX_CALL(ctx, me, utx_launch_inpaint_finish(col, H, W, C, out, out_f, (hipStream_t)stream));
 }
+// ---- sliced optimal-transport colour transfer and its bilateral regulariser (color_transfer.hip) ----
+long utx_color_transfer_ot_workspace_bytes(long N, int C) { return (long)utx_color_transfer_ot_workspace_bytes_impl(N, C); }
+int utx_color_transfer_ot(utx_ctx* ctx, const float* src, const float* dst, const float* dirs, long N, int C, int steps, int batch_size, float* out, void* work,
+                          long work_bytes, utx_stream stream) {
+    const char* const me = "utx_color_transfer_ot";
+    if (N < 1 || N >= UTX_COLOR_TRANSFER_N_MAX || C < 1 || C > 4 || steps < 0 || batch_size < 1) return fail(ctx, -2, me);
+    if (!src || !dst || !out || out == src || out == dst || misaligned(src, 3) || misaligned(dst, 3) || misaligned(out, 3)) return fail(ctx, -2, me);
+    if (steps > 0 && (!dirs || misaligned(dirs, 3) || !work || work_bytes < (long)utx_color_transfer_ot_workspace_bytes_impl(N, C))) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_color_transfer_ot(src, dst, dirs, N, C, steps, batch_size, out, work, (size_t)(steps > 0 ? work_bytes : 0), (hipStream_t)stream));
+}
+int utx_bilateral_lds_bytes(int radius, int C) {
+    if (radius < 1 || radius > 1024 || C < 1 || C > 4) return -2;
+    return (int)utx_bilateral_lds_bytes_impl(radius, C);
+}
+int utx_bilateral_filter(utx_ctx* ctx, const float* img, int H, int W, int C, int radius, const float* space_weights, float color_coef, float* out,
+                         utx_stream stream) {
+    const char* const me = "utx_bilateral_filter";
+    if (H < 1 || W < 1 || H > UTX_BILATERAL_SIDE_MAX || W > UTX_BILATERAL_SIDE_MAX || (long)H * W >= UTX_COLOR_TRANSFER_N_MAX) return fail(ctx, -2, me);
+    if ((C != 1 && C != 3) || radius < 1 || radius > UTX_BILATERAL_RADIUS_MAX || !(color_coef <= 0.0f)) return fail(ctx, -2, me);
+    if (!img || !space_weights || !out || img == out || misaligned(img, 3) || misaligned(space_weights, 3) || misaligned(out, 3)) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_bilateral_filter(img, H, W, C, radius, space_weights, color_coef, out, (hipStream_t)stream));
+}
 int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws, int n_views, float* out, utx_stream stream) {
     if (!nrm || !c2ws || !out) return fail(ctx, -2, "utx_camera_normals");
     UTX_CALL(ctx, "utx_camera_normals", utx_launch_camera_normals(nrm, V, c2ws, n_views, out, (hipStream_t)stream));

@@ -230,6 +230,12 @@ int utx_launch_inpaint_distance(const unsigned char* hole, int H, int W, int* tm
 int utx_launch_inpaint_telea_step(const float* col_in, const unsigned char* done_in, const int* d2, int H, int W, int C, int eps, float* col_out,
                                   unsigned char* done_out, int* counter, hipStream_t stream);
 int utx_launch_inpaint_finish(const float* col, int H, int W, int C, unsigned char* out, float* out_f, hipStream_t stream);
+// color_transfer.hip
+size_t utx_color_transfer_ot_workspace_bytes_impl(long N, int C);
+int utx_launch_color_transfer_ot(const float* src, const float* dst, const float* dirs, long N, int C, int steps, int batch, float* out, void* work,
+                                 size_t work_bytes, hipStream_t stream);
+size_t utx_bilateral_lds_bytes_impl(int r, int C);
+int utx_launch_bilateral_filter(const float* img, int H, int W, int C, int r, const float* ws, float coef, float* out, hipStream_t stream);
 int utx_launch_backproject(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_backproject_vis(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_composite_winner(const void* vis, int n_views, const int* order, int n_order, long T, void* winner, hipStream_t stream);

@@ -6,7 +6,8 @@ round trip is the 16-byte bounding rectangle per image, which sizes the solver's
 "Poisson image fusion"; where it follows OpenCV's choices (the 3-fold 3 x 3 erosion, the tight bounding rectangle, the source zeroed outside the mask) it is
 not pinned against OpenCV, which is not available to the tests.
 
-Built: image_fusion, image_fusion_hybrid.  Refused by name (NotImplementedError): color_transfer=True (an HSV histogram transfer through cv2.cvtColor),
+Built: image_fusion, image_fusion_hybrid.  Refused by name (NotImplementedError): color_transfer=True (an HSV histogram transfer through cv2.cvtColor; it is
+NOT the sliced optimal-transport transfer of color_transfer_ot.CTSOT, which is built and may be run on src before the fusion),
 smooth_fusion and the boundary_color_shift experiments (beside cv2.inpaint, which ops.inpaint_telea now covers, cv2 contours, scipy interpolators and k-d trees), image_soft_fusion
 (a 175-tap cv2.GaussianBlur).
 

@@ -1616,3 +1616,87 @@ def inpaint_telea(img_u8, hole_u8, radius=1, return_float=False, trace=None, rea
     out_f = torch.empty(H, W, Cc, dtype=F32, device=img.device) if return_float else None
     ctx.check(ctx.lib.utx_inpaint_finish(ctx.handle, ptr(cur), H, W, Cc, ptr(out), ptr(out_f), ctx.stream()))
     return (out, out_f, sweeps) if return_float else (out, sweeps)
+
+
+# ---- sliced optimal-transport colour transfer and its regulariser (color_transfer.hip): DESIGN 8 "Colour transfer"
+
+COLOR_TRANSFER_N_MAX = 1 << 30      # utx_color_transfer_ot's bound on the pixel count (exclusive)
+BILATERAL_RADIUS_MAX = 27      # utx_bilateral_filter's cap on the radius: the 16 x 16 tile with its halo, 3 channels, stays within 64 KiB of LDS
+BILATERAL_SIDE_MAX = 32768      # ... and on the image's sides
+
+
+def _same_cuda_f32(who, **tensors):
+    first = next(iter(tensors.values()))
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.device != first.device:
+            raise ValueError("%s: %s is expected on one CUDA device with the other operands" % (who, name))
+        if t.dtype != F32:
+            raise ValueError("%s: %s is %s, expected float32" % (who, name, t.dtype))
+
+
+def color_transfer_ot(src, dst, dirs, steps, batch_size):
+    """The solver loop of sliced optimal-transport colour transfer (utx_color_transfer_ot): src, dst float32 [..., C] of one shape (1 <= C <= 4, 1 <= N < 2^30
+    pixels), dirs float32 [steps * batch_size, C] on the device (unit directions, one per step and batch in that order) -> src's shape.  Per step, for each batch
+    in order: both images projected onto the direction, the projections sorted (a stable radix sort on the total order of the bit patterns: -0 before +0, equal
+    source projections in ascending pixel order), every source pixel's advect increased by the difference of the equally ranked projections times the direction;
+    then src += advect / batch_size.  One stream, no read-back; steps = 0 returns a copy.  Non-finite pixels are not looked for: a check would cost a read-back."""
+    who = "color_transfer_ot"
+    steps, batch_size = int(steps), int(batch_size)
+    if steps < 0 or batch_size < 1:
+        raise ValueError("%s: steps is %d and batch_size %d, expected steps >= 0 and batch_size >= 1" % (who, steps, batch_size))
+    _same_cuda_f32(who, src=src, dst=dst, dirs=dirs)
+    if src.dim() < 1 or tuple(dst.shape) != tuple(src.shape):
+        raise ValueError("%s: src is %s and dst %s, expected one shape [..., C]" % (who, tuple(src.shape), tuple(dst.shape)))
+    Cc = src.shape[-1]
+    if not 1 <= Cc <= 4:
+        raise ValueError("%s: %d channels, 1 .. 4 are built" % (who, Cc))
+    N = src.numel() // Cc
+    if not 1 <= N < COLOR_TRANSFER_N_MAX:
+        raise ValueError("%s: %d pixels, 1 .. 2^30 - 1 are built" % (who, N))
+    if tuple(dirs.shape) != (steps * batch_size, Cc):
+        raise ValueError("%s: dirs is %s, expected [steps * batch_size, C] = [%d, %d]" % (who, tuple(dirs.shape), steps * batch_size, Cc))
+    ctx = get_ctx(src.device.index)
+    s, d, dd = src.contiguous(), dst.contiguous(), dirs.contiguous()
+    out = torch.empty_like(s)
+    wb = int(ctx.lib.utx_color_transfer_ot_workspace_bytes(N, Cc)) if steps else 0
+    work = torch.empty(max(wb, 4), dtype=U8, device=src.device)
+    ctx.check(ctx.lib.utx_color_transfer_ot(ctx.handle, ptr(s), ptr(d), ptr(dd) if steps else None, N, Cc, steps, batch_size, ptr(out), ptr(work), wb, ctx.stream()))
+    return out
+
+
+def bilateral_radius(sigma_space):
+    """the window radius of cv2.bilateralFilter with d = 0: max(1, rint(1.5 sigma_space)), halves to even"""
+    return max(1, int(np.rint(1.5 * float(sigma_space))))
+
+
+def bilateral_space_weights(sigma_space):
+    """float32 [r + 1, r + 1], indexed [|dy|, |dx|]: exp(-(dx^2 + dy^2) / (2 sigma_space^2)) computed in float64 on the host and rounded once"""
+    r = bilateral_radius(sigma_space)
+    a = np.arange(r + 1, dtype=np.float64)
+    return np.exp(-(a[:, None] ** 2 + a[None, :] ** 2) / (2.0 * float(sigma_space) ** 2)).astype(np.float32)
+
+
+def bilateral_filter(img, sigma_color, sigma_space):
+    """Joint bilateral filter of a float32 [H, W, C] image, C 1 or 3, by this library's rule on cv2.bilateralFilter(img, 0, sigma_color, sigma_space)'s documented
+    parameters (utx_bilateral_filter; unpinned against OpenCV): radius bilateral_radius(sigma_space) <= BILATERAL_RADIUS_MAX, circular support, space weights
+    bilateral_space_weights, colour weight exp(-(sum_c |delta_c|)^2 / (2 sigma_color^2)) on the L1 colour distance, reflect-101 borders, sum(w v) / sum(w)."""
+    who = "bilateral_filter"
+    _same_cuda_f32(who, img=img)
+    if img.dim() != 3 or img.shape[2] not in (1, 3):
+        raise ValueError("%s: img is %s, expected [H, W, C] with C 1 or 3" % (who, tuple(img.shape)))
+    sigma_color, sigma_space = float(sigma_color), float(sigma_space)
+    if not (sigma_color > 0.0 and sigma_space > 0.0 and math.isfinite(sigma_color) and math.isfinite(sigma_space)):
+        raise ValueError("%s: sigma_color is %r and sigma_space %r, expected positive finite values" % (who, sigma_color, sigma_space))
+    r = bilateral_radius(sigma_space)
+    if r > BILATERAL_RADIUS_MAX:
+        raise ValueError("%s: sigma_space %g asks for a radius of %d, at most BILATERAL_RADIUS_MAX = %d is built" % (who, sigma_space, r, BILATERAL_RADIUS_MAX))
+    H, W, Cc = img.shape
+    if not (1 <= H <= BILATERAL_SIDE_MAX and 1 <= W <= BILATERAL_SIDE_MAX and H * W < COLOR_TRANSFER_N_MAX):
+        raise ValueError("%s: an image of %d x %d, sides of 1 .. %d and fewer than 2^30 pixels are built" % (who, H, W, BILATERAL_SIDE_MAX))
+    ctx = get_ctx(img.device.index)
+    ws = torch.from_numpy(bilateral_space_weights(sigma_space)).to(img.device)
+    coef = float(np.float32(-0.5 / (sigma_color * sigma_color)))
+    src = img.contiguous()
+    out = torch.empty_like(src)
+    ctx.check(ctx.lib.utx_bilateral_filter(ctx.handle, ptr(src), H, W, Cc, r, ptr(ws), coef, ptr(out), ctx.stream()))
+    return out
