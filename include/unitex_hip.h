@@ -893,6 +893,24 @@ int utx_bilateral_lds_bytes(int radius, int C);
 int utx_bilateral_filter(utx_ctx* ctx, const float* img, int H, int W, int C, int radius, const float* space_weights, float color_coef, float* out,
                          utx_stream stream);
 
+/* Silhouette antialiasing of screen-space buffers: the forward pass of what the reference calls dr.antialias on alpha and on every buffer of simple_rendering
+ * (render/nvdiffrast/renderer_base.py:143-336).  DESIGN 8 "Silhouette antialiasing".  The rule is this library's, after Laine et al. 2020 section 3.5, and is
+ * NOT pinned against nvdiffrast's samples [3p]; csrc/antialias.hip's header states it with its exact float32 operation order.  All fp32, stream-ordered,
+ * row-major, bit-reproducible; no atomics, no workspace, no read-back.
+ * utx_antialias_analyze: rast [B][H][W][4] (utx_rasterize's records (u, v, z/w, id + 1), one raster per view), pos the clip-space vertices the rasters were made
+ *   from ([V][4] shared by the views with pos_view_stride = 0, [B][V][4] with pos_view_stride = 4 V), tri [F][3], opp [F][3] (the vertex of the face across edge
+ *   e = (v_e, v_e+1) that is not on the edge, -1 on a border) -> weights [B][H][W][4] = (left, right, up, down): the share of the difference to that neighbour
+ *   that the pixel takes, in [0, 0.5]; 0 where the pair of pixels shows one triangle, no silhouette edge of the nearer triangle crosses the segment between the
+ *   two centres, the crossing is nearer to the other pixel, or the neighbour lies outside the view.  Indices of tri and opp outside [0, V), ids outside [0, F)
+ *   and vertices with a non-finite x, y, w or w <= 0 are tolerated: the pair contributes nothing, or the edge counts as a silhouette (opp).
+ * utx_antialias_apply: color, out [B][H][W][C], any C >= 1:  out = (((color + k_left) + k_right) + k_up) + k_down per channel, k_n = w_n (color[n] - color) where
+ *   w_n != 0 and +0 elsewhere, in this order.  One set of weights serves every buffer of the rasterisation.
+ * -2, outputs untouched: a null pointer; F, V, B, H, W or C < 1; a pos_view_stride other than 0 and 4 V; rast, weights or pos off a 16-byte boundary, any other
+ *   operand off a 4-byte one; weights equal to rast; out equal to color or to weights. */
+int utx_antialias_analyze(utx_ctx* ctx, const float* rast, const float* pos, long pos_view_stride, const int* tri, const int* opp, int F, int V, int B, int H, int W,
+                          float* weights, utx_stream stream);
+int utx_antialias_apply(utx_ctx* ctx, const float* color, const float* weights, int B, int H, int W, int C, float* out, utx_stream stream);
+
 /* fused per-(view, texel) gather + visibility of uv_to_pcd (renderer_inverse.py:277-298,316-325) */
 typedef struct utx_backproject_desc {
     const void* rast2d;                 /* [T][4] f32 UV-space raster */

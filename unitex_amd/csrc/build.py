@@ -52,6 +52,7 @@ GEOM = [
     ("image_fusion.hip", ["-ffp-contract=off"] + NO_PK),      # Poisson image fusion: mask morphology, right-hand side, multigrid V-cycles; bit-reproducible
     ("inpaint.hip", ["-ffp-contract=off"] + NO_PK),      # Telea inpainting: exact distance map, propagation sweeps through an LDS tile, rounding; bit-reproducible
     ("color_transfer.hip", ["-ffp-contract=off"] + NO_PK),      # sliced-OT colour transfer: projection, rocPRIM sorts, scatter; bilateral filter through an LDS tile; bit-reproducible
+    ("antialias.hip", ["-ffp-contract=off"] + NO_PK),      # silhouette antialiasing: per-pixel blend weights from the geometry, a stencil per buffer; bit-reproducible
     ("texture_post.hip", ["-ffp-contract=off"] + NO_PK),
     ("knn.hip", ["-ffp-contract=off"]),
     ("sampling.hip", ["-ffp-contract=off"]),

@@ -601,6 +601,22 @@ int utx_bilateral_filter(utx_ctx* ctx, const float* img, int H, int W, int C, in
     if (!img || !space_weights || !out || img == out || misaligned(img, 3) || misaligned(space_weights, 3) || misaligned(out, 3)) return fail(ctx, -2, me);
     UTX_CALL(ctx, me, utx_launch_bilateral_filter(img, H, W, C, radius, space_weights, color_coef, out, (hipStream_t)stream));
 }
+// ---- silhouette antialiasing of screen-space buffers (antialias.hip) ----
+int utx_antialias_analyze(utx_ctx* ctx, const float* rast, const float* pos, long pos_view_stride, const int* tri, const int* opp, int F, int V, int B, int H, int W,
+                          float* weights, utx_stream stream) {
+    const char* const me = "utx_antialias_analyze";
+    if (F <= 0 || V <= 0 || B <= 0 || H <= 0 || W <= 0 || (pos_view_stride != 0 && pos_view_stride != 4L * V)) return fail(ctx, -2, me);
+    if (!rast || !pos || !tri || !opp || !weights || (const void*)rast == (const void*)weights) return fail(ctx, -2, me);
+    if (misaligned(rast, 15) || misaligned(weights, 15) || misaligned(pos, 15) || misaligned(tri, 3) || misaligned(opp, 3)) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_antialias_analyze(rast, pos, pos_view_stride, tri, opp, F, V, B, H, W, weights, (hipStream_t)stream));
+}
+int utx_antialias_apply(utx_ctx* ctx, const float* color, const float* weights, int B, int H, int W, int C, float* out, utx_stream stream) {
+    const char* const me = "utx_antialias_apply";
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0) return fail(ctx, -2, me);
+    if (!color || !weights || !out || out == color || out == weights) return fail(ctx, -2, me);
+    if (misaligned(weights, 15) || misaligned(color, 3) || misaligned(out, 3)) return fail(ctx, -2, me);
+    UTX_CALL(ctx, me, utx_launch_antialias_apply(color, weights, B, H, W, C, out, (hipStream_t)stream));
+}
 int utx_camera_normals(utx_ctx* ctx, const float* nrm, int V, const float* c2ws, int n_views, float* out, utx_stream stream) {
     if (!nrm || !c2ws || !out) return fail(ctx, -2, "utx_camera_normals");
     UTX_CALL(ctx, "utx_camera_normals", utx_launch_camera_normals(nrm, V, c2ws, n_views, out, (hipStream_t)stream));

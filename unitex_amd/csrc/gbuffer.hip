@@ -171,7 +171,7 @@ extern "C" int utx_launch_camera_normals(const float* nrm, int V, const float* c
 }
 
 // ---- the per-pixel geometry of the atlas (utx_uv_gbuffer: simple_inverse_rendering, render/nvdiffrast/renderer_base.py:352-489) and of the screen
-// (utx_screen_gbuffer: simple_rendering, :101-350), both with alpha = coverage (no dr.antialias).  A pixel is a texel of the UV raster or a pixel of
+// (utx_screen_gbuffer: simple_rendering, :101-350), both with alpha = coverage (dr.antialias is not wired here: antialias.hip runs after the screen kernel, on request).  A pixel is a texel of the UV raster or a pixel of
 // one view's raster; its record is (u, v, z/w, id + 1), w = (1 - u) - v is formed once.  torch.lerp(bg, x, alpha) with alpha in {0, 1} returns x or
 // bg exactly, so it is a select.
 //
@@ -435,7 +435,7 @@ extern "C" int utx_launch_screen_gbuffer(const float* rast, const int* tri, cons
 }
 
 // ---- atlas-space view projection: render_uv / render_map_attr of NVDiffRendererBase.simple_inverse_rendering (render/nvdiffrast/renderer_base.py:504-559)
-// with alpha = coverage (no dr.antialias), every texel of every view in ONE launch.
+// with alpha = coverage (dr.antialias is not wired here), every texel of every view in ONE launch.
 //
 // One thread per (view, texel) of the atlas raster rast2d [H2D][W2D][4], x fastest.  With tri = rast2d.w - 1:
 //   vis       tri >= 0 and face_mask[b][tri]                     (:513-520: the raster with the faces the view does not see taken out)

@@ -236,6 +236,10 @@ int utx_launch_color_transfer_ot(const float* src, const float* dst, const float
                                  size_t work_bytes, hipStream_t stream);
 size_t utx_bilateral_lds_bytes_impl(int r, int C);
 int utx_launch_bilateral_filter(const float* img, int H, int W, int C, int r, const float* ws, float coef, float* out, hipStream_t stream);
+// antialias.hip
+int utx_launch_antialias_analyze(const float* rast, const float* pos, long pos_view_stride, const int* tri, const int* opp, int F, int V, int B, int H, int W,
+                                 float* weights, hipStream_t stream);
+int utx_launch_antialias_apply(const float* color, const float* weights, int B, int H, int W, int C, float* out, hipStream_t stream);
 int utx_launch_backproject(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_backproject_vis(const utx_backproject_desc* p, const float* eyes, int sample, const utx_bvh* bvh, hipStream_t stream);
 int utx_launch_composite_winner(const void* vis, int n_views, const int* order, int n_order, long T, void* winner, hipStream_t stream);

@@ -866,6 +866,26 @@ def face_adjacency(faces):
     return adj.reshape(F, 3)
 
 
+def edge_opposites(faces):
+    """opp [F,3] int32: the vertex of the face across edge e = (v_e, v_{e+1}) of each face (face_adjacency's numbering and its rule for a
+    non-manifold edge: the first two faces link, the others get -1) that is not on that edge; -1 where no face lies across it.  What the
+    silhouette test of ops.antialias reads."""
+    faces = np.asarray(faces)
+    F = len(faces)
+    if F == 0:
+        return np.zeros((0, 3), np.int32)
+    adj = face_adjacency(faces)
+    f64 = faces.astype(np.int64)
+    a, b = f64, f64[:, [1, 2, 0]]                           # [F,3]: the two ends of edge e
+    nb = f64[np.maximum(adj, 0)]                           # [F,3,3]: the vertices of the face across
+    on_edge = (nb == a[..., None]) | (nb == b[..., None])
+    # the one vertex of the neighbour that is not on the edge; a degenerate neighbour that repeats an end has none (or two): the first is taken, -1 if none
+    first = np.argmax(~on_edge, axis=2)
+    opp = np.take_along_axis(nb, first[..., None], axis=2)[..., 0]
+    opp[on_edge.all(axis=2) | (adj < 0)] = -1
+    return opp.astype(np.int32)
+
+
 def chart_buckets(verts, faces, adj, smooth_iters=2, cos_accept=6.0 / 7.0, dirs=None):
     """projection bucket per face: the projection direction closest to the face normal, then a few majority-vote sweeps that move a face
     into the bucket of >= 2 of its neighbours when its normal still faces that direction by more than acos(cos_accept) -- removes the

@@ -1700,3 +1700,89 @@ def bilateral_filter(img, sigma_color, sigma_space):
     out = torch.empty_like(src)
     ctx.check(ctx.lib.utx_bilateral_filter(ctx.handle, ptr(src), H, W, Cc, r, ptr(ws), coef, ptr(out), ctx.stream()))
     return out
+
+
+# ---- silhouette antialiasing of screen-space buffers (antialias.hip): DESIGN 8 "Silhouette antialiasing"
+
+def _antialias_operands(who, dtypes, **tensors):
+    """type and dtype of the operands; the shapes follow, the devices come last (_antialias_devices), so that every shape error is raised without a device"""
+    for name, t in tensors.items():
+        if not isinstance(t, torch.Tensor) or t.dtype != dtypes[name]:
+            raise ValueError("%s: %s is expected as a %s tensor" % (who, name, str(dtypes[name]).replace("torch.", "")))
+
+
+def _antialias_devices(who, **tensors):
+    first = next(iter(tensors.values()))
+    for name, t in tensors.items():
+        if not t.is_cuda or t.device != first.device:
+            raise ValueError("%s: %s is expected on one CUDA device with the other operands" % (who, name))
+
+
+def _antialias_geometry(who, rast, pos_clip, tri, opp):
+    """the shapes of the analysis' operands -> (rast [B,H,W,4], pos_clip, tri, opp, per-view stride of pos_clip, squeeze the batch of the result?)"""
+    _antialias_operands(who, dict(rast=F32, pos_clip=F32, tri=I32, opp=I32), rast=rast, pos_clip=pos_clip, tri=tri, opp=opp)
+    if rast.dim() not in (3, 4) or rast.shape[-1] != 4 or min(rast.shape) < 1:
+        raise ValueError("%s: rast is %s, expected [B, H, W, 4] or [H, W, 4] with no empty side" % (who, tuple(rast.shape)))
+    squeeze = rast.dim() == 3
+    rast4 = rast[None] if squeeze else rast
+    B = rast4.shape[0]
+    if pos_clip.dim() not in (2, 3) or pos_clip.shape[-1] != 4 or pos_clip.shape[-2] < 1 or (pos_clip.dim() == 3 and pos_clip.shape[0] != B):
+        raise ValueError("%s: pos_clip is %s, expected [V, 4] or [B = %d, V, 4]" % (who, tuple(pos_clip.shape), B))
+    if tri.dim() != 2 or tri.shape[1] != 3 or tri.shape[0] < 1 or tuple(opp.shape) != tuple(tri.shape):
+        raise ValueError("%s: tri is %s and opp %s, expected [F >= 1, 3] both" % (who, tuple(tri.shape), tuple(opp.shape)))
+    _antialias_devices(who, rast=rast, pos_clip=pos_clip, tri=tri, opp=opp)
+    V = pos_clip.shape[-2]
+    return rast4.contiguous(), pos_clip.contiguous(), tri.contiguous(), opp.contiguous(), (4 * V if pos_clip.dim() == 3 else 0), squeeze
+
+
+def antialias_weights(rast, pos_clip, tri, opp):
+    """The geometry half of silhouette antialiasing (utx_antialias_analyze): rast [B,H,W,4] or [H,W,4] (ops.rasterize's records, one raster per view),
+    pos_clip [B,V,4] or [V,4] (the clip-space vertices the rasters were made from; [V,4] is shared by the views), tri [F,3] int32, opp [F,3] int32
+    (meshes.edge_opposites) -> weights float32 of rast's shape: per pixel (left, right, up, down), the share in [0, 0.5] of the difference to that
+    neighbour that the pixel takes.  Non-zero only where a pair of neighbouring pixels shows two different triangles (or one and the background) and a
+    silhouette edge of the nearer one crosses the segment between the two pixel centres nearer to the other pixel than to this one.  It depends on the
+    geometry alone: compute it once per rasterisation and hand it to antialias_apply for every buffer."""
+    who = "antialias_weights"
+    rast4, pos, tri, opp, stride, squeeze = _antialias_geometry(who, rast, pos_clip, tri, opp)
+    B, H, W = rast4.shape[:3]
+    ctx = get_ctx(rast4.device.index)
+    weights = torch.empty_like(rast4)
+    ctx.check(ctx.lib.utx_antialias_analyze(ctx.handle, ptr(rast4), ptr(pos), stride, ptr(tri), ptr(opp), tri.shape[0], pos.shape[-2], B, H, W, ptr(weights),
+                                            ctx.stream()))
+    return weights[0] if squeeze else weights
+
+
+def antialias_apply(color, weights):
+    """The stencil half of silhouette antialiasing (utx_antialias_apply): color float32 [B,H,W,C] or [H,W,C], any C >= 1, weights [B,H,W,4] or [H,W,4]
+    from antialias_weights -> out = (((color + k_left) + k_right) + k_up) + k_down per channel, k_n = w_n * (color[n] - color) where w_n != 0, in this
+    order: a new tensor, bit-reproducible."""
+    who = "antialias_apply"
+    _antialias_operands(who, dict(color=F32, weights=F32), color=color, weights=weights)
+    if color.dim() not in (3, 4) or min(color.shape) < 1:
+        raise ValueError("%s: color is %s, expected [B, H, W, C] or [H, W, C] with no empty side" % (who, tuple(color.shape)))
+    if weights.dim() != color.dim() or tuple(weights.shape) != tuple(color.shape[:-1]) + (4,):
+        raise ValueError("%s: weights is %s, expected %s for a color of %s" % (who, tuple(weights.shape), tuple(color.shape[:-1]) + (4,), tuple(color.shape)))
+    _antialias_devices(who, color=color, weights=weights)
+    B, H, W, Cc = ((1,) + tuple(color.shape))[-4:]
+    ctx = get_ctx(color.device.index)
+    src, w = color.contiguous(), weights.contiguous()
+    out = torch.empty_like(src)
+    ctx.check(ctx.lib.utx_antialias_apply(ctx.handle, ptr(src), ptr(w), B, H, W, Cc, ptr(out), ctx.stream()))
+    return out
+
+
+def antialias(color, rast, pos_clip, tri, opp=None):
+    """Silhouette antialiasing of one screen-space buffer, the forward pass of what the reference calls dr.antialias(color, rast, pos_clip, tri):
+    antialias_apply(color, antialias_weights(rast, pos_clip, tri, opp)), bit-identical to the two calls.  opp=None computes the topology from tri on
+    the host (meshes.edge_opposites): a caller with more than one buffer or call keeps opp, and the weights.  The rule is this library's, after Laine
+    et al. 2020 section 3.5; nvdiffrast's samples are not pinned (DESIGN 8 "Silhouette antialiasing")."""
+    who = "antialias"
+    if opp is None:
+        if not isinstance(tri, torch.Tensor) or tri.dtype != I32 or tri.dim() != 2 or tri.shape[1:] != (3,):
+            raise ValueError("%s: tri is expected as an int32 tensor [F, 3]" % who)
+        from . import meshes
+        opp = torch.from_numpy(meshes.edge_opposites(tri.cpu().numpy())).to(tri.device)
+    _antialias_operands(who, dict(color=F32, rast=F32), color=color, rast=rast)
+    if color.dim() != rast.dim() or tuple(color.shape[:-1]) != tuple(rast.shape[:-1]):
+        raise ValueError("%s: color is %s and rast %s, expected one screen" % (who, tuple(color.shape), tuple(rast.shape)))
+    return antialias_apply(color, antialias_weights(rast, pos_clip, tri, opp))

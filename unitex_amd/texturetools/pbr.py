@@ -9,7 +9,7 @@ return RGB), which is what the file means.
 Tangent-space normal maps (the bump texture of the 9-channel bake, glTF's normalTexture): export_orbit_video(normal_map=...) shades with
 bsdf_prepare_shading_normal's normal (renderutils/bsdf.py:28-51, two-sided, OpenGL convention; ops.pbr_shading_normal, ops.pbr_shade(normal_map=...));
 mirrored UV charts (tangent handedness -1) are not handled, as in the reference.
-Not built (the reference's render_pbr has them or nvdiffrast does): dr.antialias, backward passes, and render_pbr's lambda_* knobs other than
+Not built (the reference's render_pbr has them or nvdiffrast does): dr.antialias (ops.antialias exists, it is not wired here), backward passes, and render_pbr's lambda_* knobs other than
 lambda_diffuse / lambda_specular."""
 import re
 

@@ -91,6 +91,7 @@ class DeviceMesh:
         self.normals = ops.face_normals(self.vertices, self.faces)      # HIP, bit-exact vs the oracle's op order
         self._bvh = None
         self._vertex_normals = None
+        self._edge_opposites = None
 
     @property
     def vertex_normals(self):
@@ -99,6 +100,13 @@ class DeviceMesh:
             from .video import _vertex_normals
             self._vertex_normals = _vertex_normals(self.vertices.cpu(), self.faces.cpu(), weighting="area").to(self.device)
         return self._vertex_normals
+
+    @property
+    def edge_opposites(self):
+        """[F,3] int32 on the device: the vertex across each edge, -1 on a border (meshes.edge_opposites; built on the host once per mesh)"""
+        if getattr(self, "_edge_opposites", None) is None:
+            self._edge_opposites = torch.from_numpy(meshes.edge_opposites(self.faces.cpu().numpy())).to(self.device).contiguous()
+        return self._edge_opposites
 
     def set_vertex_normals(self, normals):
         """per-vertex normals [V,3] of the caller's own (e.g. the file's, or analytic ones) in place of the area-weighted ones; they need not be unit"""
@@ -332,7 +340,7 @@ class NVDiffRendererInverse:
         c2ws [B,4,4], 'camera_normal' / 'camera_position' / 'ray_direction' [B,H,W,3], 'distance' / 'z_depth' / 'cos_ray_normal' [B,H,W,1].
         texture_size: int or (H, W).  Row 0 is v = 0 (the raster's orientation; TexturedMesh.texture is the flipped one).  Only c2ws enters: the
         function never projects, so it takes no intrinsics.  Vertex normals are pbr_mesh.vertex_normals.
-        enable_antialis is accepted and has no effect: alpha is the coverage mask (no dr.antialias in this build, as on the turntable).
+        enable_antialis is accepted and has no effect: alpha is the coverage mask (dr.antialias is not wired here: ops.antialias serves simple_rendering(antialias=True) only).
         render_v_attr (:491-502) adds 'v_attr' [1,H,W,Ca]: the per-vertex attribute v_attr [V,Ca] interpolated into the atlas by the screen kernel
         (ops.screen_gbuffer on the atlas raster as a batch of one), then the background rule of simple_rendering: None leaves the interpolated value
         (0 outside the charts), a number or a tensor that broadcasts to [1,H,W,Ca] fills the uncovered texels.
@@ -475,7 +483,8 @@ class NVDiffRendererInverse:
     def simple_rendering(self, c2ws, intrinsics, render_size, perspective=True, v_attr=None, map_attr=None, render_z_depth=False,
                          render_distance=False, render_world_normal=False, render_camera_normal=False, render_world_position=False,
                          render_camera_position=False, render_ray_direction=False, render_cos_ray_normal=False, render_v_attr=False,
-                         render_uv=False, render_map_attr=False, background=None, grid_interpolate_mode="bilinear", enable_antialis=True, **kwargs):
+                         render_uv=False, render_map_attr=False, background=None, grid_interpolate_mode="bilinear", enable_antialis=True, antialias=False,
+                         **kwargs):
         """NVDiffRendererBase.simple_rendering (render/nvdiffrast/renderer_base.py:101-350) on the mesh of update_from_file / update_from_arrays: the
         buffers of a batch of cameras c2ws [B,4,4] / intrinsics [B,3,3] (normalised) on a screen of render_size (int or (H, W)).  One rasterisation
         per view (the loop mv_to_pcd uses), then every requested buffer of every view in ONE kernel launch (ops.screen_gbuffer).  Returns the
@@ -491,7 +500,14 @@ class NVDiffRendererInverse:
         render_map_attr without render_uv is a ValueError here instead of being dropped.
         background (v_attr and map_attr only): None leaves the interpolated / sampled value on every pixel (uncovered pixels: 0, and the maps'
         sample at uv = (-1, -1)); a number or a tensor that broadcasts to the buffer ([C], [H,W,C], [B,H,W,C]) fills the uncovered pixels.
-        enable_antialis is accepted and has no effect: there is no dr.antialias in this build, alpha is the coverage mask, as on the turntable.
+        enable_antialis is accepted and has no effect: without antialias=True alpha is the coverage mask, as on the turntable.
+        antialias=True (this build's keyword, off by default) reproduces the reference's order of operations at enable_antialis=True (:143-336) with
+        ops.antialias in the place of dr.antialias (this library's rule, DESIGN 8 "Silhouette antialiasing"; nvdiffrast's samples are not pinned):
+        alpha = antialias(mask.float()); every buffer is blended with its background by torch.lerp(bg, x, alpha) with that alpha (v_attr / map_attr only
+        when a background is given) and then antialiased with the ONE set of weights of the rasterisation (ops.antialias_weights once,
+        ops.antialias_apply per buffer).  x is what the screen kernel computes, with 0 on the uncovered pixels, where dr.interpolate / F.normalize leave
+        0.  As in the reference, with render_camera_position set 'distance' and 'ray_direction' are taken from the ALREADY antialiased camera position
+        (:245-256), 'map_attr' is sampled at the un-antialiased uv (:299, :309-311), and 'mask' is unchanged.
         Refused, never dropped (NotImplementedError when set): render_voxel_attr / render_voxel_network (the reference's branch cannot execute: it
         permutes the 5-D voxel_attr.expand(batch_size, *shape[-4:]) with four indices, :203-204), render_all_point_cloud /
         render_visible_point_cloud (draw_mask hands the float pixel coordinates of discretize to torch.scatter as the index, :151-154, :28-36)
@@ -527,14 +543,54 @@ class NVDiffRendererInverse:
         with self._stage("screen_gbuffer"):
             out = ops.screen_gbuffer(rast, m.faces, m.vertices, v_nrm=m.vertex_normals if _reads_vertex_normals(want) else None, v_uv=m.uvs_2d if render_uv else None,
                                      v_attr=v_attr if render_v_attr else None, maps=maps, c2ws=c2ws_cpu, want=["mask", "alpha"] + want,
-                                     background=background, filter=grid_interpolate_mode,
+                                     background=None if antialias else background, filter=grid_interpolate_mode,
                                      clip_w=clip[..., 3].contiguous() if render_z_depth else None)
+        if antialias:      # the launch above ran without the background: the blend below needs the raw value on the uncovered pixels as well
+            with self._stage("antialias"):
+                out = self._antialias_buffers(out, want, rast, clip, background)
         out["mask"] = out["mask"].bool()[..., None]
         return out
 
+    # buffer -> the background the reference blends it with at enable_antialis=True (renderer_base.py:165-303)
+    _SCREEN_FILL = dict(z_depth=0.0, world_normal=-1.0, camera_normal=-1.0, world_position=-1.0, camera_position=0.0, distance=0.0, ray_direction=-1.0,
+                        cos_ray_normal=-1.0, uv=-1.0)
+
+    def _antialias_buffers(self, out, want, rast, clip, background):
+        """simple_rendering(antialias=True): the buffers of the antialias=False launch -> the reference's at enable_antialis=True.  The kernel's covered
+        pixels are the raw values x; its uncovered pixels are put back to the 0 that dr.interpolate / F.normalize leave there, then lerp and stencil."""
+        m = self.pbr_mesh
+        weights = ops.antialias_weights(rast, clip, m.faces, m.edge_opposites)
+        covered = out["mask"].bool()[..., None]
+        alpha = ops.antialias_apply(out["alpha"], weights)
+        res = {"mask": out["mask"], "alpha": alpha}
+
+        def blend(x, fill):
+            return ops.antialias_apply(torch.lerp(torch.full_like(x, fill), x, alpha).contiguous(), weights)
+
+        for k in want:
+            x = out[k]
+            if k in ("v_attr", "map_attr"):
+                if background is None:      # no pre-blend: the value as computed on every pixel
+                    res[k] = ops.antialias_apply(x, weights)
+                    continue
+                bg = torch.full_like(x, float(background)) if isinstance(background, (int, float)) else \
+                    torch.as_tensor(background, dtype=torch.float32).to(x.device).expand_as(x)
+                res[k] = ops.antialias_apply(torch.lerp(bg, x, alpha).contiguous(), weights)
+                continue
+            x = torch.where(covered, x, torch.zeros_like(x))
+            # `want` follows _SCREEN_FLAGS, which lists camera_position BEFORE distance and ray_direction: with render_camera_position set its
+            # antialiased buffer is in `res` by now and the two are taken from it, as the reference overwrites its local (:245-256); without it
+            # they keep the kernel's raw value (:243, :250, :256)
+            assert self._SCREEN_FLAGS.index("camera_position") < min(self._SCREEN_FLAGS.index("distance"), self._SCREEN_FLAGS.index("ray_direction"))
+            if k in ("distance", "ray_direction") and "camera_position" in res:
+                cp = res["camera_position"]
+                x = torch.norm(cp, p=2, dim=-1, keepdim=True) if k == "distance" else torch.nn.functional.normalize(cp, dim=-1)
+            res[k] = blend(x, self._SCREEN_FILL[k])
+        return res
+
     def geometry_rendering(self, c2ws, intrinsics, render_size, render_all_point_cloud=False, render_visible_point_cloud=False, render_z_depth=True,
                            render_distance=True, render_world_normal=True, render_camera_normal=True, render_world_position=True,
-                           render_camera_position=True, render_ray_direction=True, render_cos_ray_normal=True, render_uv=True, background=None, **kwargs):
+                           render_camera_position=True, render_ray_direction=True, render_cos_ray_normal=True, render_uv=True, background=None, antialias=False, **kwargs):
         """NVDiffRendererBase.geometry_rendering (renderer_base.py:745-780): simple_rendering with every geometry buffer on by default and neither v_attr nor
         map_attr.  The two point-cloud flags default to False, what simple_rendering builds (the reference's True); True raises as it does there, and so does
         every other keyword simple_rendering refuses."""
@@ -543,25 +599,25 @@ class NVDiffRendererInverse:
                                      render_world_normal=render_world_normal, render_camera_normal=render_camera_normal,
                                      render_world_position=render_world_position, render_camera_position=render_camera_position,
                                      render_ray_direction=render_ray_direction, render_cos_ray_normal=render_cos_ray_normal, render_v_attr=False,
-                                     render_uv=render_uv, render_map_attr=False, background=background, **kwargs)
+                                     render_uv=render_uv, render_map_attr=False, background=background, antialias=antialias, **kwargs)
 
     def vertex_rendering(self, v_rgb, c2ws, intrinsics, render_size, render_rgb=True, render_all_point_cloud=False, render_visible_point_cloud=False,
                          render_z_depth=False, render_distance=False, render_world_normal=False, render_camera_normal=False, render_world_position=False,
-                         render_camera_position=False, render_ray_direction=False, render_cos_ray_normal=False, background=None, **kwargs):
+                         render_camera_position=False, render_ray_direction=False, render_cos_ray_normal=False, background=None, antialias=False, **kwargs):
         """NVDiffRendererBase.vertex_rendering (renderer_base.py:782-820): simple_rendering of the per-vertex colour v_rgb [V,C]; 'rgb' is 'v_attr'."""
         out = self.simple_rendering(c2ws, intrinsics, render_size, v_attr=v_rgb, render_all_point_cloud=render_all_point_cloud,
                                     render_visible_point_cloud=render_visible_point_cloud, render_z_depth=render_z_depth, render_distance=render_distance,
                                     render_world_normal=render_world_normal, render_camera_normal=render_camera_normal,
                                     render_world_position=render_world_position, render_camera_position=render_camera_position,
                                     render_ray_direction=render_ray_direction, render_cos_ray_normal=render_cos_ray_normal, render_v_attr=render_rgb,
-                                    render_uv=False, render_map_attr=False, background=background, **kwargs)
+                                    render_uv=False, render_map_attr=False, background=background, antialias=antialias, **kwargs)
         if render_rgb:
             out["rgb"] = out["v_attr"]
         return out
 
     def uv_rendering(self, map_Kd, c2ws, intrinsics, render_size, render_rgb=True, render_all_point_cloud=False, render_visible_point_cloud=False,
                      render_z_depth=False, render_distance=False, render_world_normal=False, render_camera_normal=False, render_world_position=False,
-                     render_camera_position=False, render_ray_direction=False, render_cos_ray_normal=False, background=None, **kwargs):
+                     render_camera_position=False, render_ray_direction=False, render_cos_ray_normal=False, background=None, antialias=False, **kwargs):
         """NVDiffRendererBase.uv_rendering (renderer_base.py:822-860): simple_rendering of the texture map_Kd ([Ht,Wt,C], [1,Ht,Wt,C] or a tuple of maps) with
         'uv' always on, as in the reference; 'rgb' is 'map_attr'."""
         out = self.simple_rendering(c2ws, intrinsics, render_size, map_attr=map_Kd, render_all_point_cloud=render_all_point_cloud,
@@ -569,7 +625,7 @@ class NVDiffRendererInverse:
                                     render_world_normal=render_world_normal, render_camera_normal=render_camera_normal,
                                     render_world_position=render_world_position, render_camera_position=render_camera_position,
                                     render_ray_direction=render_ray_direction, render_cos_ray_normal=render_cos_ray_normal, render_v_attr=False,
-                                    render_uv=True, render_map_attr=render_rgb, background=background, **kwargs)
+                                    render_uv=True, render_map_attr=render_rgb, background=background, antialias=antialias, **kwargs)
         if render_rgb:
             out["rgb"] = out["map_attr"]
         return out
@@ -598,7 +654,7 @@ class NVDiffRendererInverse:
         perspective replaces the reference's enable_perspective() / enable_orthogonal() state.
         grid_interpolate_mode keeps the reference's default 'linear', which -- like 'barycentric' -- is a scipy Delaunay interpolator on the host and is
         refused (NotImplementedError): pass 'nearest'.  An unknown mode, texture_attr without texture_mask (or the reverse), n_neighbors outside 1..32 or
-        above the number of covered texels, and a call in which no pixel passes the sample mask raise ValueError; an unknown keyword is a TypeError."""
+        above the number of covered texels, and a call in which no pixel passes the sample mask raise ValueError; an unknown keyword is a TypeError, `antialias` among them (not wired here)."""
         who = "global_inverse_rendering"
         for k_ in kwargs:
             raise TypeError("%s() got an unexpected keyword argument %r" % (who, k_))

@@ -7,7 +7,7 @@ uint8 conversion kernel; orthographic box views (the pipeline's) or, as the refe
 camera (fov_deg) and / or the orbit ring (orbit=True).  export_orbit_video (video/export_nvdiffrast_video.py:141-256): per frame clip transform ->
 perspective raster -> fused UV interpolation + bilinear texture fetch + background composite (utx_texture_shade);
 the geometry video types (world / camera normal, world / camera position, z_depth, distance) swap that last kernel for the fused geometry-buffer
-shade (utx_gbuffer_shade; alpha = coverage, no dr.antialias); frames are muxed on the host (Motion-JPEG in an MP4 container, or GIF -- there is
+shade (utx_gbuffer_shade; alpha = coverage, dr.antialias is not wired here); frames are muxed on the host (Motion-JPEG in an MP4 container, or GIF -- there is
 no video encoder in this image)."""
 import io
 import math
