@@ -624,10 +624,12 @@ def knn_gather(src_pos, src_attr, dst_pos, k, src_mask=None, dst_mask=None, out=
         sn = np.asarray(src_nrm, np.float32).reshape(-1, 3); dn = np.asarray(dst_nrm, np.float32).reshape(-1, 3)[sel]
         with np.errstate(divide="ignore", invalid="ignore"):
             inv = (np.float32(1.0) / d2).astype(np.float32)
-        inv = np.where(np.isnan(inv) | (idx < 0), np.float32(0), inv)
+        # nan_to_num(nan=0.0) also brings 1/0 = +inf down to the largest finite float: one coincident source takes weight 1
+        inv = np.where(np.isnan(inv) | (idx < 0), np.float32(0), np.minimum(inv, np.finfo(np.float32).max))
         l1 = np.zeros(len(sel), np.float32)
-        for j in range(idx.shape[1]):
-            l1 = (l1 + np.abs(inv[:, j])).astype(np.float32)
+        with np.errstate(over="ignore"):                       # two coincident sources: the L1 sum overflows, every weight is 0, the row is 0
+            for j in range(idx.shape[1]):
+                l1 = (l1 + np.abs(inv[:, j])).astype(np.float32)
         ndn = np.maximum(np.sqrt(((dn[:, 0] * dn[:, 0] + dn[:, 1] * dn[:, 1]) + dn[:, 2] * dn[:, 2]).astype(np.float32)), np.float32(1e-8))
         wsum = np.zeros(len(sel), np.float32)
         acc = np.zeros((len(sel), C), np.float32)

@@ -11,6 +11,7 @@
 // (mode 1, arXiv 2411.02336 sec. 3.2 as the reference states it: normalised inverse score times normal cosine).
 #include "common.h"
 #include "kernels.h"
+#include <cfloat>
 #include <cstring>
 #include <string.h>
 #include <rocprim/rocprim.hpp>
@@ -94,9 +95,11 @@ __global__ __launch_bounds__(128) void knn_query_kernel(KnnParams p, const int* 
             p.out_attr[t * C + c] = s / (float)have;
         }
     } else {
-        // w_q = (1/score_q) / sum(1/score) * cos(n_src_q, n_dst); out = sum(w c) / sum(w); non-finite results -> 0
+        // w_q = (1/score_q) / sum(1/score) * cos(n_src_q, n_dst); out = sum(w c) / sum(w); non-finite results -> 0.
+        // The reference's nan_to_num(nan=0) leaves 1/0 at the largest finite float, not at inf: ONE coincident source (d2 = 0) takes weight 1 and
+        // gives its own colour; two or more overflow the L1 sum, every weight is 0 and the row is 0.
         float inv[KNN_KMAX], wsum_inv = 0.f;
-        for (int q = 0; q < have; ++q) { const float v = 1.0f / bd[q]; inv[q] = (v != v) ? 0.f : v; wsum_inv += fabsf(inv[q]); }
+        for (int q = 0; q < have; ++q) { const float v = 1.0f / bd[q]; inv[q] = (v != v) ? 0.f : fminf(v, FLT_MAX); wsum_inv += fabsf(inv[q]); }
         const float nx = p.dst_nrm[3 * t], ny = p.dst_nrm[3 * t + 1], nz = p.dst_nrm[3 * t + 2];
         const float nd = fmaxf(sqrtf((nx * nx + ny * ny) + nz * nz), 1e-8f);
         float w[KNN_KMAX], wsum = 0.f;
@@ -111,7 +114,7 @@ __global__ __launch_bounds__(128) void knn_query_kernel(KnnParams p, const int* 
             float s = 0.f;
             for (int q = 0; q < have; ++q) s += p.src_attr[(long)bi[q] * C + c] * w[q];
             float o = s / wsum;
-            if (!(fabsf(o) <= 3.0e38f)) o = 0.f;
+            if (!(fabsf(o) <= FLT_MAX)) o = 0.f;
             p.out_attr[t * C + c] = o;
         }
     }

@@ -843,10 +843,12 @@ def view_visibility(attr6, rast, fnormal, dirs, grad_thr=0.20, angle_deg=115.0, 
 
 
 def knn_gather(src_pos, dst_pos, k, src_attr=None, src_mask=None, dst_mask=None, out=None, mode="mean", src_nrm=None, dst_nrm=None,
-               want_index=False):
+               want_index=False, out_index=None):
     """exact k-NN in 3-D over dense, byte-masked point sets (bake_mv_to_uv_kdtree, renderer_inverse.py:367-433).
     src_pos [N,3], dst_pos [M,3]; src_attr [N,C] -> out [M,C] (written only where dst_mask): mean of the k neighbours'
-    attributes, or the MVPaint weighting (mode='mvpaint').  want_index: also return (idx [M,k] i32, d2 [M,k] f32)."""
+    attributes, or the MVPaint weighting (mode='mvpaint').  want_index: also return (idx [M,k] i32, d2 [M,k] f32).
+    out_index: a pair of contiguous tensors (idx, d2) of those shapes and types on src_pos's device, written in place and returned as with
+    want_index (rows outside dst_mask keep their contents)."""
     from .._lib import KnnDesc
     ctx = get_ctx(src_pos.device.index)
     dev = src_pos.device
@@ -875,14 +877,20 @@ def knn_gather(src_pos, dst_pos, k, src_attr=None, src_mask=None, dst_mask=None,
             keep.append(t)
             setattr(d, name, ptr(t))
     idx = d2 = None
-    if want_index:
+    if out_index is not None:
+        idx, d2 = out_index
+        for name, t, dt in (("idx", idx, I32), ("d2", d2, F32)):
+            if not (isinstance(t, torch.Tensor) and t.dtype == dt and t.device == dev and t.is_contiguous() and t.numel() == M * int(k)):
+                raise ValueError("out_index: %s must be a contiguous %s tensor of %d x %d elements on %s" % (name, dt, M, int(k), dev))
+        d.out_idx, d.out_d2 = ptr(idx), ptr(d2)
+    elif want_index:
         idx = torch.empty(M, int(k), dtype=I32, device=dev)
         d2 = torch.empty(M, int(k), dtype=F32, device=dev)
         d.out_idx, d.out_d2 = ptr(idx), ptr(d2)
     wb = ctx.lib.utx_knn_workspace_bytes(N)
     work = torch.empty(wb, dtype=U8, device=dev)
     ctx.check(ctx.lib.utx_knn(ctx.handle, C.byref(d), ptr(work), wb, ctx.stream()))
-    if want_index:
+    if want_index or out_index is not None:
         return out, idx, d2
     return out
 
